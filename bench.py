@@ -1,6 +1,6 @@
 """Benchmark of the hot path on N MI355X GPUs of one node (one process per GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,12 +12,15 @@ RCCL all-gather of the saliency maps.  Metric: frames/s = N * clips * frames * K
 wall time.  The K steps are issued as a stream of batches through the engine's two-stage software pipeline
 (SaliencyEngine.stream: the static stage of batch k+1 on a second HIP stream beside the ConvLSTM of batch k; the
 pipeline starts empty and is drained INSIDE the timed region; every batch's maps are the bits the one-by-one form
-gives); the same K steps issued one by one are timed right after and reported as `sequential` (--sequential makes
-them the headline).  The timed region carries NO instrumentation; the per-kernel roofline of the dominant
-kernel (the ConvLSTM convolution: its Winograd-domain GEMM) is measured with HIP events in a separate short pass
-after it.  Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`,
-`cpu_baseline` (the oracle on the host cores, bounded sample, N = 1 only) and `secondary`: the other
-precisions / BASELINE configs timed by the same invocation (N = 1 only; --no-secondary skips them).
+gives).  The timed region carries NO instrumentation.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set up, W warmup steps, the K timed steps, the outputs
+(--dump-outputs DIR: the maps of the last timed step as DIR/<name>.npy, same inputs on every run) and the line.
+Everything else is measured only under --full: the same K steps issued one by one right after, reported as
+`sequential` (--sequential makes them the headline), the stage split, the all-gather alone, the per-kernel roofline
+of the dominant kernel (the ConvLSTM convolution: its Winograd-domain GEMM, measured with HIP events in a separate
+short pass), the clock probe, `cpu_baseline` (the oracle on the host cores, bounded sample, N = 1 only) and
+`secondary`: the other precisions / BASELINE configs (N = 1 only; --no-secondary / --no-cpu-baseline skip them).
 """
 import argparse
 import json
@@ -290,9 +293,28 @@ def static_roofline(ms_per_step, B, T, cd, precision):
     return r
 
 
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as ``path/<name>.npy`` in float32 (float64 if computed in it).  An array above its share
+    of DUMP_BYTES is written as a fixed, seeded sample of its flat elements, with the flat indices it took (as float64) in
+    ``path/<name>_index.npy``."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, share // (a.itemsize + 8)))
+            np.save(os.path.join(path, name + '_index.npy'), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def run_workload(dev, rank, world, H, W, cd, B, T, precision, steps, warmup, graph=False, static_only=False,
                  frame_chunk=None, source_hw=None, want_roofline=False, static_precision=None, all_steps=False,
-                 f32_input=False, stub=False, want_split=False, want_plan=False, clock_after=False, pipelined=False):
+                 f32_input=False, stub=False, want_split=False, want_plan=False, clock_after=False, pipelined=False,
+                 want_sequential=False, want_allgather=False, want_outputs=False):
     if stub:
         eng = StubEngine(cd, B, T)
     else:
@@ -343,7 +365,12 @@ def run_workload(dev, rank, world, H, W, cd, B, T, precision, steps, warmup, gra
     assert (static_only or out.shape[0] == n_clips) and bool(torch.isfinite(out).all())
     res = {'value': round(world * B * T * steps / elapsed, 3), 'ms_per_step': round(1000.0 * elapsed / steps, 3),
            'roofline': None, 'pipelined': pipelined}
-    if pipelined:
+    if want_outputs:
+        # what a caller of the timed path receives from its last step, copied before anything below reuses the buffers:
+        # the gathered saliency maps, or (static path only) the CAM [frames, 6 w w, 1000]
+        res['outputs'] = {k: v.detach().to('cpu', torch.float32, copy=True).numpy()
+                          for k, v in ({'cam': eng.cam} if static_only else {'saliency': out}).items()}
+    if pipelined and want_sequential:
         # the same K steps one batch at a time (engine(frames): nothing of batch k+1 starts before batch k's maps are out) -
         # the form every round before this one quoted as the headline; reported beside it, never as `value`
         out_p = out.clone()                                # (gather_maps reuses its result buffer)
@@ -358,6 +385,9 @@ def run_workload(dev, rank, world, H, W, cd, B, T, precision, steps, warmup, gra
     # diagnosis of the N > 1 runs (never part of `value`): every rank's own ms per step and the all-gather alone
     res['ms_per_step_per_rank'] = [round(1000.0 * v / steps, 3) for v in cpdist.all_ranks(mine, dev)]
     if not static_only:
+        res['allgather_bytes_per_rank'] = int(B * out[0].numel() * out.element_size())
+        res['map_shape'] = list(out.shape)
+    if want_allgather and not static_only:
         sal = eng(frames)
         sync(dev)
         cpdist.barrier()
@@ -366,8 +396,6 @@ def run_workload(dev, rank, world, H, W, cd, B, T, precision, steps, warmup, gra
             cpdist.gather_maps(sal, n_clips, rank, world, reuse=True)
         sync(dev)
         res['allgather_ms'] = round(cpdist.max_over_ranks(time.perf_counter() - t0, dev) * 100.0, 4)
-        res['allgather_bytes_per_rank'] = int(sal.numel() * sal.element_size())
-        res['map_shape'] = list(out.shape)
     # diagnostics after the timed region: a failure here is reported in the line, it never costs the measured value
     if want_split and not static_only and not stub:
         if graph:
@@ -383,7 +411,7 @@ def run_workload(dev, rank, world, H, W, cd, B, T, precision, steps, warmup, gra
             res['roofline'] = roofline_pass(eng, frames, precision)
         except Exception as e:                      # noqa: BLE001
             res['roofline'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:200])}
-    if static_only and not stub:
+    if want_roofline and static_only and not stub:
         res['roofline'] = static_roofline(res['ms_per_step'], B, T, cd, eng.static_precision)
     if want_plan and not stub:
         # which path the static stage takes at this cube size (cp360_resnet_plan_describe): fused kernels exist for cube 224 / 512
@@ -644,6 +672,11 @@ def main():
     ap.add_argument('--cpu-anchor', action='store_true',
                     help='no GPU: time the oracle on the pieces BASELINE.md section 2 timed with the reference itself '
                          '(CAM of one cube, one ConvLSTM step) - the sanity anchor of the cpu_baseline leg')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: sequential form, stage split, all-gather alone, roofline '
+                         'pass, clock probe, cpu_baseline and the secondary configs')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
     if args.cpu_anchor:
         print(json.dumps(cpu_anchor()))
@@ -665,11 +698,14 @@ def main():
 
     head = run_workload(dev, rank, world, H, W, args.cube, B, T, args.precision, args.steps, args.warmup,
                         graph=args.graph, static_only=args.static_only, frame_chunk=args.frame_chunk or None,
-                        source_hw=src_hw, want_roofline=(rank == 0), static_precision=args.static_precision or None,
-                        all_steps=args.all_steps, f32_input=args.f32_input, stub=args.stub_engine, want_split=(rank == 0),
-                        pipelined=not args.sequential)
+                        source_hw=src_hw, want_roofline=(rank == 0 and args.full), static_precision=args.static_precision or None,
+                        all_steps=args.all_steps, f32_input=args.f32_input, stub=args.stub_engine,
+                        want_split=(rank == 0 and args.full), pipelined=not args.sequential, want_sequential=args.full,
+                        want_allgather=args.full, want_outputs=bool(args.dump_outputs) and rank == 0)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, head['outputs'])
         line = {
             'metric': 'frames/sec end-to-end %dx%d equi->saliency' % (H, W),
             'value': head['value'], 'unit': 'frames/s', 'n_gpus': world,
@@ -681,6 +717,7 @@ def main():
                      else '%s+%s' % (DTYPE[args.precision], head['static_dtype']),
             'mixed_precision': head['static_dtype'] != DTYPE[args.precision],
             'data': 'synthetic',
+            'full': bool(args.full),         # the measurements beyond the headline below are taken only under --full
             'config': {'workload': ('' if args.static_only else 'C3/C4 per-GPU shard: ')
                                    + workload_name(args.static_only, B, T, H, W, args.cube, head['w'], src_hw,
                                                    args.all_steps, args.f32_input),
@@ -710,16 +747,16 @@ def main():
             # attribution of one box's number (measured after the timed region): where a step's time goes, and the shader
             # clock this chip holds under a dense bf16 MFMA load (boxes differ: MI355X_MICROARCH.md, DVFS give-back)
             'stage_ms': head.get('stage_ms'),
-            'held_clock_ghz': None if args.stub_engine else _safe(lambda: ops.held_clock_ghz(dev)),
+            'held_clock_ghz': _safe(lambda: ops.held_clock_ghz(dev)) if args.full and not args.stub_engine else None,
             # ... that probe is a register-only MFMA loop: it ranks boxes, it is NOT the clock the dominant kernel holds (LDS, DMA
             # and HBM traffic beside the matrix pipe draw power too).  The counter-derived clock of that kernel, from the tracked
             # PMC summary of the same launch shape (SQ_BUSY_CYCLES / 32 / launch time; not re-measured in this run):
-            'dominant_kernel_clock': pmc_clock(args.precision, B, head.get('w')),
+            'dominant_kernel_clock': pmc_clock(args.precision, B, head.get('w')) if args.full else None,
         }
         if args.stub_engine:
             line['stub_engine'] = True
             line['data'] = 'stub'
-        if world == 1 and not args.no_secondary and not args.stub_engine:
+        if args.full and world == 1 and not args.no_secondary and not args.stub_engine:
             sec = []
 
             def guarded(name, fn):
@@ -733,7 +770,8 @@ def main():
 
             def add(name, H2, W2, cd2, B2, T2, prec, steps, warmup, **kw):
                 def run():
-                    r = run_workload(dev, 0, 1, H2, W2, cd2, B2, T2, prec, steps, warmup, want_roofline=True, **kw)
+                    r = run_workload(dev, 0, 1, H2, W2, cd2, B2, T2, prec, steps, warmup, want_roofline=True,
+                                     want_sequential=True, want_allgather=True, **kw)
                     return {'name': name, 'workload': workload_name(kw.get('static_only', False), B2, T2, H2, W2, cd2, r['w'],
                                                                     None, kw.get('all_steps', False), kw.get('f32_input', False)),
                             'dtype': DTYPE[prec], 'static_stage_dtype': r['static_dtype'], 'graph_replay': bool(kw.get('graph')),
@@ -773,7 +811,7 @@ def main():
                                                'timed_region_s': sus.get('timed_region_s'), 'pipelined': sus.get('pipelined'),
                                                'sequential': (sus.get('sequential') or {}).get('value'),
                                                'held_clock_ghz_after': sus.get('held_clock_ghz_after')}
-        if world == 1 and not args.no_cpu_baseline and not args.stub_engine:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.stub_engine:
             try:
                 line['cpu_baseline'] = cpu_baseline(args.precision, dev, args.static_precision or None, clips=B)
             except Exception as e:                          # noqa: BLE001 - the headline line is printed whatever happens here

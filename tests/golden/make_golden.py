@@ -195,12 +195,22 @@ def gen_resnet(R, out):
     arrs['wsm_pick'] = wsm[::97, ::53].astype(np.float32).copy()   # before the restore: wsm aliases fc.weight
     # CAM() mutates fc.weight in place through the numpy view (survey a7); restore
     model.fc.weight.data.copy_(torch.from_numpy(sd['fc.weight']))
-    arrs['cam_f'] = score.astype(np.float32)
+    # the CAM scores in two halves (faces 0-2 / 3-5), each in its own file: no fixture file above 1 MiB
+    score = score.astype(np.float32)
+    arrs['cam_f_0'] = score[:3]
     arrs['layer4_f'] = feat[:, ::8].astype(np.float32)
     arrs['layer4_sum_f'] = np.float64(np.sum(feat.astype(np.float64)))
     arrs['wsm_min'] = np.float32(np.min(sd['fc.weight']))
     np.savez_compressed(os.path.join(out, 'resnet_cam.npz'), **arrs)
+    np.savez_compressed(os.path.join(out, 'resnet_cam_f1.npz'), cam_f_1=score[3:])
     print('resnet/CAM fixtures written')
+
+
+def load_resnet_cam(golden_dir=HERE):
+    """resnet_cam.npz + resnet_cam_f1.npz as one dict, the CAM scores [6, 1000, 7, 7] rejoined under ``cam_f``."""
+    z = dict(np.load(os.path.join(golden_dir, 'resnet_cam.npz')))
+    z['cam_f'] = np.concatenate([z.pop('cam_f_0'), np.load(os.path.join(golden_dir, 'resnet_cam_f1.npz'))['cam_f_1']])
+    return z
 
 
 # --------------------------------------------------------------------------- clstm

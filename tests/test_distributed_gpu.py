@@ -47,7 +47,7 @@ def test_bench_py_pipelined_steps_through_torchrun_on_rccl():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
            os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--clips', '2', '--frames', '3',
-           '--equi', '256x512', '--cube', '64', '--no-secondary', '--no-cpu-baseline']
+           '--equi', '256x512', '--cube', '64', '--full', '--no-secondary', '--no-cpu-baseline']
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

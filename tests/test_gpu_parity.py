@@ -1044,7 +1044,7 @@ def test_resnet_state_dict_keys_match_reference_names():
 
 
 def test_resnet_layer4_small_golden(golden_dir):
-    z = np.load(os.path.join(golden_dir, 'resnet_cam.npz'))
+    z = mg.load_resnet_cam(golden_dir)
     m, _ = _load_resnet()
     cubes = mg.synth_cubes(4000 + 64, 64)
     x = torch.from_numpy(np.ascontiguousarray(cubes.transpose(0, 3, 1, 2))).to(DEV)
@@ -1059,7 +1059,7 @@ def test_resnet_layer4_small_golden(golden_dir):
 
 
 def test_cam_full_golden(golden_dir):
-    z = np.load(os.path.join(golden_dir, 'resnet_cam.npz'))
+    z = mg.load_resnet_cam(golden_dir)
     m, sd = _load_resnet()
     cubes = mg.synth_cubes(4000 + 224, 224)
     score, feat, wsm = CAM(cubes, None, m, 'layer4', 'fc.weight', use_gpu=True)
@@ -1075,7 +1075,7 @@ def test_cam_full_golden(golden_dir):
 
 
 def test_cam_bf16_close_to_fp32_oracle(golden_dir):
-    z = np.load(os.path.join(golden_dir, 'resnet_cam.npz'))
+    z = mg.load_resnet_cam(golden_dir)
     m, _ = _load_resnet('bf16')
     score, _, _ = CAM(mg.synth_cubes(4000 + 224, 224), None, m, 'layer4', 'fc.weight')
     # random-init weights amplify bf16 rounding through 16 residual blocks (a few % of

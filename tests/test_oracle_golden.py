@@ -108,7 +108,7 @@ def _resnet_sd():
 
 
 def test_resnet_cam_small(golden_dir):
-    z = np.load(os.path.join(golden_dir, 'resnet_cam.npz'))
+    z = mg.load_resnet_cam(golden_dir)
     sd = _resnet_sd()
     cubes = mg.synth_cubes(4000 + 64, 64)
     chw = np.ascontiguousarray(np.transpose(cubes, (0, 3, 1, 2)))
@@ -120,7 +120,7 @@ def test_resnet_cam_small(golden_dir):
 
 @pytest.mark.slow
 def test_resnet_cam_full(golden_dir):
-    z = np.load(os.path.join(golden_dir, 'resnet_cam.npz'))
+    z = mg.load_resnet_cam(golden_dir)
     sd = _resnet_sd()
     cubes = mg.synth_cubes(4000 + 224, 224)
     chw = np.ascontiguousarray(np.transpose(cubes, (0, 3, 1, 2)))
