@@ -69,3 +69,109 @@ def cubepad_sweep(dev):
         want = o_cubepad.cubepad(x, pad)
         got = CubePad(pad)(buf[off:].view(n6, C, n, n)).cpu().numpy()
         assert got.shape == want.shape and np.array_equal(got, want), (case, n, pad, C, n6, dt, off)
+
+
+# ------------------------------------------------------------------ per-layer parity of the 16-bit static stage
+# one output rounding: 2^-8 relative for bf16, 2^-11 for fp16 (tests/test_gpu_parity.py::_TOL)
+TOL = {'fp32': 2e-5, 'bf16': 1.2e-2, 'fp16': 1.5e-3}
+# bound factor per layer, as the fused-kernel tests of tests/test_gpu_parity.py use them against torch-CPU in f32: the stem
+# against rounded weights (test_stem_resident_patch_kernel_cube224), a whole layer of 3-4 blocks x4, layer3 (6 blocks) x6, one
+# Bottleneck x2 (test_layer2_first_block_fused_kernel), the CAM one 1x1 convolution
+LAYER_FACTOR = {'stem': 1, 'layer1': 4, 'layer2': 4, 'layer3': 6, 'layer4.0': 2, 'layer4.1': 2, 'layer4.2': 2, 'cam': 1}
+
+
+def sample_cubes(n_cubes, seed=0):
+    """The cubes a per-layer check recomputes on the CPU: 0, 1, the middle one, the last two and 3 seeded random ones
+    (whole cubes: CubePad reads across the faces of a cube).  Sorted; the last one is the last cube of the batch."""
+    fixed = sorted({0, 1, n_cubes // 2, n_cubes - 2, n_cubes - 1})
+    rest = [c for c in range(n_cubes) if c not in fixed]
+    picks = np.random.RandomState(seed).choice(rest, min(3, len(rest)), replace=False) if rest else []
+    return sorted(fixed + [int(c) for c in picks])
+
+
+def static_layer_trace(model, faces_p3, cubes):
+    """The Python-planned static stage (ResNet.features_nhwc's launches, then the CAM conv) one layer at a time on the GPU
+    over ALL faces of ``faces_p3`` ([6N, cd+6, cd+6, 4], the model's dtype), so every launch has the real batch's shape.
+    Returns {layer: f32 CPU NHWC output of the sampled cubes' faces} (16-bit outputs widened; the CAM's raw f32 scores), with
+    'input' = the unpadded 3-channel faces the stem read."""
+    from cp_360_weakly_supervised_saliency_amd import ops
+    from cp_360_weakly_supervised_saliency_amd.model import resnet_cubic as rc
+    faces = torch.tensor([6 * c + f for c in cubes for f in range(6)], device=faces_p3.device)
+    take = lambda t: t.index_select(0, faces).float().cpu()
+    out = {'input': take(faces_p3[:, 3:-3, 3:-3, :3])}
+    with torch.no_grad(), ops.launch_order(rc.LAUNCH_ORDER):
+        x = model.stem_nhwc(faces_p3, padded=True)
+        out['stem'] = take(x)
+        x, mid2 = model.layer1_nhwc(x, want_next=True)
+        out['layer1'] = take(x)
+        x = model.layer2_nhwc(x, mid2)
+        out['layer2'] = take(x)
+        x = model.layer3_nhwc(x)
+        out['layer3'] = take(x)
+        for b, blk in enumerate(model.layer4):
+            x = blk.forward_nhwc(x)
+            out['layer4.%d' % b] = take(x)
+        out['cam'] = take(model.cam_conv().raw_sum_f32(x, None))
+    return out
+
+
+def static_layer_reference(trace, resnet_sd, prec):
+    """torch-CPU f32 of every layer of ``static_layer_trace``, each from the GPU's own rounded input to that layer (so a layer
+    is checked alone): o_resnet's stem / Bottleneck / CAM arithmetic.  The stem uses the BN-folded weights rounded to the
+    16-bit type as the kernels hold them (the bound of its kernel test); the blocks and the CAM use the f32 weights."""
+    import torch.nn.functional as Fn
+    sd = sd_t(resnet_sd)
+    nchw = lambda t: t.permute(0, 3, 1, 2).contiguous()
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous()
+    want = {}
+    with torch.no_grad():
+        scale = sd['bn1.weight'] / torch.sqrt(sd['bn1.running_var'] + 1e-5)
+        bias = sd['bn1.bias'] - sd['bn1.running_mean'] * scale
+        w = sd['conv1.weight'] * scale[:, None, None, None]
+        if prec != 'fp32':
+            w = w.to({'bf16': torch.bfloat16, 'fp16': torch.float16}[prec]).float()
+        y = Fn.relu(Fn.conv2d(o_resnet.cubepad_t(nchw(trace['input']), 3), w, bias, stride=2))
+        want['stem'] = nhwc(Fn.max_pool2d(o_resnet.cubepad_t(y, 1), 3, 2, 0))
+        prev = 'stem'
+        for li, nblk in ((1, 3), (2, 4), (3, 6)):
+            x = nchw(trace[prev])
+            for b in range(nblk):
+                x = o_resnet._bottleneck(x, sd, 'layer%d.%d' % (li, b), 2 if (b == 0 and li > 1) else 1, b == 0)
+            prev = 'layer%d' % li
+            want[prev] = nhwc(x)
+        for b in range(3):
+            x = o_resnet._bottleneck(nchw(trace[prev]), sd, 'layer4.%d' % b, 2 if b == 0 else 1, b == 0)
+            prev = 'layer4.%d' % b
+            want[prev] = nhwc(x)
+        feat = nchw(trace[prev]).numpy()
+        want['cam'] = nhwc(torch.from_numpy(o_resnet.cam_scores(feat, sd['fc.weight'].numpy())))
+    return {k: v.numpy() for k, v in want.items()}
+
+
+def per_face_error(got, want, bound, label, cubes=None):
+    """Per-face relative error of f32 NHWC [F, h, w, C] arrays: max|got - want| over a face / max|want| over that face, so one
+    bad face cannot hide behind the maximum of the tensor.  -> (worst ratio, per-face ratios, message naming the worst element:
+    cube, face, pixel (y, x) and channel; ``cubes`` maps the rows' cube blocks back to batch cube indices)."""
+    F = got.shape[0]
+    assert got.shape == want.shape, (label, got.shape, want.shape)
+    d = np.abs(got - want).reshape(F, -1)
+    m = np.maximum(np.abs(want).reshape(F, -1).max(1), 1e-30)
+    r = d.max(1) / m
+    f = int(np.argmax(r))
+    y, x, c = np.unravel_index(int(np.argmax(d[f])), got.shape[1:])
+    cube = f // 6 if cubes is None else cubes[f // 6]
+    msg = ('%s: per-face max|d| / max|want| = %.3e > bound %.3e at cube %d face %d pixel (%d, %d) channel %d '
+           '(got %.6g want %.6g, face max|want| %.4g)' % (label, r[f], bound, cube, f % 6, y, x, c, got[f, y, x, c],
+                                                          want[f, y, x, c], m[f]))
+    return float(r[f]), r, msg
+
+
+def perturb_band(got, want, bound, face, rows=7, chans=64):
+    """A copy of ``got`` with one band of one face moved by 4 x bound x (that face's max |want|): ``rows`` rows (from the
+    middle of the face, all columns) x ``chans`` channels - what a per-face check at ``bound`` must reject."""
+    bad = got.copy()
+    h, C = got.shape[1], got.shape[3]
+    r0 = max(0, h // 2 - rows // 2)
+    c0 = max(0, C // 2 - chans // 2)
+    bad[face, r0:r0 + rows, :, c0:c0 + chans] += 4.0 * bound * float(np.abs(want[face]).max())
+    return bad
