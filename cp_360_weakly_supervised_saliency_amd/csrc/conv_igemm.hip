@@ -11,7 +11,7 @@
 //
 // Kernels in this file (the launch planner plan_of() picks one per call):
 //   conv_igemm_kernel<T,WN,WM>   c_out < 256: 128x128 / 64x256 tile, 4 waves, register-staged (described below)
-//   conv_igemm_dma_kernel<T,MJ>  c_out >= 256, small M: 256x128 tile, three LDS-DMA stages
+//   conv_igemm_dma_kernel<T,4>   c_out >= 256, small M: 256x128 tile, three LDS-DMA stages
 //   conv_igemm_ring_kernel<T,BM> c_out >= 256: 256x256 / 256x304 tile, four 64-byte-K stages, staggered waves
 //   conv_igemm_ring2_kernel<T>   1x1 with K of 128..512 elements, 16-bit: 256x128, two workgroups per CU
 //   conv_clip_kernel<T,MODE>     CubePad(1)+3x3 on 7x7 faces (ConvLSTM, one cube per tile), 8x8 faces (half a cube per
@@ -470,7 +470,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst /* wav
 // the same with the non-temporal hint: a weight stream much larger than the 256 MB Infinity Cache, past the head of a workgroup's
 // share (ConvK::w_pin) - it then no longer sweeps the cache of the split-K slabs / activations the next launches read, and the heads
 // of the streams, which every workgroup asks for at once when the launch starts, are still there from the previous step (measured on
-// the Winograd GEMM first: csrc/wino.hip fill_one, tools/wino_upin_probe.sh)
+// the Winograd GEMM first: csrc/wino.hip fill_one)
 __device__ __forceinline__ void glds16_nt(const void* gsrc, unsigned lds_dst /* wave-uniform */) {
     unsigned keep;
     asm volatile(
@@ -484,7 +484,7 @@ __device__ __forceinline__ void glds16_nt(const void* gsrc, unsigned lds_dst /* 
         : "memory");
 }
 
-template <typename T, int MJ>      // MJ = 16-pixel sub-tiles per wave: 4 -> 256x128 tile, 3 LDS stages; 8 -> 256x256, 2 stages
+template <typename T, int MJ>      // MJ = 16-pixel sub-tiles per wave: 4 -> 256x128 tile, 3 LDS stages (the only instance)
 __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     constexpr int BN = 256, BM = 32 * MJ, NSTAGE = (MJ == 4) ? 3 : 2;
     constexpr int EPC = Elem<T>::EPC;
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
 }
 
 // ------------------------------------------------------------------ 256 x {256, 304} tile, 4-stage ring
-// Same 8-wave / 256-channel tile as conv_igemm_dma_kernel<T, 8>, but the K step is HALF a line
+// The 8-wave / 256-channel tile of the former 256x256 DMA kernel (two 128-byte stages), but the K step is HALF a line
 // (64 bytes per tile row = one MFMA k-block) and the LDS holds a ring of FOUR stages:
 // the DMA of sub-step s+3 is issued at the start of sub-step s, so a load has three MFMA
 // phases (1.5 of the 2-stage kernel's steps) to arrive - the 2-stage kernel spent ~30 % of its
@@ -1744,13 +1744,9 @@ static ConvPlan plan_candidate(const cp360_conv_desc* d, int bn, int bm, int slo
 // K step (128 bytes per tile row: 16 KB into the CU, 1024 MFMA cycles per SIMD) takes 0.70 us per workgroup on a CU - the
 // CU's ~10 bytes / clock of global-load throughput, not the matrix pipe (0.43 us), is what a step waits for - so a launch
 // costs about (workgroups per CU) x steps x 0.7 us + a fixed 3 us per wave of 1024 workgroups.
+// The planner offers them to f32 only; a 16-bit launch reaches them when its caller forces tile_px 6464.
 static bool small_eligible(const cp360_conv_desc* d) {
-    static const int small = []() {
-        const char* e = getenv("CP360_SMALL");               // A/B switch: 0 = never, 1 = f32 only (default), 2 = every dtype
-        return e ? atoi(e) : 1;
-    }();
-    if (!small || (d->dtype != CP360_F32 && small < 2)) return false;
-    return small_shape_status(d) == CP360_OK;
+    return d->dtype == CP360_F32 && small_shape_status(d) == CP360_OK;
 }
 
 static ConvPlan plan_small(const cp360_conv_desc* d) {
@@ -1819,36 +1815,20 @@ static ConvPlan plan_big(const cp360_conv_desc* d) {
     ConvPlan best = plan_candidate(d, 256, 256, 256, 2.2);
     const ConvPlan b = plan_candidate(d, 256, 128, 256, 1.25);
     if (b.cost < best.cost) best = b;
-    static const int no304 = []() {
-        const char* e = getenv("CP360_NO304");             // A/B switch for tools/bench_conv.py
-        return e ? atoi(e) : 0;
-    }();
     const ConvPlan c = plan_candidate(d, 256, 304, 256, 2.2 * 304.0 / 256.0);   // 19 pixel blocks: 7x7 cube faces
-    if (!no304 && c.cost < best.cost) best = c;
+    if (c.cost < best.cost) best = c;
     // 160-pixel tile (16-bit types): wins where the larger tiles cannot give every CU a workgroup
-    static const int use160 = []() {
-        const char* e = getenv("CP360_TILE160");           // A/B switch
-        return e ? atoi(e) : 1;
-    }();
-    if (use160 && d->dtype != CP360_F32 && d->c_in2 == 0) {
+    if (d->dtype != CP360_F32 && d->c_in2 == 0) {
         const ConvPlan t160 = plan_candidate(d, 256, 160, 256, 2.2 * 176.0 / 256.0);
         if (t160.cost < best.cost) best = t160;
     }
     // short-K 1x1 convolutions (HBM-bound): 256x128 tile with two workgroups per CU (pixel tile id 129)
-    static const int ring2 = []() {
-        const char* e = getenv("CP360_RING2");             // A/B switch for tools/bench_conv.py
-        return e ? atoi(e) : 1;
-    }();
     // (K of at least two 128-byte steps: at K = 64 elements the one-workgroup 256x304 tile measured faster)
+    // K of at most four 128-byte steps.  (Up to 1 KiB it used to take the HBM-bound 1x1 convolutions of layers 2-4;
+    // measured per launch, 64 frames: l2.0 conv3 + downsample (K = 768 B) 232 -> 199 us on the 256x304 ring, l3.0
+    // conv1 (1 KiB) 153 -> 124, l4 conv3 (1 KiB) 84 -> 71; at 512 B - l3 conv3 - the two tie.)
     const int kbytes = (d->c_in + d->c_in2) * elem_bytes(d->dtype);
-    static const int ring2_kmax = []() {
-        // K of at most four 128-byte steps.  (Up to 1 KiB it used to take the HBM-bound 1x1 convolutions of layers 2-4;
-        // measured per launch, 64 frames: l2.0 conv3 + downsample (K = 768 B) 232 -> 199 us on the 256x304 ring, l3.0
-        // conv1 (1 KiB) 153 -> 124, l4 conv3 (1 KiB) 84 -> 71; at 512 B - l3 conv3 - the two tie.)  A/B switch.
-        const char* e = getenv("CP360_RING2_KMAX");
-        return e ? atoi(e) : 512;
-    }();
-    if (ring2 && d->dtype != CP360_F32 && d->kh * d->kw == 1 && kbytes >= 256 && kbytes <= ring2_kmax) {
+    if (d->dtype != CP360_F32 && d->kh * d->kw == 1 && kbytes >= 256 && kbytes <= 512) {
         ConvPlan r2 = plan_candidate(d, 256, 128, 512, 1.25);
         r2.bm = 129;
         if (r2.cost < best.cost) best = r2;
@@ -1897,8 +1877,6 @@ extern "C" int cp360_conv_prefer_clip(const cp360_conv_desc* d) {
     if (check_desc(&c)) return 0;
     cp360_conv_desc t = c;
     t.clip_resident = 0;
-    static const int force = []() { const char* e = getenv("CP360_PREFER_CLIP"); return e ? atoi(e) : -1; }();   // A/B switch
-    if (force >= 0 && !check_desc(&t)) return force ? 1 : 0;
     if (check_desc(&t) || !small_eligible(&t)) return 1;
     return plan_big(&c).cost <= plan_small(&t).cost ? 1 : 0;
 }
@@ -1994,6 +1972,18 @@ static void launch_conv(ConvK& k, hipStream_t st) {
     hipLaunchKernelGGL((conv_igemm_kernel<T, WN, WM>), grid, dim3(256), 0, st, k);
 }
 
+// the 8-wave 256-channel kernels: ring tiles of 256 / 304 / 160 (16-bit types only) pixels, the DMA kernel for 128
+template <typename T>
+static int launch_wide(const ConvK& k, int bm, dim3 grid, hipStream_t st) {
+    if (bm == 304) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 304>), grid, dim3(512), 0, st, k);
+    else if (bm == 160) {
+        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 160>), grid, dim3(512), 0, st, k);
+        else return CP360_ERR_UNSUPPORTED;
+    } else if (bm >= 256) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 256>), grid, dim3(512), 0, st, k);
+    else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4>), grid, dim3(512), 0, st, k);
+    return CP360_OK;
+}
+
 extern "C" int cp360_conv_forward(const cp360_conv_desc* d, const void* in, const void* packed_w, const float* bias,
                                   const void* residual, void* out, float* partial, void* stream) {
     return cp360_conv_forward2(d, in, nullptr, packed_w, bias, residual, out, partial, stream);
@@ -2037,20 +2027,13 @@ extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, con
     k.nsub = k.k_total / (bk / 2);
     k.sub_per_split = (k.nsub + d->splits - 1) / d->splits;
     {   // weight streams that cannot stay in the 256 MB Infinity Cache (the ConvLSTM's 148 - 590 MB per launch): non-temporal past
-        // the first CP360_CLIP_WPIN (default 8) sub-steps of every workgroup; small filters (layer4: 4.7 MB) keep the default policy
-        static const int wpin = []() { const char* e = getenv("CP360_CLIP_WPIN"); return e ? atoi(e) : 8; }();
+        // the first 8 sub-steps of every workgroup; small filters (layer4: 4.7 MB) keep the default policy
         const size_t wbytes = (size_t)((d->c_out + 255) / 256) * 256 * k.k_total * (d->dtype == CP360_F32 ? 4 : 2);
-        k.w_pin = wbytes >= ((size_t)96 << 20) ? wpin : 0x7fffffff;
+        k.w_pin = wbytes >= ((size_t)96 << 20) ? 8 : 0x7fffffff;
     }
-    // Epilogue of the ring kernels: LDS-staged full-line stores by default; the direct 16-byte-piece
-    // epilogue measured the same on the big tiles (within 1 %) and is what the two-workgroups-per-CU
-    // short-K kernel uses (no LDS left for a staged tile there).  CP360_EPI=1 selects it everywhere.
-    static const int epi_mode = []() {
-        const char* e = getenv("CP360_EPI");
-        return e ? atoi(e) : 0;
-    }();
-    const bool epi_ok = d->c_out % 8 == 0 && d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && d->ld_res % 8 == 0;
-    k.epi_direct = (epi_mode && epi_ok) ? 1 : 0;
+    // Epilogue of the ring kernels: LDS-staged full-line stores; the direct 16-byte-piece epilogue measured the same on the
+    // big tiles (within 1 %) and is what the two-workgroups-per-CU short-K kernel uses (no LDS left for a staged tile there)
+    k.epi_direct = 0;
     hipStream_t st = (hipStream_t)stream;
     if (d->clip_resident) {
         const int mode = d->h_in == 16 ? 1 : d->h_in == 8 ? 2 : 0;   // tile = a face + its ring / half a cube / a cube
@@ -2079,9 +2062,8 @@ extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, con
         CP360_CHECK_HIP();
         return CP360_OK;
     }
-    // pointwise 64 -> 64 in a 16-bit type (layer1.0's conv1): the streaming kernel; CP360_PW64=0 keeps the generic tile kernel (A/B)
-    static const int use_pw64 = []() { const char* e = getenv("CP360_PW64"); return e ? atoi(e) : 1; }();
-    if (use_pw64 && d->dtype != CP360_F32 && d->kh == 1 && d->kw == 1 && d->sy == 1 && d->sx == 1 && d->pad == 0 && d->c_in == 64 &&
+    // pointwise 64 -> 64 in a 16-bit type (layer1.0's conv1): the streaming kernel (a caller-chosen tile_px keeps the generic one)
+    if (d->dtype != CP360_F32 && d->kh == 1 && d->kw == 1 && d->sy == 1 && d->sx == 1 && d->pad == 0 && d->c_in == 64 &&
         d->c_out == 64 && d->c_in2 == 0 && d->splits <= 1 && !residual && d->tile_px == 0 && d->pix_stride % 8 == 0 &&
         d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && k.M >= 4096 && k.out != nullptr && k.partial == nullptr) {
         long long blocks = ((long long)(k.M + 15) / 16 + 7) / 8;                 // two passes of PWU blocks per wave at most ...
@@ -2102,33 +2084,19 @@ extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, con
         // pixel count pads badly (small-M launches) - then 256x128
         const bool big = bm_ >= 256;
         const int bm = bm_ == 129 ? 128 : bm_;
-        if (bm_ == 129 && epi_ok) k.epi_direct = 1;
+        if (bm_ == 129) k.epi_direct = d->c_out % 8 == 0 && d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && d->ld_res % 8 == 0;
         k.nt = (k.c_out + 255) / 256;
         k.mt = (k.M + bm - 1) / bm;
         k.m_fast = ((long long)k.c_out * k.k_total > (long long)k.M * k.kh * k.kw * k.c_in) ? 1 : 0;
         dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-        static const int use_ring = []() {
-            const char* e = getenv("CP360_RING");           // A/B switch for tools/bench_conv.py
-            return e ? atoi(e) : 1;
-        }();
-        // the DMA kernels have no second-source loader (their K loop would run the extra tap on the first tensor):
-        // a second-source descriptor always takes a ring kernel, whatever CP360_RING says
-        const bool ring = use_ring || d->c_in2 > 0;
+        // the DMA kernel has no second-source loader (its K loop would run the extra tap on the first tensor)
         if (d->c_in2 > 0 && !big && bm_ != 129) return CP360_ERR_UNSUPPORTED;
-#define CP360_WIDE(TT)                                                                                     \
-        {                                                                                                      \
-            if (bm == 304) hipLaunchKernelGGL((conv_igemm_ring_kernel<TT, 304>), grid, dim3(512), 0, st, k);   \
-            else if (bm == 160) { if constexpr (sizeof(TT) == 2) hipLaunchKernelGGL((conv_igemm_ring_kernel<TT, 160>), grid, dim3(512), 0, st, k); } \
-            else if (big && ring) hipLaunchKernelGGL((conv_igemm_ring_kernel<TT, 256>), grid, dim3(512), 0, st, k); \
-            else if (big) hipLaunchKernelGGL((conv_igemm_dma_kernel<TT, 8>), grid, dim3(512), 0, st, k);       \
-            else          hipLaunchKernelGGL((conv_igemm_dma_kernel<TT, 4>), grid, dim3(512), 0, st, k);       \
-        }
         if (bm_ == 129 && d->dtype == CP360_F16) hipLaunchKernelGGL((conv_igemm_ring2_kernel<f16_raw>), grid, dim3(512), 0, st, k);
         else if (bm_ == 129) hipLaunchKernelGGL((conv_igemm_ring2_kernel<bf16_raw>), grid, dim3(512), 0, st, k);
-        else if (d->dtype == CP360_F32) CP360_WIDE(float)
-        else if (d->dtype == CP360_F16) CP360_WIDE(f16_raw)
-        else CP360_WIDE(bf16_raw)
-#undef CP360_WIDE
+        else if (d->dtype == CP360_F32) rc = launch_wide<float>(k, bm, grid, st);
+        else if (d->dtype == CP360_F16) rc = launch_wide<f16_raw>(k, bm, grid, st);
+        else rc = launch_wide<bf16_raw>(k, bm, grid, st);
+        if (rc) return rc;
     } else if (d->dtype == CP360_F32) {
         if (narrow) launch_conv<float, 1, 4>(k, st);
         else launch_conv<float, 2, 2>(k, st);

@@ -25,31 +25,19 @@
 // and the second source (the Bottleneck's downsample branch as one more 1x1 "tap" of conv3's K loop,
 // resnet_cubic.py:99-100).
 #include "conv_common.h"
-#include <stdlib.h>
 
 namespace {
 
-// One wave's share of a K step: one 64-byte half (16 f32 / 32 16-bit k values) of its 32 x 32 tile.  f32: a lane's 16-byte
-// chunk holds its four k values of four CONSECUTIVE v_mfma_f32_16x16x4_f32 (k = 4 * (lane >> 4) + e); the four accumulators
-// are walked inside the e loop, so two MFMAs on the same accumulator are four issues apart.
+// One wave's share of a K step: one 64-byte half (32 16-bit k values) of its 32 x 32 tile.
 template <typename T>
 __device__ __forceinline__ void mma_half(f32x4 (&acc)[2][2], const u32x4 (&a)[2], const u32x4 (&b)[2]) {
-    if constexpr (sizeof(T) == 4) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[i][e]), __uint_as_float(b[j][e]), acc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) mma_chunk<T>(acc[i][j], a[i], b[j]);
-    }
+        for (int j = 0; j < 2; ++j) mma_chunk<T>(acc[i][j], a[i], b[j]);
 }
 
+// 16-bit types (f32 has its own form below, conv_small_f32_kernel)
 template <typename T>
 __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     constexpr int BN = 64, BM = 64, NT = 512;
@@ -294,14 +282,13 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     }
     const T* res = reinterpret_cast<const T*>(p.res);
     T* outp = reinterpret_cast<T*>(p.out);
-    u32x4 rr[2][sizeof(T) == 4 ? 2 : 1];
+    u32x4 rr[2];
     if (!p.partial && res) {                               // both pixel blocks' residual pieces in flight together
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int m = m0 + wm * 32 + j * 16 + ml;
             const T* s = m < p.M ? res + (size_t)m * p.ld_res + n : reinterpret_cast<const T*>(g_zero16);
-            rr[j][0] = *reinterpret_cast<const u32x4*>(s);
-            if constexpr (sizeof(T) == 4) rr[j][1] = *reinterpret_cast<const u32x4*>(m < p.M ? s + 4 : s);
+            rr[j] = *reinterpret_cast<const u32x4*>(s);
         }
     }
 #pragma unroll
@@ -324,15 +311,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
         for (int e = 0; e < 8; ++e) v[e] += bb[e];
         if (res) {
             float r[8];
-            if constexpr (sizeof(T) == 4) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    r[e] = __uint_as_float(rr[j][0][e]);
-                    r[4 + e] = __uint_as_float(rr[j][1][e]);
-                }
-            } else {
-                unpack8(rr[j][0], r, T());
-            }
+            unpack8(rr[j], r, T());
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += r[e];
         }
@@ -341,12 +320,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
             for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
         }
         T* dst = outp + (size_t)m * p.ld_out + p.out_coff + n;
-        if constexpr (sizeof(T) == 4) {
-            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        } else {
-            *reinterpret_cast<u32x4*>(dst) = pack8(v, T());
-        }
+        *reinterpret_cast<u32x4*>(dst) = pack8(v, T());
     }
 }
 
@@ -669,10 +643,8 @@ void cp360_launch_conv_small(ConvK& k, int dtype, hipStream_t st) {
     // share whichever operand panel is larger through the XCD's L2
     k.m_fast = ((long long)k.c_out * k.k_total > (long long)k.M * k.kh * k.kw * k.c_in) ? 1 : 0;
     dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-    // f32: one wave per SIMD with the fillers inside the MFMA gaps (CP360_SMALL_F32=8 keeps the 8-wave form as an A/B path)
-    static const int f32_form = []() { const char* e = getenv("CP360_SMALL_F32"); return e ? atoi(e) : 4; }();
-    if (dtype == CP360_F32 && f32_form != 8) hipLaunchKernelGGL(conv_small_f32_kernel, grid, dim3(256), 0, st, k);
-    else if (dtype == CP360_F32) hipLaunchKernelGGL((conv_small_kernel<float>), grid, dim3(512), 0, st, k);
+    // f32: one wave per SIMD with the fillers inside the MFMA gaps
+    if (dtype == CP360_F32) hipLaunchKernelGGL(conv_small_f32_kernel, grid, dim3(256), 0, st, k);
     else if (dtype == CP360_F16) hipLaunchKernelGGL((conv_small_kernel<f16_raw>), grid, dim3(512), 0, st, k);
     else hipLaunchKernelGGL((conv_small_kernel<bf16_raw>), grid, dim3(512), 0, st, k);
 }

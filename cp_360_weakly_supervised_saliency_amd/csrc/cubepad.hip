@@ -2,7 +2,7 @@
 // NHWC for the fused pipeline) + the host-side table export.
 // Semantics: model/cube_pad.py:28-42,95-216 (see common.h: cubepad_src).
 //
-// NCHW kernels, in the order launch_nchw() tries them (each is bit-exact; A/B switches in launch_nchw; measurements and
+// NCHW kernels, in the order launch_nchw() tries them (each is bit-exact; test hooks in launch_nchw pin each one; measurements and
 // the reasoning behind the designs: profiles/r03_cubepad_plane.md):
 //   cubepad_nchw_cube_kernel     faces up to 16x16 (fallback up to 32x32): (cube, channel range) items through LDS, the
 //                                CubePad map as a per-workgroup table
@@ -1073,7 +1073,7 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
     auto try_cube = [&](int max_n) -> int {
         constexpr int ES = (int)sizeof(T);
         const int nn = g.n * g.n, HW = (g.n + g.pt + g.pd) * Wp;
-        static const int no_cube = []() { const char* e = getenv("CP360_CUBEPAD_NOCUBE"); return e ? atoi(e) : 0; }();   // A/B switch
+        static const int no_cube = []() { const char* e = getenv("CP360_CUBEPAD_NOCUBE"); return e ? atoi(e) : 0; }();   // test hook
         if (!no_cube && g.n <= max_n && HW <= 1444 && (reinterpret_cast<size_t>(x) & 15) == 0 && (reinterpret_cast<size_t>(y) & 15) == 0) {
             int CH = 0;
             for (int ch = 1; ch <= C && (size_t)6 * ch * nn * ES <= 24 * 1024; ++ch)
@@ -1091,6 +1091,8 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
         }
         return 1;                                            // not taken
     };
+    // The getenv switches of this function are test hooks: tests/test_gpu_parity.py sets them to pin each kernel of this chain (every one
+    // of which the default dispatch takes for some shape); unset, they change nothing.
     if (int r = try_cube(16); r <= 0) return r;
     {   // strip kernel: pads of at most 4 (every pad of the network is 1 or 3), strips within the 64 KiB LDS default
         const int P = max(max(g.pl, g.pr), max(g.pt, g.pd));
@@ -1098,23 +1100,23 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
         const int Hp = g.n + g.pt + g.pd;
         const size_t lds = (size_t)4 * (g.pt + g.pd + g.pl + g.pr) * g.n * ES;      // four waves' strips
         static const int no_strip = []() {
-            const char* e = getenv("CP360_CUBEPAD_ELEMENTWISE");      // A/B switch (tools/hbm_kernels.py)
+            const char* e = getenv("CP360_CUBEPAD_ELEMENTWISE");      // test hook: the element-per-lane kernel
             return e ? atoi(e) : 0;
         }();
         // (rows of at least 112 bytes - 56x56 f16 faces: 245 -> 149 us against the element-per-lane kernel, round 3; smaller
         //  faces take the whole-cube kernel above)
-        static const int strip_min = []() { const char* e = getenv("CP360_CUBEPAD_STRIP_MIN"); return e ? atoi(e) : 112; }();   // A/B switch
-        static const int strip_v1 = []() { const char* e = getenv("CP360_CUBEPAD_STRIP_V1"); return e ? atoi(e) : 0; }();   // A/B switch
+        constexpr int strip_min = 112;
+        static const int strip_v1 = []() { const char* e = getenv("CP360_CUBEPAD_STRIP_V1"); return e ? atoi(e) : 0; }();   // test hook
         constexpr int E = 16 / ES;
         const int LR = g.pl + g.pr, nlines = g.pt + g.pd + LR;
         const long long ps_size = (long long)Hp * Wp - (long long)g.n * g.n;
         const int ps_alloc = (int)((ps_size + 2 * E + E - 1) / E * E);
         const size_t lds2 = 512 + (size_t)4 * ps_alloc * ES;
-        static const int no_channel = []() { const char* e = getenv("CP360_CUBEPAD_NOCHANNEL"); return e ? atoi(e) : 0; }();   // A/B switch
-        static const int channel_min = []() { const char* e = getenv("CP360_CUBEPAD_CHANNEL_MIN"); return e ? atoi(e) : 96; }();
+        static const int no_channel = []() { const char* e = getenv("CP360_CUBEPAD_NOCHANNEL"); return e ? atoi(e) : 0; }();   // test hook
+        static const int channel_min = []() { const char* e = getenv("CP360_CUBEPAD_CHANNEL_MIN"); return e ? atoi(e) : 96; }();   // test hook
         {   // six padded planes assembled in LDS, one linear store stream
-            static const int no_lds6 = []() { const char* e = getenv("CP360_CUBEPAD_NOLDS6"); return e ? atoi(e) : 0; }();   // A/B switch
-            static const int lds6_min = []() { const char* e = getenv("CP360_CUBEPAD_LDS6_MIN"); return e ? atoi(e) : 64; }();
+            static const int no_lds6 = []() { const char* e = getenv("CP360_CUBEPAD_NOLDS6"); return e ? atoi(e) : 0; }();   // test hook
+            static const int lds6_min = []() { const char* e = getenv("CP360_CUBEPAD_LDS6_MIN"); return e ? atoi(e) : 64; }();   // test hook
             const long long HW = (long long)Hp * Wp, nn = (long long)g.n * g.n;
             // channels per item: one for faces whose six planes fill the LDS; for small faces the largest divisor of C that
             // keeps the six ranges within ~40 KB (>= 4 workgroups per CU) and leaves >= 512 items
@@ -1132,10 +1134,8 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
                 CH * HW < (1 << 22) && items >= lds6_min && items < (1ll << 31) && (reinterpret_cast<size_t>(y) % ES) == 0 &&
                 (reinterpret_cast<size_t>(x) % ES) == 0 &&
                 ensure_big_lds<&cubepad_nchw_lds6_kernel<ES>>() == CP360_OK) {    // (refused: on down the chain to the <= 64 KB kernels)
-                static const int force_nt6 = []() { const char* e = getenv("CP360_CUBEPAD_LDS6_NT"); return e ? atoi(e) : 0; }();
                 int per_cu = (int)((size_t)160 * 1024 / lds6);
-                int nt = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
-                if (force_nt6 == 256 || force_nt6 == 512 || force_nt6 == 1024) nt = force_nt6;
+                const int nt = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
                 if (per_cu > 2048 / nt) per_cu = 2048 / nt;
                 long long blocks = items < 256ll * per_cu ? items : 256ll * per_cu;
                 const int nstrip = nlines * g.n;
@@ -1150,8 +1150,8 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
         }
         if (int r = try_cube(32); r <= 0) return r;
         {   // planes larger than the LDS: row bands assembled in LDS, linear stores
-            static const int no_band = []() { const char* e = getenv("CP360_CUBEPAD_NOBAND"); return e ? atoi(e) : 0; }();   // A/B switch
-            static const int band_min_row = []() { const char* e = getenv("CP360_CUBEPAD_BAND_MINROW"); return e ? atoi(e) : 256; }();
+            static const int no_band = []() { const char* e = getenv("CP360_CUBEPAD_NOBAND"); return e ? atoi(e) : 0; }();   // test hook
+            static const int band_min_row = []() { const char* e = getenv("CP360_CUBEPAD_BAND_MINROW"); return e ? atoi(e) : 256; }();   // test hook
             int R = 16384 / (Wp * ES);                       // ~16 KB of output per item
             if (R < 2) R = 2;
             if (R > Hp) R = Hp;
@@ -1178,9 +1178,7 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
                 (reinterpret_cast<size_t>(x) % ES) == 0 &&
                 ensure_big_lds<&cubepad_nchw_channel_kernel<ES>>() == CP360_OK) {
                 // one wave per face while that gives >= 12 waves per CU, two (768 threads) for few / large items
-                static const int force_nt = []() { const char* e = getenv("CP360_CUBEPAD_CHANNEL_NT"); return e ? atoi(e) : 0; }();
-                int nt = items >= 512 ? 384 : 768;
-                if (force_nt == 384 || force_nt == 768) nt = force_nt;
+                const int nt = items >= 512 ? 384 : 768;
                 int per_cu = (int)((size_t)160 * 1024 / lds3);
                 if (per_cu > 2048 / nt) per_cu = 2048 / nt;
                 if (per_cu < 1) per_cu = 1;
@@ -1347,12 +1345,11 @@ extern "C" int cp360_cubepad_nhwc(const void* x, void* y, int n6, int C, int Cy,
     if (blocks < 1) blocks = 1;
     const uint32_t* xi = (const uint32_t*)x;
     uint32_t* yo = (uint32_t*)y;
-    static const int no_px = []() { const char* e = getenv("CP360_CUBEPAD_NHWC_NOPX"); return e ? atoi(e) : 0; }();   // A/B switch
     const long long total_px = (long long)n6 * Hp * Wp;
     long long pb = (total_px + 255) / 256;
     if (pb > 256 * 16) pb = 256 * 16;
     // narrow pixels: a thread per pixel (32-bit pixel index: the grid-stride increment must not wrap either)
-    if (!no_px && vec < 4 && cw <= 4 && cyw <= 8 && total_px < (1ll << 32) - pb * 256) {
+    if (vec < 4 && cw <= 4 && cyw <= 8 && total_px < (1ll << 32) - pb * 256) {
 #define CP360_PX(CWV) hipLaunchKernelGGL((cubepad_nhwc_px_kernel<CWV>), dim3((unsigned)pb), dim3(256), 0, st, xi, yo, (unsigned)total_px, cyw, g)
         if (cw == 1) CP360_PX(1); else if (cw == 2) CP360_PX(2); else if (cw == 3) CP360_PX(3); else CP360_PX(4);
 #undef CP360_PX

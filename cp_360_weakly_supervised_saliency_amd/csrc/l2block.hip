@@ -9,7 +9,7 @@
 // an HBM-bound 1x1 (conv3, 0.15 ms) with t making a round trip through HBM in between.  Here, as in l1block.hip:
 //   * a workgroup of 4 waves owns a band of 4 output rows (112 pixels = 7 MFMA pixel blocks, no padding columns: a
 //     band's pixels are consecutive in memory), two workgroups per CU (NB = 2 - one workgroup of 8 waves with two
-//     bands - exists as an A/B variant and measured slower);
+//     bands - measured slower; every launch has NB = 1);
 //   * stage 1 (conv2): each band's 6 x 30 cube-padded pixels (256 B each, 45 KB) are gathered ONCE by LDS-DMA through
 //     cubepad_src(); the nine taps read them there (the 16-byte chunk c of patch pixel (row, col) sits at chunk
 //     c ^ ((row * N + col) & 15): the 16 pixels of an MFMA block are consecutive OUTPUT pixels, so this key runs through
@@ -27,7 +27,6 @@
 // HBM traffic per block (64 frames): mid 77 MB + residual 308 MB + out 308 MB; t (77 MB x 2) never leaves the CU.
 // Work-item order: cp360_set_launch_order (descending band order when `reverse`).
 #include "common.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -567,8 +566,6 @@ static int bt_launch(int layer, int dtype, const void* mid, const void* w2_packe
     const int co = layer == 2 ? 512 : 1024;
     if ((long long)n_img * face * face * co >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    static const int nb_env = []() { const char* e = getenv("CP360_L2_BANDS"); return e ? atoi(e) : 1; }();   // A/B switch
-    const int nb = (nb_env == 2 && layer == 2 && face == 28 && !out_next) ? 2 : 1;
 #define CP360_L2B(TT, CV, NBV, NV, BV, NX)                                                                           \
     hipLaunchKernelGGL((l2block_kernel<TT, CV, NBV, NV, BV, NX>), dim3((unsigned)(n_img * (NV / BV) / NBV)), dim3(256 * NBV), 0, st, \
                        (const TT*)mid, (const TT*)w2_packed, bias2, (const TT*)w3_frags, bias3, (const TT*)residual, (TT*)out, \
@@ -579,7 +576,6 @@ static int bt_launch(int layer, int dtype, const void* mid, const void* w2_packe
         else if (layer == 3) CP360_L2B(TT, 256, 1, 14, 7, false);        \
         else if (out_next) CP360_L2B(TT, 128, 1, 28, 4, true);           \
         else if (face == 64) CP360_L2B(TT, 128, 1, 64, 2, false);        \
-        else if (nb == 2) CP360_L2B(TT, 128, 2, 28, 4, false);           \
         else CP360_L2B(TT, 128, 1, 28, 4, false);                        \
     }
     if (dtype == CP360_BF16) CP360_L2B_T(bf16_raw)

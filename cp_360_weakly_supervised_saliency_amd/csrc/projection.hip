@@ -1,7 +1,6 @@
 // K1 equi -> cube (+ /255, ImageNet normalise, layout, dtype) and K6 cube -> equi
 // (+ channel max).  Both are gathers bounded by HBM bandwidth.
 #include "common.h"
-#include <stdlib.h>
 
 // ------------------------------------------------------------------ K1
 // utils/equi_to_cube.py:112-129 = cv2.remap(img[:, :, c], inX, inY, INTER_LINEAR) per
@@ -141,21 +140,17 @@ __global__ __launch_bounds__(256) void equi2cube_kernel(const TI* __restrict__ e
 template <typename TI, typename TO>
 static int launch_e2c(const void* equi, const float* grid, void* out, int F, int H, int W, int cd, const float* mean,
                       const float* istd, float scale, int layout, int fixed, hipStream_t st) {
-    static const int fu_env = []() { const char* e = getenv("CP360_E2C_FU"); return e ? atoi(e) : 0; }();
-    static const int cap_env = []() { const char* e = getenv("CP360_E2C_CAP"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v; }();
-    const int fu = fu_env == 8 ? 8 : (fu_env == 2 ? 2 : 4);
-    const long long total = (long long)((F + fu - 1) / fu) * 6 * cd * cd;      // one thread per pixel and group of FU frames
+    constexpr int FU = 4;                                          // frames per thread
+    const long long total = (long long)((F + FU - 1) / FU) * 6 * cd * cd;      // one thread per pixel and group of FU frames
     long long blocks = (total + 255) / 256;
-    if (blocks > 256LL * cap_env) blocks = 256LL * cap_env;
+    if (blocks > 256LL * 64) blocks = 256LL * 64;
     blocks = (blocks + 7) / 8 * 8;                                  // XCD mapping in the kernel
-#define E2C_LAUNCH(L, FX, FUV)                                                                                  \
-    hipLaunchKernelGGL((equi2cube_kernel<TI, TO, L, FX, FUV>), dim3((unsigned)blocks), dim3(256), 0, st,        \
+#define E2C_LAUNCH(L, FX)                                                                                       \
+    hipLaunchKernelGGL((equi2cube_kernel<TI, TO, L, FX, FU>), dim3((unsigned)blocks), dim3(256), 0, st,         \
                        (const TI*)equi, (const float2*)grid, (TO*)out, F, H, W, cd, mean[0], mean[1], mean[2],  \
                        istd[0], istd[1], istd[2], scale)
-#define E2C_FU(L, FX) { if (fu == 8) E2C_LAUNCH(L, FX, 8); else if (fu == 2) E2C_LAUNCH(L, FX, 2); else E2C_LAUNCH(L, FX, 4); }
-    if (layout == 0) { if (fixed) E2C_FU(0, true) else E2C_FU(0, false) }
-    else             { if (fixed) E2C_FU(1, true) else E2C_FU(1, false) }
-#undef E2C_FU
+    if (layout == 0) { if (fixed) E2C_LAUNCH(0, true); else E2C_LAUNCH(0, false); }
+    else             { if (fixed) E2C_LAUNCH(1, true); else E2C_LAUNCH(1, false); }
 #undef E2C_LAUNCH
     CP360_CHECK_HIP();
     return CP360_OK;

@@ -234,12 +234,11 @@ extern "C" int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int
         return CP360_OK;
     }
     const uint8_t* cur = (const uint8_t*)in;
-    static const int slow = []() { const char* e = getenv("CP360_RESIZE_BYTEWISE"); return e ? atoi(e) : 0; }();   // A/B switch
     if (need_h) {       // [F, h_in, w_in] -> [F, h_in, w_out]
         uint8_t* dst = need_v ? (uint8_t*)tmp : (uint8_t*)out;
         // (the window kernel loads aligned dwords relative to the input base: a base that is not 4-byte aligned - a slice
         // of a batch of odd-sized images - takes the bytewise pass)
-        if (!slow && h_window_fits(w_in, w_out, hksize) && (long long)F * h_in < (1 << 24) && (reinterpret_cast<size_t>(cur) & 3) == 0) {
+        if (h_window_fits(w_in, w_out, hksize) && (long long)F * h_in < (1 << 24) && (reinterpret_cast<size_t>(cur) & 3) == 0) {
             const int xblocks = (w_out + 255) / 256;
             long long items = (long long)F * h_in * xblocks;
             unsigned blocks = (unsigned)(items > 256 * 16 ? 256 * 16 : (items + 7) / 8 * 8);
@@ -252,7 +251,7 @@ extern "C" int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int
         cur = dst;
     }
     if (need_v) {       // [F, h_in, w_out] -> [F, h_out, w_out]
-        if (!slow && (w_out * 3) % 4 == 0 && (reinterpret_cast<size_t>(cur) & 3) == 0 && (reinterpret_cast<size_t>(out) & 3) == 0) {
+        if ((w_out * 3) % 4 == 0 && (reinterpret_cast<size_t>(cur) & 3) == 0 && (reinterpret_cast<size_t>(out) & 3) == 0) {
             const long long total = (long long)F * h_out * (w_out * 3 / 4);
             long long b = (total + 255) / 256;
             if (b > 256 * 32) b = 256 * 32;

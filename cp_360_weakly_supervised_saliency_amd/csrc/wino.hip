@@ -609,11 +609,8 @@ int wino_check(const cp360_wino_desc* d, WinoGeom* g) {
 }  // namespace
 
 // Sub-steps (64 bytes of K) at the head of every workgroup's weight stream that keep the default cache policy (see fill_one):
-// 4 x 256 workgroups x 16 KiB = 16 MB per convolution (2 - 8 measured alike, 12 and more slower).  CP360_WINO_UPIN overrides it (A/B; a value >= the K loop = all default).
-static int wino_u_pin() {
-    static const int v = []() { const char* e = getenv("CP360_WINO_UPIN"); return e ? atoi(e) : 4; }();
-    return v;
-}
+// 4 x 256 workgroups x 16 KiB = 16 MB per convolution (2 - 8 measured alike, 12 and more slower).
+static constexpr int WINO_U_PIN = 4;
 
 extern "C" size_t cp360_wino_packed_bytes(const cp360_wino_desc* d) {
     WinoGeom g;
@@ -687,7 +684,7 @@ extern "C" int cp360_wino_gemm(const cp360_wino_desc* d, const void* v, const vo
     k.u = (const unsigned char*)packed; k.v = (const unsigned char*)v; k.m = m;
     k.nsub = g.nsub; k.nt = g.nt; k.mt = g.mt; k.m_pad = g.m_pad; k.ldm = g.ldm; k.c_out = d->c_out;
     k.tpf = g.tpf; k.th = g.th; k.odd = d->face & 1;
-    k.u_pin = wino_u_pin();
+    k.u_pin = WINO_U_PIN;
     k.reverse = cp360_launch_reverse();
     dim3 grid((unsigned)(16 * g.nt * g.mt));
     hipStream_t st = (hipStream_t)stream;
@@ -798,7 +795,7 @@ extern "C" int cp360_wino_gemm_raw(int dtype, const void* u, const void* v, floa
     k.u = (const unsigned char*)u; k.v = (const unsigned char*)v; k.m = m;
     k.nsub = nsub; k.nt = nt; k.mt = mt; k.m_pad = mt * WG_BM; k.ldm = ldm; k.c_out = c_out;
     k.tpf = 16; k.th = 4; k.odd = 0;
-    k.u_pin = wino_u_pin();
+    k.u_pin = WINO_U_PIN;
     k.reverse = cp360_launch_reverse();
     dim3 grid((unsigned)(16 * nt * mt));
     hipStream_t st = (hipStream_t)stream;

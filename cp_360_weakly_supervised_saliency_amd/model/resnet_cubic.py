@@ -14,7 +14,6 @@ physical NHWC) so hooks and callers see the reference's shapes.
 
 Inference only (the north star is the inference path): no autograd through the HIP ops.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -30,12 +29,12 @@ FUSE_DOWNSAMPLE = True
 FUSE_LAYER1 = True
 FUSE_LAYER2 = True
 FUSE_LAYER3 = True
-FUSE_STEM_POOL = os.environ.get('CP360_FUSE_STEM_POOL', '1') != '0'    # A/B switch: 0 = stem kernel, then max-pool kernel
-LAUNCH_ORDER = int(os.environ.get('CP360_LAUNCH_ORDER', '2'))   # 0: every launch ascending (A/B switch)
+FUSE_STEM_POOL = True     # False: stem kernel, then max-pool kernel
+LAUNCH_ORDER = 2          # 0: every launch ascending
 FUSE_LAYER2_NEXT = True    # the next identity block's conv1 chained onto the layer2 tail kernel (csrc/l2block.hip, NEXT)
 FUSE_L2_FIRST = True       # layer2.0 after its conv1 as one launch (csrc/lfirst.hip): stride-2 conv2 -> conv3 + downsample
 CHAIN_L1_L2 = True         # layer2.0's conv1 (256 -> 128) chained onto layer1's last tail kernel (csrc/l1block.hip, wide)
-FUSE_L1_FIRST = os.environ.get('CP360_L1_FIRST', '1') != '0'   # layer1.0's own conv1 inside its tail kernel (csrc/l1block.hip, FIRST); 0 = its own launch
+FUSE_L1_FIRST = True       # layer1.0's own conv1 inside its tail kernel (csrc/l1block.hip, FIRST); False = its own launch
 
 
 
@@ -208,7 +207,7 @@ class ResNet(nn.Module):
         xp = x_nhwc4 if padded else ops.cubepad_nhwc(x_nhwc4, 3)
         conv = self._stem_conv()
         if FUSE_STEM_POOL:
-            y = conv.stem_pool(xp)               # one kernel at cube 224 / 16-bit (csrc/stem.hip, stem_pool_kernel)
+            y = conv.stem_pool(xp)               # one kernel at cube 224 / 16-bit (csrc/stem.hip, stem_pool4_kernel)
             if y is not None:
                 return y
         return ops.cubepad_maxpool3s2(conv(xp))

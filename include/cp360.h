@@ -248,8 +248,7 @@ int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, const void* in
 /* out = act(sum_s partial[s] + bias (+ residual)) in d->dtype at the desc's ld_out/out_coff. */
 int cp360_conv_finish(const cp360_conv_desc* d, const float* partial, const float* bias,
                       const void* residual, void* out, void* stream);
-/* The same with one more f32 addend `extra` [M, c_out] in the slabs' column order (d->slab_rows), e.g. the batched
- * x half of the ConvLSTM's first convolution (cp360_clstm_window). */
+/* The same with one more f32 addend `extra` [M, c_out] in the slabs' column order (d->slab_rows). */
 int cp360_conv_finish_add(const cp360_conv_desc* d, const float* partial, const float* extra, const float* bias,
                           const void* residual, void* out, void* stream);
 
@@ -462,11 +461,8 @@ int cp360_clstm_step(cp360_ctx* ctx, void* xh, const float* c_prev, float* c_nex
  *   h_out     f32 [6 n_clips, face, face, H]: the final hidden state (:80);  h_all (optional) f32 [T, 6 n_clips, face, face, H]:
  *             the hidden state after EVERY step (return_all_steps)
  *   minmax    f32 [n_clips, 2] (out), mm_scratch f32 [n_clips * 512]
- * Needs Cin == H (:70-73).  By default the window issues exactly the launches of T cp360_clstm_step calls (same bits).
- * Opt-in, CP360_XBATCH=1 (measured performance-neutral; it changes Conv1's accumulation order): the x half of Conv1
- * (K = 9 Cin, no recurrence) runs ONCE for all T frames (one M = T * 6 face^2 * n_clips GEMM without split-K; its f32 result
- * joins the h half's split-K slabs in cp360_conv_finish_add), so Conv1's x weights stream once per window instead of T
- * times, at T * M * 4H * 4 bytes more workspace.  workspace: cp360_clstm_window_workspace_bytes. */
+ * Needs Cin == H (:70-73).  The window issues exactly the launches of T cp360_clstm_step calls (same bits).
+ * workspace: cp360_clstm_window_workspace_bytes. */
 size_t cp360_clstm_window_workspace_bytes(cp360_ctx* ctx, int n_clips, int T, int face);
 int cp360_clstm_window(cp360_ctx* ctx, const float* cam, size_t clip_stride, int n_clips, int T, int face, void* xh,
                        float* cell0, float* cell1, float* h_out, float* h_all, float* minmax, float* mm_scratch,

@@ -29,7 +29,7 @@ int cp360_stem_pack_weights(int dtype, const float* w_oihw /* [64,3,7,7] */, con
 int cp360_stem_forward(int dtype, const void* xp, const void* packed, const float* bias, void* out,
                        int n_img, int cube_dim, int relu, void* stream);
 /* The stem AND the max-pool behind it (CubePad(1) + MaxPool2d(3, 2), resnet_cubic.py:169-170) in one kernel: cube size
- * 224, CP360_BF16 / CP360_F16, ReLU on (csrc/stem.hip, stem_pool_kernel): xp as above -> y [n_img, 56, 56, 64]; the
+ * 224, CP360_BF16 / CP360_F16, ReLU on (csrc/stem.hip, stem_pool4_kernel): xp as above -> y [n_img, 56, 56, 64]; the
  * 112x112x64 stem output is never written.  `border`: scratch of cp360_stem_pool_border_bytes(n_img) bytes (the four
  * border rows / columns of every face's stem output, from which a second small launch folds the max-pool's cube padding
  * into pooled row 0 / column 0).  Bit-identical to cp360_stem_forward + cp360_cubepad_maxpool3s2.  Other cube sizes:

@@ -390,8 +390,9 @@ def test_conv_small_tile_is_what_one_frame_fp32_runs():
     assert torch.equal(auto, forced)
 
 
-def _pw64_case(prec, n_img, n, order):
-    """One 1x1, 64 -> 64 convolution + bn + relu on seeded operands (shared by the test below and its CP360_PW64=0 child)."""
+def _pw64_case(prec, n_img, n, order, tile_px=0):
+    """One 1x1, 64 -> 64 convolution + bn + relu on seeded operands.  A caller-chosen tile (tile_px != 0, one split) keeps the
+    launch off the streaming kernel: c_out < 256 then takes the generic 64 x 256-tile kernel (conv_igemm_kernel<T, 1, 4>)."""
     dt = _TDT[prec]
     w = hashrng.normal(9801, (64, 64, 1, 1), 0, (2.0 / 64) ** 0.5)
     scale = hashrng.normal(9802, (64,), 1.0, 0.1)
@@ -399,7 +400,7 @@ def _pw64_case(prec, n_img, n, order):
     conv = ops.Conv(torch.from_numpy(w), torch.from_numpy(scale), torch.from_numpy(bias), 1, 0, True, dt, DEV)
     xt = torch.from_numpy(hashrng.normal(9800 + n, (n_img, n, n, 64))).to(DEV).to(dt)
     with ops.launch_order(order):
-        got = conv(xt)
+        got = conv(xt, tile_px=tile_px, splits=1) if tile_px else conv(xt)
     wr = (torch.from_numpy(w[:, :, 0, 0]) * torch.from_numpy(scale)[:, None]).to(dt).float()
     want = torch.relu(xt.float().cpu() @ wr.t() + torch.from_numpy(bias).float())
     return got.cpu(), want
@@ -407,28 +408,18 @@ def _pw64_case(prec, n_img, n, order):
 
 @pytest.mark.parametrize('prec', ['bf16', 'fp16'])
 @pytest.mark.parametrize('n_img,n', [(24, 56), (6, 27)])
-def test_pointwise_64_to_64_streaming_kernel(prec, n_img, n, tmp_path):
+def test_pointwise_64_to_64_streaming_kernel(prec, n_img, n):
     """csrc/conv_igemm.hip conv_pw64_kernel (layer1.0's conv1, model/resnet_cubic.py:88-90: 1x1, 64 -> 64, + bn1 + relu): the
     filter in a wave's registers, 16-pixel blocks streamed from global memory.  Against torch-CPU on identically rounded
-    operands in both traversal orders, and bit for bit against the generic 64 x 256-tile kernel on the same launch (a child
-    process with CP360_PW64=0: the switch is read once per process); 6 x 27 x 27 pixels: a ragged last block."""
-    import subprocess
-    import sys
+    operands in both traversal orders, and bit for bit against the generic 64 x 256-tile kernel on the same launch (forced by
+    tile_px 256); 6 x 27 x 27 pixels: a ragged last block."""
     outs = []
     for order in (0, 1):
         got, want = _pw64_case(prec, n_img, n, order)
         assert rel_err(got.float().numpy(), want.numpy()) <= _TOL[prec]
         outs.append(got)
     assert torch.equal(outs[0], outs[1])                          # the traversal order never changes a result
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    f = str(tmp_path / 'generic.pt')
-    code = ("import torch; from tests import test_gpu_parity as t; "
-            "torch.save(t._pw64_case(%r, %d, %d, 0)[0], %r)" % (prec, n_img, n, f))
-    e = dict(os.environ, CP360_PW64='0')
-    e['PYTHONPATH'] = root + os.pathsep + e.get('PYTHONPATH', '')
-    r = subprocess.run([sys.executable, '-c', code], cwd=root, env=e, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert torch.equal(outs[0], torch.load(f))
+    assert torch.equal(outs[0], _pw64_case(prec, n_img, n, 0, tile_px=256)[0])
 
 
 @pytest.mark.parametrize('prec', ['bf16', 'fp16'])
@@ -966,8 +957,7 @@ def test_stem_pool_fused_kernel_bit_exact(prec, order):
     """csrc/stem.hip stem_pool4_kernel (round 6: two 4-wave workgroups per CU, 4 stem rows per band; + stem_pool_fix_kernel): stem
     conv + BN + ReLU -> CubePad(1) -> max-pool 3x3 s2 in one kernel at cube 224 must equal the two-kernel path (resident stem,
     then cubepad_maxpool3s2) bit for bit - the same MFMA order per output and maxima of identical values; 12 faces (every band of
-    a face in its own workgroup) and 300 faces (8400 band tiles on 512 persistent workgroups, several cubes), both launch orders.
-    The 8-wave form of rounds 2-5 (CP360_STEM_POOL=8, read once per process): test_stem_pool_8wave_form_bit_exact."""
+    a face in its own workgroup) and 300 faces (8400 band tiles on 512 persistent workgroups, several cubes), both launch orders."""
     dt = _TDT[prec]
     w = hashrng.normal(9641, (64, 3, 7, 7), 0, (2.0 / (49 * 64)) ** 0.5)
     scale = hashrng.uniform(9642, (64,), 0.5, 1.5)
@@ -988,19 +978,6 @@ def test_stem_pool_fused_kernel_bit_exact(prec, order):
         assert got is not None and got.shape == want.shape == (n_img, 56, 56, 64)
         assert torch.equal(got.view(torch.int16), want.view(torch.int16)), \
             int((got.view(torch.int16) != want.view(torch.int16)).sum())
-
-
-def test_stem_pool_8wave_form_bit_exact():
-    """CP360_STEM_POOL=8: stem_pool_kernel (one 8-wave workgroup per CU, double-buffered patch) stays buildable for A/B and must give
-    the same bits - the test above in a child process with the switch set."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = "from tests import test_gpu_parity as t; t.test_stem_pool_fused_kernel_bit_exact('fp16', 0); t.test_stem_pool_fused_kernel_bit_exact('bf16', 1)"
-    e = dict(os.environ, CP360_STEM_POOL='8')
-    e['PYTHONPATH'] = root + os.pathsep + e.get('PYTHONPATH', '')
-    r = subprocess.run([sys.executable, '-c', code], cwd=root, env=e, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
 
 
 @pytest.mark.parametrize('prec', ['bf16', 'fp16'])

@@ -1,5 +1,5 @@
 """K1 (equi2cube, 64 frames 1024x2048 u8 -> padded f16 faces) alone, a few launches: for rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
-passes with the CP360_E2C_FU / CP360_E2C_CAP switches.  Prints the HIP-event time per launch.
+passes.  Prints the HIP-event time per launch.
 
 Under the profiler put the interpreter itself after ``--`` (never ``env``, a shell or this file as an executable: the profiler's
 preloaded library has initialised the GPU by then and such a hop is an exec the pool forbids):
@@ -22,4 +22,4 @@ a.record()
 for _ in range(5):
     y = e2c.to_cube_batch(frames, out_dtype=torch.float16, layout='nhwc4p3')
 b.record(); torch.cuda.synchronize()
-print('K1 FU=%s CAP=%s: %.1f us per launch' % (os.environ.get('CP360_E2C_FU', '4'), os.environ.get('CP360_E2C_CAP', '64'), a.elapsed_time(b) * 200))
+print('K1: %.1f us per launch' % (a.elapsed_time(b) * 200))
