@@ -26,7 +26,7 @@ def precision_dtype(precision):
         raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
 OK = 0
 # must equal CP360_VERSION of include/cp360.h (checked against the loaded library in lib())
-ABI_VERSION = 305
+ABI_VERSION = 306
 
 
 # every exported symbol of include/cp360.h - the documented boundary (checked by tests/test_abi.py)
@@ -46,6 +46,10 @@ PUBLIC_SYMBOLS = [
     'cp360_conv_plan_describe', 'cp360_resnet_plan_describe', 'cp360_wino_packed_bytes', 'cp360_wino_v_bytes',
     'cp360_wino_m_bytes', 'cp360_wino_preferred', 'cp360_wino_pack_weights', 'cp360_wino_input', 'cp360_wino_gemm',
     'cp360_wino_output', 'cp360_wino_output_gates', 'cp360_wino_forward', 'cp360_wino_output_input', 'cp360_clstm_wino_state', 'cp360_clstm_load_wino',
+    # K5t: ConvLSTM training
+    'cp360_train_gates', 'cp360_train_gates_backward', 'cp360_train_dgrad_packed_bytes', 'cp360_train_dgrad_pack',
+    'cp360_train_dgrad', 'cp360_train_cubepad_inverse_host', 'cp360_train_cubepad_adjoint', 'cp360_train_wgrad',
+    'cp360_train_saliency_forward', 'cp360_train_c2e_inverse_host', 'cp360_train_saliency_backward',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -208,6 +212,18 @@ def lib():
     L.cp360_wino_gemm_raw.argtypes = [i, vp, vp, vp, i, i, i, i, i, vp]
     L.cp360_clstm_wino_state.argtypes = [vp, i, i]
     L.cp360_clstm_load_wino.argtypes = [vp, vp, vp, vp, vp]
+    L.cp360_train_gates.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp, vp, i, i, vp]
+    L.cp360_train_gates_backward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
+    L.cp360_train_dgrad_packed_bytes.restype = sz
+    L.cp360_train_dgrad_packed_bytes.argtypes = [i, i, i]
+    L.cp360_train_dgrad_pack.argtypes = [i, vp, i, i, i, i, vp, vp]
+    L.cp360_train_dgrad.argtypes = [i, vp, i, i, i, vp, i, vp, vp]
+    L.cp360_train_cubepad_inverse_host.argtypes = [i, vp, vp]
+    L.cp360_train_cubepad_adjoint.argtypes = [vp, vp, vp, i, i, i, vp, i, i, i, vp, i, i, vp]
+    L.cp360_train_wgrad.argtypes = [i, vp, vp, i, vp, i, i, i, i, vp, vp, i, vp]
+    L.cp360_train_saliency_forward.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
+    L.cp360_train_c2e_inverse_host.argtypes = [vp, vp, i, vp, vp]
+    L.cp360_train_saliency_backward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

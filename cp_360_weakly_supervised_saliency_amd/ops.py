@@ -945,3 +945,159 @@ def held_clock_ghz(device='cuda', ms=6.0, launches=3):
         return None
     ghz = 0.1 * s[ok, 0] / s[ok, 1]
     return round(float(ghz.median()), 4)
+
+
+# ----------------------------------------------------------------------------- K5t: ConvLSTM training
+_TRAIN_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _train_dtype(dt):
+    if dt not in _TRAIN_DTYPES:
+        raise ValueError("ConvLSTM training runs in f32 or bf16 operands (got %s)" % dt)
+    return dtype_code(dt)
+
+
+def train_gates(partial, splits, bias, c_prev, c_next, h_out, h_coff, h_f32, acts, M, Hc):
+    """cp360_train_gates: lstm_gates on plain [splits, M, 4 Hc] slabs that also keeps the activated gates acts f32 [M, 4 Hc]."""
+    require_gpu(partial, bias, c_prev, c_next, h_out, h_f32, acts)
+    _check_buf('gates partial', partial, torch.float32, numel=splits * M * 4 * Hc)
+    _check_buf('gates bias', bias, torch.float32, numel=4 * Hc)
+    for name, t, n in (('c_prev', c_prev, M * Hc), ('c_next', c_next, M * Hc), ('h_f32', h_f32, M * Hc), ('acts', acts, M * 4 * Hc)):
+        _check_buf(name, t, torch.float32, numel=n)
+    if not h_out.is_contiguous() or h_out.numel() < M * h_out.shape[-1] or h_coff + Hc > h_out.shape[-1]:
+        raise ValueError("h_out must be contiguous [.., ld] with M pixels and h_coff + Hc <= ld")
+    check(lib().cp360_train_gates(ptr(partial), splits, ptr(bias), ptr(c_prev), ptr(c_next), ptr(h_out),
+                                  _train_dtype(h_out.dtype), h_out.shape[-1], h_coff, ptr(h_f32), ptr(acts), M, Hc, stream()))
+
+
+def train_gates_backward(dh, dc, acts, c_prev, c_next, dgates, M, Hc):
+    """cp360_train_gates_backward: dgates [M, 4 Hc] (compute dtype) from dh, dc; dc becomes d c_prev in place."""
+    require_gpu(dh, dc, acts, c_prev, c_next, dgates)
+    for name, t, n in (('dh', dh, M * Hc), ('dc', dc, M * Hc), ('acts', acts, M * 4 * Hc), ('c_prev', c_prev, M * Hc),
+                       ('c_next', c_next, M * Hc)):
+        _check_buf(name, t, torch.float32, numel=n)
+    _check_buf('dgates', dgates, dgates.dtype, numel=M * 4 * Hc)
+    check(lib().cp360_train_gates_backward(ptr(dh), ptr(dc), ptr(acts), ptr(c_prev), ptr(c_next), ptr(dgates),
+                                           _train_dtype(dgates.dtype), M, Hc, stream()))
+
+
+def cubepad_inverse(face):
+    """Host int32 (offsets [6 face^2 + 1], entries [6 (face+2)^2]): the padded positions of CubePad(1) that copy each source
+    pixel of a cube, ascending (cp360_train_cubepad_inverse_host, no GPU needed)."""
+    off = np.empty(6 * face * face + 1, dtype=np.int32)
+    ent = np.empty(6 * (face + 2) * (face + 2), dtype=np.int32)
+    check(lib().cp360_train_cubepad_inverse_host(int(face), off.ctypes.data_as(C.c_void_p), ent.ctypes.data_as(C.c_void_p)))
+    return off, ent
+
+
+def c2e_inverse(face_map, coord, w):
+    """Host int32 (offsets [6 w^2 + 1], entries): the (output pixel << 2 | bilinear tap) pairs of cube -> equirectangular
+    sampling that read each cube pixel, ascending (cp360_train_c2e_inverse_host)."""
+    fm = np.ascontiguousarray(face_map, dtype=np.int8)
+    pc = np.ascontiguousarray(coord, dtype=np.float32)
+    if fm.shape != (2 * w, 4 * w) or pc.shape != (2 * w, 4 * w, 2):
+        raise ValueError("face_map [2w, 4w] and coord [2w, 4w, 2] expected")
+    off = np.empty(6 * w * w + 1, dtype=np.int32)
+    ent = np.empty(32 * w * w, dtype=np.int32)
+    n = lib().cp360_train_c2e_inverse_host(fm.ctypes.data_as(C.c_void_p), pc.ctypes.data_as(C.c_void_p), int(w),
+                                           off.ctypes.data_as(C.c_void_p), ent.ctypes.data_as(C.c_void_p))
+    check(min(n, 0))
+    return off, ent[:n].copy()
+
+
+class DgradPack:
+    """The dgrad operand of one CubePad(1) + 3x3 convolution: filter f32 [c_out, c_in, 3, 3], input channels [ci0, ci0 + n)
+    packed [n][9 c_out] in ``dtype`` (cp360_train_dgrad_pack).  Re-made by the owner when the weight's version changes."""
+
+    def __init__(self, weight, ci0, n, dtype):
+        require_gpu(weight)
+        self.c_out, self.c_in = int(weight.shape[0]), int(weight.shape[1])
+        if tuple(weight.shape[2:]) != (3, 3):
+            raise ValueError("a [c_out, c_in, 3, 3] filter")
+        self.ci0, self.n, self.dtype = int(ci0), int(n), dtype
+        L = lib()
+        code = _train_dtype(dtype)
+        nbytes = L.cp360_train_dgrad_packed_bytes(code, self.c_out, self.n)
+        self.packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        w = weight.detach().float().contiguous()
+        check(L.cp360_train_dgrad_pack(code, ptr(w), self.c_out, self.c_in, self.ci0, self.n, ptr(self.packed), stream()))
+
+    def dgrad(self, dy, dxpad=None):
+        """dy [n_img, face, face, c_out] -> f32 [n_img, face+2, face+2, n] (the full correlation onto the padded grid)."""
+        require_gpu(dy, dxpad)
+        n_img, face, _, co = dy.shape
+        if co != self.c_out or dy.dtype != self.dtype or not dy.is_contiguous():
+            raise ValueError("dy must be a contiguous %s [n_img, face, face, %d] tensor" % (self.dtype, self.c_out))
+        if dxpad is None:
+            dxpad = torch.empty((n_img, face + 2, face + 2, self.n), dtype=torch.float32, device=dy.device)
+        _check_buf('dxpad', dxpad, torch.float32, numel=n_img * (face + 2) ** 2 * self.n)
+        check(lib().cp360_train_dgrad(_train_dtype(self.dtype), ptr(dy), n_img, face, self.c_out, ptr(self.packed), self.n,
+                                      ptr(dxpad), stream()))
+        return dxpad
+
+
+def cubepad_adjoint(dxpad, inv_off, inv_ent, dx, act=None, act_coff=0, accumulate=False):
+    """cp360_train_cubepad_adjoint: dxpad f32 [n_img, face+2, face+2, n] -> dx [n_img, face, face, n] (written, or added
+    onto with accumulate), masked by (act > 0) when act [n_img, face, face, ld] is given."""
+    require_gpu(dxpad, inv_off, inv_ent, dx, act)
+    n_img, fp, _, n = dxpad.shape
+    face = fp - 2
+    _check_buf('dxpad', dxpad, torch.float32)
+    _check_buf('dx', dx, dx.dtype, (n_img, face, face, n))
+    if inv_off.dtype != torch.int32 or inv_ent.dtype != torch.int32 or inv_off.numel() != 6 * face * face + 1 \
+            or inv_ent.numel() != 6 * fp * fp:
+        raise ValueError("inverse table of a different face size")
+    act_ld = 0
+    if act is not None:
+        _check_buf('act', act, act.dtype)
+        if tuple(act.shape[:3]) != (n_img, face, face) or act_coff + n > act.shape[3]:
+            raise ValueError("act must be [n_img, face, face, >= act_coff + n]")
+        act_ld = act.shape[3]
+    check(lib().cp360_train_cubepad_adjoint(ptr(dxpad), ptr(inv_off), ptr(inv_ent), n_img, face, n, ptr(act),
+                                            0 if act is None else _train_dtype(act.dtype), act_ld, act_coff, ptr(dx),
+                                            _train_dtype(dx.dtype), int(bool(accumulate)), stream()))
+    return dx
+
+
+def conv_wgrad(dy, x, c_in, pad_table, dw, db=None, accumulate=False):
+    """cp360_train_wgrad: dy [n_img, face, face, c_out], x [n_img, face, face, ld >= c_in] (same dtype; n_img may stack
+    several steps) -> dw f32 [c_out, c_in, 3, 3] (+ db f32 [c_out]) of CubePad(1) + 3x3 convolution, in ONE launch."""
+    require_gpu(dy, x, pad_table, dw, db)
+    n_img, face, _, c_out = dy.shape
+    if dy.dtype != x.dtype or not dy.is_contiguous() or not x.is_contiguous() or tuple(x.shape[:3]) != (n_img, face, face) \
+            or x.shape[3] < c_in:
+        raise ValueError("dy / x must be contiguous, of one dtype and of the same [n_img, face, face] geometry")
+    if pad_table.dtype != torch.int32 or pad_table.numel() != 6 * (face + 2) ** 2:
+        raise ValueError("pad_table must be the int32 CubePad(1) table of the face size")
+    _check_buf('dw', dw, torch.float32, numel=c_out * c_in * 9)
+    _check_buf('db', db, torch.float32, numel=c_out)
+    check(lib().cp360_train_wgrad(_train_dtype(dy.dtype), ptr(dy), ptr(x), x.shape[3], ptr(pad_table), n_img, face, c_out,
+                                  c_in, ptr(dw), ptr(db), int(bool(accumulate)), stream()))
+
+
+def saliency_forward(h, face_map, coord, out_max, argmax):
+    """cp360_train_saliency_forward: h f32 [6B, w, w, C] -> map f32 [B, 2w, 4w] and its argmax channel (int32)."""
+    require_gpu(h, face_map, coord, out_max, argmax)
+    n6, w, _, Cc = h.shape
+    B = n6 // 6
+    _check_buf('h', h, torch.float32)
+    _check_buf('out_max', out_max, torch.float32, numel=B * 8 * w * w)
+    _check_buf('argmax', argmax, torch.int32, numel=B * 8 * w * w)
+    if n6 % 6 or face_map.dtype != torch.int8 or coord.dtype != torch.float32:
+        raise ValueError("h needs 6B faces, face_map int8 and coord f32")
+    check(lib().cp360_train_saliency_forward(ptr(h), ptr(face_map.contiguous()), ptr(coord.contiguous()), ptr(out_max),
+                                             ptr(argmax), B, Cc, w, stream()))
+
+
+def saliency_backward(dmap, argmax, coord, inv_off, inv_ent, dh):
+    """cp360_train_saliency_backward: ADD d(map) f32 [B, 2w, 4w] onto dh f32 [6B, w, w, C] through the argmax channel."""
+    require_gpu(dmap, argmax, coord, inv_off, inv_ent, dh)
+    n6, w, _, Cc = dh.shape
+    B = n6 // 6
+    _check_buf('dh', dh, torch.float32)
+    _check_buf('dmap', dmap, torch.float32, numel=B * 8 * w * w)
+    _check_buf('argmax', argmax, torch.int32, numel=B * 8 * w * w)
+    if inv_off.dtype != torch.int32 or inv_off.numel() != 6 * w * w + 1 or inv_ent.dtype != torch.int32:
+        raise ValueError("inverse table of a different face size")
+    check(lib().cp360_train_saliency_backward(ptr(dmap), ptr(argmax), ptr(coord.contiguous()), ptr(inv_off), ptr(inv_ent),
+                                              ptr(dh), B, Cc, w, stream()))

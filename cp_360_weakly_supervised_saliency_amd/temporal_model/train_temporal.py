@@ -1,0 +1,142 @@
+"""Weakly supervised ConvLSTM training from optical flow: /root/reference/temporal_model/train_temporal.py:24-193 with the
+reference's names.  The window's cell updates, saliency maps and their backward pass run in libcp360.so
+(``model.clstm_train``); the flow loss is a few small torch ops on the device (maps of 14 x 28 upsampled to the flow size),
+and its gradient reaches the kernels through autograd.
+
+Behaviour kept from the reference:
+  * min / max normalisation over the WHOLE batch - all clips, all frames (:74-82), not per window as in test_temporal;
+  * ``fscale = flow_h / flow.size(2)`` divides by the flow's WIDTH (:110-111): flow stored at the loss resolution
+    [flow_h, 2 flow_h] is multiplied by 0.5;
+  * ``upsample(mode='bilinear')`` and ``grid_sample`` with the align_corners defaults of torch >= 1.3 (False), while
+    ``generate_meshgrid`` uses the (h - 1) convention;
+  * the reference scales ``flow_buff`` entries in place (:128-129); each entry is used once, so that is harmless - here the
+    scaled flow is a new tensor.
+The reference resizes every flow with cv2.resize(INTER_CUBIC) to (2 flow_h, flow_h) (:112-113).  That resize is the identity
+for flow already at that size, the only size accepted here: anything else raises ValueError.
+"""
+import os
+import time
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..model.clstm_train import window_maps
+
+
+def generate_meshgrid(flow):
+    """flow [N, h, w, ...] -> [N, 2, h, w] f32: (x, y) in [-1, 1] on the (size - 1) grid (:24-30), on flow's device."""
+    h = flow.size(1)
+    w = flow.size(2)
+    y = torch.arange(0, h).unsqueeze(1).repeat(1, w) / (h - 1) * 2 - 1
+    x = torch.arange(0, w).unsqueeze(0).repeat(h, 1) / (w - 1) * 2 - 1
+    mesh_grid = torch.stack([x, y], 0).unsqueeze(0).repeat(flow.size(0), 1, 1, 1).to(flow.device)
+    return mesh_grid.float()
+
+
+def _stack(items):
+    return items if torch.is_tensor(items) else torch.stack(list(items), 1)
+
+
+def normalize_batch(seq):
+    """seq [B, T, 6, C, w, w] -> (seq - min) / max(seq - min), both over the whole batch (:74-85)."""
+    min_seq = seq.min()
+    max0min_seq = (seq - min_seq).max()
+    return (seq - min_seq) / max0min_seq
+
+
+def check_flow(flow, flow_h):
+    """flow [B, T, H_f, W_f, 2]: only the loss resolution (flow_h, 2 flow_h) is accepted (cv2.resize would be the identity)."""
+    if flow.dim() != 5 or flow.shape[-1] != 2:
+        raise ValueError("flow must be [B, T, H, W, 2], got %s" % (tuple(flow.shape),))
+    if tuple(flow.shape[2:4]) != (flow_h, 2 * flow_h):
+        raise ValueError("flow must already be at the loss resolution %dx%d (the reference's cv2.resize INTER_CUBIC to "
+                         "(2 flow_h, flow_h) is not reproduced), got %dx%d" % (flow_h, 2 * flow_h, flow.shape[2], flow.shape[3]))
+
+
+def flow_losses(maps, flow, cfg, tmp_loss_len=3, criterion=None):
+    """The three loss terms of :115-167.  maps [B, tmp_loss_len + 1, 2w, 4w]: the saliency maps of steps
+    seq_len - tmp_loss_len - 1 .. seq_len - 1; flow [B, T, flow_h, 2 flow_h, 2].  Returns (loss_sm, loss_temp, loss_mask)."""
+    criterion = criterion or nn.MSELoss(reduction='sum')
+    B = maps.shape[0]
+    flow_h = cfg.flow_h
+    check_flow(flow, flow_h)
+    first = cfg.seq_len - tmp_loss_len - 1
+    fscale = flow_h / float(flow.size(3))                      # flow[idx].size(2) of a [B, H, W, 2] tensor: the width
+    size = (flow.size(2), flow.size(3))
+    mesh_grid = generate_meshgrid(flow[0, 0].unsqueeze(0)).permute(0, 2, 3, 1)
+    loss_sm = loss_temp = loss_mask = None
+    for i_b in range(B):
+        for fidx in range(tmp_loss_len):
+            tmp_flow = (fscale * flow[i_b, first + fidx]).unsqueeze(0)
+            motion_mask = torch.sqrt(tmp_flow[0, :, :, 0] ** 2 + tmp_flow[0, :, :, 1] ** 2) < cfg.mm_th
+            tmp_feat = F.interpolate(maps[i_b, fidx][None, None], size=size, mode='bilinear', align_corners=False)
+            tmp_feat_next = F.interpolate(maps[i_b, fidx + 1][None, None], size=size, mode='bilinear', align_corners=False)
+            tmp_flow = torch.stack([tmp_flow[..., 0] / tmp_feat.size()[3] * 2, tmp_flow[..., 1] / tmp_feat.size()[2] * 2], -1)
+            tmp_grid = tmp_flow + mesh_grid
+            warp_prediction = F.grid_sample(tmp_feat, tmp_grid, align_corners=False).detach()
+            tmp_feat_val = tmp_feat.detach()
+            tmp_feat_val_mask = tmp_feat_next.detach().clone()
+            tmp_feat_val_mask[:, :, motion_mask] = 0
+            terms = (criterion(tmp_feat_next, warp_prediction), criterion(tmp_feat_next, tmp_feat_val),
+                     criterion(tmp_feat_next, tmp_feat_val_mask))
+            if loss_sm is None:
+                loss_sm, loss_temp, loss_mask = terms
+            else:
+                loss_sm, loss_temp, loss_mask = loss_sm + terms[0], loss_temp + terms[1], loss_mask + terms[2]
+    return loss_sm, loss_temp, loss_mask
+
+
+def train_step(cell, seq, flow, optimizer, cfg, tmp_loss_len=3, criterion=None):
+    """One iteration of train() on one batch: seq = T tensors [B, 6, C, w, w] (or [B, T, 6, C, w, w]), flow = T tensors
+    [B, flow_h, 2 flow_h, 2] (or [B, T, ...]).  Normalise, forward, loss, ``optimizer.zero_grad(); loss.backward();
+    optimizer.step()``.  Returns the three loss terms (loss_sm, loss_temp, loss_mask) as detached tensors."""
+    dev = cell.Conv1.weight.device
+    seq = _stack(seq).to(dev, torch.float32)
+    flow = _stack(flow).to(dev, torch.float32)
+    if seq.dim() != 6 or seq.shape[2] != 6:
+        raise ValueError("seq must be T tensors [B, 6, C, w, w]")
+    B, T, _, C, w, _ = seq.shape
+    if T != cfg.seq_len or flow.shape[1] != T:
+        raise ValueError("seq / flow must hold seq_len = %d frames" % cfg.seq_len)
+    if not 0 <= cfg.seq_len - tmp_loss_len - 1:
+        raise ValueError("tmp_loss_len must be < seq_len")
+    check_flow(flow, cfg.flow_h)
+    frames = normalize_batch(seq).permute(0, 1, 2, 4, 5, 3).reshape(B, T, 6 * w * w, C).contiguous()
+    first = cfg.seq_len - tmp_loss_len - 1
+    maps = window_maps(cell, frames, range(first, T))
+    loss_sm, loss_temp, loss_mask = flow_losses(maps, flow, cfg, tmp_loss_len, criterion)
+    loss = cfg.l_s * loss_sm + cfg.l_t * loss_temp + cfg.l_m * loss_mask
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss_sm.detach(), loss_temp.detach(), loss_mask.detach()
+
+
+def train(train_loader, model, criterion, optimizer, epoch, out_model_path, init_iter, cfg, tmp_loss_len=3):
+    """Train the temporal model for one epoch (:33-193): checkpoints 'CLSTM_[epoch]_[iteration].pth' every save_freq."""
+    assert cfg.use_gpu
+    model.train()
+    batch_time = 0.0
+    running_loss = 0.0
+    for i, (seq, flow, _, _) in enumerate(train_loader):
+        ttime = time.time()
+        i += init_iter
+        if i > len(train_loader) + 1:
+            break
+        loss_sm, loss_temp, loss_mask = train_step(model, seq, flow, optimizer, cfg, tmp_loss_len, criterion)
+        loss = cfg.l_s * loss_sm + cfg.l_t * loss_temp + cfg.l_m * loss_mask
+        if i % cfg.summary_freq == (cfg.summary_freq - 1):
+            print("Smooth loss: {0:.3f}, Tmp loss: {1:.3f}, MMask loss: {2:.3f}".format(cfg.l_s * loss_sm.item(),
+                                                                                        cfg.l_t * loss_temp.item(),
+                                                                                        cfg.l_m * loss_mask.item()))
+        batch_time += time.time() - ttime
+        running_loss += loss.item()
+        if i % cfg.summary_freq == (cfg.summary_freq - 1):
+            print("Epoch: [{}][{}/{}]\t Loss (avg.): {:.3f}\t Batch Time (avg.):{:.3f}".format(epoch,
+                  i + 1, len(train_loader), running_loss / cfg.summary_freq, batch_time / cfg.summary_freq))
+            batch_time = 0.0
+            running_loss = 0.0
+        if i % cfg.save_freq == (cfg.save_freq - 1):
+            print(os.path.join(out_model_path, 'CLSTM_{0:02}_{1:06}.pth'.format(epoch, i)))
+            torch.save(model.state_dict(), os.path.join(out_model_path, 'CLSTM_{0:02}_{1:06}.pth'.format(epoch, i)))

@@ -53,7 +53,7 @@ const char* cp360_strerror(int status);
 /* library / ABI version: major*10000 + minor*100 + patch.  Bumped on EVERY change of a struct, a
  * signature or a packed-weight layout: the binding (_lib.py: ABI_VERSION) refuses a library whose
  * version or sizeof(cp360_conv_desc) differs, so a stale out-of-band .so fails at load time. */
-#define CP360_VERSION 305
+#define CP360_VERSION 306
 int cp360_version(void);
 /* sizeof(cp360_conv_desc) as the library was compiled. */
 size_t cp360_conv_desc_bytes(void);
@@ -280,6 +280,52 @@ int cp360_lstm_gates_next(const float* gates_partial, int splits, const float* b
                           int ld_h, int h_coff, float* h_f32, int M, int Hc, int slab_rows,
                           const float* x_next, const float* minmax, int x_coff, int P, size_t clip_stride,
                           void* stream);
+
+/* ------------------------------------------------------------------ K5t: ConvLSTM training
+ * The backward pass of one cell update (model/clstm.py:54-80) and of the saliency map (to_equi_nn + channel max), for
+ * temporal_model/train_temporal.py.  Operand dtypes: CP360_F32 or CP360_BF16 (GEMM operands / activations); accumulation,
+ * cell state, gate activations and every gradient of a parameter are f32.  Each gradient element is written by one thread
+ * in a fixed order: results are bit-reproducible.  M = pixels = n_img * face^2, n_img = 6 * clips, Hc = hidden channels.
+ *
+ * Forward gate epilogue: cp360_lstm_gates (plain slabs, slab_rows 0) that also keeps acts f32 [M, 4 Hc]: the activated gates
+ * in|remember|out|cell (clstm.py:68-76) for the backward pass. */
+int cp360_train_gates(const float* gates_partial, int splits, const float* bias, const float* c_prev, float* c_next,
+                      void* h_out, int h_dtype, int ld_h, int h_coff, float* h_f32, float* acts, int M, int Hc, void* stream);
+/* dh f32 [M, Hc] (d hidden_t), dc f32 [M, Hc] (in: d cell_t from step t+1, out: d cell_{t-1}), acts / c_prev / c_next as saved
+ * by cp360_train_gates  ->  dgates [M, 4 Hc] (dtype dg_dtype): the gradient of the Gates convolution's output. */
+int cp360_train_gates_backward(const float* dh, float* dc, const float* acts, const float* c_prev, const float* c_next,
+                               void* dgates, int dg_dtype, int M, int Hc, void* stream);
+/* Data gradient ("dgrad") of CubePad(1) + 3x3 convolution, in two launches.  The filter f32 OIHW [c_out, c_in, 3, 3] is packed
+ * once per weight version for input channels [ci0, ci0 + n): packed [n][9 c_out] (k = tap * c_out + co).
+ * cp360_train_dgrad: dy [n_img, face, face, c_out] -> dxpad f32 [n_img, face+2, face+2, n], the "full" correlation onto the
+ * zero-padded grid.  cp360_train_cubepad_adjoint then sums each padded position onto its CubePad source (a gather over the
+ * inverse table of cp360_train_cubepad_inverse_host: offsets [6 face^2 + 1], entries [6 (face+2)^2] = padded positions of
+ * one cube, ascending), masks with (act > 0) when act (dtype act_dtype: F32 or dx_dtype, [.., act_ld], channels from
+ * act_coff) is given, and writes (accumulate 0) or adds onto (1) dx [n_img, face, face, n] of dtype dx_dtype. */
+size_t cp360_train_dgrad_packed_bytes(int dtype, int c_out, int n);
+int cp360_train_dgrad_pack(int dtype, const float* w, int c_out, int c_in, int ci0, int n, void* packed, void* stream);
+int cp360_train_dgrad(int dtype, const void* dy, int n_img, int face, int c_out, const void* packed, int n, float* dxpad,
+                      void* stream);
+int cp360_train_cubepad_inverse_host(int face, int32_t* offsets, int32_t* entries);
+int cp360_train_cubepad_adjoint(const float* dxpad, const int32_t* offsets, const int32_t* entries, int n_img, int face, int n,
+                                const void* act, int act_dtype, int act_ld, int act_coff, void* dx, int dx_dtype,
+                                int accumulate, void* stream);
+/* Weight gradient ("wgrad"), ONE launch for all steps: dy [n_img, face, face, c_out] and x [n_img, face, face, ldx] (channels
+ * [0, c_in) are the convolution's input) of the same dtype, n_img = steps * 6 * clips; pad_table int32 [6, face+2, face+2]
+ * = cp360_cubepad_table_host(face, 1, 1, 1, 1) on the device.  dw f32 OIHW [c_out, c_in, 3, 3] = sum dy * CubePad(x), db f32
+ * [c_out] = sum dy (NULL: not computed); written (accumulate 0) or added onto (1). */
+int cp360_train_wgrad(int dtype, const void* dy, const void* x, int ldx, const int32_t* pad_table, int n_img, int face,
+                      int c_out, int c_in, float* dw, float* db, int accumulate, void* stream);
+/* Saliency map of the hidden state h f32 [6B, w, w, C] (NHWC) as cp360_cube2equi(want_max) plus the argmax channel per output
+ * pixel (int32 [B, 2w, 4w]; ties: the lowest channel, as torch.max on the CPU), and its backward: dmap f32 [B, 2w, 4w] is
+ * ADDED onto dh f32 [6B, w, w, C] through the argmax channel and the bilinear taps (zero padding), a gather over the inverse
+ * table of cp360_train_c2e_inverse_host (offsets [6 w^2 + 1], entries [32 w^2] = output pixel << 2 | tap; returns the number
+ * of entries or a negative status). */
+int cp360_train_saliency_forward(const float* h, const int8_t* face_map, const float* coord, float* out_max, int32_t* argmax,
+                                 int B, int C, int w, void* stream);
+int cp360_train_c2e_inverse_host(const int8_t* face_map, const float* coord, int w, int32_t* offsets, int32_t* entries);
+int cp360_train_saliency_backward(const float* dmap, const int32_t* argmax, const float* coord, const int32_t* offsets,
+                                  const int32_t* entries, float* dh, int B, int C, int w, void* stream);
 
 /* ------------------------------------------------------------------ K5w: CubePad(1) + 3x3 convolution in the Winograd domain
  * The three ConvLSTM convolutions of model/clstm.py:56-64 as F(2x2, 3x3) for the 16-bit types: a w x w face is cut into
