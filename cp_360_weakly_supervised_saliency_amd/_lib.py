@@ -50,6 +50,9 @@ PUBLIC_SYMBOLS = [
     'cp360_train_gates', 'cp360_train_gates_backward', 'cp360_train_dgrad_packed_bytes', 'cp360_train_dgrad_pack',
     'cp360_train_dgrad', 'cp360_train_cubepad_inverse_host', 'cp360_train_cubepad_adjoint', 'cp360_train_wgrad',
     'cp360_train_saliency_forward', 'cp360_train_c2e_inverse_host', 'cp360_train_saliency_backward',
+    # K5f: flow resize and flow loss
+    'cp360_flow_resize_coeffs_host', 'cp360_flow_resize', 'cp360_flow_loss_work_bytes', 'cp360_flow_loss_forward',
+    'cp360_flow_loss_backward',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -224,6 +227,12 @@ def lib():
     L.cp360_train_saliency_forward.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
     L.cp360_train_c2e_inverse_host.argtypes = [vp, vp, i, vp, vp]
     L.cp360_train_saliency_backward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
+    L.cp360_flow_resize_coeffs_host.argtypes = [i, i, vp, vp]
+    L.cp360_flow_resize.argtypes = [i, vp, i, i, i, vp, i, i, vp, vp, vp, vp, f, vp]
+    L.cp360_flow_loss_work_bytes.restype = sz
+    L.cp360_flow_loss_work_bytes.argtypes = [i, i, i, i, i]
+    L.cp360_flow_loss_forward.argtypes = [i, vp, vp, i, i, i, i, i, f, vp, vp, vp]
+    L.cp360_flow_loss_backward.argtypes = [i, vp, vp, vp, i, i, i, i, i, f, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

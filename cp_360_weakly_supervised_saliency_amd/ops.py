@@ -1101,3 +1101,91 @@ def saliency_backward(dmap, argmax, coord, inv_off, inv_ent, dh):
         raise ValueError("inverse table of a different face size")
     check(lib().cp360_train_saliency_backward(ptr(dmap), ptr(argmax), ptr(coord.contiguous()), ptr(inv_off), ptr(inv_ent),
                                               ptr(dh), B, Cc, w, stream()))
+
+
+# ----------------------------------------------------------------------------- K5f: flow resize and flow loss
+def flow_resize_coeffs(in_size, out_size):
+    """Host tables of one axis of cv2.resize(INTER_CUBIC) (cp360_flow_resize_coeffs_host, no GPU needed): first-tap index + 1
+    int32 [out_size] and the four Keys coefficients f32 [out_size, 4]."""
+    ofs = np.empty(int(out_size), dtype=np.int32)
+    coef = np.empty((int(out_size), 4), dtype=np.float32)
+    check(lib().cp360_flow_resize_coeffs_host(int(in_size), int(out_size), ofs.ctypes.data_as(C.c_void_p),
+                                              coef.ctypes.data_as(C.c_void_p)))
+    return ofs, coef
+
+
+_FLOW_TABLES = {}
+
+
+def _flow_tables(in_size, out_size, dev):
+    key = (int(in_size), int(out_size), str(dev))
+    t = _FLOW_TABLES.get(key)
+    if t is None:
+        ofs, coef = flow_resize_coeffs(in_size, out_size)
+        t = _FLOW_TABLES[key] = (torch.from_numpy(ofs).to(dev), torch.from_numpy(coef).to(dev))
+    return t
+
+
+def flow_resize(flow, h_out, w_out, fscale, out=None):
+    """cp360_flow_resize: f32 [..., h_in, w_in, 2] on the GPU -> cv2.resize(INTER_CUBIC) to [..., h_out, w_out, 2] times fscale
+    (equal sizes: the scale alone, as cv2 copies)."""
+    require_gpu(flow, out)
+    if flow.dim() < 3 or flow.shape[-1] != 2:
+        raise ValueError("flow must be [..., H, W, 2], got %s" % (tuple(flow.shape),))
+    lead = tuple(flow.shape[:-3])
+    h_in, w_in = int(flow.shape[-3]), int(flow.shape[-2])
+    F = int(np.prod(lead)) if lead else 1
+    _check_buf('flow', flow, torch.float32)
+    if out is None:
+        out = torch.empty(lead + (int(h_out), int(w_out), 2), dtype=torch.float32, device=flow.device)
+    _check_buf('out', out, torch.float32, numel=F * h_out * w_out * 2)
+    if (h_in, w_in) == (h_out, w_out):
+        yo = yc = xo = xc = None
+    else:
+        yo, yc = _flow_tables(h_in, h_out, flow.device)
+        xo, xc = _flow_tables(w_in, w_out, flow.device)
+    check(lib().cp360_flow_resize(_lib.F32, ptr(flow), F, h_in, w_in, ptr(out), int(h_out), int(w_out), ptr(yo), ptr(yc),
+                                  ptr(xo), ptr(xc), float(fscale), stream()))
+    return out
+
+
+def _flow_loss_geometry(maps, flow):
+    if maps.dim() != 4 or flow.dim() != 5 or flow.shape[-1] != 2:
+        raise ValueError("maps must be [B, L + 1, 2w, 4w] and flow [B, L, H, W, 2]")
+    B, n, mh, mw = (int(s) for s in maps.shape)
+    L, h, wl = int(flow.shape[1]), int(flow.shape[2]), int(flow.shape[3])
+    w = mh // 2
+    if flow.shape[0] != B or n != L + 1 or mh != 2 * w or mw != 4 * w:
+        raise ValueError("maps %s and flow %s disagree: maps must be [B, L + 1, 2w, 4w] for flow [B, L, H, W, 2]"
+                         % (tuple(maps.shape), tuple(flow.shape)))
+    _check_buf('maps', maps, torch.float32)
+    _check_buf('flow', flow, torch.float32)
+    nbytes = lib().cp360_flow_loss_work_bytes(B, L, w, h, wl)
+    if nbytes == 0:
+        raise ValueError("flow loss: unsupported geometry (faces up to 16 x 16, flow of at least 2 x 2): maps %s, flow %s"
+                         % (tuple(maps.shape), tuple(flow.shape)))
+    return B, L, w, h, wl, nbytes
+
+
+def flow_loss_forward(maps, flow, mm_th):
+    """cp360_flow_loss_forward: maps f32 [B, L + 1, 2w, 4w], scaled flow f32 [B, L, H, W, 2] -> f32 [3] (smooth, temporal,
+    motion-mask sum-MSE terms over all B x L pairs)."""
+    require_gpu(maps, flow)
+    B, L, w, h, wl, nbytes = _flow_loss_geometry(maps, flow)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=maps.device)
+    loss = torch.empty(3, dtype=torch.float32, device=maps.device)
+    check(lib().cp360_flow_loss_forward(_lib.F32, ptr(maps), ptr(flow), B, L, w, h, wl, float(mm_th), ptr(loss), ptr(work),
+                                        stream()))
+    return loss
+
+
+def flow_loss_backward(maps, flow, grad_loss, mm_th):
+    """cp360_flow_loss_backward: grad_loss f32 [3] (device) -> dmaps f32 [B, L + 1, 2w, 4w] (map 0 of each clip: zero)."""
+    require_gpu(maps, flow, grad_loss)
+    B, L, w, h, wl, nbytes = _flow_loss_geometry(maps, flow)
+    _check_buf('grad_loss', grad_loss, torch.float32, numel=3)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=maps.device)
+    dmaps = torch.empty_like(maps)
+    check(lib().cp360_flow_loss_backward(_lib.F32, ptr(maps), ptr(flow), ptr(grad_loss), B, L, w, h, wl, float(mm_th),
+                                         ptr(dmaps), ptr(work), stream()))
+    return dmaps

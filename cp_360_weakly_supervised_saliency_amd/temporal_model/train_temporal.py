@@ -1,27 +1,31 @@
-"""Weakly supervised ConvLSTM training from optical flow: /root/reference/temporal_model/train_temporal.py:24-193 with the
+"""Weakly supervised ConvLSTM training from optical flow: the reference's temporal_model/train_temporal.py:24-193 with the
 reference's names.  The window's cell updates, saliency maps and their backward pass run in libcp360.so
-(``model.clstm_train``); the flow loss is a few small torch ops on the device (maps of 14 x 28 upsampled to the flow size),
-and its gradient reaches the kernels through autograd.
+(``model.clstm_train``); so do the flow resize and the flow loss with its backward pass (``resize_flow``,
+``device_flow_losses``: csrc/flow_loss.hip), whose gradient reaches the window's kernels through autograd.
 
 Behaviour kept from the reference:
   * min / max normalisation over the WHOLE batch - all clips, all frames (:74-82), not per window as in test_temporal;
-  * ``fscale = flow_h / flow.size(2)`` divides by the flow's WIDTH (:110-111): flow stored at the loss resolution
-    [flow_h, 2 flow_h] is multiplied by 0.5;
+  * every flow the loss reads is resized with cv2.resize(INTER_CUBIC) to (2 flow_h, flow_h) (:112-113) - OpenCV's generic
+    float path restated in HIP; cv2 copies at equal sizes - and multiplied by ``fscale = flow_h / W`` of the ORIGINAL flow
+    (:110-111): it divides by the flow's WIDTH, so flow stored at the loss resolution [flow_h, 2 flow_h] is multiplied by 0.5;
   * ``upsample(mode='bilinear')`` and ``grid_sample`` with the align_corners defaults of torch >= 1.3 (False), while
     ``generate_meshgrid`` uses the (h - 1) convention;
   * the reference scales ``flow_buff`` entries in place (:128-129); each entry is used once, so that is harmless - here the
     scaled flow is a new tensor.
-The reference resizes every flow with cv2.resize(INTER_CUBIC) to (2 flow_h, flow_h) (:112-113).  That resize is the identity
-for flow already at that size, the only size accepted here: anything else raises ValueError.
+Flow of any [H, W] is accepted; only the tmp_loss_len flows the loss reads are copied to the device.  ``flow_losses`` is the torch
+restatement of the loss at the loss resolution (flow already [flow_h, 2 flow_h]): the reference for the HIP loss, and the path
+``train_step`` takes for a criterion other than the reference's sum-MSE.
 """
 import os
 import time
+import types
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..model.clstm_train import window_maps
+from .. import ops
+from ..model.clstm_train import trainer_of, window_maps
 
 
 def generate_meshgrid(flow):
@@ -87,25 +91,121 @@ def flow_losses(maps, flow, cfg, tmp_loss_len=3, criterion=None):
     return loss_sm, loss_temp, loss_mask
 
 
+def resize_flow(flow, flow_h):
+    """The reference's :110-113 on the device: flow f32 [..., H, W, 2] (a GPU tensor) -> cv2.resize(flow, (2 flow_h, flow_h),
+    INTER_CUBIC) * (flow_h / W), f32 [..., flow_h, 2 flow_h, 2].  OpenCV's generic float path (csrc/flow_loss.hip); cv2 itself
+    is not pinned by the tests, which check a restatement of that path (as for the cv2.remap of SURVEY a2): an IPP build of
+    OpenCV may differ in the last bits."""
+    if flow.dim() < 3 or flow.shape[-1] != 2:
+        raise ValueError("flow must be [..., H, W, 2], got %s" % (tuple(flow.shape),))
+    fscale = flow_h / float(flow.shape[-2])
+    return ops.flow_resize(flow.contiguous(), int(flow_h), 2 * int(flow_h), fscale)
+
+
+class DeviceFlowLoss(torch.autograd.Function):
+    """(loss_sm, loss_temp, loss_mask) = DeviceFlowLoss.apply(maps, flow_scaled, mm_th, events): the three sum-MSE terms of
+    ``flow_losses`` over all B x tmp_loss_len pairs in HIP (cp360_flow_loss_forward / _backward).  The gradient reaches maps only
+    (map fidx + 1 of each pair); the backward recomputes the residuals from the maps and the flow."""
+
+    @staticmethod
+    def forward(ctx, maps, flow_scaled, mm_th, events):
+        maps = maps.detach().float().contiguous()
+        flow_scaled = flow_scaled.detach().contiguous()
+        _mark(events, 'loss')
+        loss = ops.flow_loss_forward(maps, flow_scaled, mm_th)
+        _mark(events, 'loss_end')
+        ctx.save_for_backward(maps, flow_scaled)
+        ctx.mm_th, ctx.events = mm_th, events
+        return loss[0], loss[1], loss[2]
+
+    @staticmethod
+    def backward(ctx, g_sm, g_t, g_m):
+        maps, flow_scaled = ctx.saved_tensors
+        z = lambda g: torch.zeros((), dtype=torch.float32, device=maps.device) if g is None else g.float().reshape(())
+        _mark(ctx.events, 'loss_bwd')
+        dmaps = ops.flow_loss_backward(maps, flow_scaled, torch.stack([z(g_sm), z(g_t), z(g_m)]).contiguous(), ctx.mm_th)
+        _mark(ctx.events, 'loss_bwd_end')
+        return dmaps, None, None, None
+
+
+def _mark(events, name):
+    """Measurement hook (tools/train_bench.py, never set in training): (phase, HIP event) pairs on the launch stream."""
+    if events is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        events.append((name, e))
+
+
+def device_flow_losses(maps, flow_scaled, cfg, tmp_loss_len=3, events=None):
+    """``flow_losses`` in HIP: maps f32 [B, tmp_loss_len + 1, 2w, 4w] (the saliency maps of steps seq_len - tmp_loss_len - 1
+    .. seq_len - 1, on the GPU), flow_scaled f32 [B, tmp_loss_len, H, W, 2] = ``resize_flow`` of the flows of steps
+    seq_len - tmp_loss_len - 1 .. seq_len - 2.  Returns (loss_sm, loss_temp, loss_mask), differentiable with respect to maps."""
+    if maps.dim() != 4 or maps.shape[1] != tmp_loss_len + 1:
+        raise ValueError("maps must be [B, tmp_loss_len + 1 = %d, 2w, 4w], got %s" % (tmp_loss_len + 1, tuple(maps.shape)))
+    if flow_scaled.dim() != 5 or flow_scaled.shape[1] != tmp_loss_len or flow_scaled.shape[0] != maps.shape[0]:
+        raise ValueError("flow_scaled must be [B, tmp_loss_len = %d, H, W, 2], got %s" % (tmp_loss_len, tuple(flow_scaled.shape)))
+    return DeviceFlowLoss.apply(maps, flow_scaled, float(cfg.mm_th), events)
+
+
+def _is_sum_mse(criterion):
+    return criterion is None or (type(criterion) is nn.MSELoss and criterion.reduction == 'sum')
+
+
+def _loss_flows(flow, T, first, tmp_loss_len, dev):
+    """The tmp_loss_len flows the loss reads as f32 [B, tmp_loss_len, H, W, 2] on dev: only those are copied, each from a
+    contiguous piece of the host tensors (a clip's run of frames, or one frame's batch)."""
+    sel = range(first, first + tmp_loss_len)
+    if torch.is_tensor(flow):
+        if flow.dim() != 5 or flow.shape[-1] != 2 or flow.shape[1] != T:
+            raise ValueError("flow must be [B, T = %d, H, W, 2], got %s" % (T, tuple(flow.shape)))
+        B, _, H, W, _ = flow.shape
+        out = torch.empty((B, tmp_loss_len, H, W, 2), dtype=torch.float32, device=dev)
+        for b in range(B):
+            out[b].copy_(flow[b, first:first + tmp_loss_len])
+        return out
+    flow = list(flow)
+    if len(flow) != T:
+        raise ValueError("flow must hold seq_len = %d frames" % T)
+    parts = [torch.as_tensor(flow[t]) for t in sel]
+    if any(f.dim() != 4 or f.shape[-1] != 2 or f.shape != parts[0].shape for f in parts):
+        raise ValueError("flow must be T tensors [B, H, W, 2] of one shape")
+    out = torch.empty((parts[0].shape[0], tmp_loss_len) + tuple(parts[0].shape[1:]), dtype=torch.float32, device=dev)
+    for l, f in enumerate(parts):
+        out[:, l].copy_(f)
+    return out
+
+
 def train_step(cell, seq, flow, optimizer, cfg, tmp_loss_len=3, criterion=None):
     """One iteration of train() on one batch: seq = T tensors [B, 6, C, w, w] (or [B, T, 6, C, w, w]), flow = T tensors
-    [B, flow_h, 2 flow_h, 2] (or [B, T, ...]).  Normalise, forward, loss, ``optimizer.zero_grad(); loss.backward();
-    optimizer.step()``.  Returns the three loss terms (loss_sm, loss_temp, loss_mask) as detached tensors."""
+    [B, H, W, 2] (or [B, T, H, W, 2]) of any H x W.  Normalise, forward, resize the flows the loss reads, loss,
+    ``optimizer.zero_grad(); loss.backward(); optimizer.step()``.  Returns the three loss terms (loss_sm, loss_temp, loss_mask)
+    as detached tensors.  The loss runs in HIP for the reference's criterion (None or ``nn.MSELoss(reduction='sum')``); any
+    other criterion goes through ``flow_losses`` on the same resized flow."""
     dev = cell.Conv1.weight.device
     seq = _stack(seq).to(dev, torch.float32)
-    flow = _stack(flow).to(dev, torch.float32)
     if seq.dim() != 6 or seq.shape[2] != 6:
         raise ValueError("seq must be T tensors [B, 6, C, w, w]")
     B, T, _, C, w, _ = seq.shape
-    if T != cfg.seq_len or flow.shape[1] != T:
+    if T != cfg.seq_len:
         raise ValueError("seq / flow must hold seq_len = %d frames" % cfg.seq_len)
     if not 0 <= cfg.seq_len - tmp_loss_len - 1:
         raise ValueError("tmp_loss_len must be < seq_len")
-    check_flow(flow, cfg.flow_h)
-    frames = normalize_batch(seq).permute(0, 1, 2, 4, 5, 3).reshape(B, T, 6 * w * w, C).contiguous()
     first = cfg.seq_len - tmp_loss_len - 1
+    events = trainer_of(cell).events
+    _mark(events, 'resize')
+    flow = _loss_flows(flow, T, first, tmp_loss_len, dev)
+    if flow.shape[0] != B:
+        raise ValueError("flow must hold the batch's %d clips" % B)
+    scaled = resize_flow(flow, cfg.flow_h)                                          # [B, tmp_loss_len, flow_h, 2 flow_h, 2]
+    _mark(events, 'resize_end')
+    frames = normalize_batch(seq).permute(0, 1, 2, 4, 5, 3).reshape(B, T, 6 * w * w, C).contiguous()
     maps = window_maps(cell, frames, range(first, T))
-    loss_sm, loss_temp, loss_mask = flow_losses(maps, flow, cfg, tmp_loss_len, criterion)
+    if _is_sum_mse(criterion):
+        loss_sm, loss_temp, loss_mask = device_flow_losses(maps, scaled, cfg, tmp_loss_len, events)
+    else:
+        # flow_losses multiplies by flow_h / (2 flow_h) = 0.5 itself: 2 * scaled undoes that exactly
+        sub = types.SimpleNamespace(flow_h=cfg.flow_h, mm_th=cfg.mm_th, seq_len=tmp_loss_len + 1)
+        loss_sm, loss_temp, loss_mask = flow_losses(maps, 2.0 * scaled, sub, tmp_loss_len, criterion)
     loss = cfg.l_s * loss_sm + cfg.l_t * loss_temp + cfg.l_m * loss_mask
     optimizer.zero_grad()
     loss.backward()

@@ -374,6 +374,30 @@ int cp360_wino_output_input(const cp360_wino_desc* d, const float* m, const floa
 int cp360_wino_forward(const cp360_wino_desc* d, const void* in, const void* packed, const float* bias, void* out, void* v,
                        float* m, void* stream);
 
+/* ------------------------------------------------------------------ K5f: flow resize and flow loss
+ * The part of a training iteration that grows with the flow's resolution (temporal_model/train_temporal.py:110-167), for
+ * temporal_model/train_temporal.py.  f32 only (dtype CP360_F32); no atomics, fixed-order sums: results are bit-reproducible.
+ *
+ * Flow resize: cv2.resize(flow, (w_out, h_out), INTER_CUBIC) * fscale, OpenCV's generic float path (taps s-1 .. s+2 of
+ * s = floor((d + 0.5) * in / out - 0.5), Keys coefficients with A = -0.75 in float, replicated borders, horizontal pass first,
+ * f32 accumulation).  cp360_flow_resize_coeffs_host builds one axis: ofs int32 [out_size] (= s), coef f32 [out_size, 4].
+ * cp360_flow_resize: flow f32 [F, h_in, w_in, 2] -> out f32 [F, h_out, w_out, 2]; the tables of both axes on the device
+ * (16-byte aligned coef).  Equal sizes: a copy times fscale (cv2 copies), the tables may be NULL. */
+int cp360_flow_resize_coeffs_host(int in_size, int out_size, int32_t* ofs, float* coef);
+int cp360_flow_resize(int dtype, const float* flow, int F, int h_in, int w_in, float* out, int h_out, int w_out,
+                      const int32_t* yofs, const float* ycoef, const int32_t* xofs, const float* xcoef, float fscale,
+                      void* stream);
+/* Flow loss of B clips x L pairs: maps f32 [B, L + 1, 2w, 4w] (the saliency maps of steps seq_len - L - 1 ..), flow f32
+ * [B, L, h, w_loss, 2] (resized and scaled; pair (b, l) warps map l towards map l + 1).  Forward: loss f32 [3] = the sum-MSE
+ * terms (smooth, temporal, motion mask) over all pairs.  Backward: grad_loss f32 [3] (device: d loss / d term) -> dmaps f32
+ * [B, L + 1, 2w, 4w] (written; map 0 of each clip gets zero).  work: cp360_flow_loss_work_bytes (0: unsupported geometry),
+ * shared by both directions.  Faces w <= 16, h and w_loss >= 2. */
+size_t cp360_flow_loss_work_bytes(int B, int L, int w, int h, int w_loss);
+int cp360_flow_loss_forward(int dtype, const float* maps, const float* flow, int B, int L, int w, int h, int w_loss, float mm_th,
+                            float* loss, float* work, void* stream);
+int cp360_flow_loss_backward(int dtype, const float* maps, const float* flow, const float* grad_loss, int B, int L, int w, int h,
+                             int w_loss, float mm_th, float* dmaps, float* work, void* stream);
+
 /* ------------------------------------------------------------------ K7: window normalise
  * temporal_model/test_temporal.py:66-67,70-73,77: per clip min / max over the whole
  * window, then (x - mn) / (mx - mn).
