@@ -13,6 +13,9 @@
 The tables are built in float32 exactly as the spec says; the resize itself runs in float64 here (the library accumulates in
 float32).  cv2 is not a test dependency, so this pins the restatement, not cv2 itself; an IPP build of OpenCV may differ in the
 last bits.
+
+``loss_terms`` at the end is the float64 reference of the flow loss for the GPU tests: the torch lines of ``flow_losses`` for
+already-scaled flow of any [H, W] (tests/test_flow_cpu.py pins it to ``flow_losses`` where W = 2 H).
 """
 import numpy as np
 
@@ -68,3 +71,33 @@ def resize(flow, h_out, w_out):
 def resize_flow(flow, flow_h):
     """The reference's :110-113: resize to (flow_h, 2 flow_h), times flow_h / W of the original flow (float64)."""
     return resize(flow, flow_h, 2 * flow_h) * (flow_h / float(np.shape(flow)[-2]))
+
+
+def loss_terms(maps, flow_scaled, mm_th):
+    """The three sum-MSE terms of ``flow_losses`` (train_temporal.py:115-167 of the reference) for ALREADY SCALED flow of any
+    size: maps torch [B, L + 1, mh, mw], flow_scaled torch [B, L, H, W, 2], both of one floating dtype (float64 for a reference).
+    The same torch lines as ``flow_losses`` (bilinear ``F.interpolate`` and ``grid_sample``, align_corners False, zero padding;
+    the mesh on the (size - 1) grid, built in float32 as ``generate_meshgrid`` does); no W = 2 H restriction, no rescaling.
+    Returns (loss_sm, loss_temp, loss_mask), differentiable with respect to maps (the next map of each pair only)."""
+    import torch
+    import torch.nn.functional as F
+    B, n, _, _ = maps.shape
+    L, H, W = flow_scaled.shape[1], flow_scaled.shape[2], flow_scaled.shape[3]
+    assert n == L + 1 and flow_scaled.shape[0] == B
+    y = torch.arange(0, H).unsqueeze(1).repeat(1, W) / (H - 1) * 2 - 1
+    x = torch.arange(0, W).unsqueeze(0).repeat(H, 1) / (W - 1) * 2 - 1
+    mesh = torch.stack([x, y], -1).float().to(maps.dtype)[None]                       # [1, H, W, 2]
+    terms = [0, 0, 0]
+    for b in range(B):
+        for l in range(L):
+            fl = flow_scaled[b, l]
+            static = torch.sqrt(fl[..., 0] ** 2 + fl[..., 1] ** 2) < mm_th
+            cur = F.interpolate(maps[b, l][None, None], size=(H, W), mode='bilinear', align_corners=False)
+            nxt = F.interpolate(maps[b, l + 1][None, None], size=(H, W), mode='bilinear', align_corners=False)
+            grid = torch.stack([fl[..., 0] / W * 2, fl[..., 1] / H * 2], -1)[None] + mesh
+            warp = F.grid_sample(cur, grid, mode='bilinear', padding_mode='zeros', align_corners=False).detach()
+            masked = nxt.detach().clone()
+            masked[:, :, static] = 0
+            for k, target in enumerate((warp, cur.detach(), masked)):
+                terms[k] = terms[k] + ((nxt - target) ** 2).sum()
+    return tuple(terms)

@@ -60,12 +60,43 @@ def test_restatement_scale_divides_by_width():
     np.testing.assert_allclose(fr.resize_flow(flow, 480), 0.5, rtol=0)
 
 
-@pytest.mark.parametrize('n_in,n_out', [(480, 240), (960, 480), (480, 28), (240, 480), (640, 480), (56, 56)])
+@pytest.mark.parametrize('n_in,n_out', [(480, 240), (960, 480), (480, 28), (240, 480), (640, 480), (56, 56),
+                                        # inputs of 1 to 3 pixels (every tap clamped) up to 8 and 16, both directions
+                                        (1, 1), (1, 7), (1, 28), (2, 5), (2, 13), (3, 2), (3, 7), (3, 56), (5, 3), (8, 28),
+                                        (16, 56), (16, 3), (8, 1)])
 def test_host_tables_equal_restatement(n_in, n_out):
     got_o, got_c = ops.flow_resize_coeffs(n_in, n_out)
     want_o, want_c = fr.cubic_tables(n_in, n_out)
     np.testing.assert_array_equal(got_o, want_o)
     np.testing.assert_array_equal(got_c.view(np.uint32), want_c.view(np.uint32))
+
+
+def test_loss_restatement_equals_flow_losses():
+    """tests/flow_restate.py ``loss_terms`` (any [H, W], already-scaled flow: the float64 reference of the GPU tests) gives
+    the terms and the map gradient of ``flow_losses`` on a W = 2 H case, in float64, to rounding (1e-13)."""
+    import types
+
+    import torch
+
+    from cp_360_weakly_supervised_saliency_amd.temporal_model import train_temporal as tt
+    B, L, h, w = 2, 3, 20, 3
+    maps = hashrng.uniform(9510, (B, L + 1, 2 * w, 4 * w), 0.0, 1.0, dtype=np.float64)
+    n = hashrng.normal(9511, (B, L, h, 2 * h, 2), dtype=np.float64)
+    u = hashrng.uniform(9512, (B, L, h, 2 * h, 1))
+    scaled = n * np.where(u < 0.1, 6.0, 0.12)                   # both mask branches, some warps outside the image
+    st = np.sqrt((scaled ** 2).sum(-1)) < 0.15
+    assert 0.2 < st.mean() < 0.9
+    res = []
+    for fn in (lambda m: tt.flow_losses(m, torch.from_numpy(2.0 * scaled), types.SimpleNamespace(flow_h=h, mm_th=0.15, seq_len=L + 1), L),
+               lambda m: fr.loss_terms(m, torch.from_numpy(scaled), 0.15)):
+        m = torch.from_numpy(maps).requires_grad_(True)
+        terms = fn(m)
+        (0.7 * terms[0] + terms[1] + 0.01 * terms[2]).backward()
+        res.append((np.array([t.item() for t in terms]), m.grad.numpy()))
+    assert np.all(res[0][0] > 0)
+    np.testing.assert_allclose(res[1][0], res[0][0], rtol=1e-13, atol=0)
+    np.testing.assert_allclose(res[1][1], res[0][1], rtol=0, atol=1e-13 * np.max(np.abs(res[0][1])))
+    assert np.all(res[1][1][:, 0] == 0) and np.max(np.abs(res[1][1][:, 1:])) > 0
 
 
 def test_flow_entry_points_declared_and_bound():
