@@ -15,12 +15,8 @@
 // Wave w computes output row w of the band: 56 pixels as 4 MFMA pixel blocks (8 of the 64 columns are
 // padding) x 64 channels.  Two workgroups (256 threads, 68 KiB LDS) share a CU, so one band's gather /
 // epilogue overlaps the other's MFMAs.  Epilogue: bias + ReLU, one rounding, 16-byte pieces (acc_chan).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
+#include "tile.h"
 
 namespace {
 constexpr int N = 56, NP = N + 2, C = 64, BAND = 4;
@@ -29,45 +25,6 @@ constexpr int PATCH_INST = (PATCH_PX + 7) / 8;               // 44 DMA instructi
 constexpr int PATCH_LDS = PATCH_INST * 1024;                 // 45,056
 constexpr int W_TAP = 64 * 128;                              // 8 KiB: one tap's 64 rows x 64 channels
 constexpr int W_SLOTS = 3;
-
-__device__ __attribute__((aligned(16))) unsigned int b_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-__device__ __forceinline__ int px_swz(int p) { return ((p >> 1) & 3) << 1; }
-__device__ __forceinline__ int w_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename T> __device__ __forceinline__ void mma(f32x4& acc, const u32x4& a, const u32x4& b);
-template <> __device__ __forceinline__ void mma<bf16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma<f16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], bf16_raw) {
-    u32x4 o;
-    o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-    o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-    return o;
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = {(f16_raw)v[0], (f16_raw)v[1], (f16_raw)v[2], (f16_raw)v[3],
-                      (f16_raw)v[4], (f16_raw)v[5], (f16_raw)v[6], (f16_raw)v[7]};
-    return __builtin_bit_cast(u32x4, h);
-}
 }  // namespace
 
 // packed weights: [tap][row r][64 channels], row r <- output channel in acc_chan order, BN scale folded
@@ -100,7 +57,7 @@ __global__ __launch_bounds__(256, 2) void band3x3_kernel(const T* __restrict__ x
 #pragma unroll 1
         for (int inst = wave; inst < PATCH_INST; inst += 4) {
             const int q = inst * 8 + (lane >> 3);
-            const void* src = b_zero16;
+            const void* src = g_zero16;
             if (q < PATCH_PX) {
                 const int pr = q / NP, pc = q - pr * NP;
                 const int sp = cubepad_src(f, BAND * band + pr, pc, geom);       // pixel index inside the cube
@@ -145,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void band3x3_kernel(const T* __restrict__ x
         for (int kk = 0; kk < 2; ++kk) {
             u32x4 a[4], b[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const u32x4*>(Ws + w_off(i * 16 + lrow, kk * 4 + lchunk));
+            for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const u32x4*>(Ws + lds_swz(i * 16 + lrow, kk * 4 + lchunk));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int p = pbase + 16 * j;
@@ -154,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void band3x3_kernel(const T* __restrict__ x
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mma<T>(acc[i][j], a[i], b[j]);
+                for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], a[i], b[j]);
         }
     }
     // ---- epilogue: output row band*4 + wave of image img

@@ -19,7 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(256) void train_gates_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < 4; ++k) g[k] += base[k * Hc];
         }
-        const float ig = sigm(g[0]), fg = sigm(g[1]), og = sigm(g[2]), cg = tanhf(g[3]);
+        const float ig = fast_sigmoid(g[0]), fg = fast_sigmoid(g[1]), og = fast_sigmoid(g[2]), cg = tanhf(g[3]);
         const float cn = fg * c_prev[(size_t)m * Hc + j] + ig * cg;
         const float hn = og * tanhf(cn);
         float* a = acts + (size_t)m * G + j;

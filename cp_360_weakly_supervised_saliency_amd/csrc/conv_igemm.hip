@@ -443,47 +443,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
 // ------------------------------------------------------------------ wide-tile LDS-DMA kernel
 // For c_out >= 256 (ConvLSTM, layers 2-4, CAM): 256 (channels) x 128 (pixels) tile, 8 waves
 // (4 x 2, each 64 x 64), K step 128 bytes, THREE LDS stages (3 x 48 KiB) filled by LDS-DMA
-// (global_load_lds_dwordx4: global -> LDS with no VGPR staging).  A DMA wave-instruction
-// writes 1 KiB = 8 tile rows linearly (LDS address = M0 + lane*16), so the XOR swizzle of
-// the LDS image is applied on the SOURCE side: lane l, which lands in physical chunk l&7
-// of row r, fetches logical chunk (l&7) ^ ((r>>1)&7) - the same involution the ds_read side
-// applies.  The per-lane source address also carries the CubePad / im2col gather.
-// Pipeline (one barrier per K step): at step `it` a wave waits (counted vmcnt) for its own
-// DMA of step `it`, meets the barrier (everyone's step-`it` data has landed and everyone has
-// finished reading the buffer of step it-1), issues the DMA of step it+2 into that freed
-// buffer and computes step `it`: every HBM/L2 load has two full MFMA phases to arrive.
-// The DMA is issued from inline asm (the compiler would otherwise drain vmcnt(0) before
-// every ds_read); its completion is counted by hand: DMA_PER_STEP per thread per step.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst /* wave-uniform */) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
-// the same with the non-temporal hint: a weight stream much larger than the 256 MB Infinity Cache, past the head of a workgroup's
-// share (ConvK::w_pin) - it then no longer sweeps the cache of the split-K slabs / activations the next launches read, and the heads
-// of the streams, which every workgroup asks for at once when the launch starts, are still there from the previous step (measured on
-// the Winograd GEMM first: csrc/wino.hip fill_one)
-__device__ __forceinline__ void glds16_nt(const void* gsrc, unsigned lds_dst /* wave-uniform */) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off nt\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
+// (glds16 of tile.h, where the source-side swizzle, the pipeline of one barrier per K step and the
+// hand-counted completion are described).  A DMA wave-instruction writes 8 tile rows (lds_swz on
+// the source side); DMA_PER_STEP instructions per thread per step.
 template <typename T, int MJ>      // MJ = 16-pixel sub-tiles per wave: 4 -> 256x128 tile, 3 LDS stages (the only instance)
 __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     constexpr int BN = 256, BM = 32 * MJ, NSTAGE = (MJ == 4) ? 3 : 2;
@@ -704,21 +666,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
 //        two waves that share a SIMD (w and w+4) carry 10 + 9 blocks, so every SIMD's matrix
 //        pipe has the same work.  The 48 extra activation rows are one more DMA instruction
 //        for waves 0-2 (their vmcnt budget is counted separately).
-__device__ __forceinline__ int lds_swz64(int row, int chunk) {
-    return row * 64 + ((chunk ^ ((0 - (row >> 2)) & 3)) << 4);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt_upto(int n);   // s_waitcnt vmcnt(min(n, N)), n wave-uniform
-template <> __device__ __forceinline__ void wait_vmcnt_upto<0>(int) { wait_vmcnt<0>(); }
-template <int N> __device__ __forceinline__ void wait_vmcnt_upto(int n) {
-    if (n >= N) wait_vmcnt<N>();
-    else wait_vmcnt_upto<N - 1>(n);
-}
-
 template <int BM, int NS = 4> struct RingGeom {
     static constexpr int BN = 256, NSTAGE = NS;
     static constexpr int A_PASSES = BN / 128;                    // 128 tile rows per 512-thread pass
@@ -1503,7 +1450,6 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(const float* __restric
 
 // ------------------------------------------------------------------ ConvLSTM gate epilogue
 // model/clstm.py:68-80: gates = [in | remember | out | cell] chunks of Hc channels.
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void lstm_gates_kernel(const float* __restrict__ gp, int splits,
@@ -1539,7 +1485,7 @@ __global__ __launch_bounds__(256) void lstm_gates_kernel(const float* __restrict
         float cn[4], hn[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float ig = sigmoidf_(g[0][e]), fg = sigmoidf_(g[1][e]), og = sigmoidf_(g[2][e]);
+            const float ig = fast_sigmoid(g[0][e]), fg = fast_sigmoid(g[1][e]), og = fast_sigmoid(g[2][e]);
             const float cg = tanhf(g[3][e]);
             cn[e] = fg * cpv[e] + ig * cg;
             hn[e] = og * tanhf(cn[e]);
@@ -1618,7 +1564,6 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------ host side
-static int elem_bytes(int dtype) { return dtype == CP360_F32 ? 4 : ((dtype == CP360_BF16 || dtype == CP360_F16) ? 2 : 0); }
 static int bk_of(int dtype) { return 128 / elem_bytes(dtype); }
 // K padding per tap: a 128-byte step for the tap-major layout, a 64-byte sub-step for the channel-major one
 static int c_pad_of(const cp360_conv_desc* d) {

@@ -13,7 +13,7 @@
 //   cubepad_nchw_plane_kernel    (plane, face) items, runs + pad stream
 //   cubepad_nchw_strip_kernel    round-2 form of the plane kernel
 //   cubepad_nchw_kernel          element per lane, any geometry
-#include "common.h"
+#include "tile.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -93,7 +93,6 @@ template <> struct ElemOf<1> { typedef uint8_t T; };
 template <> struct ElemOf<2> { typedef uint16_t T; };
 template <> struct ElemOf<4> { typedef uint32_t T; };
 template <> struct ElemOf<8> { typedef uint64_t T; };
-typedef __attribute__((ext_vector_type(4))) unsigned int cp_u32x4;
 
 template <int ES>
 __global__ __launch_bounds__(256) void cubepad_nchw_strip_kernel(const unsigned char* __restrict__ x,
@@ -172,9 +171,9 @@ __global__ __launch_bounds__(256) void cubepad_nchw_strip_kernel(const unsigned 
                     if (je >= Wp) { je -= Wp; ++ie; }        // E <= Wp (launcher)
                     tmp[e] = elem(ie, je);
                 }
-                cp_u32x4 v;
+                u32x4 v;
                 __builtin_memcpy(&v, tmp, 16);
-                *reinterpret_cast<cp_u32x4*>(ca) = v;
+                *reinterpret_cast<u32x4*>(ca) = v;
             } else {                                         // head / tail of the plane: element stores
                 for (int e = 0; e < E; ++e) {
                     const int q = q0 + e;
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_strip_kernel(const unsigned 
         const float rcp_cpr = 1.0f / (float)cpr;
         const int nfast = n * cpr;
         for (int base = lane; base < nfast; base += 64 * 4) {
-            cp_u32x4 v[4];
+            u32x4 v[4];
             unsigned char* dst[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -207,7 +206,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_strip_kernel(const unsigned 
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (dst[u]) *reinterpret_cast<cp_u32x4*>(dst[u]) = v[u];
+                if (dst[u]) *reinterpret_cast<u32x4*>(dst[u]) = v[u];
         }
         // ---- pass 2: what the runs leave: the pad rows above / below and the 1-2 chunks between consecutive runs
         {
@@ -324,8 +323,8 @@ __global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned 
         const int rowA = g.pt * Wp + g.pl + head;
         auto run_begin = [&](int r) -> int { return (r * Wp + rowA + E - 1) >> LOG_E; };   // first chunk fully inside centre row r
         auto run_end = [&](int r) -> int { return (r * Wp + rowA + n) >> LOG_E; };
-        auto load_vec = [&](long long goff) -> cp_u32x4 {     // 16 bytes at element goff of x; the tensor's first / last chunk may hang over its ends
-            cp_u32x4 v;
+        auto load_vec = [&](long long goff) -> u32x4 {     // 16 bytes at element goff of x; the tensor's first / last chunk may hang over its ends
+            u32x4 v;
             if (goff >= 0 && goff + E <= total_in) {
                 __builtin_memcpy(&v, reinterpret_cast<const T*>(x) + goff, 16);
             } else {
@@ -351,8 +350,8 @@ __global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned 
             const int eA = q0c ? min(E, g.pl + n - jA) : 0;                    // leading elements from centre stream A
             const int aB = q0c ? a + 1 : (a < 0 ? 0 : (rowc ? (jA < g.pl ? a : a + 1) : n));   // centre row that starts next
             const int eB = aB < n ? min(max((g.pt + aB) * Wp + g.pl - q0, 0), E) : E;   // elements from e = eB on are its centre
-            const cp_u32x4 va = load_vec(xf_off + (eA > 0 ? cpos : 0));
-            const cp_u32x4 vb = load_vec(xf_off + (eB < E ? aB * n - eB : 0));
+            const u32x4 va = load_vec(xf_off + (eA > 0 ? cpos : 0));
+            const u32x4 vb = load_vec(xf_off + (eB < E ? aB * n - eB : 0));
             T ta[E], tb[E], tv[E];
             __builtin_memcpy(ta, &va, 16);
             __builtin_memcpy(tb, &vb, 16);
@@ -364,9 +363,9 @@ __global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned 
             }
             unsigned char* ca = c0p + ((size_t)ch << 4);
             if (q0 >= 0 && q0 + E <= plane_elems) {
-                cp_u32x4 v;
+                u32x4 v;
                 __builtin_memcpy(&v, tv, 16);
-                *reinterpret_cast<cp_u32x4*>(ca) = v;
+                *reinterpret_cast<u32x4*>(ca) = v;
             } else {                                                           // chunk shared with the neighbouring plane
 #pragma unroll
                 for (int e = 0; e < E; ++e)
@@ -384,7 +383,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned 
                 const int rq = div_by(lane, cpr, rcp_cpr);
                 int r = r0 + rq, k = lane - rq * cpr;
                 while (r < rend) {
-                    cp_u32x4 v[UNR];
+                    u32x4 v[UNR];
                     unsigned doff[UNR];
                     bool ok[UNR];
 #pragma unroll
@@ -403,7 +402,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned 
                     }
 #pragma unroll
                     for (int u = 0; u < UNR; ++u)
-                        if (ok[u]) *reinterpret_cast<cp_u32x4*>(c0p + doff[u]) = v[u];
+                        if (ok[u]) *reinterpret_cast<u32x4*>(c0p + doff[u]) = v[u];
                 }
             }
             const int n_top = r0 == 0 ? top_end : 0, n_bot = rend == n ? nchunks - bot_begin : 0;
@@ -533,14 +532,14 @@ __global__ __launch_bounds__(768) void cubepad_nchw_channel_kernel(const unsigne
             const int rend = min(r0 + rbw, rb);
             for (int t = lane; t < 2 * (rend - r0); t += 64) {                  // row ends of this block
                 const int row = r0 + (t >> 1), side = t & 1;
-                cp_u32x4 v;
+                u32x4 v;
                 __builtin_memcpy(&v, xf + (unsigned)(row * n + (side ? n - E : 0)), 16);
-                *reinterpret_cast<cp_u32x4*>(buf + ((f * n + row) * 2 + side) * E) = v;
+                *reinterpret_cast<u32x4*>(buf + ((f * n + row) * 2 + side) * E) = v;
             }
             const int rq = div_by(lane, cpr, rcp_cpr);
             int r = r0 + rq, k = lane - rq * cpr;
             while (r < rend) {
-                cp_u32x4 v[UNR];
+                u32x4 v[UNR];
                 unsigned doff[UNR];
                 bool ok[UNR];
 #pragma unroll
@@ -559,7 +558,7 @@ __global__ __launch_bounds__(768) void cubepad_nchw_channel_kernel(const unsigne
                 }
 #pragma unroll
                 for (int u = 0; u < UNR; ++u)
-                    if (ok[u]) *reinterpret_cast<cp_u32x4*>(c0p + doff[u]) = v[u];
+                    if (ok[u]) *reinterpret_cast<u32x4*>(c0p + doff[u]) = v[u];
             }
         }
         __syncthreads();
@@ -626,9 +625,9 @@ __global__ __launch_bounds__(768) void cubepad_nchw_channel_kernel(const unsigne
                 }
                 unsigned char* ca = c0p + ((size_t)ch << 4);
                 if (q0 >= 0 && q0 + E <= plane_elems) {
-                    cp_u32x4 v;
+                    u32x4 v;
                     __builtin_memcpy(&v, tv, 16);
-                    *reinterpret_cast<cp_u32x4*>(ca) = v;
+                    *reinterpret_cast<u32x4*>(ca) = v;
                 } else {
 #pragma unroll
                     for (int e = 0; e < E; ++e)
@@ -707,7 +706,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
         auto head_b = [&](int f) -> int { return (int)((yc_addr + (size_t)f * out_face_b) & 15); };   // bytes of chunk 0 before face f's range
         // ---- 1: input chunks to their padded places
         for (int base = tid; base < 6 * cpf; base += NT * UNR) {
-            cp_u32x4 v[UNR];
+            u32x4 v[UNR];
             int lo[UNR], wrap_at[UNR], wrap_add[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
@@ -728,7 +727,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
             for (int u = 0; u < UNR; ++u) {
                 if (lo[u] < 0) continue;
                 T* d = reinterpret_cast<T*>(planes + lo[u]);  // element-aligned only: E element stores
-                const cp_u32x4 w = v[u];
+                const u32x4 w = v[u];
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
                     T val;
@@ -770,7 +769,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
         __syncthreads();
         // ---- 3: linear store
         for (int base = tid; base < 6 * nchmax; base += NT * UNR) {
-            cp_u32x4 v[UNR];
+            u32x4 v[UNR];
             int fs[UNR], chs[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
@@ -781,7 +780,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
                     if (ch * 16 < head_b(f) + out_reg * ES) {
                         fs[u] = f;
                         chs[u] = ch;
-                        v[u] = *reinterpret_cast<const cp_u32x4*>(planes + f * pstride_b + ch * 16);
+                        v[u] = *reinterpret_cast<const u32x4*>(planes + f * pstride_b + ch * 16);
                     }
                 }
             }
@@ -792,7 +791,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
                 unsigned char* ca = yc + (size_t)fs[u] * out_face_b - hb + (size_t)chs[u] * 16;
                 const int q0 = chs[u] * E - hb / ES;
                 if (q0 >= 0 && q0 + E <= out_reg) {
-                    *reinterpret_cast<cp_u32x4*>(ca) = v[u];
+                    *reinterpret_cast<u32x4*>(ca) = v[u];
                 } else {                                     // chunk shared with the neighbouring range
                     T tv[E];
                     __builtin_memcpy(tv, &v[u], 16);
@@ -874,7 +873,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_band_kernel(const unsigned c
             const T* src = xf + (size_t)a0 * n;
             const int pos0 = (g.pt + a0 - i0) * Wp + g.pl;
             for (int base = tid; base < nck; base += 256 * UNR) {
-                cp_u32x4 v[UNR];
+                u32x4 v[UNR];
                 int lo[UNR], wrap_at[UNR];
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
@@ -892,7 +891,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_band_kernel(const unsigned c
                 for (int u = 0; u < UNR; ++u) {
                     if (lo[u] < 0) continue;
                     T* d = bp + lo[u];
-                    const cp_u32x4 w = v[u];
+                    const u32x4 w = v[u];
 #pragma unroll
                     for (int e = 0; e < E; ++e) {
                         T val;
@@ -950,11 +949,11 @@ __global__ __launch_bounds__(256) void cubepad_nchw_band_kernel(const unsigned c
             const int nch = (head + nband + E - 1) >> LOG_E;
             unsigned char* c0p = gb - hb;
             for (int base = tid; base < nch; base += 256 * UNR) {
-                cp_u32x4 v[UNR];
+                u32x4 v[UNR];
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
                     const int ch = base + 256 * u;
-                    if (ch < nch) v[u] = *reinterpret_cast<const cp_u32x4*>(band + ch * 16);
+                    if (ch < nch) v[u] = *reinterpret_cast<const u32x4*>(band + ch * 16);
                 }
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
@@ -963,7 +962,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_band_kernel(const unsigned c
                     const int q0 = ch * E - head;
                     unsigned char* ca = c0p + (size_t)ch * 16;
                     if (q0 >= 0 && q0 + E <= nband) {
-                        *reinterpret_cast<cp_u32x4*>(ca) = v[u];
+                        *reinterpret_cast<u32x4*>(ca) = v[u];
                     } else {                                 // chunk shared with the neighbouring band / plane
                         T tv[E];
                         __builtin_memcpy(tv, &v[u], 16);
@@ -1020,8 +1019,8 @@ __global__ __launch_bounds__(256) void cubepad_nchw_cube_kernel(const unsigned c
         const unsigned char* xin = x + (size_t)grp * 6 * in_face + (size_t)c0 * nn * ES;
         for (int k = tid; k < 6 * in_chunks; k += 256) {
             const int f = k / in_chunks, ck = k - f * in_chunks;
-            const cp_u32x4 v = *reinterpret_cast<const cp_u32x4*>(xin + (size_t)f * in_face + (size_t)ck * 16);
-            *reinterpret_cast<cp_u32x4*>(reinterpret_cast<unsigned char*>(in_s) + ((size_t)f * in_chunks + ck) * 16) = v;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(xin + (size_t)f * in_face + (size_t)ck * 16);
+            *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(in_s) + ((size_t)f * in_chunks + ck) * 16) = v;
         }
         __syncthreads();
         unsigned char* yout = y + (size_t)grp * 6 * out_face + (size_t)c0 * HW * ES;
@@ -1037,9 +1036,9 @@ __global__ __launch_bounds__(256) void cubepad_nchw_cube_kernel(const unsigned c
                 tmp[e] = in_s[(t >> 10) * (CH * nn) + ch * nn + (t & 1023u)];
                 if (++q == HW) { q = 0; ++ch; }
             }
-            cp_u32x4 v;
+            u32x4 v;
             __builtin_memcpy(&v, tmp, 16);
-            *reinterpret_cast<cp_u32x4*>(yout + (size_t)f * out_face + (size_t)ck * 16) = v;
+            *reinterpret_cast<u32x4*>(yout + (size_t)f * out_face + (size_t)ck * 16) = v;
         }
     }
 }

@@ -27,12 +27,8 @@
 // fit next to the tail's registers for 64 pixels per wave, so stage 3 runs twice over HALF of the wave's pixel blocks
 // (2 x 8 passes; conv3's fragments - 4 KiB per pass - then come from L2 one pass ahead instead of from LDS, which holds
 // the 64 KiB of next-conv1 fragments).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
+#include "tile.h"
 
 namespace {
 constexpr int C = 64, CO = 256;
@@ -56,58 +52,6 @@ template <int N_, int BAND_> struct L1Geom {
     static constexpr int LDS_BYTES_W = STAGE1_LDS > STAGE3W_LDS ? STAGE1_LDS : STAGE3W_LDS;            // 67,072 (NEXTC = 128)
     static_assert(N % BAND == 0 && 64 * WPR >= N && 4 % BAND == 0, "band geometry");
 };
-
-__device__ __attribute__((aligned(16))) unsigned int l_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-__device__ __forceinline__ int px_swz(int p) { return ((p >> 1) & 3) << 1; }
-
-template <typename T> __device__ __forceinline__ void mma(f32x4& acc, const u32x4& a, const u32x4& b);
-template <> __device__ __forceinline__ void mma<bf16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma<f16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], bf16_raw) {
-    u32x4 o;
-    o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-    o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-    return o;
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = {(f16_raw)v[0], (f16_raw)v[1], (f16_raw)v[2], (f16_raw)v[3],
-                      (f16_raw)v[4], (f16_raw)v[5], (f16_raw)v[6], (f16_raw)v[7]};
-    return __builtin_bit_cast(u32x4, h);
-}
-__device__ __forceinline__ void unpack8(const u32x4& r, float v[8], bf16_raw) {
-    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-    v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-    v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-__device__ __forceinline__ void unpack8(const u32x4& r, float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = __builtin_bit_cast(f16x8v, r);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
-}
-// packed row R of a 32-row group <- channel (acc_chan order: MFMA blocks 2q, 2q+1 give a lane 8 consecutive channels)
-__host__ __device__ __forceinline__ int row_chan(int R) { return (R & ~31) + ((R >> 2) & 3) * 8 + ((R >> 4) & 1) * 4 + (R & 3); }
 }  // namespace
 
 // conv2 weights [64, 64, 3, 3] (times scale) -> MFMA A fragments [tap 9][row block 4][kk 2][lane][8]: lane l holds row
@@ -199,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll 1
         for (int inst = wave; inst < PATCH_INST; inst += 4) {
             const int q = inst * 8 + (lane >> 3);
-            const void* src = l_zero16;
+            const void* src = g_zero16;
             if (q < PATCH_PX) {
                 const int pr = q / NP, pc = q - pr * NP;
                 const int sp = cubepad_src(f, BAND * band + pr, pc, geom);
@@ -256,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                for (int rb = 0; rb < 4; ++rb) mma<T>(c[rb], a0[rb][kb], b[kb]);
+                for (int rb = 0; rb < 4; ++rb) mma_chunk<T>(c[rb], a0[rb][kb], b[kb]);
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
                 float v[8];
@@ -288,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mma<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
+                for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -338,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
             const int xo = x0 + j * 16 + lrow;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                const T* src = xo < N ? xds + (row_px + j * 16 + lrow) * C + kb * 32 + lchunk * 8 : reinterpret_cast<const T*>(l_zero16);
+                const T* src = xo < N ? xds + (row_px + j * 16 + lrow) * C + kb * 32 + lchunk * 8 : reinterpret_cast<const T*>(g_zero16);
                 bx[kb][j] = *reinterpret_cast<const u32x4*>(src);
             }
         }
@@ -353,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int xo = x0 + j * 16 + lrow;
-            const T* src = xo < N ? res + (row_px + j * 16 + lrow) * CO + p * 32 + lchunk * 8 : reinterpret_cast<const T*>(l_zero16);
+            const T* src = xo < N ? res + (row_px + j * 16 + lrow) * CO + p * 32 + lchunk * 8 : reinterpret_cast<const T*>(g_zero16);
             r[j] = *reinterpret_cast<const u32x4*>(src);
         }
     };
@@ -412,14 +356,14 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mma<T>(c3[rb][j], a3[rb][kb], bt[kb][j]);
+                for (int j = 0; j < 4; ++j) mma_chunk<T>(c3[rb][j], a3[rb][kb], bt[kb][j]);
         if (DS) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) mma<T>(c3[rb][j], ad[rb][kb], bx[kb][j]);
+                    for (int j = 0; j < 4; ++j) mma_chunk<T>(c3[rb][j], ad[rb][kb], bx[kb][j]);
         }
         u32x4 o[4];
 #pragma unroll
@@ -450,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mma<T>(acc[rb][j], a1[rb], o[j]);
+                for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[rb][j], a1[rb], o[j]);
         }
         if (!DS) {
 #pragma unroll
@@ -518,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
 #pragma unroll 1
         for (int inst = wave; inst < PATCH_INST; inst += 4) {
             const int q = inst * 8 + (lane >> 3);
-            const void* src = l_zero16;
+            const void* src = g_zero16;
             if (q < PATCH_PX) {
                 const int pr = q / NP, pc = q - pr * NP;
                 const int sp = cubepad_src(f, BAND * band + pr, pc, geom);
@@ -564,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) mma<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
+                    for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -621,7 +565,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = 2 * h + jj;
                 const int xo = x0 + j * 16 + lrow;
-                const T* src = xo < N ? res + (row_px + j * 16 + lrow) * CO + p * 32 + lchunk * 8 : reinterpret_cast<const T*>(l_zero16);
+                const T* src = xo < N ? res + (row_px + j * 16 + lrow) * CO + p * 32 + lchunk * 8 : reinterpret_cast<const T*>(g_zero16);
                 r[jj] = *reinterpret_cast<const u32x4*>(src);
             }
         };
@@ -651,7 +595,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) mma<T>(c3[rb][jj], a3[rb][kb], bt[kb][2 * h + jj]);
+                    for (int jj = 0; jj < 2; ++jj) mma_chunk<T>(c3[rb][jj], a3[rb][kb], bt[kb][2 * h + jj]);
             u32x4 o[2];
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
@@ -679,7 +623,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
 #pragma unroll
                 for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) mma<T>(acc[half * 4 + rb][jj], a1[rb], o[jj]);
+                    for (int jj = 0; jj < 2; ++jj) mma_chunk<T>(acc[half * 4 + rb][jj], a1[rb], o[jj]);
             }
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {

@@ -26,12 +26,8 @@
 //     slice per pass (see the NEXT branch).
 // HBM traffic per block (64 frames): mid 77 MB + residual 308 MB + out 308 MB; t (77 MB x 2) never leaves the CU.
 // Work-item order: cp360_set_launch_order (descending band order when `reverse`).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
+#include "tile.h"
 
 namespace {
 constexpr int W_STEP = 16 * 1024;                            // conv2 weights per step: 4 fragments for each of the 4 waves
@@ -69,55 +65,6 @@ template <int C_, int N_, int BAND_, int NB> struct BtGeom {
     static_assert(PATCH_PX % PPI == 0 && N % BAND == 0 && PX * T_STRIDE <= PATCH_LDS && KB3 % 4 == 0,
                   "band geometry");
 };
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-__device__ __forceinline__ int w_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename T> __device__ __forceinline__ void mma(f32x4& acc, const u32x4& a, const u32x4& b);
-template <> __device__ __forceinline__ void mma<bf16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma<f16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], bf16_raw) {
-    u32x4 o;
-    o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-    o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-    return o;
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = {(f16_raw)v[0], (f16_raw)v[1], (f16_raw)v[2], (f16_raw)v[3],
-                      (f16_raw)v[4], (f16_raw)v[5], (f16_raw)v[6], (f16_raw)v[7]};
-    return __builtin_bit_cast(u32x4, h);
-}
-__device__ __forceinline__ void unpack8(const u32x4& r, float v[8], bf16_raw) {
-    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-    v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-    v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-__device__ __forceinline__ void unpack8(const u32x4& r, float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = __builtin_bit_cast(f16x8v, r);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
-}
-__host__ __device__ __forceinline__ int row_chan(int R) { return (R & ~31) + ((R >> 2) & 3) * 8 + ((R >> 4) & 1) * 4 + (R & 3); }
 }  // namespace
 
 // conv2 weights [C, C, 3, 3] (times scale) -> MFMA A fragments [channel half hc][step s = tap * SPT + sub][wave 4][i 2][kk 2]
@@ -254,7 +201,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
             if constexpr ((GI) + 1 < KK * NG) CP360_BT_READ(bq[((GI) + 1) & 1], (GI) + 1, POFF, KOFF, SUB)    \
             _Pragma("unroll") for (int i = 0; i < RBW; ++i)                                                   \
                 _Pragma("unroll") for (int u = 0; u < JG; ++u)                                                \
-                    if (j0_ + u < PB) mma<T>(acc[i][j0_ + u], aq[(SLOT) % (DEPTH + 1)][i][kk_], bq[(GI) & 1][u]); \
+                    if (j0_ + u < PB) mma_chunk<T>(acc[i][j0_ + u], aq[(SLOT) % (DEPTH + 1)][i][kk_], bq[(GI) & 1][u]); \
             __builtin_amdgcn_sched_barrier(0);                                                                \
         }
 #define CP360_BT_STEP(S, SLOT, POFF, KOFF, SUB)                                                                \
@@ -376,7 +323,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                     for (int v = 0; v < 4; ++v)
-                        if (j0 + v < PB) mma<T>(acc[rb][j0 + v], a3[rb][kb], b[v]);
+                        if (j0 + v < PB) mma_chunk<T>(acc[rb][j0 + v], a3[rb][kb], b[v]);
                 __builtin_amdgcn_sched_barrier(0);             // keep the next group's fragment reads from being hoisted (spills)
             }
         }
@@ -452,7 +399,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
                     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
-                            if (j0 + u < PB) mma<T>(acc[rb][j0 + u], a3[rb][kb], b[u]);
+                            if (j0 + u < PB) mma_chunk<T>(acc[rb][j0 + u], a3[rb][kb], b[u]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -488,7 +435,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
                     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
-                            if (j0 + u < PB) mma<T>(acc1[rb][j0 + u], a1[rb][kb], b[u]);
+                            if (j0 + u < PB) mma_chunk<T>(acc1[rb][j0 + u], a1[rb][kb], b[u]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }

@@ -24,12 +24,8 @@
 //     convolution) also go to an LDS slice, and after a barrier each wave accumulates its 32 conv1 channels over it (8 A
 //     fragments from L2, 32 MFMAs): layer2.1's conv1 launch (96 us, 308 MB re-read) is gone.
 // HBM traffic (64 frames): mid 308 MB + x 154 MB (every other pixel and row: whole 512-byte pixels) + out 308 MB.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
+#include "tile.h"
 
 namespace {
 constexpr int C = 128, CX = 256, CO = 512, K3 = C + CX;     // conv2 channels, block-input channels, outputs, stage 3's K
@@ -47,43 +43,6 @@ constexpr int LDS_BYTES = OFF_BIAS + (C + CO + C) * 4;        // 77,824: two wor
 constexpr int S_STRIDE = C * 2 + 16;                         // NEXT: pixel stride of the 128-channel slice of `out` (272)
 constexpr int OFF_SLICE = PX * T_STRIDE;                     // behind the stage-3 tile, inside the dead patch
 static_assert(PX * T_STRIDE + PX * S_STRIDE <= PATCH_LDS, "the stage-3 tile and the slice replace the patch");
-
-__device__ __attribute__((aligned(16))) unsigned int f_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-template <typename T> __device__ __forceinline__ void mma(f32x4& acc, const u32x4& a, const u32x4& b);
-template <> __device__ __forceinline__ void mma<bf16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma<f16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], bf16_raw) {
-    u32x4 o;
-    o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-    o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-    return o;
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = {(f16_raw)v[0], (f16_raw)v[1], (f16_raw)v[2], (f16_raw)v[3],
-                      (f16_raw)v[4], (f16_raw)v[5], (f16_raw)v[6], (f16_raw)v[7]};
-    return __builtin_bit_cast(u32x4, h);
-}
-__host__ __device__ __forceinline__ int row_chan(int R) { return (R & ~31) + ((R >> 2) & 3) * 8 + ((R >> 4) & 1) * 4 + (R & 3); }
 }  // namespace
 
 // [W3 * s3 | Wd * sd] (f32 [512, 128] and [512, 256]) -> MFMA A fragments of the K = 384 stage-3 convolution, 1 KiB each
@@ -133,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll 1
         for (int inst = w4; inst < PATCH_INST; inst += 4) {
             const int q = inst * 4 + (lane >> 4);
-            const void* src = f_zero16;
+            const void* src = g_zero16;
             if (q < PATCH_PX) {
                 const int pr = q / NPI, pc = q - pr * NPI;
                 const int sp = cubepad_src(f, 2 * BAND * band + pr, pc, geom);
@@ -205,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < PB; ++j) mma<T>(acc[i][j], aq[s % (DEPTH + 1)][i][kk], bq[hs & 1][j]);
+            for (int j = 0; j < PB; ++j) mma_chunk<T>(acc[i][j], aq[s % (DEPTH + 1)][i][kk], bq[hs & 1][j]);
         __builtin_amdgcn_sched_barrier(0);
     }
     // ---- stage 2: every wave is done with the patch: the stage-3 tile [64 px][128 t | 256 x] takes its place
@@ -289,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                    for (int j = 0; j < PB; ++j) mma<T>(acc[rb][j], a3[rb][kb], b3[kbg & 1][j]);
+                    for (int j = 0; j < PB; ++j) mma_chunk<T>(acc[rb][j], a3[rb][kb], b3[kbg & 1][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (u + 1 < PASSES * H3) {
@@ -325,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-                    for (int j = 0; j < PB; ++j) mma<T>(acc1[rb][j], a1[rb][kb], b[j]);
+                    for (int j = 0; j < PB; ++j) mma_chunk<T>(acc1[rb][j], a1[rb][kb], b[j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

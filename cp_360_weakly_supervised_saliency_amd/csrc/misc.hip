@@ -1,6 +1,6 @@
 // HBM-bound glue kernels of the fused pipeline: CubePad+max-pool (K3b), layout / dtype
 // conversion at the module boundary, window min/max + normalise (K7).
-#include "common.h"
+#include "tile.h"
 
 template <typename T> __device__ __forceinline__ float ld_f32(const T* p);
 template <> __device__ __forceinline__ float ld_f32<float>(const float* p) { return *p; }
@@ -49,7 +49,6 @@ __global__ __launch_bounds__(256) void cubepad_maxpool_kernel(const T* __restric
 
 // 16-bit types with C % 8 == 0: a thread owns 8 channels = one 16-byte piece (half the index
 // arithmetic of the 4-channel form per byte moved, 16-byte loads / stores).
-typedef __attribute__((ext_vector_type(4))) unsigned int mp_u32x4;
 template <typename T>
 __global__ __launch_bounds__(256) void cubepad_maxpool16_kernel(const T* __restrict__ x, T* __restrict__ y, int n6, int n,
                                                                 int C, int ho, int reverse) {
@@ -71,11 +70,11 @@ __global__ __launch_bounds__(256) void cubepad_maxpool16_kernel(const T* __restr
         const int oy = (int)(t % ho);
         const int img = (int)(t / ho);
         const int grp = img / 6, f = img - grp * 6;
-        mp_u32x4 v[9];
+        u32x4 v[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int s = cubepad_src(f, oy * 2 + k / 3, ox * 2 + k % 3, g);
-            v[k] = *reinterpret_cast<const mp_u32x4*>(x + ((size_t)grp * 6 * n * n + s) * C + c);
+            v[k] = *reinterpret_cast<const u32x4*>(x + ((size_t)grp * 6 * n * n + s) * C + c);
         }
         float m[8];
 #pragma unroll
@@ -86,11 +85,11 @@ __global__ __launch_bounds__(256) void cubepad_maxpool16_kernel(const T* __restr
 #pragma unroll
             for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], ld_f32<T>(pv + e));
         }
-        mp_u32x4 o;
+        u32x4 o;
         T* po = reinterpret_cast<T*>(&o);
 #pragma unroll
         for (int e = 0; e < 8; ++e) st_f32<T>(po + e, m[e]);      // max of representable values: exact
-        *reinterpret_cast<mp_u32x4*>(y + (size_t)(t * ho + ox) * C + c) = o;
+        *reinterpret_cast<u32x4*>(y + (size_t)(t * ho + ox) * C + c) = o;
     }
 }
 
@@ -180,7 +179,6 @@ static int transpose_dispatch(const void* x, void* y, int N, int R, int Cc, size
     return CP360_ERR_BAD_DTYPE;
 }
 
-static int elem_sz(int dtype) { return dtype == CP360_F32 ? 4 : ((dtype == CP360_BF16 || dtype == CP360_F16) ? 2 : 0); }
 
 extern "C" int cp360_nchw_to_nhwc(const void* x, void* y, int N, int C, int H, int W, int in_dtype, int out_dtype,
                                   int ld_y, int y_coff, void* stream) {
@@ -188,7 +186,7 @@ extern "C" int cp360_nchw_to_nhwc(const void* x, void* y, int N, int C, int H, i
     if (ld_y < C + y_coff || y_coff < 0) return CP360_ERR_BAD_SHAPE;
     const size_t hw = (size_t)H * W;
     // x[n][c][hw] -> y[n][hw][ld_y] (+ y_coff)
-    void* yb = y ? (void*)((char*)y + (size_t)y_coff * elem_sz(out_dtype)) : y;
+    void* yb = y ? (void*)((char*)y + (size_t)y_coff * elem_bytes(out_dtype)) : y;
     return transpose_dispatch(x, yb, N, C, (int)hw, (size_t)C * hw, hw, hw * ld_y, (size_t)ld_y, in_dtype, out_dtype,
                               (hipStream_t)stream);
 }
@@ -198,7 +196,7 @@ extern "C" int cp360_nhwc_to_nchw(const void* x, void* y, int N, int C, int H, i
     if (ld_x < C + x_coff || x_coff < 0) return CP360_ERR_BAD_SHAPE;
     const size_t hw = (size_t)H * W;
     // x[n][hw][ld_x] (+ x_coff) -> y[n][c][hw]
-    const void* xb = x ? (const void*)((const char*)x + (size_t)x_coff * elem_sz(in_dtype)) : x;
+    const void* xb = x ? (const void*)((const char*)x + (size_t)x_coff * elem_bytes(in_dtype)) : x;
     return transpose_dispatch(xb, y, N, (int)hw, C, hw * ld_x, (size_t)ld_x, (size_t)C * hw, hw, in_dtype, out_dtype,
                               (hipStream_t)stream);
 }
@@ -390,11 +388,8 @@ extern "C" int cp360_window_normalize_frames(const float* x, const float* minmax
 // that nothing else reads; no output of the library is computed from them.  bench.py reports the median over workgroups as
 // `held_clock_ghz`, so two driver runs on different boxes can be told apart.
 __global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long* __restrict__ stamps, int iters) {
-    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-    typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
     const unsigned tid = threadIdx.x + blockIdx.x * 256u;
-    u32x4_t a[4], b[4];
+    u32x4 a[4], b[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -405,11 +400,11 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long* __
             a[i][e] = 0x3F803F80u | (h & 0x807F807Fu);
             b[i][e] = 0x3F803F80u | ((h * 0xC2B2AE35u) & 0x807F807Fu);
         }
-    f32x4_t acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
 #pragma unroll 1
@@ -418,7 +413,7 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long* __
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[i]), __builtin_bit_cast(bf16x8_t, b[j]),
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[i]), __builtin_bit_cast(bf16x8, b[j]),
                                                                     acc[i][j], 0, 0, 0);
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();

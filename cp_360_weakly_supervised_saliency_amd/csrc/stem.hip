@@ -14,12 +14,8 @@
 // Wave w computes output row w of the band: 112 pixels x 64 channels = 7 x 4 MFMA tiles, 7 k-steps.
 // Epilogue: bias + ReLU, one rounding, 16-byte pieces straight to global (acc_chan row order: a lane
 // holds 8 consecutive channels), 128 contiguous bytes per pixel.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
+#include "tile.h"
 
 namespace {
 // Geometry per cube size.  BAND output rows per workgroup, WPR waves per output row (8 waves in all): cube 224 ->
@@ -38,45 +34,6 @@ template <int CD_> struct StemGeom {
     static_assert(WO % (16 * WPR) == 0 && WO % BAND == 0, "cube size");
 };
 constexpr int W_BYTES = 7 * 64 * 64;                         // [ky][64 rows][32 k] 16-bit
-
-__device__ __attribute__((aligned(16))) unsigned int s_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-__device__ __forceinline__ int w_swz(int row, int chunk) {   // 64-byte weight rows: as the ring kernel's stages
-    return row * 64 + ((chunk ^ ((0 - (row >> 2)) & 3)) << 4);
-}
-template <typename T> __device__ __forceinline__ void mma(f32x4& acc, const u32x4& a, const u32x4& b);
-template <> __device__ __forceinline__ void mma<bf16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma<f16_raw>(f32x4& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], bf16_raw) {
-    u32x4 o;
-    o.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    o.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    o.z = (unsigned)f32_to_bf16(v[4]) | ((unsigned)f32_to_bf16(v[5]) << 16);
-    o.w = (unsigned)f32_to_bf16(v[6]) | ((unsigned)f32_to_bf16(v[7]) << 16);
-    return o;
-}
-__device__ __forceinline__ u32x4 pack8(const float v[8], f16_raw) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8v;
-    const f16x8v h = {(f16_raw)v[0], (f16_raw)v[1], (f16_raw)v[2], (f16_raw)v[3],
-                      (f16_raw)v[4], (f16_raw)v[5], (f16_raw)v[6], (f16_raw)v[7]};
-    return __builtin_bit_cast(u32x4, h);
-}
 }  // namespace
 
 // packed stem weights: [ky][row r][k] with row r <- channel acc_chan order (row 32q + 16b + 4g + e holds
@@ -121,7 +78,7 @@ __global__ __launch_bounds__(512, 2) void stem_kernel(const T* __restrict__ xp, 
             const int inst = wave + 8 * q;
             if (inst < PATCH_INST) {
                 const int off = inst * 1024 + lane * 16;
-                const void* src = off < PATCH_BYTES ? (const void*)(src0 + off) : (const void*)s_zero16;
+                const void* src = off < PATCH_BYTES ? (const void*)(src0 + off) : (const void*)g_zero16;
                 glds16(src, __builtin_amdgcn_readfirstlane(lds_base + W_BYTES + b * PATCH_LDS + inst * 1024));
             }
         }
@@ -170,13 +127,13 @@ __global__ __launch_bounds__(512, 2) void stem_kernel(const T* __restrict__ xp, 
             u32x4 a[4], b[MJ];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                a[i] = *reinterpret_cast<const u32x4*>(lds + w_swz(ky * 64 + i * 16 + lrow, lchunk));
+                a[i] = *reinterpret_cast<const u32x4*>(lds + lds_swz64(ky * 64 + i * 16 + lrow, lchunk));
 #pragma unroll
             for (int j = 0; j < MJ; ++j) b[j] = *reinterpret_cast<const u32x4*>(P + ky * ROW_BYTES + j * 256);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < MJ; ++j) mma<T>(acc[i][j], a[i], b[j]);
+                for (int j = 0; j < MJ; ++j) mma_chunk<T>(acc[i][j], a[i], b[j]);
         }
         // epilogue: output row (band*8 + wave) of image img
         const int tt = reverse ? ntiles - 1 - t : t;
@@ -276,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool4_kernel(const T* __restrict_
             if (inst < SQ_PATCH_INST) {
                 const int off = inst * 1024 + lane * 16;
                 const bool ok = off < SQ_PATCH_BYTES && (band > 0 || off >= 2 * ROW_BYTES);
-                const void* src = ok ? (const void*)(src0 + off) : (const void*)s_zero16;
+                const void* src = ok ? (const void*)(src0 + off) : (const void*)g_zero16;
                 glds16(src, __builtin_amdgcn_readfirstlane(lds_base + OFF_PATCH + inst * 1024));
             }
         }
@@ -313,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool4_kernel(const T* __restrict_
         auto load_w = [&](int ky, u32x4 (&a)[4]) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                a[i] = *reinterpret_cast<const u32x4*>(lds + w_swz(ky * 64 + i * 16 + lrow, lchunk));
+                a[i] = *reinterpret_cast<const u32x4*>(lds + lds_swz64(ky * 64 + i * 16 + lrow, lchunk));
         };
 #pragma unroll 1
         for (int ky = 0; ky < 7; ++ky) {
@@ -326,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool4_kernel(const T* __restrict_
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int u = 0; u < 9; ++u) mma<T>(acc[i][u], a[i], b[u]);
+                for (int u = 0; u < 9; ++u) mma_chunk<T>(acc[i][u], a[i], b[u]);
         }
         __syncthreads();                                           // every wave is done reading the patch
         // ---- bias + ReLU + one rounding; border copies; horizontal 3-maximum; pooled rows / halo row -> LDS

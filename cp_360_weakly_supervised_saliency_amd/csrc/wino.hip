@@ -34,16 +34,6 @@ struct WinoK {
 __device__ __forceinline__ bool wino_dead_row(int pos, int ty, int th) { return (pos >> 2) == 3 && ty == th - 1; }
 __device__ __forceinline__ bool wino_dead_col(int pos, int tx, int th) { return (pos & 3) == 3 && tx == th - 1; }
 
-__device__ __forceinline__ int swz64(int row, int chunk) { return row * 64 + ((chunk ^ ((0 - (row >> 2)) & 3)) << 4); }
-
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void vm_wait_upto(int n);
-template <> __device__ __forceinline__ void vm_wait_upto<0>(int) { vm_wait<0>(); }
-template <int N> __device__ __forceinline__ void vm_wait_upto(int n) {
-    if (n >= N) vm_wait<N>();
-    else vm_wait_upto<N - 1>(n);
-}
-
 #ifdef WINO_LAB
 // the A/B laboratory's form of this section (every knob, the timing ablations, the in-kernel stamps): tools/lab/wino_lab.h, used
 // only by tools/wino_variants.sh / wino_stamps.sh / wino_cell_ab.sh - never by the Makefile
@@ -144,9 +134,9 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
         const unsigned char* As = lds + stage * WG_STAGE;                                                  \
         const unsigned char* Bs = As + WG_BN * 64;                                                         \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                      \
-            a[i] = *reinterpret_cast<const u32x4*>(As + swz64(wch0 + i * 16 + lrow, lchunk));              \
+            a[i] = *reinterpret_cast<const u32x4*>(As + lds_swz64(wch0 + i * 16 + lrow, lchunk));          \
         _Pragma("unroll") for (int j = 0; j < JH; ++j)                                                     \
-            b[j] = *reinterpret_cast<const u32x4*>(Bs + swz64(wrow0 + j * 16 + lrow, lchunk));             \
+            b[j] = *reinterpret_cast<const u32x4*>(Bs + lds_swz64(wrow0 + j * 16 + lrow, lchunk));         \
         if (REFILL) {                                                                                      \
             refill_begin(stage == 0 ? NS - 1 : stage - 1);                                                 \
             _Pragma("unroll") for (int u = 0; u < NU; ++u) dma(u);                                         \
@@ -155,7 +145,7 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
         if (LAG) __builtin_amdgcn_s_setprio(1);                                                            \
         _Pragma("unroll") for (int j = 0; j < JH; ++j) {                                                   \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) mma_chunk<T>(acc[i][j], a[i], b[j]);             \
-            b[j] = *reinterpret_cast<const u32x4*>(Bs + swz64(wrow0 + (JH + j) * 16 + lrow, lchunk));      \
+            b[j] = *reinterpret_cast<const u32x4*>(Bs + lds_swz64(wrow0 + (JH + j) * 16 + lrow, lchunk));  \
         }                                                                                                  \
         if (LAG) __builtin_amdgcn_s_setprio(0);                                                            \
         stage = stage == NS - 1 ? 0 : stage + 1;                                                           \
@@ -179,11 +169,11 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
     // vmcnt (DMAs complete in issue order): before sub-step `it` its stage must have landed; younger are the NS - 2 stages behind it
     int it = 0;
     for (; it + NS - 1 < nsub; ++it) {
-        vm_wait<(NS - 2) * NU>();
+        wait_vmcnt<(NS - 2) * NU>();
         WINO_STEP(true)
     }
     for (; it < nsub; ++it) {
-        vm_wait_upto<(NS - 2) * NU>(min(NS - 2, nsub - 1 - it) * NU);
+        wait_vmcnt_upto<(NS - 2) * NU>(min(NS - 2, nsub - 1 - it) * NU);
         WINO_STEP(false)
     }
     if (LAG) WINO_TAIL()
@@ -523,7 +513,6 @@ __global__ __launch_bounds__(768, TH == 4 ? 6 : 5) void wino_out_in_kernel(const
 
 // The Gates convolution's output transform + the cell update of model/clstm.py:68-80 (gate order in, remember, out, cell),
 // with the optional window normalisation of the NEXT frame into the x half (as lstm_gates_kernel, conv_igemm.hip).
-__device__ __forceinline__ float wsigmoid(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // A block = 64 (tile, 4-channel group) items x 4 waves.  Wave k brings in gate k's 16 positions of every item (1 KiB contiguous
 // per position and wave: 16 independent loads in flight per lane - with one thread per item doing all four gates the launch
@@ -564,7 +553,7 @@ __global__ __launch_bounds__(256, 6) void wino_gates_kernel(const float* __restr
     float cn[4], hn[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float ig = wsigmoid(gi[e]), fg = wsigmoid(gf[e]), og = wsigmoid(go[e]);
+        const float ig = fast_sigmoid(gi[e]), fg = fast_sigmoid(gf[e]), og = fast_sigmoid(go[e]);
         const float cg = tanhf(gc[e]);
         cn[e] = fg * cp[e] + ig * cg;
         hn[e] = og * tanhf(cn[e]);

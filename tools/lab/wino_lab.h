@@ -179,9 +179,9 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
         const unsigned char* As = lds + stage * WG_STAGE;                                                  \
         const unsigned char* Bs = As + WG_BN * 64;                                                         \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                      \
-            a[i] = *reinterpret_cast<const u32x4*>(As + swz64(wch0 + i * 16 + lrow, lchunk));              \
+            a[i] = *reinterpret_cast<const u32x4*>(As + lds_swz64(wch0 + i * 16 + lrow, lchunk));          \
         _Pragma("unroll") for (int j = 0; j < JH; ++j)                                                     \
-            b[j] = *reinterpret_cast<const u32x4*>(Bs + swz64(wrow0 + j * 16 + lrow, lchunk));             \
+            b[j] = *reinterpret_cast<const u32x4*>(Bs + lds_swz64(wrow0 + j * 16 + lrow, lchunk));         \
         if (LOADER && REFILL && (WINO_DMA_PLACE == 0 || !LAG)) refill_begin(stage == 0 ? NS - 1 : stage - 1); \
         if (LOADER && REFILL && WINO_DMA_PLACE == 0) {                                                     \
             _Pragma("unroll") for (int u = 0; u < NU; ++u) dma(u);                                         \
@@ -190,7 +190,7 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
         if (WINO_HEAD_PRIO > 0 && LAG) __builtin_amdgcn_s_setprio(WINO_HEAD_PRIO);                         \
         _Pragma("unroll") for (int j = 0; j < JH; ++j) {                                                   \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) WINO_MMA(acc[i][j], a[i], b[j]);                 \
-            b[j] = *reinterpret_cast<const u32x4*>(Bs + swz64(wrow0 + (JH + j) * 16 + lrow, lchunk));      \
+            b[j] = *reinterpret_cast<const u32x4*>(Bs + lds_swz64(wrow0 + (JH + j) * 16 + lrow, lchunk));  \
         }                                                                                                  \
         if (WINO_HEAD_PRIO > 0 && LAG) __builtin_amdgcn_s_setprio(0);                                      \
         stage = stage == NS - 1 ? 0 : stage + 1;                                                           \
@@ -227,11 +227,11 @@ __device__ __forceinline__ void gemm_body(const WinoK& p, unsigned char* lds, co
     int it = 0;
     for (; it + NS - 1 < nsub; ++it) {
         WINO_STAMP(0)
-        if (LOADER) vm_wait<(NS - 2) * NU>();
+        if (LOADER) wait_vmcnt<(NS - 2) * NU>();
         WINO_STEP(true)
     }
     for (; it < nsub; ++it) {
-        if (LOADER) vm_wait_upto<(NS - 2) * NU>(min(NS - 2, nsub - 1 - it) * NU);
+        if (LOADER) wait_vmcnt_upto<(NS - 2) * NU>(min(NS - 2, nsub - 1 - it) * NU);
         WINO_STEP(false)
     }
     if (LAG) WINO_TAIL(false)
