@@ -37,5 +37,5 @@ template <> struct Elem<f16_raw> { static constexpr int EPC = 8; };
 #define CP360_SMALL_MAX_TAPS 16
 
 // conv_small.hip: the 64 x 64-tile kernel for launches whose pixel count cannot fill the chip with the big tiles
-// (k.nt / k.mt / k.m_fast are set inside).  dtype: CP360_F32 / CP360_BF16 / CP360_F16.
-void cp360_launch_conv_small(ConvK& k, int dtype, hipStream_t st);
+// (k.nt / k.mt / k.m_fast: 64 x 64 tiles, from resolve_launch of conv_igemm.hip).  dtype: CP360_F32 / CP360_BF16 / CP360_F16.
+void cp360_launch_conv_small(const ConvK& k, int dtype, hipStream_t st);

@@ -9,7 +9,7 @@
 // The CubePad(p) in front of every 3x3 conv (cube_pad.py:95-216) is NOT materialised:
 // src(m, tap) goes through cubepad_src() while the activation tile is gathered.
 //
-// Kernels in this file (the launch planner plan_of() picks one per call):
+// Kernels in this file (resolve_launch() picks one per call):
 //   conv_igemm_kernel<T,WN,WM>   c_out < 256: 128x128 / 64x256 tile, 4 waves, register-staged (described below)
 //   conv_igemm_dma_kernel<T,4>   c_out >= 256, small M: 256x128 tile, three LDS-DMA stages
 //   conv_igemm_ring_kernel<T,BM> c_out >= 256: 256x256 / 256x304 tile, four 64-byte-K stages, staggered waves
@@ -243,10 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
     // Placement only affects speed, never results (bijective map, any placement valid).
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -463,10 +460,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     const int wn = wave >> 1, wm = wave & 1;
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -926,10 +920,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_ring_kernel(const ConvK p) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -976,10 +967,7 @@ __global__ __launch_bounds__(512, 4) void conv_igemm_ring2_kernel(const ConvK p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -1388,10 +1376,7 @@ __global__ __launch_bounds__(512, 2) void conv_clip_kernel(const ConvK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, clip, split;
     {   // XCD-aware mapping, clips fastest: the workgroups of one (channel tile, split) share the weight stream
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         clip = w % p.mt;
         const int rest = w / p.mt;
         n0 = (rest % p.nt) * G::BN;
@@ -1574,7 +1559,7 @@ static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static int c_pad2_of(const cp360_conv_desc* d) { return d->c_in2 > 0 ? round_up(d->c_in2, bk_of(d->dtype)) : 0; }
 
 // What conv_small_kernel (csrc/conv_small.hip) requires of a descriptor - ONE predicate for the planner (small_eligible) and
-// for a caller that forces the tile (tile_px == 6464, check_desc): shape limits -> UNSUPPORTED, alignment of its 16-byte
+// for a caller that forces the small tile (check_desc): shape limits -> UNSUPPORTED, alignment of its 16-byte
 // output / residual accesses in the 16-bit types -> ALIGN.
 static int small_shape_status(const cp360_conv_desc* d) {
     if (d->clip_resident || d->c_out % 8 != 0) return CP360_ERR_UNSUPPORTED;
@@ -1656,20 +1641,48 @@ extern "C" size_t cp360_conv_partial_bytes(const cp360_conv_desc* d) {
 // 256x128 (one 8-wave workgroup per CU) and 1.5 us for the 4-wave tiles (two per CU); f32
 // steps are MFMA-bound and about 3x longer.  A launch runs ceil(workgroups / slots) rounds
 // of (fixed cost + steps x step cost); split-K adds the f32 slab round trip through HBM.
+//
+// Every kernel a convolution can be launched on, and one table row for each: the name cp360_conv_plan_describe prints, the
+// tile (output channels x pixels) and the resident workgroups of the chip the cost model counts rounds with.  A new kernel
+// variant is one enumerator, one row, its rule in resolve_launch and its case in cp360_conv_forward2's switch.
+enum ConvKernel {
+    K_CLIP_CUBE, K_CLIP_FACE, K_CLIP_HALF, K_SMALL, K_PW64, K_NARROW, K_T128, K_DMA, K_RING160, K_RING256, K_RING304, K_RING2
+};
+struct ConvKernelInfo {
+    const char* name;
+    int bn, bm, slots;
+};
+static const ConvKernelInfo kConvKernels[] = {
+    /* K_CLIP_CUBE */ {"conv_clip 256 ch x one cube (activations LDS-resident)", 256, 304, 256},
+    /* K_CLIP_FACE */ {"conv_clip 256 ch x one 16x16 face (activations LDS-resident)", 256, 256, 256},
+    /* K_CLIP_HALF */ {"conv_clip 256 ch x half a cube of 8x8 faces (the cube LDS-resident)", 256, 192, 256},
+    /* K_SMALL     */ {"conv_small 64 ch x 64 px (8 waves)", 64, 64, 1024},
+    /* K_PW64      */ {"conv_pw64 64 ch x 16 px blocks, grid-stride (4 waves)", 64, 16, 2048},
+    /* K_NARROW    */ {"conv_igemm 64 ch x 256 px (4 waves)", 64, 256, 512},
+    /* K_T128      */ {"conv_igemm 128 ch x 128 px (4 waves)", 128, 128, 512},
+    /* K_DMA       */ {"conv_igemm_dma 256 ch x 128 px", 256, 128, 256},
+    /* K_RING160   */ {"conv_igemm_ring 256 ch x 160 px", 256, 160, 256},
+    /* K_RING256   */ {"conv_igemm_ring 256 ch x 256 px", 256, 256, 256},
+    /* K_RING304   */ {"conv_igemm_ring 256 ch x 304 px", 256, 304, 256},
+    /* K_RING2     */ {"conv_igemm_ring2 256 ch x 128 px (two workgroups per CU)", 256, 128, 512},
+};
+
 struct ConvPlan {
-    int bn, bm, slots, splits;
+    ConvKernel kernel;
+    int splits;
     double cost;
     long long wgs = 0;           // workgroups of the launch (tiles x splits)
 };
 
-static ConvPlan plan_candidate(const cp360_conv_desc* d, int bn, int bm, int slots, double t_step) {
+static ConvPlan plan_candidate(const cp360_conv_desc* d, ConvKernel kernel, double t_step) {
+    const int bn = kConvKernels[kernel].bn, bm = kConvKernels[kernel].bm, slots = kConvKernels[kernel].slots;
     const long long M = (long long)d->n_img * d->h_out * d->w_out;
     const long long wgs = ((d->c_out + bn - 1) / bn) * ((M + bm - 1) / bm);
     const int bk = bk_of(d->dtype);
     const int nsteps = d->kh * d->kw * (round_up(d->c_in, bk) / bk) + c_pad2_of(d) / bk;
     if (d->dtype == CP360_F32) t_step *= 3.0;
     const double t_fixed = 4.0;
-    ConvPlan best{bn, bm, slots, 1, 0.0};
+    ConvPlan best{kernel, 1, 0.0};
     for (int s = 1; s <= 32; ++s) {
         if (s > 1 && nsteps / s < 8) break;
         const long long rounds = (wgs * s + slots - 1) / slots;
@@ -1689,7 +1702,7 @@ static ConvPlan plan_candidate(const cp360_conv_desc* d, int bn, int bm, int slo
 // K step (128 bytes per tile row: 16 KB into the CU, 1024 MFMA cycles per SIMD) takes 0.70 us per workgroup on a CU - the
 // CU's ~10 bytes / clock of global-load throughput, not the matrix pipe (0.43 us), is what a step waits for - so a launch
 // costs about (workgroups per CU) x steps x 0.7 us + a fixed 3 us per wave of 1024 workgroups.
-// The planner offers them to f32 only; a 16-bit launch reaches them when its caller forces tile_px 6464.
+// The planner offers them to f32 only; a 16-bit launch reaches them when its caller forces the small tile.
 static bool small_eligible(const cp360_conv_desc* d) {
     return d->dtype == CP360_F32 && small_shape_status(d) == CP360_OK;
 }
@@ -1700,7 +1713,7 @@ static ConvPlan plan_small(const cp360_conv_desc* d) {
     const int bk = bk_of(d->dtype);
     const int nsteps = d->kh * d->kw * (round_up(d->c_in, bk) / bk) + c_pad2_of(d) / bk;
     const double t_step = d->dtype == CP360_F32 ? 0.7 : 0.35;
-    ConvPlan best{64, 64, 1024, 1, 0.0};
+    ConvPlan best{K_SMALL, 1, 0.0};
     for (int s = 1; s <= 32; ++s) {
         if (s > 1 && nsteps / s < 4) break;
         const long long W = tiles * s;
@@ -1717,95 +1730,147 @@ static ConvPlan plan_small(const cp360_conv_desc* d) {
     return best;
 }
 
-static ConvPlan plan_big(const cp360_conv_desc* d);
 // pixel tiles of the clip-resident kernel: a face at 16x16, half a cube at 8x8, otherwise a cube
 static int clip_tiles(const cp360_conv_desc* d) { return d->h_in == 16 ? d->n_img : d->h_in == 8 ? d->n_img / 3 : d->n_img / 6; }
 
-static ConvPlan plan_of(const cp360_conv_desc* d) {
-    ConvPlan best = plan_big(d);
-    if (d->tile_px == 6464) return plan_small(d);
-    if (d->tile_px == 0 && small_eligible(d)) {
-        // the small tiles when the model says so - or when the best big-tile launch cannot even give every CU a workgroup
-        // (the two cost models are calibrated separately, and the big-tile one is optimistic exactly there: layer1's conv3
-        // + downsample of ONE frame: modelled 19 us on 147 workgroups, measured 47; the small tiles: 21)
-        const ConvPlan sm = plan_small(d);
-        if (sm.cost < best.cost || best.wgs < 256) best = sm;
+// the clip-resident kernel (cp360_conv_desc.clip_resident)
+static ConvPlan plan_clip(const cp360_conv_desc* d) {
+    // one 256-channel x clip tile per workgroup, 64-byte sub-steps; about 0.9 us per sub-step
+    const int wgs = ((d->c_out + 255) / 256) * clip_tiles(d);
+    const int nsub = 9 * (c_pad_of(d) / (bk_of(d->dtype) / 2));
+    const double t_sub = (d->dtype == CP360_F32 ? 2.7 : 0.9) * (d->h_in == 8 ? 0.7 : 1.0);   // (6 + 6 instead of 10 + 9 pixel blocks)
+    const long long M = (long long)d->n_img * d->h_out * d->w_out;
+    ConvPlan best{d->h_in == 16 ? K_CLIP_FACE : d->h_in == 8 ? K_CLIP_HALF : K_CLIP_CUBE, 1, 0.0};
+    for (int s = 1; s <= 32; ++s) {
+        if (s > 1 && nsub / s < 16) break;
+        const int rounds = (wgs * s + 255) / 256;
+        double cost = (double)rounds * (4.0 + (double)((nsub + s - 1) / s) * t_sub);
+        if (s > 1) cost += 4.0 + (double)s * (double)M * d->c_out * 8.0 / 4.0e6;
+        if (s == 1 || cost < best.cost) {
+            best.splits = s;
+            best.cost = cost;
+            best.wgs = (long long)wgs * s;
+        }
     }
     return best;
 }
 
+// the generic kernels of this file (tap-major weights)
 static ConvPlan plan_big(const cp360_conv_desc* d) {
-    if (d->clip_resident) {
-        // one 256-channel x clip tile per workgroup, 64-byte sub-steps; about 0.9 us per sub-step
-        const int wgs = ((d->c_out + 255) / 256) * clip_tiles(d);
-        const int nsub = 9 * (c_pad_of(d) / (bk_of(d->dtype) / 2));
-        const double t_sub = (d->dtype == CP360_F32 ? 2.7 : 0.9) * (d->h_in == 8 ? 0.7 : 1.0);   // (6 + 6 instead of 10 + 9 pixel blocks)
-        const long long M = (long long)d->n_img * d->h_out * d->w_out;
-        ConvPlan best{256, 304, 256, 1, 0.0};
-        for (int s = 1; s <= 32; ++s) {
-            if (s > 1 && nsub / s < 16) break;
-            const int rounds = (wgs * s + 255) / 256;
-            double cost = (double)rounds * (4.0 + (double)((nsub + s - 1) / s) * t_sub);
-            if (s > 1) cost += 4.0 + (double)s * (double)M * d->c_out * 8.0 / 4.0e6;
-            if (s == 1 || cost < best.cost) {
-                best.splits = s;
-                best.cost = cost;
-                best.wgs = (long long)wgs * s;
-            }
-        }
-        return best;
-    }
-    if (d->c_out <= 64) return plan_candidate(d, 64, 256, 512, 1.5);
-    if (d->c_out < 256) return plan_candidate(d, 128, 128, 512, 1.5);
-    ConvPlan best = plan_candidate(d, 256, 256, 256, 2.2);
-    const ConvPlan b = plan_candidate(d, 256, 128, 256, 1.25);
+    if (d->c_out <= 64) return plan_candidate(d, K_NARROW, 1.5);
+    if (d->c_out < 256) return plan_candidate(d, K_T128, 1.5);
+    ConvPlan best = plan_candidate(d, K_RING256, 2.2);
+    const ConvPlan b = plan_candidate(d, K_DMA, 1.25);
     if (b.cost < best.cost) best = b;
-    const ConvPlan c = plan_candidate(d, 256, 304, 256, 2.2 * 304.0 / 256.0);   // 19 pixel blocks: 7x7 cube faces
+    const ConvPlan c = plan_candidate(d, K_RING304, 2.2 * 304.0 / 256.0);   // 19 pixel blocks: 7x7 cube faces
     if (c.cost < best.cost) best = c;
     // 160-pixel tile (16-bit types): wins where the larger tiles cannot give every CU a workgroup
     if (d->dtype != CP360_F32 && d->c_in2 == 0) {
-        const ConvPlan t160 = plan_candidate(d, 256, 160, 256, 2.2 * 176.0 / 256.0);
+        const ConvPlan t160 = plan_candidate(d, K_RING160, 2.2 * 176.0 / 256.0);
         if (t160.cost < best.cost) best = t160;
     }
-    // short-K 1x1 convolutions (HBM-bound): 256x128 tile with two workgroups per CU (pixel tile id 129)
+    // short-K 1x1 convolutions (HBM-bound): 256x128 tile with two workgroups per CU (conv_igemm_ring2_kernel)
     // (K of at least two 128-byte steps: at K = 64 elements the one-workgroup 256x304 tile measured faster)
     // K of at most four 128-byte steps.  (Up to 1 KiB it used to take the HBM-bound 1x1 convolutions of layers 2-4;
     // measured per launch, 64 frames: l2.0 conv3 + downsample (K = 768 B) 232 -> 199 us on the 256x304 ring, l3.0
     // conv1 (1 KiB) 153 -> 124, l4 conv3 (1 KiB) 84 -> 71; at 512 B - l3 conv3 - the two tie.)
     const int kbytes = (d->c_in + d->c_in2) * elem_bytes(d->dtype);
     if (d->dtype != CP360_F32 && d->kh * d->kw == 1 && kbytes >= 256 && kbytes <= 512) {
-        ConvPlan r2 = plan_candidate(d, 256, 128, 512, 1.25);
-        r2.bm = 129;
+        const ConvPlan r2 = plan_candidate(d, K_RING2, 1.25);
         if (r2.cost < best.cost) best = r2;
     }
-    // the 3-stage 256x128 DMA kernel has no second-source loader: its ring equivalents take over
-    if (d->c_in2 > 0 && best.bm == 128) best.bm = d->dtype == CP360_F32 ? 256 : 129;
     return best;
 }
 
-// Tile geometry for a given (caller-chosen) split count: same candidates, splits fixed.
-static void tile_of(const cp360_conv_desc* d, int* bn, int* bm, int* slots) {
-    ConvPlan pl = plan_of(d);      // a caller-chosen split count keeps the tile the model prefers at ITS best split
-    *bn = pl.bn;
-    *bm = pl.bm;
-    *slots = pl.slots;
-    if (pl.bm == 64) return;                         // conv_small.hip (chosen by the model or forced by tile_px 6464)
-    if (d->c_out >= 256 && d->tile_px == 64) {       // forced: the 4-wave 128x128 kernel
-        *bn = 128;
-        *bm = 128;
-        *slots = 512;
-    } else if (d->c_out >= 256 && d->tile_px) {
-        *bn = 256;
-        *bm = d->tile_px;
-        *slots = 256;
+// What one call launches.  resolve_launch is the ONLY place that turns a descriptor, its caller's tile_px and its caller's
+// split count into a kernel and a grid: cp360_conv_forward2 launches the record, cp360_conv_plan_describe prints it.
+struct ConvLaunch {
+    ConvKernel kernel;
+    int splits;                  // the split count the cost model prefers (cp360_conv_suggest_splits), not the caller's
+    double cost;                 // the model's microseconds at that split count
+    int nt, mt, m_fast;          // channel tiles, pixel tiles, which of them neighbours share (ConvK)
+    int epi_direct;              // ConvK::epi_direct
+    long long wgs;               // the grid: tiles x the DESCRIPTOR's split count
+};
+
+// plain_call: the caller gives an output tensor and no residual (with splits == 1 that also means no raw f32 sums) - the form
+// the pointwise 64 -> 64 kernel handles; cp360_conv_plan_describe, which has the descriptor alone, assumes it.
+// The model's part (splits, cost) is filled in even where the caller's tile is refused.
+static int resolve_launch(const cp360_conv_desc* d, bool plain_call, ConvLaunch* L) {
+    const long long M = (long long)d->n_img * d->h_out * d->w_out;
+    // ---- the cost model's choice
+    ConvPlan pl;
+    if (d->clip_resident) {
+        pl = plan_clip(d);
+    } else if (d->tile_px == 6464) {                           // ABI value: the small tile, forced
+        pl = plan_small(d);
+    } else {
+        pl = plan_big(d);
+        if (d->tile_px == 0 && small_eligible(d)) {
+            // the small tiles when the model says so - or when the best big-tile launch cannot even give every CU a workgroup
+            // (the two cost models are calibrated separately, and the big-tile one is optimistic exactly there: layer1's conv3
+            // + downsample of ONE frame: modelled 19 us on 147 workgroups, measured 47; the small tiles: 21)
+            const ConvPlan sm = plan_small(d);
+            if (sm.cost < pl.cost || pl.wgs < 256) pl = sm;
+        }
     }
+    L->splits = pl.splits;
+    L->cost = pl.cost;
+    ConvKernel kern = pl.kernel;
+    // ---- the caller's pixel tile (ABI values of cp360_conv_desc.tile_px; a caller-chosen split count keeps the tile the model
+    // prefers at ITS best split).  Below 256 output channels there are only the 4-wave kernels, whatever it asks for.
+    if (d->c_out >= 256) switch (d->tile_px) {
+        case 64:  kern = K_T128; break;                        // the 4-wave 128x128 kernel, two workgroups per CU
+        case 128: kern = K_DMA; break;
+        case 129: kern = K_RING2; break;                       // "256x128, two workgroups per CU"
+        case 160: kern = K_RING160; break;
+        case 256: kern = K_RING256; break;
+        case 304: kern = K_RING304; break;
+        default: break;                                        // 0: the model's; the forced small tile was taken above
+    }
+    // ---- second source: the ring kernels and the small tile have the loader for it.  The 3-stage 256x128 DMA kernel does
+    // not (its K loop would run the extra tap on the first tensor): its ring equivalents take over
+    if (d->c_in2 > 0) {
+        if (kern == K_DMA) kern = d->dtype == CP360_F32 ? K_RING256 : K_RING2;
+        else if (kern == K_T128 || kern == K_RING160) return CP360_ERR_UNSUPPORTED;
+    }
+    // ---- pointwise 64 -> 64 in a 16-bit type (layer1.0's conv1): the streaming kernel (a caller-chosen tile_px keeps the generic one)
+    if (kern == K_NARROW && plain_call && d->dtype != CP360_F32 && d->kh == 1 && d->kw == 1 && d->sy == 1 && d->sx == 1 &&
+        d->pad == 0 && d->c_in == 64 && d->c_out == 64 && d->c_in2 == 0 && d->splits <= 1 && d->tile_px == 0 &&
+        d->pix_stride % 8 == 0 && d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && M >= 4096)
+        kern = K_PW64;
+    L->kernel = kern;
+    // ---- the grid
+    const ConvKernelInfo& t = kConvKernels[kern];
+    L->nt = (d->c_out + t.bn - 1) / t.bn;
+    L->epi_direct = 0;
+    if (d->clip_resident) {
+        L->mt = clip_tiles(d);
+        L->m_fast = 1;                                         // clips fastest: one (channel tile, split) shares the weight stream
+    } else if (kern == K_PW64) {
+        const long long blocks = ((M + 15) / 16 + 7) / 8;      // two passes of PWU blocks per wave at most ...
+        L->mt = (int)(blocks > t.slots ? t.slots : blocks);    // ... and a persistent grid beyond 8 workgroups per CU
+        L->m_fast = 0;
+    } else {
+        L->mt = (int)((M + t.bm - 1) / t.bm);
+        // share whichever operand panel is larger through the XCD's L2
+        const long long k_total = (long long)d->kh * d->kw * c_pad_of(d) + c_pad2_of(d);
+        L->m_fast = ((long long)d->c_out * k_total > M * d->kh * d->kw * d->c_in) ? 1 : 0;
+        // Epilogue of the ring kernels: LDS-staged full-line stores; the direct 16-byte-piece epilogue measured the same on the
+        // big tiles (within 1 %) and is what the two-workgroups-per-CU short-K kernel uses (no LDS left for a staged tile there)
+        if (kern == K_RING2) L->epi_direct = d->c_out % 8 == 0 && d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && d->ld_res % 8 == 0;
+    }
+    L->wgs = (long long)L->nt * L->mt * d->splits;
+    return CP360_OK;
 }
 
 extern "C" int cp360_conv_suggest_splits(const cp360_conv_desc* d) {
     cp360_conv_desc t = *d;
     t.splits = 1;
     if (check_desc(&t)) return 1;
-    return plan_of(&t).splits;
+    ConvLaunch L;
+    resolve_launch(&t, true, &L);                              // (the model's split count stands whatever becomes of the caller's tile)
+    return L.splits;
 }
 
 // For a caller that holds BOTH weight layouts of a CubePad(1) + 3x3 convolution on small faces (layer4's conv2): should this
@@ -1823,7 +1888,7 @@ extern "C" int cp360_conv_prefer_clip(const cp360_conv_desc* d) {
     cp360_conv_desc t = c;
     t.clip_resident = 0;
     if (check_desc(&t) || !small_eligible(&t)) return 1;
-    return plan_big(&c).cost <= plan_small(&t).cost ? 1 : 0;
+    return plan_clip(&c).cost <= plan_small(&t).cost ? 1 : 0;
 }
 
 extern "C" int cp360_conv_plan_describe(const cp360_conv_desc* d, char* buf, size_t cap) {
@@ -1832,32 +1897,12 @@ extern "C" int cp360_conv_plan_describe(const cp360_conv_desc* d, char* buf, siz
     t.splits = 1;
     int rc = check_desc(&t);
     if (rc) return rc;
-    const ConvPlan pl = plan_of(&t);
-    int bn = 0, bm = 0, slots = 0;
-    tile_of(&t, &bn, &bm, &slots);
-    const long long M = (long long)t.n_img * t.h_out * t.w_out;
-    const char* name;
-    long long wgs;
-    if (t.clip_resident) {
-        name = t.h_in == 16 ? "conv_clip 256 ch x one 16x16 face (activations LDS-resident)"
-               : t.h_in == 8 ? "conv_clip 256 ch x half a cube of 8x8 faces (the cube LDS-resident)"
-                             : "conv_clip 256 ch x one cube (activations LDS-resident)";
-        wgs = (long long)((t.c_out + 255) / 256) * clip_tiles(&t);
-    } else if (bm == 64) {
-        name = "conv_small 64 ch x 64 px (8 waves)";
-        wgs = (long long)((t.c_out + 63) / 64) * ((M + 63) / 64);
-    } else if (t.c_out < 256 || bn != 256) {
-        const bool narrow = t.c_out <= 64;
-        name = narrow ? "conv_igemm 64 ch x 256 px (4 waves)" : "conv_igemm 128 ch x 128 px (4 waves)";
-        wgs = narrow ? (long long)((t.c_out + 63) / 64) * ((M + 255) / 256) : (long long)((t.c_out + 127) / 128) * ((M + 127) / 128);
-    } else {
-        const int px = bm == 129 ? 128 : bm;
-        name = bm == 129 ? "conv_igemm_ring2 256 ch x 128 px (two workgroups per CU)"
-               : bm == 304 ? "conv_igemm_ring 256 ch x 304 px" : bm == 160 ? "conv_igemm_ring 256 ch x 160 px" : bm >= 256 ? "conv_igemm_ring 256 ch x 256 px" : "conv_igemm_dma 256 ch x 128 px";
-        wgs = (long long)((t.c_out + 255) / 256) * ((M + px - 1) / px);
-    }
-    const int n = snprintf(buf, cap, "%s, %lld workgroups x split-K %d%s, model %.0f us", name, wgs * pl.splits, pl.splits,
-                           t.c_in2 > 0 ? " (+ second source)" : "", pl.cost);
+    ConvLaunch L;
+    rc = resolve_launch(&t, true, &L);
+    if (rc) return rc;
+    // (L.wgs is the grid at t.splits = 1: the tiles)
+    const int n = snprintf(buf, cap, "%s, %lld workgroups x split-K %d%s, model %.0f us", kConvKernels[L.kernel].name,
+                           L.wgs * L.splits, L.splits, t.c_in2 > 0 ? " (+ second source)" : "", L.cost);
     return n < 0 ? CP360_ERR_BAD_SHAPE : (n >= (int)cap ? (int)cap - 1 : n);
 }
 
@@ -1891,41 +1936,13 @@ static int pack_weights_impl(const cp360_conv_desc* d, const float* w_oihw, cons
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == CP360_F32)
-        hipLaunchKernelGGL((pack_weights_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, w_oihw, scale,
-                           (float*)packed, d->c_out, c_out_pad, d->c_in, c_pad, d->kh, d->kw, stem_mode, d->clip_resident,
-                           w2, scale2, d->c_in2, c_pad2);
-    else if (d->dtype == CP360_F16)
-        hipLaunchKernelGGL((pack_weights_kernel<f16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, w_oihw, scale,
-                           (f16_raw*)packed, d->c_out, c_out_pad, d->c_in, c_pad, d->kh, d->kw, stem_mode, d->clip_resident,
-                           w2, scale2, d->c_in2, c_pad2);
-    else
-        hipLaunchKernelGGL((pack_weights_kernel<bf16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, w_oihw, scale,
-                           (bf16_raw*)packed, d->c_out, c_out_pad, d->c_in, c_pad, d->kh, d->kw, stem_mode, d->clip_resident,
-                           w2, scale2, d->c_in2, c_pad2);
+    with_elem(d->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((pack_weights_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, w_oihw, scale, (T*)packed,
+                           d->c_out, c_out_pad, d->c_in, c_pad, d->kh, d->kw, stem_mode, d->clip_resident, w2, scale2,
+                           d->c_in2, c_pad2);
+    });
     CP360_CHECK_HIP();
-    return CP360_OK;
-}
-
-template <typename T, int WN, int WM>
-static void launch_conv(ConvK& k, hipStream_t st) {
-    k.nt = (k.c_out + WN * 64 - 1) / (WN * 64);
-    k.mt = (k.M + WM * 64 - 1) / (WM * 64);
-    // share whichever operand panel is larger through the XCD's L2
-    k.m_fast = ((long long)k.c_out * k.k_total > (long long)k.M * k.kh * k.kw * k.c_in) ? 1 : 0;
-    dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, WN, WM>), grid, dim3(256), 0, st, k);
-}
-
-// the 8-wave 256-channel kernels: ring tiles of 256 / 304 / 160 (16-bit types only) pixels, the DMA kernel for 128
-template <typename T>
-static int launch_wide(const ConvK& k, int bm, dim3 grid, hipStream_t st) {
-    if (bm == 304) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 304>), grid, dim3(512), 0, st, k);
-    else if (bm == 160) {
-        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 160>), grid, dim3(512), 0, st, k);
-        else return CP360_ERR_UNSUPPORTED;
-    } else if (bm >= 256) hipLaunchKernelGGL((conv_igemm_ring_kernel<T, 256>), grid, dim3(512), 0, st, k);
-    else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4>), grid, dim3(512), 0, st, k);
     return CP360_OK;
 }
 
@@ -1934,8 +1951,9 @@ extern "C" int cp360_conv_forward(const cp360_conv_desc* d, const void* in, cons
     return cp360_conv_forward2(d, in, nullptr, packed_w, bias, residual, out, partial, stream);
 }
 
-extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, const void* in2, const void* packed_w,
-                                   const float* bias, const void* residual, void* out, float* partial, void* stream) {
+// the descriptor and the pointers of one forward call against each other
+static int check_call(const cp360_conv_desc* d, const void* in, const void* in2, const void* packed_w, const void* residual,
+                      const void* out, const float* partial) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!in || !packed_w) return CP360_ERR_NULL;
@@ -1943,6 +1961,16 @@ extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, con
     if (d->splits > 1 && !partial) return CP360_ERR_NULL;
     if (d->splits == 1 && !out && !partial) return CP360_ERR_NULL;
     if (residual && d->ld_res < d->c_out) return CP360_ERR_BAD_SHAPE;
+    return CP360_OK;
+}
+
+extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, const void* in2, const void* packed_w,
+                                   const float* bias, const void* residual, void* out, float* partial, void* stream) {
+    int rc = check_call(d, in, in2, packed_w, residual, out, partial);
+    if (rc) return rc;
+    ConvLaunch L;
+    rc = resolve_launch(d, out && !residual, &L);
+    if (rc) return rc;
     ConvK k;
     k.in = (const unsigned char*)in;
     k.w = (const unsigned char*)packed_w;
@@ -1976,82 +2004,33 @@ extern "C" int cp360_conv_forward2(const cp360_conv_desc* d, const void* in, con
         const size_t wbytes = (size_t)((d->c_out + 255) / 256) * 256 * k.k_total * (d->dtype == CP360_F32 ? 4 : 2);
         k.w_pin = wbytes >= ((size_t)96 << 20) ? 8 : 0x7fffffff;
     }
-    // Epilogue of the ring kernels: LDS-staged full-line stores; the direct 16-byte-piece epilogue measured the same on the
-    // big tiles (within 1 %) and is what the two-workgroups-per-CU short-K kernel uses (no LDS left for a staged tile there)
-    k.epi_direct = 0;
+    k.nt = L.nt; k.mt = L.mt; k.m_fast = L.m_fast; k.epi_direct = L.epi_direct;
+    const dim3 grid((unsigned)L.wgs, 1, 1);
     hipStream_t st = (hipStream_t)stream;
-    if (d->clip_resident) {
-        const int mode = d->h_in == 16 ? 1 : d->h_in == 8 ? 2 : 0;   // tile = a face + its ring / half a cube / a cube
-        k.nt = (k.c_out + 255) / 256;
-        k.mt = clip_tiles(d);
-        k.m_fast = 1;
-        dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-#define CP360_CLIP(TT)                                                                                    \
-        {                                                                                                     \
-            if (mode == 1)      hipLaunchKernelGGL((conv_clip_kernel<TT, 1>), grid, dim3(512), 0, st, k);     \
-            else if (mode == 2) hipLaunchKernelGGL((conv_clip_kernel<TT, 2>), grid, dim3(512), 0, st, k);     \
-            else                hipLaunchKernelGGL((conv_clip_kernel<TT, 0>), grid, dim3(512), 0, st, k);     \
+    rc = with_elem(d->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        auto go = [&](void (*kernel)(const ConvK), int threads) {
+            hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, k);
+            return CP360_OK;
+        };
+        switch (L.kernel) {
+        case K_CLIP_CUBE: return go(conv_clip_kernel<T, 0>, 512);
+        case K_CLIP_FACE: return go(conv_clip_kernel<T, 1>, 512);
+        case K_CLIP_HALF: return go(conv_clip_kernel<T, 2>, 512);
+        case K_SMALL:     cp360_launch_conv_small(k, d->dtype, st); return CP360_OK;
+        case K_NARROW:    return go(conv_igemm_kernel<T, 1, 4>, 256);
+        case K_T128:      return go(conv_igemm_kernel<T, 2, 2>, 256);
+        case K_DMA:       return go(conv_igemm_dma_kernel<T, 4>, 512);
+        case K_RING256:   return go(conv_igemm_ring_kernel<T, 256>, 512);
+        case K_RING304:   return go(conv_igemm_ring_kernel<T, 304>, 512);
+        // the kernels that exist for the 16-bit types only (128-VGPR budget / register-resident filter)
+        case K_RING160:   if constexpr (sizeof(T) == 2) return go(conv_igemm_ring_kernel<T, 160>, 512); else break;
+        case K_RING2:     if constexpr (sizeof(T) == 2) return go(conv_igemm_ring2_kernel<T>, 512); else break;
+        case K_PW64:      if constexpr (sizeof(T) == 2) return go(conv_pw64_kernel<T>, 256); else break;
         }
-        if (d->dtype == CP360_F32) CP360_CLIP(float)
-        else if (d->dtype == CP360_F16) CP360_CLIP(f16_raw)
-        else CP360_CLIP(bf16_raw)
-#undef CP360_CLIP
-        CP360_CHECK_HIP();
-        return CP360_OK;
-    }
-    const bool narrow = d->c_out <= 64;
-    int bn_ = 0, bm_ = 0, slots_ = 0;
-    tile_of(d, &bn_, &bm_, &slots_);
-    if (bm_ == 64) {                                           // small-M launches: 64 x 64 tiles (conv_small.hip)
-        cp360_launch_conv_small(k, d->dtype, st);
-        CP360_CHECK_HIP();
-        return CP360_OK;
-    }
-    // pointwise 64 -> 64 in a 16-bit type (layer1.0's conv1): the streaming kernel (a caller-chosen tile_px keeps the generic one)
-    if (d->dtype != CP360_F32 && d->kh == 1 && d->kw == 1 && d->sy == 1 && d->sx == 1 && d->pad == 0 && d->c_in == 64 &&
-        d->c_out == 64 && d->c_in2 == 0 && d->splits <= 1 && !residual && d->tile_px == 0 && d->pix_stride % 8 == 0 &&
-        d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && k.M >= 4096 && k.out != nullptr && k.partial == nullptr) {
-        long long blocks = ((long long)(k.M + 15) / 16 + 7) / 8;                 // two passes of PWU blocks per wave at most ...
-        if (blocks > 256 * 8) blocks = 256 * 8;                                    // ... and a persistent grid beyond 8 workgroups per CU
-        if (d->dtype == CP360_F16) hipLaunchKernelGGL((conv_pw64_kernel<f16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, k);
-        else hipLaunchKernelGGL((conv_pw64_kernel<bf16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, k);
-        CP360_CHECK_HIP();
-        return CP360_OK;
-    }
-    if (d->c_out < 256) bn_ = bm_ = slots_ = 0;
-    const bool wide = d->c_out >= 256 && bn_ == 256;           // else: the 4-wave 128x128 kernel, two workgroups per CU
-    if (d->c_in2 > 0) {                                        // second source: ring kernels only
-        if (!wide) return CP360_ERR_UNSUPPORTED;
-        if (bm_ == 128) bm_ = d->dtype == CP360_F32 ? 256 : 129;
-    }
-    if (wide) {
-        // 256x256 tiles carry 1.5x the flops per byte brought into the CU; use them unless the
-        // pixel count pads badly (small-M launches) - then 256x128
-        const bool big = bm_ >= 256;
-        const int bm = bm_ == 129 ? 128 : bm_;
-        if (bm_ == 129) k.epi_direct = d->c_out % 8 == 0 && d->ld_out % 8 == 0 && d->out_coff % 8 == 0 && d->ld_res % 8 == 0;
-        k.nt = (k.c_out + 255) / 256;
-        k.mt = (k.M + bm - 1) / bm;
-        k.m_fast = ((long long)k.c_out * k.k_total > (long long)k.M * k.kh * k.kw * k.c_in) ? 1 : 0;
-        dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-        // the DMA kernel has no second-source loader (its K loop would run the extra tap on the first tensor)
-        if (d->c_in2 > 0 && !big && bm_ != 129) return CP360_ERR_UNSUPPORTED;
-        if (bm_ == 129 && d->dtype == CP360_F16) hipLaunchKernelGGL((conv_igemm_ring2_kernel<f16_raw>), grid, dim3(512), 0, st, k);
-        else if (bm_ == 129) hipLaunchKernelGGL((conv_igemm_ring2_kernel<bf16_raw>), grid, dim3(512), 0, st, k);
-        else if (d->dtype == CP360_F32) rc = launch_wide<float>(k, bm, grid, st);
-        else if (d->dtype == CP360_F16) rc = launch_wide<f16_raw>(k, bm, grid, st);
-        else rc = launch_wide<bf16_raw>(k, bm, grid, st);
-        if (rc) return rc;
-    } else if (d->dtype == CP360_F32) {
-        if (narrow) launch_conv<float, 1, 4>(k, st);
-        else launch_conv<float, 2, 2>(k, st);
-    } else if (d->dtype == CP360_F16) {
-        if (narrow) launch_conv<f16_raw, 1, 4>(k, st);
-        else launch_conv<f16_raw, 2, 2>(k, st);
-    } else {
-        if (narrow) launch_conv<bf16_raw, 1, 4>(k, st);
-        else launch_conv<bf16_raw, 2, 2>(k, st);
-    }
+        return CP360_ERR_UNSUPPORTED;
+    });
+    if (rc) return rc;
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -2071,18 +2050,12 @@ extern "C" int cp360_conv_finish_add(const cp360_conv_desc* d, const float* part
     long long blocks = (total + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == CP360_F32)
-        hipLaunchKernelGGL((conv_finish_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, partial, d->splits,
-                           bias, (const float*)residual, d->ld_res, (float*)out, d->ld_out, d->out_coff, M, d->c_out,
-                           d->relu, d->slab_rows, extra);
-    else if (d->dtype == CP360_F16)
-        hipLaunchKernelGGL((conv_finish_kernel<f16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, partial,
-                           d->splits, bias, (const f16_raw*)residual, d->ld_res, (f16_raw*)out, d->ld_out,
-                           d->out_coff, M, d->c_out, d->relu, d->slab_rows, extra);
-    else
-        hipLaunchKernelGGL((conv_finish_kernel<bf16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, partial,
-                           d->splits, bias, (const bf16_raw*)residual, d->ld_res, (bf16_raw*)out, d->ld_out,
-                           d->out_coff, M, d->c_out, d->relu, d->slab_rows, extra);
+    with_elem(d->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((conv_finish_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, partial, d->splits, bias,
+                           (const T*)residual, d->ld_res, (T*)out, d->ld_out, d->out_coff, M, d->c_out, d->relu,
+                           d->slab_rows, extra);
+    });
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -2105,23 +2078,17 @@ extern "C" int cp360_lstm_gates_next(const float* gates_partial, int splits, con
     if (splits < 1 || M <= 0 || Hc <= 0) return CP360_ERR_BAD_SHAPE;
     if (Hc % 4 != 0 || ld_h % 4 != 0 || h_coff % 4 != 0) return CP360_ERR_ALIGN;
     if (slab_rows && (4 * Hc) % 32 != 0) return CP360_ERR_ALIGN;
+    if (!elem_bytes(h_dtype)) return CP360_ERR_BAD_DTYPE;
     const long long total = (long long)M * (Hc / 4);
     long long blocks = (total + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipStream_t st = (hipStream_t)stream;
-    if (h_dtype == CP360_F32)
-        hipLaunchKernelGGL((lstm_gates_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, gates_partial, splits,
-                           bias, c_prev, c_next, (float*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, minmax, x_coff, P, clip_stride);
-    else if (h_dtype == CP360_BF16)
-        hipLaunchKernelGGL((lstm_gates_kernel<bf16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, gates_partial,
-                           splits, bias, c_prev, c_next, (bf16_raw*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, minmax, x_coff, P,
+    with_elem(h_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((lstm_gates_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, gates_partial, splits, bias,
+                           c_prev, c_next, (T*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, minmax, x_coff, P,
                            clip_stride);
-    else if (h_dtype == CP360_F16)
-        hipLaunchKernelGGL((lstm_gates_kernel<f16_raw>), dim3((unsigned)blocks), dim3(256), 0, st, gates_partial,
-                           splits, bias, c_prev, c_next, (f16_raw*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, minmax, x_coff, P,
-                           clip_stride);
-    else
-        return CP360_ERR_BAD_DTYPE;
+    });
     CP360_CHECK_HIP();
     return CP360_OK;
 }

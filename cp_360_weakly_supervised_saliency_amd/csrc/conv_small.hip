@@ -55,10 +55,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     // neighbours share the larger operand panel through that XCD's L2.  Placement affects speed only.
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -347,10 +344,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     const int wn = wave >> 1, wm = wave & 1;
     int n0, m0, split;
     {
-        const int nwg = p.nt * p.mt * p.splits;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
         int nt_i, mt_i;
         if (p.m_fast) {
             mt_i = w % p.mt;
@@ -637,14 +631,12 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
 
 }  // namespace
 
-void cp360_launch_conv_small(ConvK& k, int dtype, hipStream_t st) {
-    k.nt = (k.c_out + 63) / 64;
-    k.mt = (k.M + 63) / 64;
-    // share whichever operand panel is larger through the XCD's L2
-    k.m_fast = ((long long)k.c_out * k.k_total > (long long)k.M * k.kh * k.kw * k.c_in) ? 1 : 0;
-    dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
-    // f32: one wave per SIMD with the fillers inside the MFMA gaps
-    if (dtype == CP360_F32) hipLaunchKernelGGL(conv_small_f32_kernel, grid, dim3(256), 0, st, k);
-    else if (dtype == CP360_F16) hipLaunchKernelGGL((conv_small_kernel<f16_raw>), grid, dim3(512), 0, st, k);
-    else hipLaunchKernelGGL((conv_small_kernel<bf16_raw>), grid, dim3(512), 0, st, k);
+void cp360_launch_conv_small(const ConvK& k, int dtype, hipStream_t st) {
+    const dim3 grid((unsigned)(k.nt * k.mt * k.splits), 1, 1);
+    with_elem(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        // f32: one wave per SIMD with the fillers inside the MFMA gaps
+        if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(conv_small_f32_kernel, grid, dim3(256), 0, st, k);
+        else hipLaunchKernelGGL((conv_small_kernel<T>), grid, dim3(512), 0, st, k);
+    });
 }

@@ -13,6 +13,14 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vect
 
 // bytes per element of a CP360_* dtype code (0: not a floating-point activation type)
 static inline int elem_bytes(int dtype) { return dtype == CP360_F32 ? 4 : ((dtype == CP360_BF16 || dtype == CP360_F16) ? 2 : 0); }
+// dtype code -> element type: calls f with a value of the element type as a tag (a generic lambda: `using T = decltype(tag)`) and
+// returns what it returns.  The caller has checked the code (elem_bytes(dtype) != 0).  A kernel that exists for the 16-bit types
+// only stays uninstantiated for f32 behind `if constexpr (sizeof(T) == 2)`.
+template <typename F> static inline auto with_elem(int dtype, F&& f) {
+    if (dtype == CP360_F32) return f(float());
+    if (dtype == CP360_F16) return f(f16_raw());
+    return f(bf16_raw());
+}
 
 // 16 zero bytes in device memory: invalid tile rows (m >= M) and the K tail (c >= c_in)
 // load from here, so the select happens on the ADDRESS before the load and nothing has
@@ -94,6 +102,18 @@ template <> __device__ __forceinline__ void wait_vmcnt_upto<0>(int) { wait_vmcnt
 template <int N> __device__ __forceinline__ void wait_vmcnt_upto(int n) {
     if (n >= N) wait_vmcnt<N>();
     else wait_vmcnt_upto<N - 1>(n);
+}
+
+// ------------------------------------------------------------------ XCD-aware work index
+// Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2): workgroup blockIdx.x takes work item w such
+// that every XCD gets a CONTIGUOUS range of the nwg items - neighbours in w share an operand panel through that XCD's L2.
+// reverse: items in descending order (cp360_set_launch_order).  Bijective on [0, nwg): placement affects speed, never results.
+// How w splits into (channel tile, pixel tile, split) is the kernel's business.
+__device__ __forceinline__ int xcd_work_index(int nwg, int reverse) {
+    const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
+    int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
+    if (reverse) w = nwg - 1 - w;
+    return w;
 }
 
 // ------------------------------------------------------------------ LDS swizzles (byte offset of a 16-byte chunk)

@@ -209,10 +209,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(const WinoK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int pos, nt_i, mt_i;
     {   // XCD-aware mapping: the channel tiles of one (position, tile block) are neighbours on one XCD and share V_p through its L2
-        const int nwg = 16 * p.nt * p.mt;
-        const int L = blockIdx.x, xcd = L & 7, q = nwg >> 3, r = nwg & 7;
-        int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (L >> 3);
-        if (p.reverse) w = nwg - 1 - w;
+        const int w = xcd_work_index(16 * p.nt * p.mt, p.reverse);
         nt_i = w % p.nt;
         const int rest = w / p.nt;
         mt_i = rest % p.mt;
