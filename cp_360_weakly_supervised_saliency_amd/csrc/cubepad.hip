@@ -2,20 +2,17 @@
 // NHWC for the fused pipeline) + the host-side table export.
 // Semantics: model/cube_pad.py:28-42,95-216 (see common.h: cubepad_src).
 //
-// NCHW kernels, in the order launch_nchw() tries them (each is bit-exact; test hooks in launch_nchw pin each one; measurements and
-// the reasoning behind the designs: profiles/r03_cubepad_plane.md):
+// NCHW kernels, in the order launch_nchw() tries them (each is bit-exact; CP360_CUBEPAD_ONLY pins one of them for the tests;
+// measurements and the reasoning behind the designs: profiles/r03_cubepad_plane.md, profiles/cubepad_retire.md):
 //   cubepad_nchw_cube_kernel     faces up to 16x16 (fallback up to 32x32): (cube, channel range) items through LDS, the
 //                                CubePad map as a per-workgroup table
 //   cubepad_nchw_lds6_kernel     the six padded planes of a (cube, channel range) fit the LDS: assembled there, written
 //                                as one linear store stream (the network's 28x28 ... 112x112 faces)
-//   cubepad_nchw_band_kernel     rows of >= 256 bytes, planes larger than the LDS: the same per row band of one plane
-//   cubepad_nchw_channel_kernel  (cube, channel) items, every input byte read once, pads from LDS captures
-//   cubepad_nchw_plane_kernel    (plane, face) items, runs + pad stream
-//   cubepad_nchw_strip_kernel    round-2 form of the plane kernel
+//   cubepad_nchw_band_kernel     rows of >= 112 bytes: the same per row band of one plane
 //   cubepad_nchw_kernel          element per lane, any geometry
 #include "tile.h"
 #include <stdlib.h>
-#include <algorithm>
+#include <string.h>
 #include <atomic>
 
 // ---------------------------------------------------------------- NCHW
@@ -77,572 +74,17 @@ __global__ __launch_bounds__(256) void cubepad_nchw_kernel(const T* __restrict__
     }
 }
 
-// ---------------------------------------------------------------- NCHW, 16-byte chunks + LDS-staged border strips
-// The element-per-lane kernel above moves 1-4 bytes per lane and runs cubepad_src() for every element:
-// 0.09-0.17 of the HBM peak (profiles/r02_hbm_kernels.md).  A padded plane [Hp, Wp] is one contiguous byte range,
-// and all but ~2 of the 16-byte chunks of a centre row are 16 consecutive bytes of the input plane: those go
-// straight through (one possibly misaligned 16-byte load - unaligned global access is on under ROCm - and
-// one ALIGNED 16-byte store).  Everything a pad element can read lies within P = max pad of a face border
-// (cube_pad.py:114-216 copies border strips of the neighbouring faces, corners replicate a strip's end): the
-// the four pad strips of a face (output orientation) are gathered into LDS once per (plane, face) and the
-// chunks that touch padding are assembled element by element from there; the <= 4 p^2 corner elements go through
-// cubepad_src() directly.  One WAVE per (group, channel, face) item, 32-bit index arithmetic, divisions by
-// Wp / n through a float reciprocal + correction.  ES = element bytes.
+// ES = element bytes: the kernels below move raw 16-byte chunks of E = 16 / ES elements.
 template <int ES> struct ElemOf;
 template <> struct ElemOf<1> { typedef uint8_t T; };
 template <> struct ElemOf<2> { typedef uint16_t T; };
 template <> struct ElemOf<4> { typedef uint32_t T; };
 template <> struct ElemOf<8> { typedef uint64_t T; };
 
-template <int ES>
-__global__ __launch_bounds__(256) void cubepad_nchw_strip_kernel(const unsigned char* __restrict__ x,
-                                                                 unsigned char* __restrict__ y, int C, CubePadGeom g,
-                                                                 int n_items, float rcp_wp, float rcp_n) {
-    typedef typename ElemOf<ES>::T T;
-    constexpr int E = 16 / ES;                               // elements per 16-byte chunk
-    extern __shared__ __attribute__((aligned(16))) unsigned char strip_raw[];
-    const int n = g.n, Hp = n + g.pt + g.pd, Wp = n + g.pl + g.pr;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nstrip = (g.pt + g.pd + g.pl + g.pr) * n;      // one wave's strips: top [pt][n], bottom [pd][n], left [pl][n], right [pr][n]
-    T* st = reinterpret_cast<T*>(strip_raw) + (size_t)wave * nstrip;
-    const T* st_t = st;
-    const T* st_b = st_t + g.pt * n;
-    const T* st_l = st_b + g.pd * n;
-    const T* st_r = st_l + g.pl * n;
-    const size_t in_face = (size_t)C * n * n, out_face = (size_t)C * Hp * Wp;
-    const int plane_elems = Hp * Wp;
-    // exact unsigned division by a small constant through a float reciprocal + one correction (operands < 2^24)
-    auto div_by = [](int q, int d, float rcp) -> int {
-        int r = (int)((float)q * rcp);
-        r -= (r * d > q);
-        r += ((r + 1) * d <= q);
-        return r;
-    };
-    // a (plane, face) item per WAVE: small planes (14x14, 7x7 faces) would leave a 256-thread workgroup idle
-    for (int item = blockIdx.x * 4 + wave; item < n_items; item += gridDim.x * 4) {
-        const int plane = item / 6, f = item - plane * 6;
-        const int grp = plane / C, c = plane - grp * C;
-        const T* xin = reinterpret_cast<const T*>(x) + (size_t)grp * 6 * in_face + (size_t)c * n * n;
-        const T* xf = xin + (size_t)f * in_face;
-        auto src_elem = [&](int i, int j) -> T {            // any padded position through the CubePad map (global gather)
-            const int s = cubepad_src(f, i, j, g);
-            const int sf = div_by(s, n * n, rcp_n * rcp_n);
-            return xin[(size_t)sf * in_face + (s - sf * n * n)];
-        };
-        // ---- stage this face's four pad strips (output orientation, corners excluded) in LDS
-        for (int idx = lane; idx < nstrip; idx += 64) {
-            const int k = div_by(idx, n, rcp_n), a = idx - k * n;
-            int i, j;
-            if (k < g.pt)                      { i = k;                              j = g.pl + a; }
-            else if (k < g.pt + g.pd)          { i = g.pt + n + (k - g.pt);          j = g.pl + a; }
-            else if (k < g.pt + g.pd + g.pl)   { i = g.pt + a;                       j = k - g.pt - g.pd; }
-            else                               { i = g.pt + a;                       j = g.pl + n + (k - g.pt - g.pd - g.pl); }
-            st[idx] = src_elem(i, j);
-        }
-        __builtin_amdgcn_wave_barrier();
-        auto elem = [&](int i, int j) -> T {
-            const bool ri = i >= g.pt && i < g.pt + n, cj = j >= g.pl && j < g.pl + n;
-            if (ri && cj) return xf[(size_t)(i - g.pt) * n + (j - g.pl)];
-            if (cj) return i < g.pt ? st_t[i * n + (j - g.pl)] : st_b[(i - g.pt - n) * n + (j - g.pl)];
-            if (ri) return j < g.pl ? st_l[j * n + (i - g.pt)] : st_r[(j - g.pl - n) * n + (i - g.pt)];
-            return src_elem(i, j);                           // corner stitch (at most 4 p^2 elements per plane)
-        };
-        unsigned char* yb = y + ((size_t)grp * 6 * out_face + (size_t)f * out_face + (size_t)c * Hp * Wp) * ES;
-        // 16-byte-aligned chunks of the tensor's address range that overlap this plane.  Chunk ch holds plane
-        // elements [ch * E - head, ch * E - head + E); the chunks fully inside a centre row's centre columns
-        // ("runs": rows' chunk ranges [cs(r), ce(r))) are plain copies, everything else is assembled per element.
-        const size_t a0 = reinterpret_cast<size_t>(yb), a1 = a0 + (size_t)plane_elems * ES;
-        const size_t c0 = a0 & ~(size_t)15;
-        const int head = (int)(a0 - c0) / ES;                // elements of chunk 0 that belong to the previous plane
-        const int nchunks = (int)((a1 - c0 + 15) >> 4);
-        auto run_begin = [&](int r) -> int {                 // first chunk fully inside centre row r (r = 0 .. n-1)
-            return ((g.pt + r) * Wp + g.pl + head + E - 1) / E;   // (operands < 2^23: exact integer division is cheap enough per row)
-        };
-        auto run_end = [&](int r) -> int { return ((g.pt + r) * Wp + g.pl + n + head) / E; };
-        auto slow_chunk = [&](int ch) __attribute__((always_inline)) {
-            const int q0 = ch * E - head;
-            unsigned char* ca = reinterpret_cast<unsigned char*>(c0 + ((size_t)ch << 4));
-            if (q0 >= 0 && q0 + E <= plane_elems) {
-                const int i = div_by(q0, Wp, rcp_wp), j = q0 - i * Wp;
-                T tmp[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    int ie = i, je = j + e;
-                    if (je >= Wp) { je -= Wp; ++ie; }        // E <= Wp (launcher)
-                    tmp[e] = elem(ie, je);
-                }
-                u32x4 v;
-                __builtin_memcpy(&v, tmp, 16);
-                *reinterpret_cast<u32x4*>(ca) = v;
-            } else {                                         // head / tail of the plane: element stores
-                for (int e = 0; e < E; ++e) {
-                    const int q = q0 + e;
-                    if (q < 0 || q >= plane_elems) continue;
-                    const int ie = div_by(q, Wp, rcp_wp), je = q - ie * Wp;
-                    reinterpret_cast<T*>(yb)[q] = elem(ie, je);
-                }
-            }
-        };
-        // ---- pass 1: the runs.  cpr = chunks per row upper bound; lanes enumerate (row, chunk in run), four at a time
-        const int cpr = n * ES / 16 + 1;
-        const float rcp_cpr = 1.0f / (float)cpr;
-        const int nfast = n * cpr;
-        for (int base = lane; base < nfast; base += 64 * 4) {
-            u32x4 v[4];
-            unsigned char* dst[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = base + 64 * u;
-                dst[u] = nullptr;
-                if (idx < nfast) {
-                    const int r = div_by(idx, cpr, rcp_cpr), k = idx - r * cpr;
-                    const int ch = run_begin(r) + k;
-                    if (ch < run_end(r)) {
-                        const int j = ch * E - head - (g.pt + r) * Wp;       // first column of the chunk (>= pl)
-                        __builtin_memcpy(&v[u], xf + (size_t)r * n + (j - g.pl), 16);
-                        dst[u] = reinterpret_cast<unsigned char*>(c0 + ((size_t)ch << 4));
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (dst[u]) *reinterpret_cast<u32x4*>(dst[u]) = v[u];
-        }
-        // ---- pass 2: what the runs leave: the pad rows above / below and the 1-2 chunks between consecutive runs
-        {
-            const int top_end = min(run_begin(0), nchunks);
-            for (int ch = lane; ch < top_end; ch += 64) slow_chunk(ch);
-            const int bot_begin = max(run_end(n - 1), top_end);
-            for (int ch = bot_begin + lane; ch < nchunks; ch += 64) slow_chunk(ch);
-            for (int r = 1 + lane; r < n; r += 64) {
-                const int lo = max(run_end(r - 1), top_end), hi = min(run_begin(r), bot_begin);
-                for (int ch = lo; ch < hi; ++ch) slow_chunk(ch);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                     // the next item's staging overwrites the strips
-    }
-}
-
-
-// ---------------------------------------------------------------- NCHW, large faces: run copies + pad stream (round 3)
-// The strip kernel above is VALU-bound, not HBM-bound (tools/_exp timing variants, profiles/r03_cubepad_plane.md: the run
-// pass alone takes 393 us on [384,64,112,112] f16 where a plain copy of the same bytes takes 250 us - ~40 instructions
-// per 16-byte chunk, because the per-item values live in vector registers and every chunk pays two float-reciprocal
-// divisions; the pad pass costs as much again in branchy per-element code).  Same decomposition, cheaper arithmetic:
-//   * the wave index is made uniform (readfirstlane), so item / plane / face / base pointers are scalar;
-//   * pass 1 (runs = chunks fully inside a centre row) steps (row, chunk-in-row) incrementally - no division;
-//   * every pad element of the padded plane, in OUTPUT order, is staged in LDS once per item ("pad stream" PS: the padded
-//     plane with its centre elements removed: pt full rows, then [pl left | pr right] per centre row, then pd full rows;
-//     so the PS index of a pad element q is q - #centre elements before q).  Strip lines are affine in the neighbour
-//     face (cubepad_src: row / col are each one of k, n-p+k, a, n-1-a): a 16-entry (base, step) table per item replaces
-//     cubepad_src() per element; only the <= (pt+pd)(pl+pr) corner elements evaluate it;
-//   * every chunk that is not a run - pad rows, the 1-3 chunks between consecutive runs, the head / tail chunks a plane
-//     shares with its neighbours - is one branch-free routine: E consecutive output elements are [centre stream A]
-//     [pads][centre stream B] (n >= 2E + pl + pr: at most one centre -> pad -> centre transition), so two possibly
-//     misaligned 16-byte loads A, B positioned so that element e of the chunk is A[e] / B[e], E LDS reads PS[base + e]
-//     at immediate offsets, and two compares + selects per element.
-// Bit-exact like every CubePad kernel (pure copy).
-template <int ES>
-__global__ __launch_bounds__(256) void cubepad_nchw_plane_kernel(const unsigned char* __restrict__ x,
-                                                                 unsigned char* __restrict__ y, int C, CubePadGeom g,
-                                                                 int n_items, long long total_in, float rcp_wp, float rcp_n,
-                                                                 float rcp_cpr, int dq, int dm, int maxc, float rcp_maxc,
-                                                                 int ps_alloc, int rbw) {
-    typedef typename ElemOf<ES>::T T;
-    constexpr int E = 16 / ES;                               // elements per 16-byte chunk
-    constexpr int LOG_E = E == 16 ? 4 : (E == 8 ? 3 : (E == 4 ? 2 : 1));
-    constexpr int UNR = 4;                                   // run chunks in flight per lane
-    extern __shared__ __attribute__((aligned(16))) unsigned char strip_raw[];
-    const int n = g.n, Hp = n + g.pt + g.pd, Wp = n + g.pl + g.pr, LR = g.pl + g.pr;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nlines = g.pt + g.pd + LR, nstrip = nlines * n;
-    const int nn = n * n, plane_elems = Hp * Wp;
-    const int ps_mid = g.pt * Wp;                            // PS index of centre row 0's first pad
-    const int ps_bot = ps_mid + n * LR;                      // PS index of the first bottom-row element
-    int* ltab = reinterpret_cast<int*>(strip_raw) + wave * 32;                  // [16 lines][base, step]
-    T* ps = reinterpret_cast<T*>(strip_raw + 512) + (size_t)wave * ps_alloc + E;   // E elements of slack either side
-    const int in_face = C * nn;                              // (6 * in_face < 2^31: launcher)
-    const size_t out_face = (size_t)C * plane_elems;
-    const int cpr = (n >> LOG_E) + 1;                        // chunks per run, upper bound
-    auto div_by = [](int q, int d, float rcp) -> int {       // exact for 0 <= q < 2^24
-        int r = (int)((float)q * rcp);
-        r -= (r * d > q);
-        r += ((r + 1) * d <= q);
-        return r;
-    };
-    for (int item = blockIdx.x * 4 + wave; item < n_items; item += gridDim.x * 4) {
-        const int plane = item / 6, f = item - plane * 6;
-        const int grp = plane / C, c = plane - grp * C;
-        const long long cube_off = (long long)grp * 6 * in_face + (long long)c * nn;   // elements from x
-        const long long xf_off = cube_off + (long long)f * in_face;
-        const T* xin = reinterpret_cast<const T*>(x) + cube_off;
-        const T* xf = reinterpret_cast<const T*>(x) + xf_off;
-        // ---- the strip lines of this face as (element offset from xin, step) pairs
-        if (lane < nlines) {
-            const int k = lane;
-            int i0, j0, di = 0, dj = 0;
-            if (k < g.pt)                      { i0 = k;                        j0 = g.pl; dj = 1; }
-            else if (k < g.pt + g.pd)          { i0 = n + k;                    j0 = g.pl; dj = 1; }      // pt + n + (k - pt)
-            else if (k < g.pt + g.pd + g.pl)   { i0 = g.pt;                     j0 = k - g.pt - g.pd; di = 1; }
-            else                               { i0 = g.pt;                     j0 = n + k - g.pt - g.pd; di = 1; }   // pl + n + (k - pt - pd - pl)
-            const int s0 = cubepad_src(f, i0, j0, g), s1 = cubepad_src(f, i0 + di, j0 + dj, g);
-            const int sf = s0 / nn;
-            ltab[2 * k] = sf * in_face + (s0 - sf * nn);
-            ltab[2 * k + 1] = s1 - s0;
-        }
-        __builtin_amdgcn_wave_barrier();
-        // ---- pad stream: strips ...
-        for (int idx = lane; idx < nstrip; idx += 64) {
-            const int k = div_by(idx, n, rcp_n), a = idx - k * n;
-            const int base = ltab[2 * k], step = ltab[2 * k + 1];
-            int pos;
-            if (k < g.pt)                      pos = k * Wp + g.pl + a;
-            else if (k < g.pt + g.pd)          pos = ps_bot + (k - g.pt) * Wp + g.pl + a;
-            else if (k < g.pt + g.pd + g.pl)   pos = ps_mid + a * LR + (k - g.pt - g.pd);
-            else                               pos = ps_mid + a * LR + (k - g.pt - g.pd);       // pl + (k - pt - pd - pl)
-            ps[pos] = xin[base + a * step];
-        }
-        // ---- ... and corners (make_cubepad_edge: cube_pad.py:44-93)
-        const int ncorner = (g.pt + g.pd) * LR;
-        for (int idx = lane; idx < ncorner; idx += 64) {
-            const int ci = idx / LR, cj = idx - ci * LR;
-            const int i = ci < g.pt ? ci : n + ci, j = cj < g.pl ? cj : n + cj;
-            const int s = cubepad_src(f, i, j, g);
-            const int sf = s / nn;
-            const int pos = ci < g.pt ? i * Wp + j : ps_bot + (ci - g.pt) * Wp + j;
-            ps[pos] = xin[sf * in_face + (s - sf * nn)];
-        }
-        __builtin_amdgcn_wave_barrier();
-        unsigned char* yb = y + ((size_t)grp * 6 * out_face + (size_t)f * out_face + (size_t)c * plane_elems) * ES;
-        const size_t a0 = reinterpret_cast<size_t>(yb), a1 = a0 + (size_t)plane_elems * ES;
-        const size_t c0 = a0 & ~(size_t)15;
-        unsigned char* c0p = reinterpret_cast<unsigned char*>(c0);
-        const int head = (int)(a0 - c0) / ES;                // elements of chunk 0 that belong to the previous plane
-        const int nchunks = (int)((a1 - c0 + 15) >> 4);
-        const int rowA = g.pt * Wp + g.pl + head;
-        auto run_begin = [&](int r) -> int { return (r * Wp + rowA + E - 1) >> LOG_E; };   // first chunk fully inside centre row r
-        auto run_end = [&](int r) -> int { return (r * Wp + rowA + n) >> LOG_E; };
-        auto load_vec = [&](long long goff) -> u32x4 {     // 16 bytes at element goff of x; the tensor's first / last chunk may hang over its ends
-            u32x4 v;
-            if (goff >= 0 && goff + E <= total_in) {
-                __builtin_memcpy(&v, reinterpret_cast<const T*>(x) + goff, 16);
-            } else {
-                T tmp[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const long long t = goff + e;
-                    tmp[e] = (t >= 0 && t < total_in) ? reinterpret_cast<const T*>(x)[t] : (T)0;
-                }
-                __builtin_memcpy(&v, tmp, 16);
-            }
-            return v;
-        };
-        auto slow_chunk = [&](int ch) __attribute__((always_inline)) {
-            const int q0 = ch * E - head;
-            int iA, jA;
-            if (q0 < 0) { iA = -1; jA = q0 + Wp; }
-            else        { iA = div_by(q0, Wp, rcp_wp); jA = q0 - iA * Wp; }
-            const int a = iA - g.pt;                                           // centre row of row iA when 0 <= a < n
-            const bool rowc = a >= 0 && a < n;
-            const bool q0c = rowc && jA >= g.pl && jA < g.pl + n;              // q0 is a centre element
-            const int cpos = a < 0 ? 0 : (a >= n ? nn : a * n + min(max(jA - g.pl, 0), n));   // centre elements before q0
-            const int eA = q0c ? min(E, g.pl + n - jA) : 0;                    // leading elements from centre stream A
-            const int aB = q0c ? a + 1 : (a < 0 ? 0 : (rowc ? (jA < g.pl ? a : a + 1) : n));   // centre row that starts next
-            const int eB = aB < n ? min(max((g.pt + aB) * Wp + g.pl - q0, 0), E) : E;   // elements from e = eB on are its centre
-            const u32x4 va = load_vec(xf_off + (eA > 0 ? cpos : 0));
-            const u32x4 vb = load_vec(xf_off + (eB < E ? aB * n - eB : 0));
-            T ta[E], tb[E], tv[E];
-            __builtin_memcpy(ta, &va, 16);
-            __builtin_memcpy(tb, &vb, 16);
-            const T* pp = ps + (q0 - cpos - eA);                               // PS index of pad element e = (q0 - cpos) + (e - eA)
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const T pv = pp[e];
-                tv[e] = e < eA ? ta[e] : (e >= eB ? tb[e] : pv);
-            }
-            unsigned char* ca = c0p + ((size_t)ch << 4);
-            if (q0 >= 0 && q0 + E <= plane_elems) {
-                u32x4 v;
-                __builtin_memcpy(&v, tv, 16);
-                *reinterpret_cast<u32x4*>(ca) = v;
-            } else {                                                           // chunk shared with the neighbouring plane
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (q0 + e >= 0 && q0 + e < plane_elems) reinterpret_cast<T*>(ca)[e] = tv[e];
-            }
-        };
-        const int top_end = min(run_begin(0), nchunks);
-        const int bot_begin = max(run_end(n - 1), top_end);
-        // Row blocks: the runs of rows [r0, rend) (one UNR-deep body per wave), then at once the chunks around them - the
-        // 128-byte lines a run leaves incomplete are completed while they are still dirty in L2 (a partial line written
-        // back to HBM and completed later costs far more than its bytes: tools/_exp variants, profiles/r03_cubepad_plane.md).
-        for (int r0 = 0; r0 < n; r0 += rbw) {
-            const int rend = min(r0 + rbw, n);
-            {
-                const int rq = div_by(lane, cpr, rcp_cpr);
-                int r = r0 + rq, k = lane - rq * cpr;
-                while (r < rend) {
-                    u32x4 v[UNR];
-                    unsigned doff[UNR];
-                    bool ok[UNR];
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
-                        const int rw = r * Wp + rowA;
-                        const int ch = ((rw + E - 1) >> LOG_E) + k;
-                        ok[u] = r < rend && ch < ((rw + n) >> LOG_E);
-                        if (ok[u]) {
-                            const unsigned soff = (unsigned)(ch * E + r * (n - Wp) - rowA);   // centre element index of the chunk's first element
-                            __builtin_memcpy(&v[u], xf + soff, 16);
-                            doff[u] = (unsigned)ch << 4;
-                        }
-                        k += dm;
-                        r += dq;
-                        if (k >= cpr) { k -= cpr; ++r; }
-                    }
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u)
-                        if (ok[u]) *reinterpret_cast<u32x4*>(c0p + doff[u]) = v[u];
-                }
-            }
-            const int n_top = r0 == 0 ? top_end : 0, n_bot = rend == n ? nchunks - bot_begin : 0;
-            const int b0 = max(r0, 1);                                          // boundaries (rr, rr + 1) with rr + 1 in [b0, rend)
-            const int n_slow = n_top + n_bot + max(rend - b0, 0) * maxc;
-            for (int s = lane; s < n_slow; s += 64) {
-                int ch;
-                if (s < n_top) ch = s;
-                else if (s < n_top + n_bot) ch = bot_begin + (s - n_top);
-                else {
-                    const int m = s - n_top - n_bot;
-                    const int mq = div_by(m, maxc, rcp_maxc);
-                    const int rr = b0 - 1 + mq;
-                    const int lo = max(run_end(rr), top_end), hi = min(run_begin(rr + 1), bot_begin);
-                    ch = lo + (m - mq * maxc);
-                    if (ch >= hi) continue;
-                }
-                slow_chunk(ch);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                     // the next item's staging overwrites the pad stream
-    }
-}
-
-
-// ---------------------------------------------------------------- NCHW, large faces, every input byte read once (round 3)
-// The plane kernel's HBM reads are 2-3.2x the input (rocprofv3 FETCH_SIZE, profiles/r03_cubepad_plane.md): about half of
-// a cube's 24 strips are COLUMNS of the neighbouring face (cube_pad.py:114-216), so a (plane, face) item pulls a whole
-// 128-byte line per 1-4 byte pad element, and the chunks between runs re-read the first / last line of every centre row.
-// Here a workgroup item is (cube, channel) - the six planes CubePad exchanges borders between - and nothing is read twice:
-//   S1  for each face: stream the runs HBM -> registers -> HBM (as the plane kernel), and beside them capture into LDS
-//       RE[f][row][side][E]: the first and the last E elements of every centre row (one 16-byte load each, issued in the
-//       same 64-row block as the run loads of those rows, so the line is in L2), and TB[f][top|bottom][P][n]: the first /
-//       last P rows.  RE + TB hold every element a pad of ANY face of this (cube, channel) can copy (a strip lies within
-//       P <= E of a border; corners replicate strip ends) and every centre element of a non-run chunk (< E from a row end);
-//   S2  for each face: the pad stream PS (see the plane kernel) is gathered LDS -> LDS through a line table that maps the
-//       face's strip lines to affine (base, step) element offsets in RE / TB (built once per workgroup: it depends on the
-//       geometry only), then every non-run chunk is assembled from LDS alone: [row end from RE][pads from PS][row start
-//       from RE], E element reads at immediate offsets each, and written with one aligned 16-byte store.
-// HBM traffic = input + output (+ the two shared 16-byte chunks per plane).  A workgroup is 6 (or 12) waves, one (two) per
-// face: the six faces stream concurrently and independently, three workgroup barriers per item (S1 | pad streams | chunks);
-// workgroups are persistent over items.
-template <int ES>
-__global__ __launch_bounds__(768) void cubepad_nchw_channel_kernel(const unsigned char* __restrict__ x,
-                                                                   unsigned char* __restrict__ y, int C, CubePadGeom g,
-                                                                   int n_items, float rcp_wp, float rcp_n, float rcp_cpr,
-                                                                   int maxc, float rcp_maxc, int P, int ps_alloc, int rbw) {
-    typedef typename ElemOf<ES>::T T;
-    constexpr int E = 16 / ES;                               // elements per 16-byte chunk; also the width of a row-end record
-    constexpr int LOG_E = E == 16 ? 4 : (E == 8 ? 3 : (E == 4 ? 2 : 1));
-    constexpr int UNR = 8;                                   // loads in flight per lane
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int n = g.n, Hp = n + g.pt + g.pd, Wp = n + g.pl + g.pr, LR = g.pl + g.pr;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int parts = (int)(blockDim.x >> 6) / 6;            // waves per face: 1 or 2
-    const int part = wave / 6, f = wave - part * 6;          // this wave's face and its share of the rows / strips / chunks
-    const int nlines = g.pt + g.pd + LR, nstrip = nlines * n;
-    const int nn = n * n, plane_elems = Hp * Wp;
-    const int ps_mid = g.pt * Wp, ps_bot = ps_mid + n * LR;
-    const int cpr = (n >> LOG_E) + 1;
-    const int re_size = 12 * n * E, tb_face = 2 * P * n;
-    int* ltab = reinterpret_cast<int*>(smem);                                   // [6][16][base, step]
-    T* buf = reinterpret_cast<T*>(smem + 768) + E;                              // RE then TB, E elements of slack in front
-    T* ps = buf + re_size + 6 * tb_face + E + f * ps_alloc;                     // this face's pad stream (slack either side)
-    const size_t in_face = (size_t)C * nn, out_face = (size_t)C * plane_elems;
-    const int dq = 64 / cpr, dm = 64 - dq * cpr;
-    auto div_by = [](int q, int d, float rcp) -> int {       // exact for 0 <= q < 2^24
-        int r = (int)((float)q * rcp);
-        r -= (r * d > q);
-        r += ((r + 1) * d <= q);
-        return r;
-    };
-    auto lds_of = [&](int sf, int row, int col) -> int {     // RE / TB offset of element (row, col) of face sf (within E / P of a border)
-        if (row < P) return re_size + sf * tb_face + row * n + col;
-        if (row >= n - P) return re_size + sf * tb_face + (P + row - (n - P)) * n + col;
-        if (col < E) return ((sf * n + row) * 2) * E + col;
-        return ((sf * n + row) * 2 + 1) * E + col - (n - E);
-    };
-    // ---- line table (geometry only)
-    if (tid < 96) {
-        const int lf = tid >> 4, k = tid & 15;
-        if (k < nlines) {
-            int i0, j0, di = 0, dj = 0;
-            if (k < g.pt)                      { i0 = k;     j0 = g.pl; dj = 1; }
-            else if (k < g.pt + g.pd)          { i0 = n + k; j0 = g.pl; dj = 1; }
-            else if (k < g.pt + g.pd + g.pl)   { i0 = g.pt;  j0 = k - g.pt - g.pd; di = 1; }
-            else                               { i0 = g.pt;  j0 = n + k - g.pt - g.pd; di = 1; }
-            const int s0 = cubepad_src(lf, i0, j0, g), d = cubepad_src(lf, i0 + di, j0 + dj, g) - s0;
-            const int sf = s0 / nn, rem = s0 - sf * nn, row0 = rem / n, col0 = rem - row0 * n;
-            int base, step;
-            if (d == 1 || d == -1) {                         // a row of face sf: in TB
-                base = re_size + sf * tb_face + (row0 < P ? row0 : P + row0 - (n - P)) * n + col0;
-                step = d;
-            } else {                                         // a column of face sf: in RE
-                base = ((sf * n + row0) * 2 + (col0 < E ? 0 : 1)) * E + (col0 < E ? col0 : col0 - (n - E));
-                step = d > 0 ? 2 * E : -2 * E;
-            }
-            ltab[(lf * 16 + k) * 2] = base;
-            ltab[(lf * 16 + k) * 2 + 1] = step;
-        }
-    }
-    const int ra = part * n / parts, rb = (part + 1) * n / parts;               // this wave's centre rows
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int grp = item / C, c = item - grp * C;
-        const T* xf = reinterpret_cast<const T*>(x) + (size_t)grp * 6 * in_face + (size_t)c * nn + (size_t)f * in_face;
-        unsigned char* yb = y + ((size_t)grp * 6 * out_face + (size_t)c * plane_elems + (size_t)f * out_face) * ES;
-        const int head = (int)(reinterpret_cast<size_t>(yb) & 15) / ES;         // elements of chunk 0 that belong to the previous plane
-        unsigned char* c0p = yb - (size_t)head * ES;
-        const int rowA = g.pt * Wp + g.pl + head;
-        // ================= S1: runs + capture (wave = face f, rows [ra, rb))
-        {   // first / last P rows
-            const int t0 = part * tb_face / parts, t1 = (part + 1) * tb_face / parts;
-            for (int base = t0 + lane; base < t1; base += 64 * UNR) {
-                T v[UNR];
-#pragma unroll
-                for (int u = 0; u < UNR; ++u) {
-                    const int idx = base + 64 * u;
-                    if (idx < t1) v[u] = xf[idx < P * n ? idx : (n - 2 * P) * n + idx];
-                }
-#pragma unroll
-                for (int u = 0; u < UNR; ++u)
-                    if (base + 64 * u < t1) buf[re_size + f * tb_face + base + 64 * u] = v[u];
-            }
-        }
-        for (int r0 = ra; r0 < rb; r0 += rbw) {
-            const int rend = min(r0 + rbw, rb);
-            for (int t = lane; t < 2 * (rend - r0); t += 64) {                  // row ends of this block
-                const int row = r0 + (t >> 1), side = t & 1;
-                u32x4 v;
-                __builtin_memcpy(&v, xf + (unsigned)(row * n + (side ? n - E : 0)), 16);
-                *reinterpret_cast<u32x4*>(buf + ((f * n + row) * 2 + side) * E) = v;
-            }
-            const int rq = div_by(lane, cpr, rcp_cpr);
-            int r = r0 + rq, k = lane - rq * cpr;
-            while (r < rend) {
-                u32x4 v[UNR];
-                unsigned doff[UNR];
-                bool ok[UNR];
-#pragma unroll
-                for (int u = 0; u < UNR; ++u) {
-                    const int rw = r * Wp + rowA;
-                    const int ch = ((rw + E - 1) >> LOG_E) + k;
-                    ok[u] = r < rend && ch < ((rw + n) >> LOG_E);
-                    if (ok[u]) {
-                        const unsigned soff = (unsigned)(ch * E + r * (n - Wp) - rowA);
-                        __builtin_memcpy(&v[u], xf + soff, 16);
-                        doff[u] = (unsigned)ch << 4;
-                    }
-                    k += dm;
-                    r += dq;
-                    if (k >= cpr) { k -= cpr; ++r; }
-                }
-#pragma unroll
-                for (int u = 0; u < UNR; ++u)
-                    if (ok[u]) *reinterpret_cast<u32x4*>(c0p + doff[u]) = v[u];
-            }
-        }
-        __syncthreads();
-        // ================= S2: pads and the chunks around them, from LDS
-        {
-            const int t0 = part * nstrip / parts, t1 = (part + 1) * nstrip / parts;
-            for (int idx = t0 + lane; idx < t1; idx += 64) {
-                const int k = div_by(idx, n, rcp_n), a = idx - k * n;
-                const int base = ltab[(f * 16 + k) * 2], step = ltab[(f * 16 + k) * 2 + 1];
-                int pos;
-                if (k < g.pt)                      pos = k * Wp + g.pl + a;
-                else if (k < g.pt + g.pd)          pos = ps_bot + (k - g.pt) * Wp + g.pl + a;
-                else                               pos = ps_mid + a * LR + (k - g.pt - g.pd);
-                ps[pos] = buf[base + a * step];
-            }
-            const int ncorner = part == 0 ? (g.pt + g.pd) * LR : 0;
-            for (int idx = lane; idx < ncorner; idx += 64) {
-                const int ci = idx / LR, cj = idx - ci * LR;
-                const int i = ci < g.pt ? ci : n + ci, j = cj < g.pl ? cj : n + cj;
-                const int s = cubepad_src(f, i, j, g);
-                const int sf = s / nn, rem = s - sf * nn, row = rem / n;
-                ps[ci < g.pt ? i * Wp + j : ps_bot + (ci - g.pt) * Wp + j] = buf[lds_of(sf, row, rem - row * n)];
-            }
-        }
-        __syncthreads();
-        {
-            const int nchunks = (head + plane_elems + E - 1) >> LOG_E;
-            const int top_end = min((rowA + E - 1) >> LOG_E, nchunks);                       // run_begin(0)
-            const int bot_begin = max(((n - 1) * Wp + rowA + n) >> LOG_E, top_end);          // run_end(n - 1)
-            const int n_tb = top_end + (nchunks - bot_begin);
-            const int n_slow = n_tb + (n - 1) * maxc;
-            const int s0 = part * n_slow / parts, s1 = (part + 1) * n_slow / parts;
-            for (int s = s0 + lane; s < s1; s += 64) {
-                int ch;
-                if (s < top_end) ch = s;
-                else if (s < n_tb) ch = bot_begin + (s - top_end);
-                else {
-                    const int m = s - n_tb;
-                    const int rr = div_by(m, maxc, rcp_maxc);
-                    const int lo = max((rr * Wp + rowA + n) >> LOG_E, top_end);              // run_end(rr)
-                    const int hi = min(((rr + 1) * Wp + rowA + E - 1) >> LOG_E, bot_begin);  // run_begin(rr + 1)
-                    ch = lo + (m - rr * maxc);
-                    if (ch >= hi) continue;
-                }
-                const int q0 = ch * E - head;
-                int iA, jA;
-                if (q0 < 0) { iA = -1; jA = q0 + Wp; }
-                else        { iA = div_by(q0, Wp, rcp_wp); jA = q0 - iA * Wp; }
-                const int a = iA - g.pt;
-                const bool rowc = a >= 0 && a < n;
-                const bool q0c = rowc && jA >= g.pl && jA < g.pl + n;
-                const int cpos = a < 0 ? 0 : (a >= n ? nn : a * n + min(max(jA - g.pl, 0), n));
-                const int eA = q0c ? min(E, g.pl + n - jA) : 0;
-                const int aB = q0c ? a + 1 : (a < 0 ? 0 : (rowc ? (jA < g.pl ? a : a + 1) : n));
-                const int eB = aB < n ? min(max((g.pt + aB) * Wp + g.pl - q0, 0), E) : E;
-                const T* pa = buf + (eA > 0 ? ((f * n + a) * 2 + 1) * E + (E - eA) : 0);     // row a's last eA elements at e = 0 ..
-                const T* pb = buf + (eB < E ? ((f * n + aB) * 2) * E - eB : 0);               // row aB's first elements at e = eB ..
-                const T* pp = ps + (q0 - cpos - eA);
-                T tv[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const T va = pa[e], vb = pb[e], pv = pp[e];
-                    tv[e] = e < eA ? va : (e >= eB ? vb : pv);
-                }
-                unsigned char* ca = c0p + ((size_t)ch << 4);
-                if (q0 >= 0 && q0 + E <= plane_elems) {
-                    u32x4 v;
-                    __builtin_memcpy(&v, tv, 16);
-                    *reinterpret_cast<u32x4*>(ca) = v;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < E; ++e)
-                        if (q0 + e >= 0 && q0 + e < plane_elems) reinterpret_cast<T*>(ca)[e] = tv[e];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
 
 // ---------------------------------------------------------------- NCHW, six padded planes assembled in LDS (round 3)
-// What the timing variants of the two kernels above show (profiles/r03_cubepad_plane.md): HBM rewards ONE linear sweep of
-// whole 128-byte lines and punishes everything else - run chunks that leave holes, holes filled later, even whole lines
+// What the timing variants of the retired channel / plane kernels show (profiles/r03_cubepad_plane.md): HBM rewards ONE
+// linear sweep of whole 128-byte lines and punishes everything else - run chunks that leave holes, holes filled later, even whole lines
 // written sparsely all land at 3-3.5 TB/s where the same structure with a linear store stream reaches 4.8-5 (= a plain
 // copy).  So when the six padded planes of a (cube, channel) fit the 160 KB of LDS (n <= 114 for 2-byte elements, every
 // face of the network from layer1 down), the item is assembled there and written once, linearly.  An item is (cube,
@@ -812,7 +254,7 @@ __global__ __launch_bounds__(1024) void cubepad_nchw_lds6_kernel(const unsigned 
 //   1  the band's centre rows: 16-byte chunks of the contiguous input rows to their padded places (a chunk that runs over
 //      a row end continues pl + pr elements later);
 //   2  its pads straight from the neighbouring faces in global memory through the affine line table (base + a * step per
-//      strip line; a column strip costs one 128-byte line per row - the read amplification the channel kernel avoids,
+//      strip line; a column strip costs one 128-byte line per row - a read amplification of
 //      ~1.2x at 896-byte rows - but nothing is written twice or out of order); corners through cubepad_src();
 //   3  aligned 16-byte LDS reads -> aligned 16-byte global stores; the chunk a band shares with the previous / next band
 //      goes element by element.
@@ -992,7 +434,7 @@ __global__ __launch_bounds__(256) void cubepad_nchw_band_kernel(const unsigned c
 //     with aligned 16-byte stores.
 // Workgroups are persistent over items, so the table costs 6 Hp Wp / 256 evaluations per thread once.  Needs n <= 32,
 // 16-byte aligned ranges (checked by the launcher: c0 * n^2 * ES and c0 * Hp * Wp * ES multiples of 16); anything else
-// takes the kernels above.  Bit-exact like every CubePad kernel (pure copy).
+// takes the other kernels.  Bit-exact like every CubePad kernel (pure copy).
 template <int ES>
 __global__ __launch_bounds__(256) void cubepad_nchw_cube_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y,
                                                                 int C, CubePadGeom g, int CH, int n_items, int ranges) {
@@ -1060,165 +502,93 @@ static int ensure_big_lds() {
     return CP360_OK;
 }
 
+// The launchers: each returns 1 ("not taken") where its kernel's correctness conditions do not hold, a status otherwise.
+// What is only a measured preference (face size, item count, row bytes) is an argument, set by launch_nchw().
+//
+// Small faces: whole cubes through LDS.  CH channels per item: the largest divisor-free choice whose input fits
+// ~24 KiB and whose per-face input / output ranges are whole 16-byte chunks at 16-byte aligned addresses.  The table packs
+// a source as sf << 10 | offset: faces up to 32x32.
+template <int ES>
+static int try_cube(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st, int max_n) {
+    const int nn = g.n * g.n, HW = (g.n + g.pt + g.pd) * (g.n + g.pl + g.pr);
+    if (g.n > max_n || g.n > 32 || HW > 1444 || (reinterpret_cast<size_t>(x) & 15) || (reinterpret_cast<size_t>(y) & 15)) return 1;
+    int CH = 0;
+    for (int ch = 1; ch <= C && (size_t)6 * ch * nn * ES <= 24 * 1024; ++ch)
+        if (C % ch == 0 && (ch * nn * ES) % 16 == 0 && (ch * HW * ES) % 16 == 0) CH = ch;
+    if (CH == 0 || ((size_t)C * nn * ES) % 16 || ((size_t)C * HW * ES) % 16) return 1;
+    const int ranges = C / CH;
+    const long long items = (long long)(n6 / 6) * ranges;
+    const size_t lds = (size_t)((6 * HW * 2 + 15) & ~15) + (size_t)6 * CH * nn * ES;
+    long long blocks = items < 256 * 4 ? items : 256 * 4;
+    hipLaunchKernelGGL((cubepad_nchw_cube_kernel<ES>), dim3((unsigned)blocks), dim3(256), lds, st,
+                       (const unsigned char*)x, (unsigned char*)y, C, g, CH, (int)items, ranges);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// Six padded planes assembled in LDS, one linear store stream; worth its three barriers from min_items items on.
+template <int ES>
+static int try_lds6(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st, long long min_items) {
+    constexpr int E = 16 / ES;
+    const int nlines = g.pt + g.pd + g.pl + g.pr;
+    const long long HW = (long long)(g.n + g.pt + g.pd) * (g.n + g.pl + g.pr), nn = (long long)g.n * g.n;
+    // channels per item: one for faces whose six planes fill the LDS; for small faces the largest divisor of C that
+    // keeps the six ranges within ~40 KB (>= 4 workgroups per CU) and leaves >= 512 items
+    int CH = 1;
+    for (int ch = 2; ch <= C && ch <= 64; ++ch) {
+        if (C % ch) continue;
+        const long long ps = ((ch * HW + E) * ES + 15) / 16 * 16;
+        if (768 + 6 * ps > 40 * 1024 || (long long)(n6 / 6) * (C / ch) < 512) break;
+        CH = ch;
+    }
+    const long long items = (long long)(n6 / 6) * (C / CH);
+    const long long pstride = ((CH * HW + E) * ES + 15) / 16 * 16;
+    const size_t lds6 = 768 + (size_t)6 * pstride;
+    if (nlines < 1 || nlines > 16 || g.n < E || CH * nn < E || lds6 > 160 * 1024 || CH * HW >= (1 << 22) || items < min_items ||
+        items >= (1ll << 31) || (reinterpret_cast<size_t>(y) % ES) || (reinterpret_cast<size_t>(x) % ES) ||
+        ensure_big_lds<&cubepad_nchw_lds6_kernel<ES>>() != CP360_OK)      // (refused: on to the <= 64 KB kernels)
+        return 1;
+    int per_cu = (int)((size_t)160 * 1024 / lds6);
+    const int nt = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
+    if (per_cu > 2048 / nt) per_cu = 2048 / nt;
+    long long blocks = items < 256ll * per_cu ? items : 256ll * per_cu;
+    const int nstrip = nlines * g.n;
+    const int cpf = (int)((CH * nn + E - 1) / E), nchmax = (int)((CH * HW + 2 * E - 2) / E);
+    hipLaunchKernelGGL((cubepad_nchw_lds6_kernel<ES>), dim3((unsigned)blocks), dim3(nt), lds6, st,
+                       (const unsigned char*)x, (unsigned char*)y, C, g, CH, C / CH, (int)items, (int)pstride,
+                       1.0f / (float)g.n, 1.0f / (float)nn, 1.0f / (float)cpf, 1.0f / (float)nstrip,
+                       1.0f / (float)(CH * nstrip), 1.0f / (float)nchmax);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// Row bands of one plane assembled in LDS, linear stores; rows of at least min_row_bytes.
+template <int ES>
+static int try_band(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st, int min_row_bytes) {
+    constexpr int E = 16 / ES;
+    const int Hp = g.n + g.pt + g.pd, Wp = g.n + g.pl + g.pr, LR = g.pl + g.pr, nlines = g.pt + g.pd + LR;
+    int R = 16384 / (Wp * ES);                       // ~16 KB of output per item
+    if (R < 2) R = 2;
+    if (R > Hp) R = Hp;
+    const int nb = (Hp + R - 1) / R;
+    const long long items = (long long)(n6 / 6) * C * 6 * nb;
+    const size_t ldsb = 768 + (size_t)((long long)R * Wp + 2 * E) * ES + 16;
+    if (nlines < 1 || nlines > 16 || g.n < E || g.n * ES < min_row_bytes || ldsb > 64 * 1024 || (long long)Hp * Wp >= (1 << 22) ||
+        (long long)6 * C * g.n * g.n >= (1ll << 31) || items >= (1ll << 31) || (reinterpret_cast<size_t>(y) % ES) ||
+        (reinterpret_cast<size_t>(x) % ES))
+        return 1;
+    long long blocks = items < 256 * 8 ? items : 256 * 8;
+    hipLaunchKernelGGL((cubepad_nchw_band_kernel<ES>), dim3((unsigned)blocks), dim3(256), ldsb, st,
+                       (const unsigned char*)x, (unsigned char*)y, C, g, (int)items, nb, R, 1.0f / (float)g.n,
+                       1.0f / (float)Wp, 1.0f / (float)(LR > 0 ? LR : 1));
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
 template <typename T>
-static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st) {
+static int launch_elementwise(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st) {
     const int Wp = g.n + g.pl + g.pr;
     const int planes = (n6 / 6) * C;
-    // small faces: whole cubes through LDS.  CH channels per item: the largest divisor-free choice whose input fits
-    // ~24 KiB and whose per-face input / output ranges are whole 16-byte chunks at 16-byte aligned addresses.  Measured
-    // against the lds6 kernel (profiles/r03zz_hbm_kernels.md): better up to 14x14 faces (29 / 12 us against 35 / 15 us
-    // on [384,256,14,14] f16 / the ConvLSTM's [24,2000,7,7] f32), worse at 28x28 (59 against 42 us): it goes first for
-    // n <= 16 and stays the fallback up to 32.
-    auto try_cube = [&](int max_n) -> int {
-        constexpr int ES = (int)sizeof(T);
-        const int nn = g.n * g.n, HW = (g.n + g.pt + g.pd) * Wp;
-        static const int no_cube = []() { const char* e = getenv("CP360_CUBEPAD_NOCUBE"); return e ? atoi(e) : 0; }();   // test hook
-        if (!no_cube && g.n <= max_n && HW <= 1444 && (reinterpret_cast<size_t>(x) & 15) == 0 && (reinterpret_cast<size_t>(y) & 15) == 0) {
-            int CH = 0;
-            for (int ch = 1; ch <= C && (size_t)6 * ch * nn * ES <= 24 * 1024; ++ch)
-                if (C % ch == 0 && (ch * nn * ES) % 16 == 0 && (ch * HW * ES) % 16 == 0) CH = ch;
-            if (CH > 0 && ((size_t)C * nn * ES) % 16 == 0 && ((size_t)C * HW * ES) % 16 == 0) {
-                const int ranges = C / CH;
-                const long long items = (long long)(n6 / 6) * ranges;
-                const size_t lds = (size_t)((6 * HW * 2 + 15) & ~15) + (size_t)6 * CH * nn * ES;
-                long long blocks = items < 256 * 4 ? items : 256 * 4;
-                hipLaunchKernelGGL((cubepad_nchw_cube_kernel<ES>), dim3((unsigned)blocks), dim3(256), lds, st,
-                                   (const unsigned char*)x, (unsigned char*)y, C, g, CH, (int)items, ranges);
-                CP360_CHECK_HIP();
-                return CP360_OK;
-            }
-        }
-        return 1;                                            // not taken
-    };
-    // The getenv switches of this function are test hooks: tests/test_gpu_parity.py sets them to pin each kernel of this chain (every one
-    // of which the default dispatch takes for some shape); unset, they change nothing.
-    if (int r = try_cube(16); r <= 0) return r;
-    {   // strip kernel: pads of at most 4 (every pad of the network is 1 or 3), strips within the 64 KiB LDS default
-        const int P = max(max(g.pl, g.pr), max(g.pt, g.pd));
-        constexpr int ES = (int)sizeof(T);
-        const int Hp = g.n + g.pt + g.pd;
-        const size_t lds = (size_t)4 * (g.pt + g.pd + g.pl + g.pr) * g.n * ES;      // four waves' strips
-        static const int no_strip = []() {
-            const char* e = getenv("CP360_CUBEPAD_ELEMENTWISE");      // test hook: the element-per-lane kernel
-            return e ? atoi(e) : 0;
-        }();
-        // (rows of at least 112 bytes - 56x56 f16 faces: 245 -> 149 us against the element-per-lane kernel, round 3; smaller
-        //  faces take the whole-cube kernel above)
-        constexpr int strip_min = 112;
-        static const int strip_v1 = []() { const char* e = getenv("CP360_CUBEPAD_STRIP_V1"); return e ? atoi(e) : 0; }();   // test hook
-        constexpr int E = 16 / ES;
-        const int LR = g.pl + g.pr, nlines = g.pt + g.pd + LR;
-        const long long ps_size = (long long)Hp * Wp - (long long)g.n * g.n;
-        const int ps_alloc = (int)((ps_size + 2 * E + E - 1) / E * E);
-        const size_t lds2 = 512 + (size_t)4 * ps_alloc * ES;
-        static const int no_channel = []() { const char* e = getenv("CP360_CUBEPAD_NOCHANNEL"); return e ? atoi(e) : 0; }();   // test hook
-        static const int channel_min = []() { const char* e = getenv("CP360_CUBEPAD_CHANNEL_MIN"); return e ? atoi(e) : 96; }();   // test hook
-        {   // six padded planes assembled in LDS, one linear store stream
-            static const int no_lds6 = []() { const char* e = getenv("CP360_CUBEPAD_NOLDS6"); return e ? atoi(e) : 0; }();   // test hook
-            static const int lds6_min = []() { const char* e = getenv("CP360_CUBEPAD_LDS6_MIN"); return e ? atoi(e) : 64; }();   // test hook
-            const long long HW = (long long)Hp * Wp, nn = (long long)g.n * g.n;
-            // channels per item: one for faces whose six planes fill the LDS; for small faces the largest divisor of C that
-            // keeps the six ranges within ~40 KB (>= 4 workgroups per CU) and leaves >= 512 items
-            int CH = 1;
-            for (int ch = 2; ch <= C && ch <= 64; ++ch) {
-                if (C % ch) continue;
-                const long long ps = ((ch * HW + E) * ES + 15) / 16 * 16;
-                if (768 + 6 * ps > 40 * 1024 || (long long)(n6 / 6) * (C / ch) < 512) break;
-                CH = ch;
-            }
-            const long long items = (long long)(n6 / 6) * (C / CH);
-            const long long pstride = ((CH * HW + E) * ES + 15) / 16 * 16;
-            const size_t lds6 = 768 + (size_t)6 * pstride;
-            if (!no_strip && !no_lds6 && P >= 1 && nlines <= 16 && g.n >= E && CH * nn >= E && lds6 <= 160 * 1024 &&
-                CH * HW < (1 << 22) && items >= lds6_min && items < (1ll << 31) && (reinterpret_cast<size_t>(y) % ES) == 0 &&
-                (reinterpret_cast<size_t>(x) % ES) == 0 &&
-                ensure_big_lds<&cubepad_nchw_lds6_kernel<ES>>() == CP360_OK) {    // (refused: on down the chain to the <= 64 KB kernels)
-                int per_cu = (int)((size_t)160 * 1024 / lds6);
-                const int nt = per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024);
-                if (per_cu > 2048 / nt) per_cu = 2048 / nt;
-                long long blocks = items < 256ll * per_cu ? items : 256ll * per_cu;
-                const int nstrip = nlines * g.n;
-                const int cpf = (int)((CH * nn + E - 1) / E), nchmax = (int)((CH * HW + 2 * E - 2) / E);
-                hipLaunchKernelGGL((cubepad_nchw_lds6_kernel<ES>), dim3((unsigned)blocks), dim3(nt), lds6, st,
-                                   (const unsigned char*)x, (unsigned char*)y, C, g, CH, C / CH, (int)items, (int)pstride,
-                                   1.0f / (float)g.n, 1.0f / (float)nn, 1.0f / (float)cpf, 1.0f / (float)(nstrip > 0 ? nstrip : 1),
-                                   1.0f / (float)(CH * nstrip > 0 ? CH * nstrip : 1), 1.0f / (float)nchmax);
-                CP360_CHECK_HIP();
-                return CP360_OK;
-            }
-        }
-        if (int r = try_cube(32); r <= 0) return r;
-        {   // planes larger than the LDS: row bands assembled in LDS, linear stores
-            static const int no_band = []() { const char* e = getenv("CP360_CUBEPAD_NOBAND"); return e ? atoi(e) : 0; }();   // test hook
-            static const int band_min_row = []() { const char* e = getenv("CP360_CUBEPAD_BAND_MINROW"); return e ? atoi(e) : 256; }();   // test hook
-            int R = 16384 / (Wp * ES);                       // ~16 KB of output per item
-            if (R < 2) R = 2;
-            if (R > Hp) R = Hp;
-            const int nb = (Hp + R - 1) / R;
-            const long long items = (long long)planes * 6 * nb;
-            const size_t ldsb = 768 + (size_t)((long long)R * Wp + 2 * E) * ES + 16;
-            if (!no_strip && !no_band && P >= 1 && nlines <= 16 && g.n >= E && g.n * ES >= band_min_row && ldsb <= 64 * 1024 &&
-                (long long)Hp * Wp < (1 << 22) && (long long)6 * C * g.n * g.n < (1ll << 31) && items < (1ll << 31) &&
-                (reinterpret_cast<size_t>(y) % ES) == 0 && (reinterpret_cast<size_t>(x) % ES) == 0) {
-                long long blocks = items < 256 * 8 ? items : 256 * 8;
-                hipLaunchKernelGGL((cubepad_nchw_band_kernel<ES>), dim3((unsigned)blocks), dim3(256), ldsb, st,
-                                   (const unsigned char*)x, (unsigned char*)y, C, g, (int)items, nb, R, 1.0f / (float)g.n,
-                                   1.0f / (float)Wp, 1.0f / (float)(LR > 0 ? LR : 1));
-                CP360_CHECK_HIP();
-                return CP360_OK;
-            }
-        }
-        {   // every input byte once: (cube, channel) items
-            const long long items = (long long)(n6 / 6) * C;
-            const size_t lds3 = 768 + ((size_t)E + (size_t)12 * g.n * E + (size_t)12 * P * g.n + (size_t)6 * ps_alloc + 2 * E) * ES;
-            if (!no_strip && !strip_v1 && !no_channel && P >= 1 && P <= E && g.n * ES >= strip_min && nlines <= 16 &&
-                g.n >= 2 * E + LR && g.n >= 2 * P && lds3 <= 160 * 1024 && (long long)Hp * Wp < (1 << 22) && items >= channel_min &&
-                items < (1ll << 31) && (long long)g.n * g.n < (1ll << 31) && (reinterpret_cast<size_t>(y) % ES) == 0 &&
-                (reinterpret_cast<size_t>(x) % ES) == 0 &&
-                ensure_big_lds<&cubepad_nchw_channel_kernel<ES>>() == CP360_OK) {
-                // one wave per face while that gives >= 12 waves per CU, two (768 threads) for few / large items
-                const int nt = items >= 512 ? 384 : 768;
-                int per_cu = (int)((size_t)160 * 1024 / lds3);
-                if (per_cu > 2048 / nt) per_cu = 2048 / nt;
-                if (per_cu < 1) per_cu = 1;
-                long long blocks = items < 256ll * per_cu ? items : 256ll * per_cu;
-                const int cpr = g.n / E + 1, maxc = (LR + 2 * E - 2) / E;
-                int rbw = 64 * 8 / cpr;                      // rows per block: one 8-deep body of run chunks per wave
-                if (rbw < 4) rbw = 4;
-                hipLaunchKernelGGL((cubepad_nchw_channel_kernel<ES>), dim3((unsigned)blocks), dim3(nt), lds3, st,
-                                   (const unsigned char*)x, (unsigned char*)y, C, g, (int)items, 1.0f / (float)Wp,
-                                   1.0f / (float)g.n, 1.0f / (float)cpr, maxc, 1.0f / (float)maxc, P, ps_alloc, rbw);
-                CP360_CHECK_HIP();
-                return CP360_OK;
-            }
-        }
-        if (!no_strip && !strip_v1 && P >= 1 && g.n * ES >= strip_min && nlines <= 16 && g.n >= 2 * E + LR && lds2 <= 64 * 1024 &&
-            (long long)Hp * Wp < (1 << 22) && (long long)6 * C * g.n * g.n < (1ll << 31) && (reinterpret_cast<size_t>(y) % ES) == 0 &&
-            (reinterpret_cast<size_t>(x) % ES) == 0) {
-            const long long items = (long long)planes * 6;
-            long long blocks = (items + 3) / 4;
-            if (blocks > 256 * 32) blocks = 256 * 32;
-            const int cpr = g.n / E + 1, dq = 64 / cpr, dm = 64 - dq * cpr;
-            const int maxc = (LR + 2 * E - 2) / E;
-            hipLaunchKernelGGL((cubepad_nchw_plane_kernel<ES>), dim3((unsigned)blocks), dim3(256), lds2, st,
-                               (const unsigned char*)x, (unsigned char*)y, C, g, (int)items, (long long)n6 * C * g.n * g.n,
-                               1.0f / (float)Wp, 1.0f / (float)g.n, 1.0f / (float)cpr, dq, dm, maxc, 1.0f / (float)maxc, ps_alloc,
-                               std::max(4, 256 / cpr));
-            CP360_CHECK_HIP();
-            return CP360_OK;
-        }
-        if (!no_strip && P >= 1 && P <= g.n && g.n * ES >= strip_min && lds <= 64 * 1024 && (long long)Hp * Wp < (1 << 22) &&
-            (reinterpret_cast<size_t>(y) % ES) == 0) {
-            const long long items = (long long)planes * 6;
-            long long blocks = (items + 3) / 4;
-            if (blocks > 256 * 32) blocks = 256 * 32;
-            hipLaunchKernelGGL((cubepad_nchw_strip_kernel<ES>), dim3((unsigned)blocks), dim3(256), lds, st,
-                               (const unsigned char*)x, (unsigned char*)y, C, g, (int)items, 1.0f / (float)Wp,
-                               1.0f / (float)g.n);
-            CP360_CHECK_HIP();
-            return CP360_OK;
-        }
-    }
     if (Wp <= 16)
         hipLaunchKernelGGL((cubepad_nchw_kernel<T, 4>), dim3(planes), dim3(256), 0, st, (const T*)x, (T*)y, C, g);
     else if (Wp <= 32)
@@ -1227,6 +597,43 @@ static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom&
         hipLaunchKernelGGL((cubepad_nchw_kernel<T, 6>), dim3(planes), dim3(256), 0, st, (const T*)x, (T*)y, C, g);
     CP360_CHECK_HIP();
     return CP360_OK;
+}
+
+// Test hook, read once per process: CP360_CUBEPAD_ONLY=cube|lds6|band|elementwise runs the named kernel wherever it is
+// correct, whatever the thresholds of the default dispatch say, and the element-per-lane kernel everywhere else
+// (tests/test_gpu_parity.py).  Unset: 0, the default dispatch.  Any other value: -1, refused.
+static int cubepad_only() {
+    static const int only = []() {
+        const char* e = getenv("CP360_CUBEPAD_ONLY");
+        if (!e) return 0;
+        for (const char* name : {"cube", "lds6", "band", "elementwise"})
+            if (!strcmp(e, name)) return (int)name[0];
+        return -1;
+    }();
+    return only;
+}
+
+// Default order, from profiles/r03zz_hbm_kernels.md and profiles/cubepad_retire.md: the whole-cube kernel beats lds6 up to
+// 14x14 faces (29 / 12 us against 35 / 15 us on [384,256,14,14] f16 / the ConvLSTM's [24,2000,7,7] f32) and loses at 28x28
+// (59 against 42 us), so it goes first for n <= 16 and stays the fallback up to 32; row bands start at 112-byte rows, the
+// floor of the retired strip / plane / channel kernels, which they beat on every shape measured.
+template <typename T>
+static int launch_nchw(const void* x, void* y, int n6, int C, const CubePadGeom& g, hipStream_t st) {
+    constexpr int ES = (int)sizeof(T);
+    switch (cubepad_only()) {
+        case 'c': if (int r = try_cube<ES>(x, y, n6, C, g, st, 32); r <= 0) return r; break;
+        case 'l': if (int r = try_lds6<ES>(x, y, n6, C, g, st, 1); r <= 0) return r; break;
+        case 'b': if (int r = try_band<ES>(x, y, n6, C, g, st, 0); r <= 0) return r; break;
+        case 'e': break;
+        case 0:
+            if (int r = try_cube<ES>(x, y, n6, C, g, st, 16); r <= 0) return r;
+            if (int r = try_lds6<ES>(x, y, n6, C, g, st, 64); r <= 0) return r;
+            if (int r = try_cube<ES>(x, y, n6, C, g, st, 32); r <= 0) return r;
+            if (int r = try_band<ES>(x, y, n6, C, g, st, 112); r <= 0) return r;
+            break;
+        default: return CP360_ERR_UNSUPPORTED;
+    }
+    return launch_elementwise<T>(x, y, n6, C, g, st);
 }
 
 static int check_geom(int n6, int C, int n, int pl, int pr, int pt, int pd) {

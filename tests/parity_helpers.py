@@ -62,6 +62,12 @@ def cubepad_sweep(dev):
               (256, [1, 1, 1, 1], 16, 36, torch.int16, 0), (28, [1, 1, 1, 1], 128, 24, torch.int16, 0),
               (14, [1, 1, 1, 1], 256, 12, torch.int16, 0), (7, [1, 1, 1, 1], 500, 12, torch.int32, 0),
               (120, [1, 1, 1, 1], 32, 12, torch.int16, 0), (200, [2, 1, 0, 3], 20, 24, torch.uint8, 1)]
+    # rows of 112-264 bytes with few items, misaligned bases, a pad sum above 16 lines: row bands down to their floor,
+    # the element-per-lane kernel below it (rows within one wave and longer)
+    cases += [(120, [1, 1, 1, 1], 2, 6, torch.int16, 1), (60, [2, 1, 0, 3], 3, 6, torch.int32, 0),
+              (28, [1, 1, 1, 1], 5, 6, torch.int32, 1), (27, [1, 1, 1, 1], 5, 6, torch.int32, 1),
+              (128, [5, 4, 5, 4], 2, 6, torch.int16, 0), (170, [1, 0, 3, 2], 2, 6, torch.uint8, 3),
+              (33, [1, 1, 1, 1], 3, 6, torch.int64, 0)]
     for case, (n, pad, C, n6, dt, off) in enumerate(cases):
         x = rng.randint(0, 120, size=(n6, C, n, n)).astype(npd[dt])
         buf = torch.zeros(x.size + off, dtype=dt, device=dev)

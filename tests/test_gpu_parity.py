@@ -108,31 +108,25 @@ def test_cubepad_nchw_small_faces_whole_cube_kernel(shape, pad, dtype):
 
 def test_cubepad_nchw_randomised_geometry_sweep():
     """Seeded sweep over the NCHW kernels' dispatch space (csrc/cubepad.hip launch_nchw: whole-cube kernel for small
-    faces, lds6 when the six padded planes fit the LDS, row bands for long rows, channel / plane / strip kernels and the
-    element-per-lane kernel otherwise): random face size, asymmetric pads (each <= n, cube_pad.py:60-70), channel count,
+    faces, lds6 when the six padded planes fit the LDS, row bands for rows of at least 112 bytes, the element-per-lane
+    kernel otherwise): random face size, asymmetric pads (each <= n, cube_pad.py:60-70), channel count,
     element size, 1-2 cubes, and a base pointer offset by a few elements so the 16-byte alignment checks see misaligned
     planes; then shapes with enough (cube, channel) items for the read-once kernels, odd plane sizes (chunks shared between
-    planes), pads of 0 on some sides.  Bit-exact against the oracle (cube_pad.py:95-216).  tests/parity_helpers.py."""
+    planes), pads of 0 on some sides, rows just below, at and above the row bands' floor with few items, a pad sum above
+    the 16 strip lines lds6 and the row bands take.  Bit-exact against the oracle (cube_pad.py:95-216).  tests/parity_helpers.py."""
     ph.cubepad_sweep(DEV)
 
 
-@pytest.mark.parametrize('env', [
-    {'CP360_CUBEPAD_NOLDS6': '1', 'CP360_CUBEPAD_NOBAND': '1', 'CP360_CUBEPAD_CHANNEL_MIN': '1'},      # channel kernel
-    {'CP360_CUBEPAD_NOLDS6': '1', 'CP360_CUBEPAD_NOBAND': '1', 'CP360_CUBEPAD_NOCHANNEL': '1'},        # plane kernel
-    {'CP360_CUBEPAD_NOLDS6': '1', 'CP360_CUBEPAD_NOBAND': '1', 'CP360_CUBEPAD_STRIP_V1': '1'},         # round-2 strip kernel
-    {'CP360_CUBEPAD_NOLDS6': '1', 'CP360_CUBEPAD_NOCUBE': '1', 'CP360_CUBEPAD_BAND_MINROW': '1'},      # row bands everywhere
-    {'CP360_CUBEPAD_NOCUBE': '1', 'CP360_CUBEPAD_LDS6_MIN': '1'},                                       # lds6 wherever it fits
-    {'CP360_CUBEPAD_ELEMENTWISE': '1', 'CP360_CUBEPAD_NOCUBE': '1'},                                    # element-per-lane kernel
-], ids=['channel', 'plane', 'strip_v1', 'band', 'lds6', 'elementwise'])
-def test_cubepad_nchw_sweep_with_each_kernel_forced(env):
-    """The same sweep with the dispatch pinned to each NCHW kernel through its A/B switch (the switches are read once per
-    process, hence a child process per setting): every kernel is bit-exact on every geometry it accepts, not only on the
-    ones the default dispatch hands it."""
+@pytest.mark.parametrize('only', ['cube', 'lds6', 'band', 'elementwise'])
+def test_cubepad_nchw_sweep_with_each_kernel_forced(only):
+    """The same sweep with the dispatch pinned through CP360_CUBEPAD_ONLY to each NCHW kernel - whole-cube, lds6, row bands,
+    element per lane - (the variable is read once per process, hence a child process per setting): every kernel is
+    bit-exact on every geometry it accepts, not only on the ones the default dispatch hands it."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     e = dict(os.environ)
-    e.update(env)
+    e['CP360_CUBEPAD_ONLY'] = only
     e['PYTHONPATH'] = root + os.pathsep + e.get('PYTHONPATH', '')
     r = subprocess.run([sys.executable, '-c', 'from tests import parity_helpers as ph; ph.cubepad_sweep("cuda"); print("SWEEP_OK")'],
                        cwd=root, env=e, capture_output=True, text=True, timeout=600)

@@ -1,6 +1,8 @@
-"""Stand-alone NCHW CubePad timings on the network's large shapes (GPU box): python tools/cubepad_bench.py <tag>.
-A/B switches (read once per process by csrc/cubepad.hip): CP360_CUBEPAD_NOLDS6, CP360_CUBEPAD_NOCHANNEL,
-CP360_CUBEPAD_STRIP_V1, CP360_CUBEPAD_ELEMENTWISE, CP360_CUBEPAD_NOCUBE.  TB/s = (input + output bytes) / time."""
+"""Stand-alone NCHW CubePad timings (GPU box): python tools/cubepad_bench.py <tag> [--gap].
+Default: the network's large shapes A-D of profiles/r03_cubepad_plane.md (lds6 and row bands).  --gap: the shapes of
+profiles/cubepad_retire.md, which the retired channel / plane / strip kernels used to take (row bands and element per lane
+now).  CP360_CUBEPAD_ONLY=cube|lds6|band|elementwise pins one kernel and CP360_LIB names another build of the library;
+csrc/cubepad.hip and _lib.py read them once per process.  TB/s = (input + output bytes) / time."""
 import os
 import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -8,6 +10,9 @@ import torch
 from cp_360_weakly_supervised_saliency_amd.model.cube_pad import CubePad
 cases = [((384, 64, 112, 112), torch.float16, 1), ((384, 3, 224, 224), torch.float32, 3), ((384, 256, 56, 56), torch.float16, 1),
          ((96, 64, 256, 256), torch.float16, 1)]
+if '--gap' in sys.argv[2:]:
+    cases = [((384, 64, 120, 120), torch.float16, 1), ((96, 64, 200, 200), torch.uint8, 1), ((12, 32, 120, 120), torch.float16, 1),
+             ((6, 3, 56, 56), torch.float32, 3), ((96, 64, 128, 128), torch.float16, 5)]
 for shp, dt, p in cases:
     x = torch.randn(shp, device='cuda').to(dt)
     m = CubePad(p)
