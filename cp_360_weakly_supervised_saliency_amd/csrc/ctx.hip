@@ -45,6 +45,10 @@ __global__ void add_vec_kernel(float* __restrict__ a, const float* __restrict__ 
 __global__ void sub_scalar_kernel(const float* __restrict__ x, float s, float* __restrict__ y, long long n) {
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) y[i] = x[i] - s;
 }
+void launch_fold_bn(const float* g, const float* b, const float* mu, const float* var, float eps, float* scale, float* bias, int n,
+                    hipStream_t st) {
+    hipLaunchKernelGGL(fold_bn_kernel, dim3((n + 255) / 256), dim3(256), 0, st, g, b, mu, var, eps, scale, bias, n);
+}
 
 int es_of(int dtype) { return dtype == CP360_F32 ? 4 : 2; }
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -85,8 +89,9 @@ struct CConv {
     float* bias = nullptr;
 };
 
-void fill_desc(const CConv& c, int dtype, int n_img, int h_in, int w_in, int splits, int ld_out, int out_coff,
-               int ld_res, int clip_resident, int slab_rows, int h2, int w2, int ps2, cp360_conv_desc* d) {
+// The descriptor of `c` on n_img inputs of h_in x w_in with dense output, no residual and one split; a second source (the
+// downsample branch) with the geometry its stride implies.  Plan::conv adjusts what a call site states otherwise.
+void fill_desc(const CConv& c, int dtype, int n_img, int h_in, int w_in, int clip_resident, cp360_conv_desc* d) {
     *d = cp360_conv_desc{};
     d->dtype = dtype;
     d->n_img = n_img; d->h_in = h_in; d->w_in = w_in;
@@ -97,14 +102,12 @@ void fill_desc(const CConv& c, int dtype, int n_img, int h_in, int w_in, int spl
     d->w_out = c.stem ? (w_in + p2 - c.kw_w) / c.stride + 1 : (w_in + p2 - c.kw) / c.stride + 1;
     d->c_out = c.c_out;
     d->pad_mode = c.pad > 0 ? 1 : 0; d->pad = c.pad;
-    d->ld_out = ld_out > 0 ? ld_out : c.c_out;
-    d->out_coff = out_coff; d->ld_res = ld_res;
-    d->relu = c.relu; d->splits = splits; d->tile_px = 0;
-    d->clip_resident = clip_resident; d->slab_rows = slab_rows;
+    d->ld_out = c.c_out;
+    d->relu = c.relu; d->splits = 1;
+    d->clip_resident = clip_resident;
     if (c.c_in2 > 0) {
         d->c_in2 = c.c_in2; d->sy2 = d->sx2 = c.stride2;
-        if (h2 > 0) { d->h_in2 = h2; d->w_in2 = w2; d->pix_stride2 = ps2; }
-        else { d->h_in2 = (d->h_out - 1) * c.stride2 + 1; d->w_in2 = (d->w_out - 1) * c.stride2 + 1; d->pix_stride2 = c.c_in2; }
+        d->h_in2 = (d->h_out - 1) * c.stride2 + 1; d->w_in2 = (d->w_out - 1) * c.stride2 + 1; d->pix_stride2 = c.c_in2;
     }
 }
 
@@ -113,7 +116,7 @@ int pack_conv(Owned& own, CConv& c, int dtype, const float* w, const float* scal
               bool want_plain, bool want_clip, hipStream_t st) {
     cp360_conv_desc d;
     if (want_plain) {
-        fill_desc(c, dtype, 6, c.kh > 8 ? c.kh : 8, c.stem ? 16 : (c.kw > 8 ? c.kw : 8), 1, 0, 0, 0, 0, 0, 0, 0, 0, &d);
+        fill_desc(c, dtype, 6, c.kh > 8 ? c.kh : 8, c.stem ? 16 : (c.kw > 8 ? c.kw : 8), 0, &d);
         const size_t nb = cp360_conv_packed_bytes(&d);
         if (!nb) return CP360_ERR_UNSUPPORTED;
         if (!(c.packed = own.take(nb))) return CP360_ERR_HIP;
@@ -122,7 +125,7 @@ int pack_conv(Owned& own, CConv& c, int dtype, const float* w, const float* scal
         if (rc) return rc;
     }
     if (want_clip) {
-        fill_desc(c, dtype, 6, 7, 7, 1, 0, 0, 0, 1, 0, 0, 0, 0, &d);
+        fill_desc(c, dtype, 6, 7, 7, 1, &d);
         const size_t nb = cp360_conv_packed_bytes(&d);
         if (!nb) return CP360_ERR_UNSUPPORTED;
         if (!(c.packed_clip = own.take(nb))) return CP360_ERR_HIP;
@@ -136,86 +139,15 @@ bool clip_geometry(const CConv& c, int n_img, int h, int w) {
     return c.clip_ok && h == w && (6 * h * w <= 304 || h == 8 || h == 16) && n_img % 6 == 0;
 }
 
-void fill_desc(const CConv& c, int dtype, int n_img, int h_in, int w_in, int splits, int ld_out, int out_coff,
-               int ld_res, int clip_resident, int slab_rows, int h2, int w2, int ps2, cp360_conv_desc* d);
-
 // clip-resident kernel or tap-major path?  With one packing there is no choice; with both (layer4's conv2) the library's cost
 // model decides (cp360_conv_prefer_clip: one frame in f32 runs better on the 64 x 64 tiles of conv_small.hip)
 bool use_clip(const CConv& c, int dtype, int n_img, int h, int w) {
     if (!clip_geometry(c, n_img, h, w) || !c.packed_clip) return false;
     if (!c.packed) return true;
     cp360_conv_desc d;
-    fill_desc(c, dtype, n_img, h, w, 1, 0, 0, 0, 1, 0, 0, 0, 0, &d);
+    fill_desc(c, dtype, n_img, h, w, 1, &d);
     return cp360_conv_prefer_clip(&d) != 0;
 }
-
-// The launch (or, with `dry`, only the split-K workspace it needs): ops.Conv.__call__.
-//   raw: leave the f32 sums in `partial` ([splits, M, c_out]; *splits_out tells how many) for the caller's epilogue.
-struct Run {
-    bool dry = false;
-    size_t partial_need = 0;                     // dry: bytes of split-K workspace
-    float* partial = nullptr;
-    size_t partial_cap = 0;
-    hipStream_t st = nullptr;
-    int dtype = 0;
-
-    std::string* desc = nullptr;                 // dry runs: one line per planned launch (cp360_resnet_plan_describe)
-    const char* where = "";
-    void note(const char* text) {
-        if (desc) { *desc += text; *desc += "\n"; }
-    }
-
-    int conv(const CConv& c, const void* in, int n_img, int h, int w, const void* residual, int ld_res, void* out,
-             int ld_out, int out_coff, const void* x2, int h2, int w2, int ps2, bool raw, bool raw_slab_rows,
-             float* raw_dst, int force_splits, int* splits_out) {
-        cp360_conv_desc d;
-        const int cr = use_clip(c, dtype, n_img, h, w) ? 1 : 0;
-        fill_desc(c, dtype, n_img, h, w, 1, ld_out, out_coff, ld_res, cr, 0, h2, w2, ps2, &d);
-        const int splits = force_splits > 0 ? force_splits : cp360_conv_suggest_splits(&d);
-        const int sr = (c.c_out % 32 == 0 && ((splits > 1 && !raw) || (raw && raw_slab_rows))) ? 1 : 0;
-        d.splits = splits;
-        d.slab_rows = sr;
-        if (splits_out) *splits_out = splits;
-        const size_t M = (size_t)n_img * d.h_out * d.w_out;
-        const bool to_partial = raw || splits > 1;
-        // raw sums with a caller-owned destination AND split-K (the CAM scores at one frame): slabs in the workspace,
-        // reduced into raw_dst by an f32 finish
-        const bool raw_reduce = raw && raw_dst && splits > 1;
-        if (to_partial && (!raw_dst || raw_reduce)) {
-            const size_t need = (size_t)splits * M * c.c_out * sizeof(float);
-            if (need > partial_need) partial_need = need;
-            if (!dry && need > partial_cap) return CP360_ERR_BAD_SHAPE;
-        }
-        if (dry) {
-            if (desc) {
-                char plan[200], line[320];
-                cp360_conv_desc dd = d;
-                dd.splits = 1;
-                if (cp360_conv_plan_describe(&dd, plan, sizeof(plan)) < 0) plan[0] = 0;
-                snprintf(line, sizeof(line), "  %s conv %dx%d %d -> %d @ %dx%d%s: %s%s", where, c.kh_w, c.kw_w, c.c_in_w, c.c_out, h, w,
-                         c.stride > 1 ? " stride 2" : "", plan, force_splits > 0 ? " (split count fixed by the caller)" : "");
-                note(line);
-            }
-            return CP360_OK;
-        }
-        const void* pk = cr ? c.packed_clip : c.packed;
-        if (!pk) return CP360_ERR_UNSUPPORTED;
-        if (to_partial) {
-            float* dst = raw_dst && !raw_reduce ? raw_dst : partial;
-            int rc = cp360_conv_forward2(&d, in, x2, pk, nullptr, nullptr, nullptr, dst, st);
-            if (rc) return rc;
-            if (raw_reduce) {
-                cp360_conv_desc df = d;
-                df.dtype = CP360_F32;
-                df.relu = 0;
-                return cp360_conv_finish_add(&df, dst, nullptr, nullptr, nullptr, raw_dst, st);
-            }
-            if (raw) return rc;
-            return cp360_conv_finish(&d, dst, c.bias, residual, out, st);
-        }
-        return cp360_conv_forward2(&d, in, x2, pk, c.bias, residual, out, nullptr, st);
-    }
-};
 
 // ---------------------------------------------------------------- ResNet-50-cubic + CAM
 struct CBlock {
@@ -279,8 +211,7 @@ extern "C" int cp360_fold_bn(const float* bn_weight, const float* bn_bias, const
                              float* scale, float* bias, int n, void* stream) {
     if (!bn_weight || !bn_bias || !bn_mean || !bn_var || !scale || !bias) return CP360_ERR_NULL;
     if (n <= 0) return CP360_ERR_BAD_SHAPE;
-    hipLaunchKernelGGL(fold_bn_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, bn_weight, bn_bias, bn_mean,
-                       bn_var, eps, scale, bias, n);
+    launch_fold_bn(bn_weight, bn_bias, bn_mean, bn_var, eps, scale, bias, n, (hipStream_t)stream);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -313,8 +244,7 @@ int fold(Owned& own, const cp360_conv_bn& p, int n, float eps, hipStream_t st, F
     f->scale = (float*)own.take((size_t)n * 4);
     f->bias = (float*)own.take((size_t)n * 4);
     if (!f->scale || !f->bias) return CP360_ERR_HIP;
-    hipLaunchKernelGGL(fold_bn_kernel, dim3((n + 255) / 256), dim3(256), 0, st, p.bn_weight, p.bn_bias, p.bn_mean, p.bn_var,
-                       eps, f->scale, f->bias, n);
+    launch_fold_bn(p.bn_weight, p.bn_bias, p.bn_mean, p.bn_var, eps, f->scale, f->bias, n, st);
     return CP360_OK;
 }
 
@@ -465,214 +395,362 @@ extern "C" int cp360_resnet_load(cp360_ctx* ctx, int dtype, const cp360_conv_bn*
 
 namespace {
 
+// ---------------------------------------------------------------- the stage planner: plan once, then run / size / describe
+// A plan is a list of steps over SYMBOLIC operands.  plan_resnet() / plan_clstm() are the only functions that decide anything
+// (which kernel, tiles, split-K, which slot a tensor lives in, the workspace, the describing text); run_step() resolves the slots
+// to pointers and launches.  A new fused kernel is one StepKind, one rule in the planner and one `case` in run_step().
+enum Slot {
+    SLOT_NONE = -1,
+    SLOT_ACT0, SLOT_ACT1, SLOT_ACT2, SLOT_ACT3,  // activation quarters of the workspace (at most x, mid, out and the next mid live)
+    SLOT_INPUT, SLOT_CAM,                        // the caller's input (the stage's faces, the cell's [x | h]) and CAM buffer
+    SLOT_PARTIAL, SLOT_BORDER,                   // split-K partial slabs; the fused stem + max-pool kernel's border scratch
+    SLOT_COUNT
+};
+
+enum StepKind {
+    STEP_CONV,                                   // generic convolution (+ its split-K finish)
+    STEP_F32_FINISH,                             // split-K slabs -> raw f32 sums in a caller-owned buffer (the CAM at one frame)
+    STEP_STEM_POOL, STEP_STEM_RESIDENT, STEP_MAXPOOL,
+    STEP_L1_FIRST, STEP_L1, STEP_L1_WIDE,
+    STEP_L2_FIRST, STEP_L2_TAIL, STEP_L2_TAIL_NEXT, STEP_L3_TAIL
+};
+
+struct Step {
+    StepKind kind = STEP_CONV;
+    const CConv* conv = nullptr;                 // whose packs / bias the step reads (convolutions, the stem)
+    const CBlock* block = nullptr;               // ... or whose fused-tail packs
+    const void* stem_packed = nullptr;           // ... or the stem kernels' resident-patch packing
+    cp360_conv_desc d{};                         // STEP_CONV / STEP_F32_FINISH: fully resolved (splits, slab_rows, clip_resident)
+    int size = 0;                                // fused kernels: the face (stem: cube, max-pool: input) size they are told
+    // in: the input (a tail kernel's conv1 output `mid`); in2: the second source; res: the residual (tail kernels: the block
+    // input x); out; out2: the chained next conv1's output / the border scratch; sums: where raw f32 sums go (SLOT_NONE: none)
+    int in = SLOT_NONE, in2 = SLOT_NONE, res = SLOT_NONE, out = SLOT_NONE, out2 = SLOT_NONE, sums = SLOT_NONE;
+};
+
+// What a generic convolution call states beyond the convolution and its input geometry; a call site sets what it uses
+struct ConvArgs {
+    int in, out;
+    int ld_out = 0, out_coff = 0;
+    int residual = SLOT_NONE, ld_res = 0;
+    int x2 = SLOT_NONE, h2 = 0, w2 = 0, ps2 = 0;  // second source and its geometry
+    bool raw = false;                            // leave the f32 sums ([splits, M, c_out]) for the caller's epilogue ...
+    bool raw_slab_rows = false;                  // ... in packed-row order
+    int raw_dst = SLOT_NONE;                     // ... in this caller-owned buffer (reduced there when the planner splits)
+    int force_splits = 0;
+    explicit ConvArgs(int in_, int out_ = SLOT_NONE) : in(in_), out(out_) {}
+};
+
+// What both stages plan: the steps and the split-K workspace they need
+struct Plan {
+    int dtype = 0, n_img = 0;
+    std::vector<Step> steps;
+    size_t partial_need = 0;                     // bytes of split-K workspace: the maximum over the steps
+    Step& add(StepKind kind) {
+        steps.emplace_back();
+        steps.back().kind = kind;
+        return steps.back();
+    }
+
+    // One generic convolution on n_img faces of h x w (ops.Conv.__call__): appends its step (and, for raw sums that the planner
+    // splits on their way to a caller-owned buffer, the f32 finish behind it) and returns a copy of the convolution's
+    Step conv(const CConv& c, int h, int w, const ConvArgs& a) {
+        Step s;
+        s.conv = &c;
+        cp360_conv_desc& d = s.d;
+        fill_desc(c, dtype, n_img, h, w, use_clip(c, dtype, n_img, h, w) ? 1 : 0, &d);
+        if (a.ld_out > 0) d.ld_out = a.ld_out;
+        d.out_coff = a.out_coff;
+        d.ld_res = a.ld_res;
+        if (c.c_in2 > 0 && a.h2 > 0) { d.h_in2 = a.h2; d.w_in2 = a.w2; d.pix_stride2 = a.ps2; }
+        const int splits = a.force_splits > 0 ? a.force_splits : cp360_conv_suggest_splits(&d);
+        d.splits = splits;
+        d.slab_rows = (c.c_out % 32 == 0 && ((splits > 1 && !a.raw) || (a.raw && a.raw_slab_rows))) ? 1 : 0;
+        s.in = a.in;
+        s.in2 = a.x2;
+        if (!a.raw) { s.res = a.residual; s.out = a.out; }
+        // raw sums with a caller-owned destination AND split-K (the CAM scores at one frame): slabs in the workspace,
+        // reduced into raw_dst by an f32 finish
+        const bool raw_reduce = a.raw && a.raw_dst != SLOT_NONE && splits > 1;
+        if (a.raw || splits > 1) s.sums = a.raw_dst != SLOT_NONE && !raw_reduce ? a.raw_dst : SLOT_PARTIAL;
+        if (s.sums == SLOT_PARTIAL)
+            partial_need = std::max(partial_need, (size_t)splits * n_img * d.h_out * d.w_out * c.c_out * sizeof(float));
+        steps.push_back(s);
+        if (raw_reduce) {
+            Step f;
+            f.kind = STEP_F32_FINISH;
+            f.d = d;
+            f.d.dtype = CP360_F32;
+            f.d.relu = 0;
+            f.in = SLOT_PARTIAL;
+            f.out = a.raw_dst;
+            steps.push_back(f);
+        }
+        return s;
+    }
+};
+
+// the pointers behind the slots of one call
+struct Bufs {
+    void* p[SLOT_COUNT] = {};
+    void* operator[](int slot) const { return slot < 0 ? nullptr : p[slot]; }
+};
+
+int run_step(const Step& s, const Plan& P, const Bufs& at, hipStream_t st) {
+    const int dtype = P.dtype, n = P.n_img;
+    const CBlock* B = s.block;
+    switch (s.kind) {
+    case STEP_CONV: {
+        const CConv& c = *s.conv;
+        const void* pk = s.d.clip_resident ? c.packed_clip : c.packed;
+        if (!pk) return CP360_ERR_UNSUPPORTED;
+        if (s.sums == SLOT_NONE) return cp360_conv_forward2(&s.d, at[s.in], at[s.in2], pk, c.bias, at[s.res], at[s.out], nullptr, st);
+        float* sums = (float*)at[s.sums];
+        const int rc = cp360_conv_forward2(&s.d, at[s.in], at[s.in2], pk, nullptr, nullptr, nullptr, sums, st);
+        if (rc || s.out == SLOT_NONE) return rc;
+        return cp360_conv_finish(&s.d, sums, c.bias, at[s.res], at[s.out], st);
+    }
+    case STEP_F32_FINISH:
+        return cp360_conv_finish_add(&s.d, (const float*)at[s.in], nullptr, nullptr, nullptr, at[s.out], st);
+    case STEP_STEM_POOL:
+        return cp360_stem_pool_forward(dtype, at[s.in], s.stem_packed, s.conv->bias, at[s.out], at[s.out2], n, s.size, st);
+    case STEP_STEM_RESIDENT:
+        return cp360_stem_forward(dtype, at[s.in], s.stem_packed, s.conv->bias, at[s.out], n, s.size, 1, st);
+    case STEP_MAXPOOL:
+        return cp360_cubepad_maxpool3s2(at[s.in], at[s.out], n, s.size, 64, dtype, st);
+    case STEP_L1_FIRST:                                  // in: the block input x (conv1 runs inside the kernel)
+        return cp360_l1block_forward_first(dtype, at[s.in], B->w0f, B->b0, B->w2, B->b2, B->w3f, B->b3, B->wdf, at[s.out], B->w1f,
+                                           B->b1n, at[s.out2], n, s.size, st);
+    case STEP_L1:                                        // block 0: x feeds the downsample branch; later blocks: x is the residual
+        return cp360_l1block_forward(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, B->has_ds ? nullptr : at[s.res],
+                                     B->has_ds ? at[s.res] : nullptr, B->wdf, at[s.out], B->w1f, B->b1n, at[s.out2], n, s.size, st);
+    case STEP_L1_WIDE:
+        return cp360_l1block_forward_wide(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, at[s.res], at[s.out], B->w1f, B->b1n,
+                                          at[s.out2], n, s.size, st);
+    case STEP_L2_FIRST: {
+        const bool next = s.out2 != SLOT_NONE;
+        return cp360_l2first_forward(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, at[s.res], at[s.out], next ? B->w1f : nullptr,
+                                     next ? B->b1n : nullptr, at[s.out2], n, s.size, st);
+    }
+    case STEP_L2_TAIL:
+        return cp360_l2block_forward(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, at[s.res], at[s.out], n, s.size, st);
+    case STEP_L2_TAIL_NEXT:
+        return cp360_l2block_forward_next(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, at[s.res], at[s.out], B->w1f, B->b1n,
+                                          at[s.out2], n, s.size, st);
+    case STEP_L3_TAIL:
+        return cp360_l3block_forward(dtype, at[s.in], B->w2, B->b2, B->w3f, B->b3, at[s.res], at[s.out], n, s.size, st);
+    }
+    return CP360_ERR_UNSUPPORTED;
+}
+
+// an activation slot that holds none of the (up to three) live tensors
+int free_slot(int a, int b = SLOT_NONE, int c = SLOT_NONE) {
+    int s = SLOT_ACT0;
+    while (s == a || s == b || s == c) ++s;
+    return s;
+}
+
 struct ResnetWs {
     size_t act = 0, partial = 0, border = 0;
     size_t total() const { return 4 * act + partial + border; }
 };
 
-// The static stage as a launch sequence (or, dry, its workspace needs).  faces_p3: [n_img, cd+6, cd+6, 4] NHWC4.
-int resnet_run(cp360_ctx* ctx, bool dry, const void* faces_p3, int n_img, int cd, float* cam_out, void* feat_out,
-               unsigned char* ws, size_t ws_bytes, hipStream_t st, ResnetWs* need, std::string* desc = nullptr) {
-    CResnet& R = ctx->rn;
+struct StagePlan : Plan {
+    bool describe = false;                       // also write `text`: one line per note / planned generic launch
+    std::string text;
+    char where[32] = "";
+    void note(const char* line) {
+        if (describe) { text += line; text += "\n"; }
+    }
+    void at(int layer, int block) { snprintf(where, sizeof(where), "layer%d.%d", layer, block); }
+    void conv(const CConv& c, int h, int w, const ConvArgs& a) {
+        const Step s = Plan::conv(c, h, w, a);
+        if (!describe) return;
+        char plan[200], line[320];
+        cp360_conv_desc dd = s.d;
+        dd.splits = 1;
+        if (cp360_conv_plan_describe(&dd, plan, sizeof(plan)) < 0) plan[0] = 0;
+        snprintf(line, sizeof(line), "  %s conv %dx%d %d -> %d @ %dx%d%s: %s%s", where, c.kh_w, c.kw_w, c.c_in_w, c.c_out, h, w,
+                 c.stride > 1 ? " stride 2" : "", plan, a.force_splits > 0 ? " (split count fixed by the caller)" : "");
+        note(line);
+    }
+    size_t n_ordered = 0;                        // steps [0, n_ordered) run under launch order 2, the CAM after the restore
+    int feat = SLOT_NONE;                        // where layer4's output ends up, and its size
+    size_t feat_bytes = 0;
+    ResnetWs ws;
+};
+
+// The static stage on n_img faces of cd x cd (input [n_img, cd+6, cd+6, 4] NHWC4): its launch sequence, workspace and text
+int plan_resnet(const CResnet& R, int n_img, int cd, StagePlan* P) {
     if (!R.loaded) return CP360_ERR_NULL;
     if (n_img <= 0 || cd < 32 || cd % 32 != 0) return CP360_ERR_BAD_SHAPE;
     if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
     const int dtype = R.dtype, es = es_of(dtype);
     const bool h16 = dtype != CP360_F32;
-    ResnetWs w;
-    w.act = align_up((size_t)n_img * (cd / 2) * (cd / 2) * 64 * es);       // the largest activation: stem output = layer1 output
-    w.border = align_up(cp360_stem_pool_border_bytes(n_img));
-    Run run;
-    run.dry = dry;
-    run.st = st;
-    run.dtype = dtype;
-    run.desc = dry ? desc : nullptr;
-    unsigned char* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned char* border = nullptr;
-    if (!dry) {
-        if (!faces_p3 || !cam_out || !ws) return CP360_ERR_NULL;
-        if (((size_t)ws & 255) != 0) return CP360_ERR_ALIGN;
-        w.partial = need->partial;
-        if (ws_bytes < w.total()) return CP360_ERR_BAD_SHAPE;
-        for (int i = 0; i < 4; ++i) buf[i] = ws + i * w.act;
-        run.partial = (float*)(ws + 4 * w.act);
-        run.partial_cap = w.partial;
-        border = ws + 4 * w.act + w.partial;
+    P->dtype = dtype;
+    P->n_img = n_img;
+    P->steps.reserve(64);
+    P->ws.act = align_up((size_t)n_img * (cd / 2) * (cd / 2) * 64 * es);   // the largest activation: stem output = layer1 output
+    P->ws.border = align_up(cp360_stem_pool_border_bytes(n_img));
+    if (P->describe) {
+        char head[160];
+        snprintf(head, sizeof(head), "static stage, %d faces of %d^2, %s:", n_img, cd,
+                 dtype == CP360_F32 ? "f32" : (dtype == CP360_F16 ? "f16" : "bf16"));
+        P->note(head);
     }
-    int rc = CP360_OK;
-    int cur = 0;                                         // buf[cur] = the running activation x; the other three rotate
-    auto other = [&](int k) { return buf[(cur + k) & 3]; };
-    const int old_order = dry ? 0 : cp360_set_launch_order(2);
-#define CK(call) do { rc = (call); if (rc) { if (!dry) cp360_set_launch_order(old_order); return rc; } } while (0)
-    // ---- stem + CubePad(1) + max-pool
+    int x = SLOT_ACT0;                                   // the running activation
+    int mid = SLOT_NONE;                                 // the next block's conv1 output, where a fused kernel already computed it
     int face = cd / 4;
-    if (!dry) {
-        if (h16 && cd == 224) {
-            CK(cp360_stem_pool_forward(dtype, faces_p3, R.stem_packed, R.stem.bias, buf[cur], border, n_img, cd, st));
-        } else {
-            if (h16 && cd == 512) CK(cp360_stem_forward(dtype, faces_p3, R.stem_packed, R.stem.bias, other(1), n_img, cd, 1, st));
-            else CK(run.conv(R.stem, faces_p3, n_img, cd + 6, cd + 6, nullptr, 0, other(1), 0, 0, nullptr, 0, 0, 0, false, false,
-                             nullptr, 0, nullptr));
-            CK(cp360_cubepad_maxpool3s2(other(1), buf[cur], n_img, cd / 2, 64, dtype, st));
-        }
-    } else if (!(h16 && (cd == 224 || cd == 512))) {
-        run.note("stem: generic convolution (7 taps of 8 pixels x 4 channels) + cubepad_maxpool kernel");
-        run.where = "stem";
-        CK(run.conv(R.stem, nullptr, n_img, cd + 6, cd + 6, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr));
+    // ---- stem + CubePad(1) + max-pool
+    if (h16 && cd == 224) {
+        P->note("stem: FUSED stem + CubePad(1) + max-pool, one launch (K3a+K3b, cube 224, 16-bit)");
+        Step& s = P->add(STEP_STEM_POOL);
+        s.conv = &R.stem; s.stem_packed = R.stem_packed; s.in = SLOT_INPUT; s.out = x; s.out2 = SLOT_BORDER; s.size = cd;
     } else {
-        run.note(cd == 224 ? "stem: FUSED stem + CubePad(1) + max-pool, one launch (K3a+K3b, cube 224, 16-bit)"
-                           : "stem: resident-patch stem kernel (K3a, cube 512, 16-bit) + cubepad_maxpool kernel");
-    }
-    // per-convolution Bottleneck (Bottleneck.forward_nhwc): x = buf[cur] -> buf[cur] (rotated); mid0: conv1 already done
-    char wherebuf[32];
-    auto at = [&](int layer, int block) { snprintf(wherebuf, sizeof(wherebuf), "layer%d.%d", layer, block); run.where = wherebuf; };
-    auto bottleneck = [&](CBlock& B, int hin, const void* mid0) -> int {
-        const int hout = (hin + 2 - 3) / B.stride + 1;
-        const void* mid = mid0;
-        if (!mid) {
-            int r = run.conv(B.c1, buf[cur], n_img, hin, hin, nullptr, 0, other(1), 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr);
-            if (r) return r;
-            mid = other(1);
+        const int full = free_slot(x);                   // the stem's output in front of the max-pool
+        if (h16 && cd == 512) {
+            P->note("stem: resident-patch stem kernel (K3a, cube 512, 16-bit) + cubepad_maxpool kernel");
+            Step& s = P->add(STEP_STEM_RESIDENT);
+            s.conv = &R.stem; s.stem_packed = R.stem_packed; s.in = SLOT_INPUT; s.out = full; s.size = cd;
+        } else {
+            P->note("stem: generic convolution (7 taps of 8 pixels x 4 channels) + cubepad_maxpool kernel");
+            snprintf(P->where, sizeof(P->where), "stem");
+            P->conv(R.stem, cd + 6, cd + 6, ConvArgs(SLOT_INPUT, full));
         }
-        int r = run.conv(B.c2, mid, n_img, hin, hin, nullptr, 0, other(2), 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr);
-        if (r) return r;
-        if (B.has_ds)
-            r = run.conv(B.c3, other(2), n_img, hout, hout, nullptr, 0, other(3), 0, 0, buf[cur], hin, hin, B.c3.c_in2, false, false,
-                         nullptr, 0, nullptr);
-        else
-            r = run.conv(B.c3, other(2), n_img, hout, hout, buf[cur], B.c3.c_out, other(3), 0, 0, nullptr, 0, 0, 0, false, false,
-                         nullptr, 0, nullptr);
-        cur = (cur + 3) & 3;
-        return r;
+        Step& s = P->add(STEP_MAXPOOL);
+        s.in = full; s.out = x; s.size = cd / 2;
+    }
+    // per-convolution Bottleneck (Bottleneck.forward_nhwc): x -> a free slot; conv1 is skipped where `mid` already holds it
+    auto bottleneck = [&](const CBlock& B, int hin) {
+        const int hout = (hin + 2 - 3) / B.stride + 1;
+        if (mid == SLOT_NONE) {
+            mid = free_slot(x);
+            P->conv(B.c1, hin, hin, ConvArgs(x, mid));
+        }
+        const int mid2 = free_slot(x, mid), out = free_slot(x, mid, mid2);
+        P->conv(B.c2, hin, hin, ConvArgs(mid, mid2));
+        ConvArgs a(mid2, out);
+        if (B.has_ds) { a.x2 = x; a.h2 = a.w2 = hin; a.ps2 = B.c3.c_in2; }
+        else { a.residual = x; a.ld_res = B.c3.c_out; }
+        P->conv(B.c3, hout, hout, a);
+        x = out;
+        mid = SLOT_NONE;
+    };
+    // a fused tail kernel: mid (+ x as residual / second source) -> out (+ the next block's conv1 output when `chained`)
+    auto tail = [&](StepKind kind, const CBlock& B, int size, bool chained) {
+        Step& s = P->add(kind);
+        s.block = &B;
+        s.size = size;
+        s.in = kind == STEP_L1_FIRST ? x : mid;
+        s.res = x;
+        s.out = free_slot(x, mid);
+        s.out2 = chained ? free_slot(x, mid, s.out) : SLOT_NONE;
+        x = s.out;
+        mid = s.out2;
+    };
+    auto conv1 = [&](const CBlock& B) {                  // a fused tail's conv1 as its own launch, unless `mid` holds it
+        if (mid != SLOT_NONE) return;
+        mid = free_slot(x);
+        P->conv(B.c1, face, face, ConvArgs(x, mid));
     };
     // ---- layer1
-    const void* mid2 = nullptr;                           // layer2.0's conv1 output when layer1's last tail computed it
     {
-        std::vector<CBlock>& Lr = R.layer[0];
+        const std::vector<CBlock>& Lr = R.layer[0];
         if (h16 && (face == 56 || face == 128)) {
             // conv1 of block 0 inside the block's tail kernel at face 56; at face 128 (or without its packed filter) its own launch
             const bool first_in = face == 56 && Lr[0].w0f != nullptr;
-            run.note(first_in ? "layer1: ONE fused launch per Bottleneck (K3d: [block 0: its conv1 on the resident patch +] conv2 + conv3 + residual / downsample + the next conv1)"
-                              : "layer1: conv1 of block 0, then ONE fused launch per Bottleneck (K3d: conv2 + conv3 + residual / downsample + the next conv1)");
-            at(1, 0);
-            // conv1 of the first block (its own launch, or inside the tail kernel), then ONE launch per Bottleneck (K3d); the chained conv1 output ping-pongs
-            if (!first_in)
-                CK(run.conv(Lr[0].c1, buf[cur], n_img, face, face, nullptr, 0, other(1), 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr));
-            if (!dry) {
-                // x = buf[cur] (64 ch), mid = other(1); out -> other(2), mid' -> other(3)
-                if (first_in)
-                    CK(cp360_l1block_forward_first(dtype, buf[cur], Lr[0].w0f, Lr[0].b0, Lr[0].w2, Lr[0].b2, Lr[0].w3f, Lr[0].b3, Lr[0].wdf,
-                                                   other(2), Lr[0].w1f, Lr[0].b1n, other(3), n_img, face, st));
-                else
-                    CK(cp360_l1block_forward(dtype, other(1), Lr[0].w2, Lr[0].b2, Lr[0].w3f, Lr[0].b3, nullptr, buf[cur], Lr[0].wdf,
-                                             other(2), Lr[0].w1f, Lr[0].b1n, other(3), n_img, face, st));
-                // from here: out = other(2), mid = other(3); free: buf[cur], other(1)
-                unsigned char *o = other(2), *m = other(3), *f0 = buf[cur], *f1 = other(1);
-                for (size_t b = 1; b < Lr.size(); ++b) {
-                    CBlock& B = Lr[b];
-                    if (B.next_c == 128)
-                        CK(cp360_l1block_forward_wide(dtype, m, B.w2, B.b2, B.w3f, B.b3, o, f0, B.w1f, B.b1n, f1, n_img, face, st));
-                    else
-                        CK(cp360_l1block_forward(dtype, m, B.w2, B.b2, B.w3f, B.b3, o, nullptr, nullptr, f0, B.w1f, B.b1n,
-                                                 B.w1f ? f1 : nullptr, n_img, face, st));
-                    unsigned char *no = f0, *nm = f1;
-                    f0 = o; f1 = m; o = no; m = nm;
-                }
-                // re-anchor the rotation: x = o; keep mid2 = m out of the way of the next block's temporaries
-                for (int i = 0; i < 4; ++i) if (buf[i] == o) cur = i;
-                if (Lr.back().next_c == 128) {
-                    mid2 = m;
-                    // the first layer2 block writes other(2) / other(3) before it is done with mid2 (= conv2's input):
-                    // swap buffer roles so that mid2 sits in the other(1) slot, which that block leaves alone
-                    for (int i = 0; i < 4; ++i)
-                        if (buf[i] == m && i != ((cur + 1) & 3)) { unsigned char* t = buf[i]; buf[i] = buf[(cur + 1) & 3]; buf[(cur + 1) & 3] = t; break; }
-                }
-            } else if (Lr.back().next_c == 128) {
-                mid2 = (const void*)1;                   // dry: only "conv1 is not run"
-            }
+            P->note(first_in ? "layer1: ONE fused launch per Bottleneck (K3d: [block 0: its conv1 on the resident patch +] conv2 + conv3 + residual / downsample + the next conv1)"
+                             : "layer1: conv1 of block 0, then ONE fused launch per Bottleneck (K3d: conv2 + conv3 + residual / downsample + the next conv1)");
+            P->at(1, 0);
+            if (!first_in) conv1(Lr[0]);
+            // every block's kernel also computes the next conv1 - the last one layer2.0's (256 -> 128: the wide form)
+            for (size_t b = 0; b < Lr.size(); ++b)
+                tail(b == 0 && first_in ? STEP_L1_FIRST : (b > 0 && Lr[b].next_c == 128 ? STEP_L1_WIDE : STEP_L1), Lr[b], face,
+                     Lr[b].w1f != nullptr);
+            if (Lr.back().next_c != 128) mid = SLOT_NONE;      // `mid` carries over only as layer2.0's conv1 (256 -> 128)
         } else {
-            run.note("layer1: GENERIC path, one launch per convolution (the fused tail kernels need a 16-bit type and 56x56 / 128x128 faces)");
-            for (size_t b = 0; b < Lr.size(); ++b) { at(1, (int)b); CK(bottleneck(Lr[b], face, nullptr)); }
+            P->note("layer1: GENERIC path, one launch per convolution (the fused tail kernels need a 16-bit type and 56x56 / 128x128 faces)");
+            for (size_t b = 0; b < Lr.size(); ++b) { P->at(1, (int)b); bottleneck(Lr[b], face); }
         }
     }
     // ---- layer2 / layer3: first block per convolution, identity blocks as fused tails where the kernels exist
-    bool l2_mid1 = false;                                 // layer2.0's kernel also computed layer2.1's conv1
     for (int L = 1; L <= 2; ++L) {
-        std::vector<CBlock>& Lr = R.layer[L];
-        at(L + 1, 0);
+        const std::vector<CBlock>& Lr = R.layer[L];
+        if (L == 2) mid = SLOT_NONE;                     // no kernel of layer2 computes layer3.0's conv1
+        P->at(L + 1, 0);
         if (L == 1 && h16 && face == 56) {
-            run.note("layer2.0: ONE fused launch after its conv1 (K3f: stride-2 conv2 + conv3 + downsample + layer2.1's conv1)");
-            // layer2.0: conv1 (unless layer1's last tail kernel computed it), then ONE launch (K3f)
-            const void* mid = mid2;
-            if (!mid) {
-                CK(run.conv(Lr[0].c1, buf[cur], n_img, face, face, nullptr, 0, other(1), 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr));
-                mid = other(1);
-            }
-            // out -> other(3); the chained conv1 of layer2.1 (when that block runs on the fused tail) -> other(2)
-            l2_mid1 = Lr[0].w1f != nullptr;
-            if (!dry) CK(cp360_l2first_forward(dtype, mid, Lr[0].w2, Lr[0].b2, Lr[0].w3f, Lr[0].b3, buf[cur], other(3),
-                                               l2_mid1 ? Lr[0].w1f : nullptr, l2_mid1 ? Lr[0].b1n : nullptr,
-                                               l2_mid1 ? other(2) : nullptr, n_img, face / 2, st));
-            cur = (cur + 3) & 3;                          // x = old other(3); old other(2) = the new other(3)
-            if (l2_mid1 && !dry) {                        // the identity loop expects its mid in other(1): swap the two free roles
-                unsigned char* t = buf[(cur + 3) & 3]; buf[(cur + 3) & 3] = buf[(cur + 1) & 3]; buf[(cur + 1) & 3] = t;
-            }
+            // layer2.0: conv1 (unless layer1's last tail kernel computed it), then ONE launch (K3f), which also computes
+            // layer2.1's conv1
+            P->note("layer2.0: ONE fused launch after its conv1 (K3f: stride-2 conv2 + conv3 + downsample + layer2.1's conv1)");
+            conv1(Lr[0]);
+            tail(STEP_L2_FIRST, Lr[0], face / 2, Lr[0].w1f != nullptr);
         } else {
-            run.note(L == 1 ? "layer2.0: generic path, one launch per convolution (downsample branch inside conv3)"
-                            : "layer3.0: generic path, one launch per convolution (downsample branch inside conv3)");
-            CK(bottleneck(Lr[0], face, L == 1 ? mid2 : nullptr));
+            P->note(L == 1 ? "layer2.0: generic path, one launch per convolution (downsample branch inside conv3)"
+                           : "layer3.0: generic path, one launch per convolution (downsample branch inside conv3)");
+            bottleneck(Lr[0], face);
         }
         face /= 2;
         const bool fused = h16 && (L == 1 ? (face == 28 || face == 64) : (face == 14 || face == 32));
         if (!fused) {
-            run.note(L == 1 ? "layer2.1-3: GENERIC path, one launch per convolution (the fused tail kernel needs a 16-bit type and 28x28 / 64x64 faces)"
-                            : "layer3.1-5: GENERIC path, one launch per convolution (the fused tail kernel needs a 16-bit type and 14x14 / 32x32 faces)");
-            for (size_t b = 1; b < Lr.size(); ++b) { at(L + 1, (int)b); CK(bottleneck(Lr[b], face, nullptr)); }
+            P->note(L == 1 ? "layer2.1-3: GENERIC path, one launch per convolution (the fused tail kernel needs a 16-bit type and 28x28 / 64x64 faces)"
+                           : "layer3.1-5: GENERIC path, one launch per convolution (the fused tail kernel needs a 16-bit type and 14x14 / 32x32 faces)");
+            for (size_t b = 1; b < Lr.size(); ++b) { P->at(L + 1, (int)b); bottleneck(Lr[b], face); }
             continue;
         }
-        run.note(L == 1 ? "layer2.1-3: conv1 + ONE fused tail launch per Bottleneck (K3e; at 28x28 faces the next block's conv1 rides on the tail)"
-                        : "layer3.1-5: conv1 + ONE fused tail launch per Bottleneck (K3e, C = 256)");
+        P->note(L == 1 ? "layer2.1-3: conv1 + ONE fused tail launch per Bottleneck (K3e; at 28x28 faces the next block's conv1 rides on the tail)"
+                       : "layer3.1-5: conv1 + ONE fused tail launch per Bottleneck (K3e, C = 256)");
         const bool chain = L == 1 && face == 28;          // the next block's conv1 rides on the tail kernel
-        bool have_mid = L == 1 && l2_mid1;                // other(1) holds this block's conv1 output
         for (size_t b = 1; b < Lr.size(); ++b) {
-            CBlock& B = Lr[b];
-            at(L + 1, (int)b);
-            if (!have_mid)
-                CK(run.conv(B.c1, buf[cur], n_img, face, face, nullptr, 0, other(1), 0, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr));
-            if (dry) { have_mid = chain && B.w1f; continue; }
-            if (L == 1 && chain && B.w1f) {
-                CK(cp360_l2block_forward_next(dtype, other(1), B.w2, B.b2, B.w3f, B.b3, buf[cur], other(2), B.w1f, B.b1n, other(3),
-                                              n_img, face, st));
-                // x = other(2), mid = other(3): rotate by 2 so that other(1) is the new mid
-                cur = (cur + 2) & 3;
-                have_mid = true;
-            } else {
-                if (L == 1) CK(cp360_l2block_forward(dtype, other(1), B.w2, B.b2, B.w3f, B.b3, buf[cur], other(2), n_img, face, st));
-                else CK(cp360_l3block_forward(dtype, other(1), B.w2, B.b2, B.w3f, B.b3, buf[cur], other(2), n_img, face, st));
-                cur = (cur + 2) & 3;
-                have_mid = false;
-            }
+            const CBlock& B = Lr[b];
+            P->at(L + 1, (int)b);
+            conv1(B);
+            if (chain && B.w1f) tail(STEP_L2_TAIL_NEXT, B, face, true);
+            else tail(L == 1 ? STEP_L2_TAIL : STEP_L3_TAIL, B, face, false);
         }
     }
     // ---- layer4: per convolution (conv2 on the clip-resident kernel at 7x7 / 16x16 faces)
-    run.note("layer4: one launch per convolution (conv2 clip-resident or on small tiles by cp360_conv_prefer_clip; downsample inside conv3)");
+    P->note("layer4: one launch per convolution (conv2 clip-resident or on small tiles by cp360_conv_prefer_clip; downsample inside conv3)");
     for (size_t b = 0; b < R.layer[3].size(); ++b) {
-        at(4, (int)b);
-        CK(bottleneck(R.layer[3][b], face, nullptr));
+        P->at(4, (int)b);
+        bottleneck(R.layer[3][b], face);
         if (b == 0) face /= 2;
     }
-    run.note("CAM: 1x1 convolution with the shifted fc.weight, raw f32 scores (split-K reduced by an f32 finish when the planner splits)");
-    run.where = "CAM";
-    if (!dry) cp360_set_launch_order(old_order);
     // ---- CAM: raw f32 scores [n_img, face, face, num_classes] straight into the caller's buffer (no bias / activation)
-    CK(run.conv(R.cam, buf[cur], n_img, face, face, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0, true, false, dry ? (float*)1 : cam_out, 0,
-                nullptr));
-    if (!dry && feat_out &&
-        hipMemcpyAsync(feat_out, buf[cur], (size_t)n_img * face * face * 2048 * es, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return CP360_ERR_HIP;
-#undef CK
-    w.partial = align_up(run.partial_need);
-    if (need && dry) *need = w;
+    P->note("CAM: 1x1 convolution with the shifted fc.weight, raw f32 scores (split-K reduced by an f32 finish when the planner splits)");
+    snprintf(P->where, sizeof(P->where), "CAM");
+    P->n_ordered = P->steps.size();
+    ConvArgs a(x);
+    a.raw = true;
+    a.raw_dst = SLOT_CAM;
+    P->conv(R.cam, face, face, a);
+    P->feat = x;
+    P->feat_bytes = (size_t)n_img * face * face * 2048 * es;
+    P->ws.partial = align_up(P->partial_need);
+    return CP360_OK;
+}
+
+// the launch-order hint for the span of an object, restored on every exit
+struct LaunchOrder {
+    int old;
+    bool held = true;
+    explicit LaunchOrder(int mode) : old(cp360_set_launch_order(mode)) {}
+    void restore() { if (held) cp360_set_launch_order(old); held = false; }
+    ~LaunchOrder() { restore(); }
+};
+
+int run_plan(const StagePlan& P, const void* faces_p3, float* cam_out, void* feat_out, unsigned char* ws, hipStream_t st) {
+    Bufs at;
+    for (int i = 0; i < 4; ++i) at.p[SLOT_ACT0 + i] = ws + i * P.ws.act;
+    at.p[SLOT_INPUT] = const_cast<void*>(faces_p3);
+    at.p[SLOT_CAM] = cam_out;
+    at.p[SLOT_PARTIAL] = ws + 4 * P.ws.act;
+    at.p[SLOT_BORDER] = ws + 4 * P.ws.act + P.ws.partial;
+    LaunchOrder order(2);
+    for (size_t i = 0; i < P.steps.size(); ++i) {
+        if (i == P.n_ordered) order.restore();
+        const int rc = run_step(P.steps[i], P, at, st);
+        if (rc) return rc;
+    }
+    if (feat_out && hipMemcpyAsync(feat_out, at[P.feat], P.feat_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return CP360_ERR_HIP;
     return CP360_OK;
 }
 
@@ -680,26 +758,20 @@ int resnet_run(cp360_ctx* ctx, bool dry, const void* faces_p3, int n_img, int cd
 
 extern "C" int cp360_resnet_plan_describe(cp360_ctx* ctx, int n_img, int cube_dim, char* buf, size_t cap) {
     if (!ctx || !buf || cap == 0) return CP360_ERR_NULL;
-    std::string text;
-    char head[160];
-    snprintf(head, sizeof(head), "static stage, %d faces of %d^2, %s:", n_img, cube_dim,
-             ctx->rn.dtype == CP360_F32 ? "f32" : (ctx->rn.dtype == CP360_F16 ? "f16" : "bf16"));
-    text = head;
-    text += "\n";
-    ResnetWs w;
-    const int rc = resnet_run(ctx, true, nullptr, n_img, cube_dim, nullptr, nullptr, nullptr, 0, nullptr, &w, &text);
+    StagePlan plan;
+    plan.describe = true;
+    const int rc = plan_resnet(ctx->rn, n_img, cube_dim, &plan);
     if (rc) return rc;
-    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
-    memcpy(buf, text.data(), n);
+    const size_t n = plan.text.size() < cap - 1 ? plan.text.size() : cap - 1;
+    memcpy(buf, plan.text.data(), n);
     buf[n] = 0;
     return (int)n;
 }
 
 extern "C" size_t cp360_resnet_workspace_bytes(cp360_ctx* ctx, int n_img, int cube_dim) {
     if (!ctx) return 0;
-    ResnetWs w;
-    if (resnet_run(ctx, true, nullptr, n_img, cube_dim, nullptr, nullptr, nullptr, 0, nullptr, &w)) return 0;
-    return w.total();
+    StagePlan plan;
+    return plan_resnet(ctx->rn, n_img, cube_dim, &plan) ? 0 : plan.ws.total();
 }
 
 extern "C" int cp360_resnet_forward(cp360_ctx* ctx, const void* faces_p3, int n_img, int cube_dim, float* cam_out,
@@ -707,11 +779,13 @@ extern "C" int cp360_resnet_forward(cp360_ctx* ctx, const void* faces_p3, int n_
     if (!ctx) return CP360_ERR_NULL;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return CP360_ERR_HIP;
-    ResnetWs w;
-    int rc = resnet_run(ctx, true, nullptr, n_img, cube_dim, nullptr, nullptr, nullptr, 0, nullptr, &w);
+    StagePlan plan;
+    const int rc = plan_resnet(ctx->rn, n_img, cube_dim, &plan);
     if (rc) return rc;
-    return resnet_run(ctx, false, faces_p3, n_img, cube_dim, cam_out, feat_out, (unsigned char*)workspace, workspace_bytes,
-                      (hipStream_t)stream, &w);
+    if (!faces_p3 || !cam_out || !workspace) return CP360_ERR_NULL;
+    if (((size_t)workspace & 255) != 0) return CP360_ERR_ALIGN;
+    if (workspace_bytes < plan.ws.total()) return CP360_ERR_BAD_SHAPE;
+    return run_plan(plan, faces_p3, cam_out, feat_out, (unsigned char*)workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- ConvLSTM cell
@@ -790,91 +864,105 @@ struct ClstmWs {
     size_t total() const { return 2 * act + partial + wv + wm; }
 };
 
-int clstm_run(cp360_ctx* ctx, bool dry, void* xh, const float* c_prev, float* c_next, float* h_f32, int n_clips, int face,
-              const float* x_next, const float* minmax, size_t clip_stride, unsigned char* ws, size_t ws_bytes, hipStream_t st,
-              ClstmWs* need) {
-    CClstm& Cl = ctx->cl;
+struct ClstmPlan : Plan {
+    bool wino = false;                             // the cell update in the Winograd domain (csrc/wino.hip) ...
+    cp360_wino_desc d1{}, d2{}, dg{};
+    int face = 0, M = 0, splits = 1, slab_rows = 0;          // ... or on the direct kernels: `steps` = Conv1, Conv2, Gates (raw slabs)
+    ClstmWs ws;
+};
+
+// One cell update on n_clips cubes of face x face
+int plan_clstm(const CClstm& Cl, int n_clips, int face, ClstmPlan* P) {
     if (!Cl.loaded) return CP360_ERR_NULL;
     if (n_clips <= 0 || face <= 0) return CP360_ERR_BAD_SHAPE;
-    const int n6 = 6 * n_clips, c4 = 4 * Cl.ch, es = es_of(Cl.dtype);
-    const int M = n6 * face * face;
-    ClstmWs w;
-    w.act = align_up((size_t)M * c4 * es);
-    Run run;
-    run.dry = dry;
-    run.st = st;
-    run.dtype = Cl.dtype;
-    unsigned char *a1 = nullptr, *a2 = nullptr;
-    if (!dry) {
-        if (!xh || !c_prev || !c_next || !ws) return CP360_ERR_NULL;
-        if (((size_t)ws & 255) != 0) return CP360_ERR_ALIGN;
-        w.partial = need->partial;
-        if (ws_bytes < w.total()) return CP360_ERR_BAD_SHAPE;
-        a1 = ws;
-        a2 = ws + w.act;
-        run.partial = (float*)(ws + 2 * w.act);
-        run.partial_cap = w.partial;
-    }
-    int rc, splits = 1;
-    if (Cl.wino_loaded && wino_wanted(Cl, n_clips, face)) {
-        // the same cell update in the Winograd domain (csrc/wino.hip): per convolution input transform -> 16 GEMMs -> output
-        // transform (+ bias + ReLU); the Gates convolution's output transform is the gate kernel
-        cp360_wino_desc d1, d2, dg;
-        wino_descs(Cl, n6, face, &d1, &d2, &dg);
+    const int n6 = 6 * n_clips, c4 = 4 * Cl.ch;
+    P->dtype = Cl.dtype;
+    P->n_img = n6;
+    P->face = face;
+    P->M = n6 * face * face;
+    P->ws.act = align_up((size_t)P->M * c4 * es_of(Cl.dtype));
+    P->wino = Cl.wino_loaded && wino_wanted(Cl, n_clips, face);
+    if (P->wino) {
+        wino_descs(Cl, n6, face, &P->d1, &P->d2, &P->dg);
         // V / M are shared by the three convolutions: sized for the largest (Conv1's K = input + hidden channels exceeds Conv2's
         // 4 * hidden when input > 3 * hidden)
-        w.wv = align_up(std::max(cp360_wino_v_bytes(&d1), std::max(cp360_wino_v_bytes(&d2), cp360_wino_v_bytes(&dg))));
-        w.wm = align_up(std::max(cp360_wino_m_bytes(&d1), std::max(cp360_wino_m_bytes(&d2), cp360_wino_m_bytes(&dg))));
-        if (dry) {
-            if (need) *need = w;
-            return CP360_OK;
-        }
-        if (ws_bytes < w.total()) return CP360_ERR_BAD_SHAPE;
-        unsigned char* v = ws + 2 * w.act;
-        float* m = (float*)(ws + 2 * w.act + w.wv);
-        // between two convolutions the output transform of one and the input transform of the next are ONE launch (faces up to
-        // 9 x 9: cp360_wino_output_input; larger faces: the two launches through the activation buffers a1 / a2)
-        if ((rc = cp360_wino_input(&d1, xh, v, st))) return rc;
-        if ((rc = cp360_wino_gemm(&d1, v, Cl.u1, m, st))) return rc;
-        rc = cp360_wino_output_input(&d1, m, Cl.c1.bias, v, st);
-        if (rc == CP360_ERR_UNSUPPORTED) {
-            if ((rc = cp360_wino_output(&d1, m, Cl.c1.bias, a1, st))) return rc;
-            rc = cp360_wino_input(&d2, a1, v, st);
-        }
-        if (rc) return rc;
-        if ((rc = cp360_wino_gemm(&d2, v, Cl.u2, m, st))) return rc;
-        rc = cp360_wino_output_input(&d2, m, Cl.c2.bias, v, st);
-        if (rc == CP360_ERR_UNSUPPORTED) {
-            if ((rc = cp360_wino_output(&d2, m, Cl.c2.bias, a2, st))) return rc;
-            rc = cp360_wino_input(&dg, a2, v, st);
-        }
-        if (rc) return rc;
-        if ((rc = cp360_wino_gemm(&dg, v, Cl.ug, m, st))) return rc;
-        return cp360_wino_output_gates(&dg, m, Cl.gbias, c_prev, c_next, xh, Cl.cin + Cl.ch, Cl.cin, h_f32, x_next, minmax, 0,
-                                       clip_stride, st);
-    }
-    // clstm.py:55-64: cat(x, h) -> [CubePad(1) + conv3x3 + bias + relu] x 2 -> CubePad(1) + conv3x3 (Gates, bias in the gate kernel)
-    if ((rc = run.conv(Cl.c1, xh, n6, face, face, nullptr, 0, a1, c4, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr))) return rc;
-    if ((rc = run.conv(Cl.c2, a1, n6, face, face, nullptr, 0, a2, c4, 0, nullptr, 0, 0, 0, false, false, nullptr, 0, nullptr))) return rc;
-    const bool sr = c4 % 32 == 0;                            // gate slabs in packed-row order (64-byte stores)
-    if ((rc = run.conv(Cl.g, a2, n6, face, face, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0, true, sr, nullptr, 0, &splits))) return rc;
-    w.partial = align_up(run.partial_need);
-    if (dry) {
-        if (need) *need = w;
+        P->ws.wv = align_up(std::max(cp360_wino_v_bytes(&P->d1), std::max(cp360_wino_v_bytes(&P->d2), cp360_wino_v_bytes(&P->dg))));
+        P->ws.wm = align_up(std::max(cp360_wino_m_bytes(&P->d1), std::max(cp360_wino_m_bytes(&P->d2), cp360_wino_m_bytes(&P->dg))));
         return CP360_OK;
     }
+    // clstm.py:55-64: cat(x, h) -> [CubePad(1) + conv3x3 + bias + relu] x 2 -> CubePad(1) + conv3x3 (Gates, bias in the gate kernel)
+    ConvArgs a(SLOT_INPUT, SLOT_ACT0);
+    a.ld_out = c4;
+    P->conv(Cl.c1, face, face, a);
+    a.in = SLOT_ACT0;
+    a.out = SLOT_ACT1;
+    P->conv(Cl.c2, face, face, a);
+    ConvArgs g(SLOT_ACT1);
+    g.raw = true;
+    g.raw_slab_rows = c4 % 32 == 0;                // gate slabs in packed-row order (64-byte stores)
+    P->splits = P->conv(Cl.g, face, face, g).d.splits;
+    P->slab_rows = g.raw_slab_rows ? 1 : 0;
+    P->ws.partial = align_up(P->partial_need);
+    return CP360_OK;
+}
+
+// The pointers of cp360_clstm_step that the gate kernels take
+struct CellIo {
+    void* xh;
+    const float* c_prev;
+    float *c_next, *h_f32;
+    const float *x_next, *minmax;
+    size_t clip_stride;
+};
+
+int run_clstm(const ClstmPlan& P, const CClstm& Cl, const CellIo& c, unsigned char* ws, hipStream_t st) {
+    unsigned char *a1 = ws, *a2 = ws + P.ws.act;
+    int rc;
+    if (P.wino) {
+        // per convolution input transform -> 16 GEMMs -> output transform (+ bias + ReLU); the Gates convolution's output
+        // transform is the gate kernel
+        unsigned char* v = ws + 2 * P.ws.act;
+        float* m = (float*)(ws + 2 * P.ws.act + P.ws.wv);
+        // between two convolutions the output transform of one and the input transform of the next are ONE launch (faces up to
+        // 9 x 9: cp360_wino_output_input; larger faces: the two launches through the activation buffers a1 / a2)
+        if ((rc = cp360_wino_input(&P.d1, c.xh, v, st))) return rc;
+        if ((rc = cp360_wino_gemm(&P.d1, v, Cl.u1, m, st))) return rc;
+        rc = cp360_wino_output_input(&P.d1, m, Cl.c1.bias, v, st);
+        if (rc == CP360_ERR_UNSUPPORTED) {
+            if ((rc = cp360_wino_output(&P.d1, m, Cl.c1.bias, a1, st))) return rc;
+            rc = cp360_wino_input(&P.d2, a1, v, st);
+        }
+        if (rc) return rc;
+        if ((rc = cp360_wino_gemm(&P.d2, v, Cl.u2, m, st))) return rc;
+        rc = cp360_wino_output_input(&P.d2, m, Cl.c2.bias, v, st);
+        if (rc == CP360_ERR_UNSUPPORTED) {
+            if ((rc = cp360_wino_output(&P.d2, m, Cl.c2.bias, a2, st))) return rc;
+            rc = cp360_wino_input(&P.dg, a2, v, st);
+        }
+        if (rc) return rc;
+        if ((rc = cp360_wino_gemm(&P.dg, v, Cl.ug, m, st))) return rc;
+        return cp360_wino_output_gates(&P.dg, m, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.cin + Cl.ch, Cl.cin, c.h_f32, c.x_next,
+                                       c.minmax, 0, c.clip_stride, st);
+    }
+    Bufs at;
+    at.p[SLOT_INPUT] = c.xh;
+    at.p[SLOT_ACT0] = a1;
+    at.p[SLOT_ACT1] = a2;
+    at.p[SLOT_PARTIAL] = ws + 2 * P.ws.act;
+    for (const Step& s : P.steps)
+        if ((rc = run_step(s, P, at, st))) return rc;
     // clstm.py:68-80: gates, cell / hidden update; the new hidden goes into the h half of xh; with x_next the next
     // frame's window normalisation (test_temporal.py:77) is written into the x half in the same pass
-    return cp360_lstm_gates_next(run.partial, splits, Cl.gbias, c_prev, c_next, xh, Cl.dtype, Cl.cin + Cl.ch, Cl.cin, h_f32, M,
-                                 Cl.ch, sr ? 1 : 0, x_next, minmax, 0, 6 * face * face, clip_stride, st);
+    return cp360_lstm_gates_next((const float*)at[SLOT_PARTIAL], P.splits, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.dtype,
+                                 Cl.cin + Cl.ch, Cl.cin, c.h_f32, P.M, Cl.ch, P.slab_rows, c.x_next, c.minmax, 0,
+                                 6 * P.face * P.face, c.clip_stride, st);
 }
 }  // namespace
 
 extern "C" size_t cp360_clstm_workspace_bytes(cp360_ctx* ctx, int n_clips, int face) {
     if (!ctx) return 0;
-    ClstmWs w;
-    if (clstm_run(ctx, true, nullptr, nullptr, nullptr, nullptr, n_clips, face, nullptr, nullptr, 0, nullptr, 0, nullptr, &w)) return 0;
-    return w.total();
+    ClstmPlan plan;
+    return plan_clstm(ctx->cl, n_clips, face, &plan) ? 0 : plan.ws.total();
 }
 
 extern "C" int cp360_clstm_step(cp360_ctx* ctx, void* xh, const float* c_prev, float* c_next, float* h_f32, int n_clips,
@@ -884,11 +972,14 @@ extern "C" int cp360_clstm_step(cp360_ctx* ctx, void* xh, const float* c_prev, f
     if (x_next && (!minmax || ctx->cl.cin != ctx->cl.ch)) return CP360_ERR_BAD_SHAPE;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return CP360_ERR_HIP;
-    ClstmWs w;
-    int rc = clstm_run(ctx, true, nullptr, nullptr, nullptr, nullptr, n_clips, face, nullptr, nullptr, 0, nullptr, 0, nullptr, &w);
+    ClstmPlan plan;
+    const int rc = plan_clstm(ctx->cl, n_clips, face, &plan);
     if (rc) return rc;
-    return clstm_run(ctx, false, xh, c_prev, c_next, h_f32, n_clips, face, x_next, minmax, clip_stride, (unsigned char*)workspace,
-                     workspace_bytes, (hipStream_t)stream, &w);
+    if (!xh || !c_prev || !c_next || !workspace) return CP360_ERR_NULL;
+    if (((size_t)workspace & 255) != 0) return CP360_ERR_ALIGN;
+    if (workspace_bytes < plan.ws.total()) return CP360_ERR_BAD_SHAPE;
+    const CellIo cell{xh, c_prev, c_next, h_f32, x_next, minmax, clip_stride};
+    return run_clstm(plan, ctx->cl, cell, (unsigned char*)workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- one window of the temporal stage
@@ -898,10 +989,10 @@ int window_plan(cp360_ctx* ctx, int n_clips, int T, int face, size_t* ws_bytes) 
     CClstm& Cl = ctx->cl;
     if (!Cl.loaded) return CP360_ERR_NULL;
     if (n_clips <= 0 || T <= 0 || face <= 0 || Cl.cin != Cl.ch) return CP360_ERR_BAD_SHAPE;
-    ClstmWs s;
-    int rc = clstm_run(ctx, true, nullptr, nullptr, nullptr, nullptr, n_clips, face, nullptr, nullptr, 0, nullptr, 0, nullptr, &s);
+    ClstmPlan plan;
+    const int rc = plan_clstm(Cl, n_clips, face, &plan);
     if (rc) return rc;
-    *ws_bytes = s.total();
+    *ws_bytes = plan.ws.total();
     return CP360_OK;
 }
 }  // namespace

@@ -108,7 +108,7 @@ class ConvLSTMCell(nn.Module):
         # x_next = (cam, minmax, P, clip_stride, t_next): the gate kernel also writes the next step's normalised input
         xn = None if x_next is None else (x_next[0], x_next[1], 0, x_next[2], x_next[3], x_next[4])
         if self.uses_winograd(n6, w):
-            # (the same launches as csrc/ctx.hip's clstm_run: between two convolutions ONE fused output + input transform where
+            # (the same launches as csrc/ctx.hip's run_clstm: between two convolutions ONE fused output + input transform where
             # the faces allow it, else the two kernels through an activation buffer)
             convs = (p['w1'], p['w2'], p['wg'])
             v, d = convs[0].input(xh)
