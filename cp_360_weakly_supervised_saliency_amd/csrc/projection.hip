@@ -62,10 +62,16 @@ __global__ __launch_bounds__(256) void equi2cube_kernel(const TI* __restrict__ e
         const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
         const bool x0ok = ix >= 0 && ix < W, x1ok = ix + 1 >= 0 && ix + 1 < W;
         const bool y0ok = iy >= 0 && iy < H, y1ok = iy + 1 >= 0 && iy + 1 < H;
-        auto emit = [&](int fr, float v[3]) {
-            v[0] = (v[0] - m0) * s0;
-            v[1] = (v[1] - m1) * s1;
-            v[2] = (v[2] - m2) * s2;
+        // The roundings are spelled out, so that a pixel gets the same bits from the u8 fast path, from the guarded path
+        // and in every output type and layout: left to the compiler, the contraction into fused multiply-adds differed
+        // between the two paths of the NHWC4 kernels (scale and mean fused in one, rounded apart in the other).
+        auto lerp = [&](float t00, float t01, float t10, float t11) {
+            return __builtin_fmaf(t11, w11, __builtin_fmaf(t10, w10, __builtin_fmaf(t00, w00, t01 * w01)));
+        };
+        auto emit = [&](int fr, float v[3]) {                        // v: the interpolated taps, before `scale`
+            v[0] = __builtin_fmaf(v[0], scale, -m0) * s0;
+            v[1] = __builtin_fmaf(v[1], scale, -m1) * s1;
+            v[2] = __builtin_fmaf(v[2], scale, -m2) * s2;
             if (LAYOUT == 0) {   // [6F, 3, cd, cd]
                 const int face = g / (cd * cd), pix = g - face * cd * cd;
                 const size_t o = ((size_t)(fr * 6 + face) * 3) * cd * cd + pix;
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void equi2cube_kernel(const TI* __restrict__ e
                 taps(d1[u], sh1[u], t10, t11);
                 float v[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = (t00[c] * w00 + t01[c] * w01 + t10[c] * w10 + t11[c] * w11) * scale;
+                for (int c = 0; c < 3; ++c) v[c] = lerp(t00[c], t01[c], t10[c], t11[c]);
                 emit(fr0 + u, v);
             }
         } else {
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void equi2cube_kernel(const TI* __restrict__ e
                     const float t01 = (x1ok && y0ok) ? px_load<TI>(base + ((size_t)iy * W + ix + 1) * 3 + c) : 0.f;
                     const float t10 = (x0ok && y1ok) ? px_load<TI>(base + ((size_t)(iy + 1) * W + ix) * 3 + c) : 0.f;
                     const float t11 = (x1ok && y1ok) ? px_load<TI>(base + ((size_t)(iy + 1) * W + ix + 1) * 3 + c) : 0.f;
-                    v[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11) * scale;
+                    v[c] = lerp(t00, t01, t10, t11);
                 }
                 emit(fr0 + u, v);
             }

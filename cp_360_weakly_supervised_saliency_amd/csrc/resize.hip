@@ -10,6 +10,7 @@
 // integer work, bit-exact by construction (tests compare with PIL itself).
 #include "common.h"
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #define CP360_RESIZE_PRECISION_BITS (32 - 8 - 2)
@@ -214,31 +215,71 @@ static bool h_window_fits(int w_in, int w_out, int ksize) {
     return 256.0 * scale + ksize + 2 <= RH_MAX_PX;
 }
 
-extern "C" int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int F, int h_in, int w_in, int h_out,
-                                       int w_out, const int* hbounds, const int* hkk, int hksize, const int* vbounds,
-                                       const int* vkk, int vksize, void* stream) {
+// Which kernel each pass of a resize runs on, resolved once from the geometry and the three pointers:
+// cp360_resize_lanczos_u8 launches the record, cp360_resize_plan_describe prints it.
+enum ResizePass { RP_NONE = 0, RP_H_LDS, RP_V_DWORD, RP_BYTEWISE };
+struct ResizeLaunch {
+    bool copy;                 // neither axis changes: one device-to-device copy
+    ResizePass h, v;
+};
+static const char* const kResizePassNames[] = {"none", "LDS window", "dword", "bytewise"};
+
+static int resolve_resize(const void* in, const void* out, const void* tmp, int F, int h_in, int w_in, int h_out, int w_out,
+                          int hksize, int vksize, ResizeLaunch* L) {
     if (!in || !out) return CP360_ERR_NULL;
     if (F <= 0 || h_in <= 0 || w_in <= 0 || h_out <= 0 || w_out <= 0) return CP360_ERR_BAD_SHAPE;
     const bool need_h = w_out != w_in, need_v = h_out != h_in;
-    if (need_h && (!hbounds || !hkk || hksize <= 0)) return CP360_ERR_NULL;
-    if (need_v && (!vbounds || !vkk || vksize <= 0)) return CP360_ERR_NULL;
+    if (need_h && hksize <= 0) return CP360_ERR_NULL;
+    if (need_v && vksize <= 0) return CP360_ERR_NULL;
     if (need_h && need_v && !tmp) return CP360_ERR_NULL;
+    L->copy = !need_h && !need_v;
+    L->h = L->v = RP_NONE;
+    // what the vertical pass reads: the horizontal pass's destination (tmp when both run), else the input
+    const void* mid = need_h ? (need_v ? tmp : out) : in;
+    // (the window kernel loads aligned dwords relative to the input base: a base that is not 4-byte aligned - a slice
+    // of a batch of odd-sized images - takes the bytewise pass)
+    if (need_h)
+        L->h = h_window_fits(w_in, w_out, hksize) && (long long)F * h_in < (1 << 24) && (reinterpret_cast<size_t>(in) & 3) == 0
+                   ? RP_H_LDS : RP_BYTEWISE;
+    if (need_v)
+        L->v = (w_out * 3) % 4 == 0 && (reinterpret_cast<size_t>(mid) & 3) == 0 && (reinterpret_cast<size_t>(out) & 3) == 0
+                   ? RP_V_DWORD : RP_BYTEWISE;
+    return CP360_OK;
+}
+
+extern "C" int cp360_resize_plan_describe(const void* in, const void* out, const void* tmp, int F, int h_in, int w_in,
+                                          int h_out, int w_out, int hksize, int vksize, char* buf, size_t cap) {
+    if (!buf || cap == 0) return CP360_ERR_NULL;
+    ResizeLaunch L;
+    const int rc = resolve_resize(in, out, tmp, F, h_in, w_in, h_out, w_out, hksize, vksize, &L);
+    if (rc) return rc;
+    const int n = L.copy ? snprintf(buf, cap, "copy")
+                         : snprintf(buf, cap, "horizontal %s, vertical %s", kResizePassNames[L.h], kResizePassNames[L.v]);
+    return n < 0 ? CP360_ERR_BAD_SHAPE : (n >= (int)cap ? (int)cap - 1 : n);
+}
+
+extern "C" int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int F, int h_in, int w_in, int h_out,
+                                       int w_out, const int* hbounds, const int* hkk, int hksize, const int* vbounds,
+                                       const int* vkk, int vksize, void* stream) {
+    ResizeLaunch L;
+    const int rc = resolve_resize(in, out, tmp, F, h_in, w_in, h_out, w_out, hksize, vksize, &L);
+    if (rc) return rc;
+    if (L.h != RP_NONE && (!hbounds || !hkk)) return CP360_ERR_NULL;
+    if (L.v != RP_NONE && (!vbounds || !vkk)) return CP360_ERR_NULL;
     hipStream_t st = (hipStream_t)stream;
     auto blocks_of = [](long long total) {
         long long b = (total + 255) / 256;
         return (unsigned)(b > 65535 * 4 ? 65535 * 4 : b);
     };
-    if (!need_h && !need_v) {
+    if (L.copy) {
         if (hipMemcpyAsync(out, in, (size_t)F * h_in * w_in * 3, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return CP360_ERR_HIP;
         return CP360_OK;
     }
     const uint8_t* cur = (const uint8_t*)in;
-    if (need_h) {       // [F, h_in, w_in] -> [F, h_in, w_out]
-        uint8_t* dst = need_v ? (uint8_t*)tmp : (uint8_t*)out;
-        // (the window kernel loads aligned dwords relative to the input base: a base that is not 4-byte aligned - a slice
-        // of a batch of odd-sized images - takes the bytewise pass)
-        if (h_window_fits(w_in, w_out, hksize) && (long long)F * h_in < (1 << 24) && (reinterpret_cast<size_t>(cur) & 3) == 0) {
+    if (L.h != RP_NONE) {       // [F, h_in, w_in] -> [F, h_in, w_out]
+        uint8_t* dst = L.v != RP_NONE ? (uint8_t*)tmp : (uint8_t*)out;
+        if (L.h == RP_H_LDS) {
             const int xblocks = (w_out + 255) / 256;
             long long items = (long long)F * h_in * xblocks;
             unsigned blocks = (unsigned)(items > 256 * 16 ? 256 * 16 : (items + 7) / 8 * 8);
@@ -250,18 +291,16 @@ extern "C" int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int
         }
         cur = dst;
     }
-    if (need_v) {       // [F, h_in, w_out] -> [F, h_out, w_out]
-        if ((w_out * 3) % 4 == 0 && (reinterpret_cast<size_t>(cur) & 3) == 0 && (reinterpret_cast<size_t>(out) & 3) == 0) {
-            const long long total = (long long)F * h_out * (w_out * 3 / 4);
-            long long b = (total + 255) / 256;
-            if (b > 256 * 32) b = 256 * 32;
-            b = (b + 7) / 8 * 8;
-            hipLaunchKernelGGL(resize_v4_kernel, dim3((unsigned)b), dim3(256), 0, st, cur, (uint8_t*)out, vbounds, vkk, vksize,
-                               F, h_in, w_out * 3 / 4, h_out);
-        } else {
-            hipLaunchKernelGGL((resize_pass_kernel<false>), dim3(blocks_of((long long)F * h_out * w_out)), dim3(256), 0, st,
-                               cur, (uint8_t*)out, vbounds, vkk, vksize, F, h_in, w_out, h_out, w_out);
-        }
+    if (L.v == RP_V_DWORD) {    // [F, h_in, w_out] -> [F, h_out, w_out]
+        const long long total = (long long)F * h_out * (w_out * 3 / 4);
+        long long b = (total + 255) / 256;
+        if (b > 256 * 32) b = 256 * 32;
+        b = (b + 7) / 8 * 8;
+        hipLaunchKernelGGL(resize_v4_kernel, dim3((unsigned)b), dim3(256), 0, st, cur, (uint8_t*)out, vbounds, vkk, vksize,
+                           F, h_in, w_out * 3 / 4, h_out);
+    } else if (L.v == RP_BYTEWISE) {
+        hipLaunchKernelGGL((resize_pass_kernel<false>), dim3(blocks_of((long long)F * h_out * w_out)), dim3(256), 0, st,
+                           cur, (uint8_t*)out, vbounds, vkk, vksize, F, h_in, w_out, h_out, w_out);
     }
     CP360_CHECK_HIP();
     return CP360_OK;

@@ -926,6 +926,16 @@ def window_normalize(x, minmax, y, y_coff, y2, B, T, t, P, Cc, clip_stride=0):
                                        ptr(y2), B, T, t, P, Cc, clip_stride, stream()))
 
 
+def window_normalize_frames(x, minmax, y, B, T, P, Cc, clip_stride=0):
+    """All T frames of every window at once into y [T, B, P, Cc] (dense; f32 / bf16 / fp16)."""
+    require_gpu(x, minmax, y)
+    _check_buf('x', x, torch.float32, numel=(B - 1) * (clip_stride or T * P * Cc) + T * P * Cc)
+    _check_buf('minmax', minmax, torch.float32, numel=2 * B)
+    _check_buf('y', y, y.dtype, numel=T * B * P * Cc)
+    check(lib().cp360_window_normalize_frames(ptr(x), ptr(minmax), ptr(y), dtype_code(y.dtype), B, T, P, Cc, clip_stride,
+                                              stream()))
+
+
 def held_clock_ghz(device='cuda', ms=6.0, launches=3):
     """Diagnostic (never on the hot path): the shader clock the chip holds under a dense bf16 MFMA load on random operands -
     cp360_clock_probe (csrc/misc.hip), one wave per SIMD on every CU, median over the waves of the last of ``launches``

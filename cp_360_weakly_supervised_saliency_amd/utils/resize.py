@@ -51,7 +51,8 @@ class LanczosResize:
             b, k = pil_tables(self.in_hw[0], self.out_hw[0], filter)
             self.v = (torch.from_numpy(b).to(self.device), torch.from_numpy(k).to(self.device), k.shape[1])
 
-    def __call__(self, frames, out=None):
+    def _buffers(self, frames, out):
+        """The tensors of one call: (contiguous frames, out, the intermediate of a two-pass resize or None)."""
         require_gpu(frames, out)
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError("frames must be uint8 [F, H, W, 3]")
@@ -64,6 +65,24 @@ class LanczosResize:
         tmp = None
         if self.h is not None and self.v is not None:
             tmp = torch.empty((F, self.in_hw[0], self.out_hw[1], 3), dtype=torch.uint8, device=frames.device)
+        return frames, out, tmp
+
+    def describe(self, frames, out=None):
+        """cp360_resize_plan_describe: which kernels ``self(frames, out)`` runs, as text - 'horizontal <none | LDS window |
+        bytewise>, vertical <none | dword | bytewise>' or 'copy'.  The choice depends on the geometry and on the alignment
+        of the tensors' storage, so it takes the tensors of the call (an ``out`` of None is a fresh, aligned allocation)."""
+        frames, out, tmp = self._buffers(frames, out)
+        buf = C.create_string_buffer(96)
+        n = lib().cp360_resize_plan_describe(ptr(frames), ptr(out), ptr(tmp), frames.shape[0], self.in_hw[0], self.in_hw[1],
+                                             self.out_hw[0], self.out_hw[1], 0 if self.h is None else self.h[2],
+                                             0 if self.v is None else self.v[2], buf, len(buf))
+        if n < 0:
+            check(n)
+        return buf.value.decode()
+
+    def __call__(self, frames, out=None):
+        frames, out, tmp = self._buffers(frames, out)
+        F = frames.shape[0]
         hb, hk, hks = self.h if self.h is not None else (None, None, 0)
         vb, vk, vks = self.v if self.v is not None else (None, None, 0)
         check(lib().cp360_resize_lanczos_u8(ptr(frames), ptr(out), ptr(tmp), F, self.in_hw[0], self.in_hw[1],

@@ -142,6 +142,12 @@ int cp360_resize_coeffs_host2(int in_size, int out_size, int filter, int* bounds
 int cp360_resize_lanczos_u8(const void* in, void* out, void* tmp, int F, int h_in, int w_in,
                             int h_out, int w_out, const int* hbounds, const int* hkk, int hksize,
                             const int* vbounds, const int* vkk, int vksize, void* stream);
+/* Which kernels that call runs, as text, without launching: "horizontal <none | LDS window | bytewise>, vertical <none | dword |
+ * bytewise>", or "copy" when neither axis changes.  The choice depends on the geometry, F and the alignment of the three
+ * pointers (never dereferenced here; tmp as for the call).  The call launches from the same record.  Returns the length
+ * written (without the terminating 0; truncated to cap - 1) or a negative status.  HOST: needs no GPU. */
+int cp360_resize_plan_describe(const void* in, const void* out, const void* tmp, int F, int h_in, int w_in,
+                               int h_out, int w_out, int hksize, int vksize, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------ K3/K4/K5: convolution
  * Implicit-GEMM convolution on MFMA.  Replaces nn.Conv2d(+BatchNorm2d eval)(+ReLU)

@@ -37,6 +37,79 @@ def test_host_tables_equal_oracle(sizes):
     assert np.all(ko.sum(1) >= (1 << 22) - 8) and np.all(ko.sum(1) <= (1 << 22) + 8)     # weights sum to 1
 
 
+# The geometries of tests/test_side_paths_gpu.py (each takes another pair of kernels) and the full-size frame resize:
+# ((h_in, w_in), (h_out, w_out), filter, byte offset of the input, byte offset of the output, the pair expected)
+RESIZE_PLANS = [
+    ((9, 1000), (7, 250), 'lanczos', 0, 0, 'horizontal bytewise, vertical bytewise'),      # 256 * 4 + 25 + 2 > 1024 pixels
+    ((9, 1000), (9, 250), 'lanczos', 0, 0, 'horizontal bytewise, vertical none'),
+    ((5, 300), (5, 520), 'lanczos', 0, 0, 'horizontal LDS window, vertical none'),
+    ((97, 131), (61, 203), 'lanczos', 0, 0, 'horizontal LDS window, vertical bytewise'),   # 203 * 3 % 4 != 0
+    ((97, 131), (61, 203), 'lanczos', 1, 0, 'horizontal bytewise, vertical bytewise'),
+    ((97, 131), (61, 203), 'lanczos', 2, 0, 'horizontal bytewise, vertical bytewise'),
+    ((54, 96), (48, 96), 'lanczos', 0, 0, 'horizontal none, vertical dword'),
+    ((54, 96), (48, 96), 'lanczos', 0, 1, 'horizontal none, vertical bytewise'),
+    ((54, 96), (48, 96), 'lanczos', 2, 0, 'horizontal none, vertical bytewise'),           # the vertical pass reads the input
+    ((12, 20), (12, 20), 'lanczos', 0, 0, 'copy'),
+    ((12, 20), (12, 20), 'lanczos', 1, 3, 'copy'),
+    ((14, 28), (96, 192), 'bicubic', 0, 0, 'horizontal LDS window, vertical dword'),
+    ((1080, 2160), (960, 1920), 'lanczos', 0, 0, 'horizontal LDS window, vertical dword'),
+]
+
+
+def _resize_plan(in_hw, out_hw, filter='lanczos', in_off=0, out_off=0, tmp_off=0, F=2):
+    """cp360_resize_plan_describe on made-up addresses (it reads their alignment only): no GPU."""
+    import ctypes as C
+    from cp_360_weakly_supervised_saliency_amd._lib import check, lib
+    from cp_360_weakly_supervised_saliency_amd.utils.resize import FILTERS
+    L = lib()
+    hks = L.cp360_resize_ksize2(in_hw[1], out_hw[1], FILTERS[filter]) if in_hw[1] != out_hw[1] else 0
+    vks = L.cp360_resize_ksize2(in_hw[0], out_hw[0], FILTERS[filter]) if in_hw[0] != out_hw[0] else 0
+    buf = C.create_string_buffer(96)
+    n = L.cp360_resize_plan_describe(C.c_void_p(4096 + in_off), C.c_void_p(8192 + out_off), C.c_void_p(12288 + tmp_off), F,
+                                     in_hw[0], in_hw[1], out_hw[0], out_hw[1], hks, vks, buf, len(buf))
+    if n < 0:
+        check(n)
+    assert n == len(buf.value)
+    return buf.value.decode()
+
+
+def test_resize_plan_names_the_kernels_of_every_geometry():
+    """cp360_resize_plan_describe (the record cp360_resize_lanczos_u8 launches from) for the geometries the GPU tests run and
+    the full-size frame resize: today's choice of kernels, pinned."""
+    for in_hw, out_hw, filt, in_off, out_off, want in RESIZE_PLANS:
+        assert _resize_plan(in_hw, out_hw, filt, in_off, out_off) == want, (in_hw, out_hw, filt, in_off, out_off)
+    # a misaligned intermediate of a two-pass resize, and F * h_in rows past the LDS kernel's 2^24 row items
+    assert _resize_plan((54, 100), (48, 96), tmp_off=1) == 'horizontal LDS window, vertical bytewise'
+    assert _resize_plan((54, 100), (48, 96)) == 'horizontal LDS window, vertical dword'
+    assert _resize_plan((8, 100), (8, 96), F=1 << 21) == 'horizontal bytewise, vertical none'
+    assert _resize_plan((8, 100), (8, 96), F=(1 << 21) - 1) == 'horizontal LDS window, vertical none'
+    # refusals come back as the call's own status codes, and a short buffer truncates
+    import ctypes as C
+    from cp_360_weakly_supervised_saliency_amd._lib import lib
+    L, one, buf = lib(), C.c_void_p(16), C.create_string_buffer(96)
+    assert L.cp360_resize_plan_describe(None, one, None, 1, 4, 4, 2, 2, 7, 7, buf, 96) == -5
+    assert L.cp360_resize_plan_describe(one, one, None, 1, 4, 4, 2, 2, 7, 7, buf, 96) == -5          # both axes: tmp
+    assert L.cp360_resize_plan_describe(one, one, one, 0, 4, 4, 2, 2, 7, 7, buf, 96) == -1
+    assert L.cp360_resize_plan_describe(one, one, one, 1, 4, 4, 2, 2, 7, 7, None, 0) == -5
+    assert L.cp360_resize_plan_describe(one, one, one, 1, 4, 4, 4, 4, 0, 0, buf, 3) == 2 and buf.value == b'co'
+
+
+def test_oracle_resize_matches_live_pillow_on_the_side_path_geometries():
+    """The oracle against Pillow itself at the geometries of tests/test_side_paths_gpu.py (a 4x horizontal shrink with 25
+    taps, horizontal-only resizes, the bicubic upsample), on the inputs those tests use."""
+    Image = pytest.importorskip('PIL.Image')
+    for in_hw, out_hw, filt, _, _, _ in RESIZE_PLANS[:-1]:
+        a = side_path_frames(in_hw)[1]
+        resample = Image.LANCZOS if filt == 'lanczos' else Image.BICUBIC
+        want = np.array(Image.fromarray(a).convert('RGB').resize((out_hw[1], out_hw[0]), resample=resample))
+        assert np.array_equal(o_resize.resize_u8(a, out_hw, filt), want), (in_hw, out_hw, filt)
+
+
+def side_path_frames(in_hw, F=2):
+    """The seeded u8 frames [F, h, w, 3] of a side-path resize case (the frames differ)."""
+    return hashrng.uniform(7300 + in_hw[0] * 7 + in_hw[1], (F,) + tuple(in_hw) + (3,), 0.0, 256.0).astype(np.uint8)
+
+
 @pytest.mark.gpu
 def test_gpu_resize_bit_exact(golden_dir):
     z = np.load(os.path.join(golden_dir, 'resize_lanczos.npz'))
