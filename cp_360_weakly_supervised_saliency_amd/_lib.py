@@ -53,6 +53,8 @@ PUBLIC_SYMBOLS = [
     # K5f: flow resize and flow loss
     'cp360_flow_resize_coeffs_host', 'cp360_flow_resize', 'cp360_flow_loss_work_bytes', 'cp360_flow_loss_forward',
     'cp360_flow_loss_backward',
+    # K5o: fused Adam
+    'cp360_train_adam', 'cp360_train_adam_conv',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -234,6 +236,9 @@ def lib():
     L.cp360_flow_loss_work_bytes.argtypes = [i, i, i, i, i]
     L.cp360_flow_loss_forward.argtypes = [i, vp, vp, i, i, i, i, i, f, vp, vp, vp]
     L.cp360_flow_loss_backward.argtypes = [i, vp, vp, vp, i, i, i, i, i, f, vp, vp, vp]
+    dbl = C.c_double
+    L.cp360_train_adam.argtypes = [vp, vp, vp, vp, C.c_longlong, dbl, dbl, dbl, dbl, dbl, dbl, dbl, vp]
+    L.cp360_train_adam_conv.argtypes = [vp, vp, vp, vp, i, i, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i, vp, vp, vp, i, i, vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

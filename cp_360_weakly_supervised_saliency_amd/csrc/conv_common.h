@@ -33,6 +33,15 @@ template <> struct Elem<float> { static constexpr int EPC = 4; };      // elemen
 template <> struct Elem<bf16_raw> { static constexpr int EPC = 8; };
 template <> struct Elem<f16_raw> { static constexpr int EPC = 8; };
 
+// The padding of the packed forward weights [rows][tap][c_pad], ONE rule for the packers (conv_igemm.hip) and for every other
+// writer of those layouts (adam.hip): rows to 256; the channels of a tap to a 128-byte step in the tap-major layout and to a
+// 64-byte sub-step in the channel-major one (cp360_conv_desc.clip_resident).
+static inline int conv_c_pad(int c_in, int dtype, int chan_major) {
+    const int unit = (chan_major ? 64 : 128) / elem_bytes(dtype);
+    return (c_in + unit - 1) / unit * unit;
+}
+static inline int conv_rows_pad(int c_out) { return (c_out + 255) / 256 * 256; }
+
 // conv_small.hip keeps a [tap][tile row] source-offset table in LDS: kh * kw (+ 1 for a second source) must fit
 #define CP360_SMALL_MAX_TAPS 16
 

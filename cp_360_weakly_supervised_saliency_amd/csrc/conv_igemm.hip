@@ -1551,10 +1551,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
 // ------------------------------------------------------------------ host side
 static int bk_of(int dtype) { return 128 / elem_bytes(dtype); }
 // K padding per tap: a 128-byte step for the tap-major layout, a 64-byte sub-step for the channel-major one
-static int c_pad_of(const cp360_conv_desc* d) {
-    const int unit = d->clip_resident ? bk_of(d->dtype) / 2 : bk_of(d->dtype);
-    return (d->c_in + unit - 1) / unit * unit;
-}
+static int c_pad_of(const cp360_conv_desc* d) { return conv_c_pad(d->c_in, d->dtype, d->clip_resident); }
 static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static int c_pad2_of(const cp360_conv_desc* d) { return d->c_in2 > 0 ? round_up(d->c_in2, bk_of(d->dtype)) : 0; }
 
@@ -1627,7 +1624,7 @@ static int check_desc(const cp360_conv_desc* d) {
 
 extern "C" size_t cp360_conv_packed_bytes(const cp360_conv_desc* d) {
     if (check_desc(d)) return 0;
-    return (size_t)round_up(d->c_out, 256) * ((size_t)d->kh * d->kw * c_pad_of(d) + c_pad2_of(d)) * elem_bytes(d->dtype);
+    return (size_t)conv_rows_pad(d->c_out) * ((size_t)d->kh * d->kw * c_pad_of(d) + c_pad2_of(d)) * elem_bytes(d->dtype);
 }
 
 extern "C" size_t cp360_conv_partial_bytes(const cp360_conv_desc* d) {
@@ -1930,7 +1927,7 @@ static int pack_weights_impl(const cp360_conv_desc* d, const float* w_oihw, cons
     if (stem_mode && !(d->kh == 7 && d->kw == 1 && d->c_in == 32)) return CP360_ERR_UNSUPPORTED;
     if (stem_mode && d->clip_resident) return CP360_ERR_UNSUPPORTED;
     const int c_pad = c_pad_of(d);
-    const int c_out_pad = round_up(d->c_out, 256);
+    const int c_out_pad = conv_rows_pad(d->c_out);
     const int c_pad2 = c_pad2_of(d);
     const long long total = (long long)c_out_pad * ((long long)d->kh * d->kw * c_pad + c_pad2);
     long long blocks = (total + 255) / 256;

@@ -25,7 +25,8 @@ TRAIN_FACE = 7          # cube 224 after ResNet-50 (the reference's training con
 
 class ClstmTraining:
     """Device state of one cell's training: the forward convolutions, the dgrad packs and the inverse tables.  Packs are made
-    again whenever a parameter's ``_version`` changes (an optimizer step) - the rule of ``ConvLSTMCell.plans()``."""
+    again whenever a parameter's ``_version`` changes (an optimizer step) - the rule of ``ConvLSTMCell.plans()`` - unless the
+    optimizer wrote them itself (``adopt``: temporal_model.train_temporal.FusedAdam)."""
 
     def __init__(self, cell):
         if cell.precision not in TRAIN_PRECISIONS:
@@ -66,6 +67,23 @@ class ClstmTraining:
                 p[k].tag = name
             self._plan, self._stamp = p, stamp
         return self._plan
+
+    def current(self):
+        """True when the packs of ``plans()`` exist and belong to the parameters as they are now (no repack is pending)."""
+        return self._plan is not None and self._stamp == _stamp(self.cell, (self.cell.precision,))
+
+    def adopt(self):
+        """For a writer that has brought the packs up to date with the parameters itself (``FusedAdam.step`` writes the new
+        weights into them and bumps the parameters' versions): take the parameters' new stamp, so that ``plans()`` keeps
+        returning the same objects without a pack launch.  The bias copies alias their parameters when those are f32,
+        contiguous and on the device; any that do not are refreshed here."""
+        if self._plan is None:
+            return
+        cell, p = self.cell, self._plan
+        for copy, b in ((p['c1'].bias, cell.Conv1.bias), (p['c2'].bias, cell.Conv2.bias), (p['gbias'], cell.Gates.bias)):
+            if copy.data_ptr() != b.data_ptr():
+                copy.copy_(b.detach())
+        self._stamp = _stamp(cell, (cell.precision,))
 
     def tables(self, w, dev):
         key = (w, str(dev))

@@ -1113,6 +1113,71 @@ def saliency_backward(dmap, argmax, coord, inv_off, inv_ent, dh):
                                               ptr(dh), B, Cc, w, stream()))
 
 
+# ----------------------------------------------------------------------------- K5o: fused Adam
+def _adam_args(p, g, m, v, lr, betas, eps, weight_decay, step):
+    """The checks and the scalar arguments the two Adam entry points share: the bias corrections in double, as torch."""
+    require_gpu(p, g, m, v)
+    for name, t in (('p', p), ('g', g), ('m', m), ('v', v)):
+        _check_buf(name, t, torch.float32)
+        if tuple(t.shape) != tuple(p.shape) or t.device != p.device:
+            raise ValueError("%s must have the parameter's shape %s and device" % (name, tuple(p.shape)))
+    step = int(step)
+    if step < 1:
+        raise ValueError("step counts from 1 (the step being taken), got %d" % step)
+    b1, b2 = float(betas[0]), float(betas[1])
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or float(lr) < 0.0 or float(eps) < 0.0 or float(weight_decay) < 0.0:
+        raise ValueError("Adam needs lr, eps, weight_decay >= 0 and betas in [0, 1)")
+    return (float(lr), b1, b2, float(eps), float(weight_decay), 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step))
+
+
+def adam_step(p, g, m, v, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1):
+    """cp360_train_adam: step number ``step`` (from 1) of torch.optim.Adam (amsgrad False, maximize False) on f32 tensors of
+    one shape, in place: parameter p, gradient g, exp_avg m, exp_avg_sq v.  The caller bumps p's version counter."""
+    args = _adam_args(p, g, m, v, lr, betas, eps, weight_decay, step)
+    if p.numel() == 0:
+        raise ValueError("an empty parameter")
+    check(lib().cp360_train_adam(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), *args, stream()))
+
+
+def conv_pack_bytes(c_out, c_in, dtype, chan_major):
+    """Bytes of a forward pack of a CubePad(1) + 3x3 filter [c_out, c_in, 3, 3] as the library sizes it (cp360_conv_packed_bytes;
+    0: it has no kernel for that layout of this shape).  chan_major: cp360_conv_desc.clip_resident."""
+    d = ConvDesc()
+    for k, v in dict(dtype=dtype_code(dtype), n_img=6, h_in=7, w_in=7, c_in=c_in, pix_stride=c_in, kh=3, kw=3, sy=1, sx=1,
+                     h_out=7, w_out=7, c_out=c_out, pad_mode=1, pad=1, ld_out=c_out, relu=1, splits=1,
+                     clip_resident=int(bool(chan_major))).items():
+        setattr(d, k, v)
+    return lib().cp360_conv_packed_bytes(C.byref(d))
+
+
+def adam_step_conv(p, g, m, v, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1, dtype=torch.float32,
+                   fwd_tap_major=None, fwd_chan_major=None, dgrad_packed=None, ci0=0, n_dgrad=0):
+    """cp360_train_adam_conv: ``adam_step`` on a filter [c_out, c_in, 3, 3] that also writes the new weights, rounded to
+    ``dtype`` (f32 / bf16), into the packs given: the two forward layouts of ``Conv.packed_for(0 / 1)`` and ``DgradPack.packed``
+    of input channels [ci0, ci0 + n_dgrad) (uint8 tensors as those classes keep them; None: not written)."""
+    args = _adam_args(p, g, m, v, lr, betas, eps, weight_decay, step)
+    if p.dim() != 4 or tuple(p.shape[2:]) != (3, 3):
+        raise ValueError("a [c_out, c_in, 3, 3] filter")
+    c_out, c_in = int(p.shape[0]), int(p.shape[1])
+    code = _train_dtype(dtype)
+    es = torch.empty((), dtype=dtype).element_size()
+    require_gpu(fwd_tap_major, fwd_chan_major, dgrad_packed)
+    ci0, n_dgrad = int(ci0), int(n_dgrad)
+    if dgrad_packed is None:
+        ci0 = n_dgrad = 0
+    elif ci0 < 0 or n_dgrad < 1 or ci0 + n_dgrad > c_in:
+        raise ValueError("the dgrad pack's channels [%d, %d) are not inside [0, %d)" % (ci0, ci0 + n_dgrad, c_in))
+    for name, t, chan_major in (('fwd_tap_major', fwd_tap_major, False), ('fwd_chan_major', fwd_chan_major, True),
+                                ('dgrad_packed', dgrad_packed, None)):
+        if t is None:
+            continue
+        nbytes = n_dgrad * 9 * c_out * es if chan_major is None else conv_pack_bytes(c_out, c_in, dtype, chan_major)
+        if nbytes == 0 or not t.is_contiguous() or t.device != p.device or t.numel() * t.element_size() != nbytes:
+            raise ValueError("%s must be the contiguous %d-byte pack of this filter on its device" % (name, nbytes))
+    check(lib().cp360_train_adam_conv(ptr(p), ptr(g), ptr(m), ptr(v), c_out, c_in, *args, code, ptr(fwd_tap_major),
+                                      ptr(fwd_chan_major), ptr(dgrad_packed), ci0, n_dgrad, stream()))
+
+
 # ----------------------------------------------------------------------------- K5f: flow resize and flow loss
 def flow_resize_coeffs(in_size, out_size):
     """Host tables of one axis of cv2.resize(INTER_CUBIC) (cp360_flow_resize_coeffs_host, no GPU needed): first-tap index + 1

@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .._lib import PRECISIONS
 from ..model.clstm_train import trainer_of, window_maps
 
 
@@ -211,6 +212,79 @@ def train_step(cell, seq, flow, optimizer, cfg, tmp_loss_len=3, criterion=None):
     loss.backward()
     optimizer.step()
     return loss_sm.detach(), loss_temp.detach(), loss_mask.detach()
+
+
+class FusedAdam(torch.optim.Adam):
+    """``torch.optim.Adam`` over ``cell.parameters()`` whose step runs in libcp360.so (csrc/adam.hip): one pass over each
+    parameter, its gradient and its two moments that also writes the new weights into the packs the cell's training plan
+    holds (the forward convolutions' and the dgrad operands), so the next ``train_step`` repacks nothing.  Every other holder
+    of packed weights (``ConvLSTMCell.plans()``, the Winograd packs, a stage context) sees the parameters' version counters
+    move and repacks as after any optimizer step.
+
+    State and param groups are torch.optim.Adam's (``step``, ``exp_avg``, ``exp_avg_sq``), so ``state_dict()`` /
+    ``load_state_dict()`` interchange with it in both directions; ``zero_grad``, ``param_groups`` and LR schedulers are
+    inherited.  amsgrad, maximize, capturable, differentiable, a closure and sparse gradients are refused (ValueError); a
+    parameter whose ``.grad`` is None is skipped.  GPU only, f32 parameters."""
+
+    def __init__(self, cell, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False,
+                 capturable=False):
+        _refuse_adam_variants(dict(amsgrad=amsgrad, maximize=maximize, capturable=capturable))
+        super().__init__(cell.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.cell = cell
+
+    def _cell_packs(self):
+        """(trainer, {id(filter): pack arguments of ops.adam_step_conv}) when the cell's training plan is current, else
+        (None, {}): stale or absent packs are left to the lazy rule."""
+        cell = self.cell
+        tr = cell.__dict__.get('_trainer')
+        if tr is None or tr.cell is not cell or not tr.current():
+            return None, {}
+        plan = tr.plans()
+        dt = PRECISIONS[cell.precision]
+        packs = {}
+        for w, conv, dg in ((cell.Conv1.weight, plan['c1'], plan['d1']), (cell.Conv2.weight, plan['c2'], plan['d2']),
+                            (cell.Gates.weight, plan['g'], plan['dg'])):
+            packs[id(w)] = dict(dtype=dt, fwd_tap_major=conv._packed.get(0), fwd_chan_major=conv._packed.get(1),
+                                dgrad_packed=dg.packed, ci0=dg.ci0, n_dgrad=dg.n)
+        return tr, packs
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError("FusedAdam.step takes no closure")
+        tr, packs = self._cell_packs()
+        scalar = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32      # as torch.optim.Adam
+        for group in self.param_groups:
+            _refuse_adam_variants(group)
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise ValueError("FusedAdam does not take sparse gradients")
+                ops.require_gpu(p)
+                state = self.state[p]
+                if len(state) == 0:
+                    state['step'] = torch.tensor(0.0, dtype=scalar)
+                    state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state['step'] += 1
+                hyper = dict(lr=float(group['lr']), betas=group['betas'], eps=group['eps'],
+                             weight_decay=group['weight_decay'], step=int(state['step'].item()))
+                args = (p.detach(), p.grad.contiguous(), state['exp_avg'], state['exp_avg_sq'])
+                if p.dim() == 4 and tuple(p.shape[2:]) == (3, 3) and p.shape[1] % 4 == 0:
+                    ops.adam_step_conv(*args, **hyper, **packs.get(id(p), {}))
+                else:
+                    ops.adam_step(*args, **hyper)
+                torch.autograd.graph.increment_version(p)
+        if tr is not None:
+            tr.adopt()
+        return None
+
+
+def _refuse_adam_variants(group):
+    for key in ('amsgrad', 'maximize', 'capturable', 'differentiable'):
+        if group.get(key):
+            raise ValueError("FusedAdam is torch.optim.Adam with %s=False only" % key)
 
 
 def train(train_loader, model, criterion, optimizer, epoch, out_model_path, init_iter, cfg, tmp_loss_len=3):

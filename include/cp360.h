@@ -380,6 +380,24 @@ int cp360_wino_output_input(const cp360_wino_desc* d, const float* m, const floa
 int cp360_wino_forward(const cp360_wino_desc* d, const void* in, const void* packed, const float* bias, void* out, void* v,
                        float* m, void* stream);
 
+/* ------------------------------------------------------------------ K5o: fused Adam for ConvLSTM training
+ * torch.optim.Adam with amsgrad False and maximize False, one pass over p, g, m (exp_avg), v (exp_avg_sq), all f32, in place:
+ *   g' = g + weight_decay p;  m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / bias_corr1) m / (sqrt(v) / bias_corr2_sqrt + eps)
+ * f32 arithmetic with IEEE division and square root; the hyper-parameters and the bias corrections 1 - beta1^step and
+ * sqrt(1 - beta2^step) come from the host in double.  No atomics: a step is bit-reproducible.  Pointers 16-byte aligned.
+ * cp360_train_adam: any tensor of n elements.
+ * cp360_train_adam_conv: a filter OIHW [c_out, c_in, 3, 3] (c_in % 4 == 0); the same update, and in the same pass the new p
+ * rounded to dtype (CP360_F32 / CP360_BF16) is written into every pack pointer that is not NULL, in the layouts of
+ * cp360_conv_pack_weights without a scale (fwd_tap_major: clip_resident 0, fwd_chan_major: clip_resident 1) and of
+ * cp360_train_dgrad_pack, for input channels [ci0, ci0 + n_dgrad).  Padding rows and columns of the packs are not touched: the
+ * packs must have been made by those functions once.  With packs c_out % 4 == 0. */
+int cp360_train_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, double bias_corr1, double bias_corr2_sqrt, void* stream);
+int cp360_train_adam_conv(float* p, const float* g, float* m, float* v, int c_out, int c_in, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, double bias_corr1, double bias_corr2_sqrt, int dtype,
+                          void* fwd_tap_major, void* fwd_chan_major, void* dgrad_packed, int ci0, int n_dgrad, void* stream);
+
 /* ------------------------------------------------------------------ K5f: flow resize and flow loss
  * The part of a training iteration that grows with the flow's resolution (temporal_model/train_temporal.py:110-167), for
  * temporal_model/train_temporal.py.  f32 only (dtype CP360_F32); no atomics, fixed-order sums: results are bit-reproducible.

@@ -10,6 +10,7 @@ reads at the HBM rate, once per direction).  Flops and bytes of the other phases
 times: run this under `rocprofv3 --kernel-trace --stats` (a separate run: --configs bf16:4 --steps 1 --warmup 1).
 
     python tools/train_bench.py [--steps 5] [--warmup 2] [--configs fp32:1,fp32:4,bf16:1,bf16:4] [--flow 480x960 --flow-h 480]
+                                [--optimizer torch|fused]
 """
 import argparse
 import json
@@ -69,11 +70,11 @@ def time_loss(fn, maps, steps, warmup):
     return float(np.median(ts))
 
 
-def run(precision, B, steps, warmup, flow_hw, flow_h):
+def run(precision, B, steps, warmup, flow_hw, flow_h, optimizer='torch'):
     cell = ConvLSTMCell(HC, HC, precision=precision)
     cell.load_state_dict({k: torch.from_numpy(v) for k, v in synth.clstm_state(seed=2, input_size=HC, hidden_size=HC).items()})
     cell.cuda()
-    opt = torch.optim.Adam(cell.parameters(), lr=1e-6)
+    opt = (tt.FusedAdam(cell, lr=1e-6) if optimizer == 'fused' else torch.optim.Adam(cell.parameters(), lr=1e-6))
     cfg = types.SimpleNamespace(seq_len=T, flow_h=flow_h, l_s=0.7, l_t=1.0, l_m=0.01, mm_th=0.15)
     seq = torch.from_numpy(np.stack([synth.cam_clip(9000 + b, T) for b in range(B)])).cuda()       # [B, T, 6, C, 7, 7]
     # on the host, as a data loader gives it; 0.25 px (std) once scaled by flow_h / W, as the 28 x 56 rows had
@@ -121,7 +122,7 @@ def run(precision, B, steps, warmup, flow_hw, flow_h):
     med = lambda a: float(np.median(a))
     ms = med(total)
     wk = work(B, precision)
-    out = dict(precision=precision, B=B, ms_per_iter=round(ms, 2), iters_per_s=round(1000.0 / ms, 3),
+    out = dict(precision=precision, B=B, optimizer=optimizer, ms_per_iter=round(ms, 2), iters_per_s=round(1000.0 / ms, 3),
                phases_ms={k: round(med(v), 2) for k, v in phases.items()})
     for ph in ('forward', 'bptt', 'wgrad'):
         key = 'dgrad' if ph == 'bptt' else ph
@@ -130,7 +131,14 @@ def run(precision, B, steps, warmup, flow_hw, flow_h):
         out[ph + '_tflops'] = round(f / t / 1e12, 2)
         out[ph + '_tbps'] = round(b / t / 1e12, 2)
         out[ph + '_bound_fraction'] = round(max(f / PEAK[precision], b / HBM) / t, 3)
-    out['adam_tbps'] = round(wk['adam_bytes'] / (med(phases['adam']) * 1e-3) / 1e12, 2)
+    # the fused step also writes every pack the plan holds: the forward layouts that exist and the three dgrad operands
+    plan = tr.plans()
+    pack_bytes = sum(t.numel() * t.element_size() for c in ('c1', 'c2', 'g') for t in plan[c]._packed.values()) + \
+        sum(plan[k].packed.numel() * plan[k].packed.element_size() for k in ('d1', 'd2', 'dg'))
+    out['pack_bytes'] = int(pack_bytes)
+    adam_bytes = wk['adam_bytes'] + (pack_bytes if optimizer == 'fused' else 0)
+    out['adam_bytes'] = int(adam_bytes)
+    out['adam_tbps'] = round(adam_bytes / (med(phases['adam']) * 1e-3) / 1e12, 2)
     out['adam_share'] = round(med(phases['adam']) / ms, 3)
     # the loss alone, before (torch flow_losses) and after (HIP), on the same maps and resized flows
     with torch.no_grad():
@@ -150,12 +158,14 @@ def main():
     ap.add_argument('--configs', default='fp32:1,fp32:4,bf16:1,bf16:4')
     ap.add_argument('--flow', default='28x56', help='flow H x W as stored (the loader\'s resolution)')
     ap.add_argument('--flow-h', type=int, default=28, help='cfg.flow_h: the loss resolution is flow_h x 2 flow_h')
+    ap.add_argument('--optimizer', choices=('torch', 'fused'), default='torch',
+                    help='torch.optim.Adam, or train_temporal.FusedAdam (the step also writes the packs: no repack)')
     a = ap.parse_args()
     flow_hw = tuple(int(v) for v in a.flow.lower().split('x'))
     t0 = time.time()
-    res = [run(p, int(b), a.steps, a.warmup, flow_hw, a.flow_h) for p, b in (c.split(':') for c in a.configs.split(','))]
+    res = [run(p, int(b), a.steps, a.warmup, flow_hw, a.flow_h, a.optimizer) for p, b in (c.split(':') for c in a.configs.split(','))]
     print(json.dumps(dict(metric='clstm_train', hidden=HC, face=W, seq_len=T, flow=list(flow_hw), flow_h=a.flow_h,
-                          steps=a.steps, warmup=a.warmup,
+                          steps=a.steps, warmup=a.warmup, optimizer=a.optimizer,
                           device=torch.cuda.get_device_name(0), wall_s=round(time.time() - t0, 1), results=res)))
 
 
