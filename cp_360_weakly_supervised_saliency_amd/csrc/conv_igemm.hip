@@ -234,31 +234,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = wave / WM, wm = wave % WM;
-    // ---- XCD-aware work mapping.  Workgroups are dealt round-robin over the 8 XCDs
-    // (each with a private 4 MiB L2): give every XCD a CONTIGUOUS range of work items
-    // and order the items so that neighbours share an operand panel.  m_fast: the
-    // m-tiles of one (n-tile, split) are adjacent -> the weight panel is fetched from
-    // HBM once per XCD and re-read from L2 (ConvLSTM: weights >> activations);
-    // otherwise n-tiles are adjacent -> the activation panel is shared (ResNet).
-    // Placement only affects speed, never results (bijective map, any placement valid).
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * BN;
-        m0 = mt_i * BM;
-    }
+    conv_tile_of(p, BN, BM, &n0, &m0, &split);
     const int chunk = tid & 7, row0 = tid >> 3;
 
     // ---- per-thread activation rows.  Only the current element offset of each row is
@@ -459,23 +436,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave >> 1, wm = wave & 1;
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * BN;
-        m0 = mt_i * BM;
-    }
+    conv_tile_of(p, BN, BM, &n0, &m0, &split);
     // DMA role of this lane: tile row (within a 64-row pass) and the logical chunk it fetches
     const int drow = 8 * wave + (lane >> 3);
     const int dchunk = (lane & 7) ^ ((4 * wave + (lane >> 4)) & 7);      // = (l&7) ^ ((row>>1)&7)
@@ -784,19 +745,12 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
         for (int k = 1; k < NS - 1; ++k)
             if (nloc > k) { advance(); issue(k); }
         int stage = 0;
-        // A sub-step is two PHASES separated by a second barrier, and the two waves that share a
-        // SIMD (w and w+4) run half a sub-step apart (MI355X_MICROARCH.md, "Two waves per SIMD",
-        // item 9).  HEAD = fragment reads of the sub-step's stage (a[4] + the first JH pixel
+        // The two halves of a sub-step (CP360_STAGGER_STEP of conv_common.h runs them half a sub-step apart on the two
+        // waves of a SIMD).  HEAD = fragment reads of the sub-step's stage (a[4] + the first JH pixel
         // blocks), the refill DMA and the first JH*4 MFMAs, column by column: as soon as the four
         // MFMAs of column j are issued its registers are re-loaded with pixel block JH + j, so the
         // second half's operands arrive under the first half's MFMAs; TAIL = the remaining MFMAs,
-        // all operands in registers.
-        //   waves 0-3 (LAG = false):  B1  HEAD(s)    B2  TAIL(s)
-        //   waves 4-7 (LAG = true ):  B1  TAIL(s-1)  B2  HEAD(s)
-        // so while one wave of a SIMD waits for its LDS reads the other feeds the matrix pipe from
-        // registers.  Stage s is read between B1(s) and B1(s+1) by both groups and refilled (with
-        // sub-step s+4) after B1(s+1), exactly as without the stagger; a lagging wave drains its
-        // LDS reads (lgkmcnt) before B1 because the tail operands it read last are first used after it.
+        // all operands in registers.  Stage s is refilled with sub-step s+4.
         // ALLUP (the 8-wave big-tile variants): the load half issues every fragment read and the refill DMA and no
         // MFMA, the compute half all of them from registers (as the clip kernel; -8 % there); the short-K two-workgroup
         // variant (128-VGPR budget) keeps the JH / MJ - JH split with register reuse
@@ -843,29 +797,17 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
             _Pragma("unroll") for (int j = ALLUP ? 0 : JH; j < MJ; ++j)                                    \
                 _Pragma("unroll") for (int i = 0; i < 4; ++i) mma_chunk<T>(acc[i][j], a[i], b[ALLUP ? j : j - JH]); \
         }
-#define CP360_RING_STEP(REFILL)                                                                            \
-        {                                                                                                  \
-            if (LAG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                    \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (!LAG) CP360_RING_HEAD(REFILL) else CP360_RING_TAIL()                                       \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (!LAG) CP360_RING_TAIL() else CP360_RING_HEAD(REFILL)                                       \
-        }
         int it = 0;
         for (; it + NS - 1 < nloc; ++it) {          // steady state: NS-2 younger DMA groups in flight
             if (xw) wait_vmcnt<(NS - 2) * D1>(); else wait_vmcnt<(NS - 2) * D0>();
-            CP360_RING_STEP(true)
+            CP360_STAGGER_STEP(LAG, CP360_RING_HEAD(true), CP360_RING_TAIL())
         }
         for (; it < nloc; ++it) {                   // drain: no refill
             const int young = min(NS - 2, nloc - 1 - it);
             wait_vmcnt_upto<(NS - 2) * D1>(young * (xw ? D1 : D0));
-            CP360_RING_STEP(false)
+            CP360_STAGGER_STEP(LAG, CP360_RING_HEAD(false), CP360_RING_TAIL())
         }
         if (LAG) CP360_RING_TAIL()
-#undef CP360_RING_STEP
 #undef CP360_RING_HEAD
 #undef CP360_RING_TAIL
     }
@@ -919,23 +861,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_ring_kernel(const ConvK p) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * G::BN;
-        m0 = mt_i * BM;
-    }
+    conv_tile_of(p, G::BN, BM, &n0, &m0, &split);
     if constexpr (BM == 256) {
         if (wave < 4) ring_body<T, 256, 8, 4, false>(p, lds, n0, m0, split, wave, lane, tid, (wave >> 1) * 64, (wave & 1) * 128);
         else          ring_body<T, 256, 8, 4, true>(p, lds, n0, m0, split, wave, lane, tid, (wave >> 1) * 64, (wave & 1) * 128);
@@ -966,23 +892,7 @@ __global__ __launch_bounds__(512, 4) void conv_igemm_ring2_kernel(const ConvK p)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * G::BN;
-        m0 = mt_i * 128;
-    }
+    conv_tile_of(p, G::BN, 128, &n0, &m0, &split);
     if (wave < 4) ring_body<T, 128, 4, 2, false, 2>(p, lds, n0, m0, split, wave, lane, tid, (wave >> 1) * 64, (wave & 1) * 64);
     else          ring_body<T, 128, 4, 2, true, 2>(p, lds, n0, m0, split, wave, lane, tid, (wave >> 1) * 64, (wave & 1) * 64);
 }
@@ -1008,7 +918,7 @@ __global__ __launch_bounds__(512, 4) void conv_igemm_ring2_kernel(const ConvK p)
 // with this function every 16-lane ds_read_b128 group still covers 16 distinct 16-byte slots of the
 // bank row for any start (the ring's (-(r >> 2)) & 3 is conflict-free only for starts that are
 // multiples of 16: 9.6e7 conflict cycles per launch measured with it, profiles/).
-// Tile / wave layout and the half-sub-step stagger are those of the 256x304 ring kernel.
+// Tile / wave layout are those of the 256x304 ring kernel; both run the half-sub-step stagger of conv_common.h.
 __device__ __forceinline__ int clip_swz(int row) { return ((row >> 2) & 1) << 1; }
 
 // FACE variant (16x16 faces, the ConvLSTM at cube size 512 - BASELINE config C5): a tile is ONE face (256
@@ -1188,7 +1098,7 @@ __device__ __forceinline__ void clip_body(const ConvK& p, unsigned char* lds, co
 #pragma unroll
             for (int j = 0; j < MJ; ++j) b[j] = u32x4{0u, 0u, 0u, 0u};
         }
-        // HEAD / TAIL / stagger: see ring_body.  New here: B fragments come from the resident
+        // HEAD / TAIL of CP360_STAGGER_STEP (conv_common.h).  B fragments come from the resident
         // activation tile through the entries; at tap 0 the tile of the NEXT channel block is
         // requested (into the other buffer, whose block ended before this sub-step's first barrier).
 #define CP360_CLIP_HEAD(REFILL)                                                                            \
@@ -1221,17 +1131,6 @@ __device__ __forceinline__ void clip_body(const ConvK& p, unsigned char* lds, co
                 _Pragma("unroll") for (int i = 0; i < 4; ++i) mma_chunk<T>(acc[i][j], a[i], b[j]);         \
             decode();                                                                                      \
         }
-#define CP360_CLIP_STEP(REFILL)                                                                            \
-        {                                                                                                  \
-            if (LAG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                    \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (!LAG) CP360_CLIP_HEAD(REFILL) else CP360_CLIP_TAIL()                                       \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (!LAG) CP360_CLIP_TAIL() else CP360_CLIP_HEAD(REFILL)                                       \
-        }
         // vmcnt: DMAs complete in issue order.  Before sub-step `it` its weight stage (issued NW-1
         // heads earlier) must have landed; younger than it are the weight stages of the next NW-2
         // sub-steps (2 DMAs each) and an activation tile (2 or 3 DMAs, issued in front of its head's
@@ -1245,7 +1144,7 @@ __device__ __forceinline__ void clip_body(const ConvK& p, unsigned char* lds, co
             // exact count would be YW + 2 or + 3; the tile was requested up to NW-2 sub-steps ago and has long landed,
             // and the branch-free loop top measured 1.5-3 % faster.)
             wait_vmcnt<YW>();
-            CP360_CLIP_STEP(true)
+            CP360_STAGGER_STEP(LAG, CP360_CLIP_HEAD(true), CP360_CLIP_TAIL())
         }
         for (; it < nloc; ++it) {                   // drain: no weight refill
             const bool act_young = tap >= 1 && tap <= G::NW - 2 && it >= tap;
@@ -1254,10 +1153,9 @@ __device__ __forceinline__ void clip_body(const ConvK& p, unsigned char* lds, co
             // than the count assumes: wait for everything then (at most NW-2 sub-steps, once)
             if (act_young && young < YW) wait_vmcnt<0>();
             else wait_vmcnt_upto<YW + 3>(young + (act_young ? na : 0));
-            CP360_CLIP_STEP(false)
+            CP360_STAGGER_STEP(LAG, CP360_CLIP_HEAD(false), CP360_CLIP_TAIL())
         }
         if (LAG) CP360_CLIP_TAIL()
-#undef CP360_CLIP_STEP
 #undef CP360_CLIP_HEAD
 #undef CP360_CLIP_TAIL
     }
@@ -1375,13 +1273,7 @@ __global__ __launch_bounds__(512, 2) void conv_clip_kernel(const ConvK p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int n0, clip, split;
-    {   // XCD-aware mapping, clips fastest: the workgroups of one (channel tile, split) share the weight stream
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        clip = w % p.mt;
-        const int rest = w / p.mt;
-        n0 = (rest % p.nt) * G::BN;
-        split = rest / p.nt;
-    }
+    conv_tile_of<true>(p, G::BN, 1, &n0, &clip, &split);   // clips fastest, always; a pixel tile is a clip (clip_body's m0)
     constexpr int JHC = CLIP_JH;                       // MFMA columns issued in the load half of a sub-step (see clip_body)
     if constexpr (MODE == 1) {
         if (wave < 4) clip_body<T, 8, JHC, false, 1>(p, lds, n0, clip, split, wave, lane, tid, wave * 64, 0);

@@ -51,26 +51,8 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wave >> 2;                        // 0: leads (loads, then MFMAs); 1: trails by one step (MFMAs, then loads)
     const int wn = (wave >> 1) & 1, wm = wave & 1;
-    // XCD-aware work mapping (as conv_igemm_kernel): every XCD takes a contiguous range of work items, ordered so that
-    // neighbours share the larger operand panel through that XCD's L2.  Placement affects speed only.
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * BN;
-        m0 = mt_i * BM;
-    }
+    conv_tile_of(p, BN, BM, &n0, &m0, &split);
     const int chunk = tid & 7, row0 = tid >> 3;        // this thread's 16-byte chunk of weight row row0 AND of pixel row row0
 
     // ---- source-offset table: element offset of tile row r's input pixel for tap t, offtab[t * 64 + r] (-1: no such output
@@ -343,23 +325,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave >> 1, wm = wave & 1;
     int n0, m0, split;
-    {
-        const int w = xcd_work_index(p.nt * p.mt * p.splits, p.reverse);
-        int nt_i, mt_i;
-        if (p.m_fast) {
-            mt_i = w % p.mt;
-            const int rest = w / p.mt;
-            nt_i = rest % p.nt;
-            split = rest / p.nt;
-        } else {
-            nt_i = w % p.nt;
-            const int rest = w / p.nt;
-            mt_i = rest % p.mt;
-            split = rest / p.mt;
-        }
-        n0 = nt_i * BN;
-        m0 = mt_i * BM;
-    }
+    conv_tile_of(p, BN, BM, &n0, &m0, &split);
     const int chunk = tid & 7, row0 = tid >> 3;        // this thread's chunk of weight rows row0, row0 + 32 and pixel rows row0, row0 + 32
 
     __shared__ int offtab[MAX_TAPS * BM];              // see conv_small_kernel

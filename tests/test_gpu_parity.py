@@ -888,6 +888,69 @@ def test_clip_resident_conv(n, prec, splits):
     assert rel_err(got, gen) <= _TOL[prec]
 
 
+# kernel family -> (filter size, how a caller reaches it)
+_SCALAR_EPI_FAMILIES = {
+    'T128': (1, {'tile_px': 64}), 'DMA': (1, {'tile_px': 128}), 'RING256': (1, {'tile_px': 256}),
+    'RING304': (1, {'tile_px': 304}), 'RING2': (1, {'tile_px': 129}), 'CLIP_CUBE': (3, {'clip_resident': True}),
+    'SMALL': (1, {'tile_px': 6464}),
+}
+_SCALAR_EPI_REF = {}
+
+
+def _scalar_epi_operands(prec, k):
+    """One cube of 7x7 faces, 64 -> 256 channels: the operands and the float64 CPU references (on the operands rounded to
+    prec) of a k x k convolution (k = 3: behind CubePad(1)) - the raw sums, and bias + residual + ReLU.  Computed once."""
+    if (prec, k) not in _SCALAR_EPI_REF:
+        dt = _TDT[prec]
+        n_img, cin, cout, n = 6, 64, 256, 7
+        x = hashrng.normal(9600 + k, (n_img, cin, n, n))
+        w = hashrng.normal(9601 + k, (cout, cin, k, k), 0, (2.0 / (k * k * cin)) ** 0.5)
+        bias = hashrng.normal(9603, (cout,), 0, 0.1)
+        res = hashrng.normal(9604, (n_img, cout, n, n))
+        r64 = lambda a: torch.from_numpy(a).to(dt).double()
+        xp = o_resnet.cubepad_t(r64(x), 1) if k == 3 else r64(x)
+        raw = Fn.conv2d(xp, r64(w))
+        full = Fn.relu(raw + torch.from_numpy(bias).double()[None, :, None, None] + r64(res))
+        _SCALAR_EPI_REF[(prec, k)] = (x, w, bias, res, raw.numpy(), full.numpy())
+    return _SCALAR_EPI_REF[(prec, k)]
+
+
+# (the two-workgroup short-K kernel exists for the 16-bit types only: test_short_k_two_workgroup_kernel checks the refusal)
+@pytest.mark.parametrize('family,prec', [(f, p) for f in _SCALAR_EPI_FAMILIES for p in ('fp32', 'bf16') if (f, p) != ('RING2', 'fp32')])
+def test_conv_element_wise_epilogue_of_every_kernel_family(family, prec):
+    """The element-wise epilogue that ends every MFMA body of csrc/conv_igemm.hip (and the slab stores of conv_small.hip),
+    on each kernel family that has one.  One cube of 7x7 faces (M = 294: one ragged 304-pixel tile, two of 256, three of 128, five
+    of 64), 64 -> 256 channels.  (a) bias + residual + ReLU written at out_coff = 4 into a tensor with ld_out = c_out + 8: in
+    bf16 that is misaligned for the 16-byte vector epilogues, so the stores are the element-wise branch's 8-byte ones (fp32:
+    16-byte aligned, the vector path); the columns around the output keep their fill.  The small-tile kernel
+    (conv_small.hip) has 16-byte stores only and the descriptor check refuses out_coff = 4 for its 16-bit form: it runs at
+    out_coff = 8, the nearest offset it accepts.  (b) the raw f32 sums of two K splits, the slabs in true channel order and in
+    the packed-row order (slab_rows)."""
+    k, how = _SCALAR_EPI_FAMILIES[family]
+    dt = _TDT[prec]
+    x, w, bias, res, want_raw, want = _scalar_epi_operands(prec, k)
+    n_img, cout, n = x.shape[0], w.shape[0], x.shape[2]
+    conv = ops.Conv(torch.from_numpy(w), None, torch.from_numpy(bias), 1, k // 2, True, dt, DEV)
+    xt = ops.nchw_to_nhwc(torch.from_numpy(x).to(DEV), out_dtype=dt)
+    rt = ops.nchw_to_nhwc(torch.from_numpy(res).to(DEV), out_dtype=dt)
+    coff = 8 if family == 'SMALL' and prec != 'fp32' else 4
+    out = torch.full((n_img, n, n, cout + 8), -7.0, dtype=dt, device=DEV)
+    assert conv(xt, residual=rt, out=out, out_coff=coff, splits=1, **how) is out
+    o = out.float().cpu()
+    got = o[..., coff:coff + cout].permute(0, 3, 1, 2).numpy()
+    assert rel_err(got, want) <= _TOL[prec], rel_err(got, want)
+    assert bool((o[..., :coff] == -7.0).all()) and bool((o[..., coff + cout:] == -7.0).all())
+    c = np.arange(cout)
+    for slab_rows in (False, True):
+        part, ns = conv(xt, raw_f32=True, splits=2, slab_rows=slab_rows, **how)
+        assert ns == 2
+        sums = part[:2 * n_img * n * n * cout].view(2, n_img, n, n, cout).sum(0).cpu().numpy()
+        if slab_rows:       # column of channel c inside its 32-channel group: the packed-row order (slab_col, csrc/tile.h)
+            sums = sums[..., (c & ~31) + ((c >> 3) & 3) * 4 + ((c >> 2) & 1) * 16 + (c & 3)]
+        tol = 2e-5 if prec == 'fp32' else 1e-4                     # no output rounding: only the summation order differs
+        assert rel_err(sums.transpose(0, 3, 1, 2), want_raw) <= tol, (slab_rows, rel_err(sums.transpose(0, 3, 1, 2), want_raw))
+
+
 @pytest.mark.parametrize('prec', ['fp32', 'bf16', 'fp16'])
 def test_stem_conv_and_maxpool(prec):
     dt = _TDT[prec]
