@@ -15,8 +15,9 @@
 // Wave w computes output row w of the band: 56 pixels as 4 MFMA pixel blocks (8 of the 64 columns are
 // padding) x 64 channels.  Two workgroups (256 threads, 68 KiB LDS) share a CU, so one band's gather /
 // epilogue overlaps the other's MFMAs.  Epilogue: bias + ReLU, one rounding, 16-byte pieces (acc_chan).
-// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
-#include "tile.h"
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h;
+// the band gather, the epilogue piece and the host-side dispatch / checks shared with the other fused kernels: band.h.
+#include "band.h"
 
 namespace {
 constexpr int N = 56, NP = N + 2, C = 64, BAND = 4;
@@ -34,10 +35,9 @@ __global__ __launch_bounds__(256) void band3x3_pack_kernel(const float* __restri
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= 9 * 64 * 64) return;
     const int c = idx & 63, r = (idx >> 6) & 63, tap = idx >> 12;
-    const int n = (r & ~31) + ((r >> 2) & 3) * 8 + ((r >> 4) & 1) * 4 + (r & 3);
+    const int n = (r & ~31) + ((r >> 2) & 3) * 8 + ((r >> 4) & 1) * 4 + (r & 3);      // = row_chan(r)
     const float v = w[(n * 64 + c) * 9 + tap] * (scale ? scale[n] : 1.f);
-    if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-    else packed[idx] = f32_to_bf16(v);
+    store_folded(packed, idx, v);
 }
 
 template <typename T>
@@ -52,20 +52,7 @@ __global__ __launch_bounds__(256, 2) void band3x3_kernel(const T* __restrict__ x
     const CubePadGeom geom{N, 1, 1, 1, 1};
 
     // ---- gather the band's padded pixels: instruction i = patch pixels 8i .. 8i+7, 128 B each
-    {
-        const T* xg = x + (size_t)grp * 6 * N * N * C;
-#pragma unroll 1
-        for (int inst = wave; inst < PATCH_INST; inst += 4) {
-            const int q = inst * 8 + (lane >> 3);
-            const void* src = g_zero16;
-            if (q < PATCH_PX) {
-                const int pr = q / NP, pc = q - pr * NP;
-                const int sp = cubepad_src(f, BAND * band + pr, pc, geom);       // pixel index inside the cube
-                src = xg + (size_t)sp * C + (((lane & 7) ^ px_swz(q)) << 3);
-            }
-            glds16(src, __builtin_amdgcn_readfirstlane(lds_base + inst * 1024));
-        }
-    }
+    CP360_GATHER_BAND_PATCH(x + (size_t)grp * 6 * N * N * C, C, f, BAND * band, NP, geom, PATCH_PX, PATCH_INST, 8, px_swz(q_), lds_base, wave, lane)
     // weight slice of tap t -> ring slot s: 8 instructions of 8 rows x 128 B, two per wave
     const unsigned char* wb = reinterpret_cast<const unsigned char*>(wpk);
     auto load_w = [&](int t, int s) __attribute__((always_inline)) {
@@ -126,11 +113,7 @@ __global__ __launch_bounds__(256, 2) void band3x3_kernel(const T* __restrict__ x
         for (int j = 0; j < 4; ++j) {
             const int xo = j * 16 + lrow;
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = acc[2 * pr][j][e] + bb[e];
-                v[4 + e] = acc[2 * pr + 1][j][e] + bb[4 + e];
-            }
+            CP360_BIAS_ACT8(v, acc[2 * pr][j], acc[2 * pr + 1][j], bb[e_], bb[4 + e_], CP360_NOACT)
             if (relu) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
@@ -146,34 +129,19 @@ extern "C" size_t cp360_band3x3_packed_bytes(int dtype) {
 
 extern "C" int cp360_band3x3_pack_weights(int dtype, const float* w_oihw, const float* scale, void* packed, void* stream) {
     if (!w_oihw || !packed) return CP360_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((band3x3_pack_kernel<bf16_raw>), dim3(144), dim3(256), 0, st, w_oihw, scale, (bf16_raw*)packed);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((band3x3_pack_kernel<f16_raw>), dim3(144), dim3(256), 0, st, w_oihw, scale, (f16_raw*)packed);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((band3x3_pack_kernel<T>), dim3(144), dim3(256), 0, (hipStream_t)stream, w_oihw, scale, (T*)packed);
+    });
 }
 
 extern "C" int cp360_band3x3_forward(int dtype, const void* x, const void* packed, const float* bias, void* out,
                                      int n_img, int face, int channels, int relu, void* stream) {
     if (!x || !packed || !out) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (face != N || channels != C) return CP360_ERR_UNSUPPORTED;      // other shapes: the generic implicit GEMM
-    if ((long long)n_img * N * N * C >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)(n_img * (N / BAND)));
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((band3x3_kernel<bf16_raw>), grid, dim3(256), 0, st, (const bf16_raw*)x, (const bf16_raw*)packed, bias,
-                           (bf16_raw*)out, relu);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((band3x3_kernel<f16_raw>), grid, dim3(256), 0, st, (const f16_raw*)x, (const f16_raw*)packed, bias,
-                           (f16_raw*)out, relu);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    if (const int bad = check_faces(n_img, face == N && channels == C, N, C)) return bad;      // other shapes: the generic implicit GEMM
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((band3x3_kernel<T>), dim3((unsigned)(n_img * (N / BAND))), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                           (const T*)packed, bias, (T*)out, relu);
+    });
 }

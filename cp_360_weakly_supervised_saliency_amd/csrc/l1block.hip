@@ -7,7 +7,7 @@
 // Run as separate launches these are HBM-bound (layer1 = 1.9 of the static stage's 7 ms) and every
 // tensor between them makes a round trip through HBM: t (154 MB for 64 frames) twice, out (616 MB) written by conv3
 // and read again by the next conv1.  Here a workgroup owns a band of 4 output rows of one face, as band3x3.hip:
-//   stage 1  conv2 as band3x3_kernel (resident cube-padded band in LDS, nine taps read it there), its weights as MFMA
+//   stage 1  conv2 on the resident cube-padded band in LDS (band.h's gather; nine taps read it there), its weights as MFMA
 //            A fragments straight from L2 into registers two taps ahead (no LDS ring, no barrier in the stage);
 //   stage 2  the conv2 accumulators ARE the next MFMA's B operand: with the acc_chan row order of the packed
 //            weights a lane ends with EIGHT consecutive channels of one pixel per pair of MFMA row blocks - the
@@ -27,8 +27,10 @@
 // fit next to the tail's registers for 64 pixels per wave, so stage 3 runs twice over HALF of the wave's pixel blocks
 // (2 x 8 passes; conv3's fragments - 4 KiB per pass - then come from L2 one pass ahead instead of from LDS, which holds
 // the 64 KiB of next-conv1 fragments).
-// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
-#include "tile.h"
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h;
+// the band gather, the epilogue piece, the A-fragment fetch, the phase stamp and the host-side dispatch / checks shared with the other
+// fused kernels: band.h.  Stages 1 and 2 are written once below (CP360_L1_*) for l1block_kernel and l1block_wide_kernel.
+#include "band.h"
 
 namespace {
 constexpr int C = 64, CO = 256;
@@ -65,8 +67,7 @@ __global__ __launch_bounds__(256) void l1_pack_conv2_kernel(const float* __restr
     const int n = row_chan(rb * 16 + (lane & 15));
     const int c = kk * 32 + (lane >> 4) * 8 + e;
     const float v = w[((size_t)n * C + c) * 9 + tap] * (scale ? scale[n] : 1.f);
-    if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-    else packed[idx] = f32_to_bf16(v);
+    store_folded(packed, idx, v);
 }
 
 // 1x1 filter w [n_out, k] (times scale[n_out]) -> MFMA A fragments, 1 KiB each ([lane][8 elements]: lane l holds
@@ -90,8 +91,7 @@ __global__ __launch_bounds__(256) void frag_pack_kernel(const float* __restrict_
         //  compiler the multiply and the f16 conversion become one mixed-precision instruction with a single rounding, and 2 of layer1.0's
         //  4096 conv1 weights land on the other side of a tie: the in-patch conv1 must use the bits the separate launch uses)
         const float v = scale ? __fmul_rn(w[(size_t)n * k + kk], scale[n]) : w[(size_t)n * k + kk];
-        if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-        else packed[idx] = f32_to_bf16(v);
+        store_folded(packed, idx, v);
     }
 }
 
@@ -100,13 +100,69 @@ __global__ __launch_bounds__(256) void frag_pack_kernel(const float* __restrict_
 // build executes no stamp.
 #ifdef L1_STAMPS
 __device__ unsigned long long g_l1_stamps[8192 * 16];
-#define L1_STAMP(k)                                                                                         \
-    { __builtin_amdgcn_sched_barrier(0);                                                                    \
-      if (wave == 0 && lane == 0 && blockIdx.x < 8192) g_l1_stamps[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-      __builtin_amdgcn_sched_barrier(0); }
+#define L1_STAMP(k) CP360_PHASE_STAMP(g_l1_stamps, k)
 #else
 #define L1_STAMP(k)
 #endif
+
+// ---- stages 1 and 2, once for l1block_kernel and l1block_wide_kernel.  The four pieces are statements of the kernel body, in this
+// order; each reads the kernel's own names and declares names the later pieces and the kernel's stage 3 use:
+//   needed throughout:  the element type T; the constants N, NP, PATCH_PX, PATCH_INST, BAND (L1Geom), C and W2_TAP; lane, lchunk
+// the gather of the band's patch, and conv2's A fragments (8 per tap) from L2 straight into registers: load_a(tap, a)
+//   needs:    x, wpk2 (kernel arguments); grp, f, band, geom; lds_base; wave
+//   defines:  wb (the packed conv2 filter as bytes), load_a, DEPTH
+#define CP360_L1_STAGE1_HEAD()                                                                                      \
+    CP360_GATHER_BAND_PATCH(x + (size_t)grp * 6 * N * N * C, C, f, BAND * band, NP, geom, PATCH_PX, PATCH_INST, 8, px_swz(q_), lds_base, \
+                            wave, lane)                                                                           \
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(wpk2);                                       \
+    auto load_a = [&](int t, u32x4 (&a)[4][2]) __attribute__((always_inline)) {                                   \
+        CP360_LOAD_FRAGS(a, 4, 2, wb + (size_t)t * W2_TAP, fr_ * 2 + fk_)                                         \
+    };                                                                                                            \
+    constexpr int DEPTH = 2;
+// the first DEPTH taps' fragments requested, the accumulators cleared, the patch landed for every wave
+//   needs:    load_a, DEPTH (CP360_L1_STAGE1_HEAD)
+//   defines:  aq (the fragment queue, DEPTH + 1 taps), acc (f32x4 [4 row blocks][4 pixel blocks]); ends in a barrier
+#define CP360_L1_STAGE1_START()                                                                                     \
+    u32x4 aq[DEPTH + 1][4][2];                                                                                    \
+    _Pragma("unroll") for (int t = 0; t < DEPTH; ++t) load_a(t, aq[t]);                                           \
+    f32x4 acc[4][4];                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};                      \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          /* the patch DMAs (and the first fragments) */      \
+    __syncthreads();
+// the nine taps on the resident patch, A fragments DEPTH taps ahead: no weight ring in LDS and no barrier inside the stage
+//   needs:    load_a, DEPTH, aq, acc; lds (the patch); wrow, x0 (this wave's output row and first column); lrow
+//   defines:  nothing (acc holds conv2's sums afterwards)
+#define CP360_L1_CONV2_TAPS()                                                                                       \
+    _Pragma("unroll") for (int tap = 0; tap < 9; ++tap) {                                                         \
+        if (tap + DEPTH < 9) load_a(tap + DEPTH, aq[(tap + DEPTH) % (DEPTH + 1)]);                                \
+        const int ky = tap / 3, kx = tap - ky * 3;                                                                \
+        const int pbase = (wrow + ky) * NP + kx + x0 + lrow;                                                      \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                        \
+            u32x4 b[4];                                                                                           \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                const int p = pbase + 16 * j;                                                                     \
+                b[j] = *reinterpret_cast<const u32x4*>(lds + p * 128 + (((kk * 4 + lchunk) ^ px_swz(p)) << 4));   \
+            }                                                                                                     \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]); \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+        }                                                                                                         \
+    }
+// stage 2: t = relu(conv2 + b2), rounded once, as B fragments bt[k-block][pixel block]
+//   needs:    acc; bias2 (kernel argument, may be null); bt (u32x4 [2][4], declared by the kernel)
+//   defines:  nothing (fills bt; acc is dead afterwards)
+#define CP360_L1_T_FRAGS()                                                                                          \
+    _Pragma("unroll") for (int pr = 0; pr < 2; ++pr) {                                                            \
+        const int n = pr * 32 + lchunk * 8;                                                                       \
+        float bb[8];                                                                                              \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) bb[e] = bias2 ? bias2[n + e] : 0.f;                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
+            float v[8];                                                                                           \
+            CP360_BIAS_ACT8(v, acc[2 * pr][j], acc[2 * pr + 1][j], bb[e_], bb[4 + e_], CP360_RELU)              \
+            bt[pr][j] = pack8(v, T());                                                                            \
+        }                                                                                                         \
+    }
 
 // FIRST (round 6; layer1.0, with DS): `x` is the BLOCK INPUT (the pooled stem output, 64 channels) instead of conv1's output - the block's own
 // conv1 (1x1, 64 -> 64, + bn1 + relu, model/resnet_cubic.py:88-90) runs on the resident patch IN PLACE between the gather and conv2 (22 pixel
@@ -136,51 +192,14 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
     const size_t row_px = ((size_t)img * N + band * BAND + wrow) * N + x0;    // its first pixel
     L1_STAMP(0)
 
-    // ---- stage 1: conv2 on the resident cube-padded band (band3x3.hip), A fragments from L2 straight into
-    // registers two taps ahead: no weight ring in LDS and no barrier inside the stage (l2block.hip)
-    {
-        const T* xg = x + (size_t)grp * 6 * N * N * C;
-#pragma unroll 1
-        for (int inst = wave; inst < PATCH_INST; inst += 4) {
-            const int q = inst * 8 + (lane >> 3);
-            const void* src = g_zero16;
-            if (q < PATCH_PX) {
-                const int pr = q / NP, pc = q - pr * NP;
-                const int sp = cubepad_src(f, BAND * band + pr, pc, geom);
-                src = xg + (size_t)sp * C + (((lane & 7) ^ px_swz(q)) << 3);
-            }
-            glds16(src, __builtin_amdgcn_readfirstlane(lds_base + inst * 1024));
-        }
-    }
-    const unsigned char* wb = reinterpret_cast<const unsigned char*>(wpk2);
-    auto load_a = [&](int t, u32x4 (&a)[4][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-                a[i][kk] = *reinterpret_cast<const u32x4*>(wb + (size_t)t * W2_TAP + ((i * 2 + kk) * 64 + lane) * 16);
-    };
-    constexpr int DEPTH = 2;
-    u32x4 aq[DEPTH + 1][4][2];
-#pragma unroll
-    for (int t = 0; t < DEPTH; ++t) load_a(t, aq[t]);
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the patch DMAs (and the first fragments)
-    __syncthreads();
+    // ---- stage 1: conv2 on the resident cube-padded band, A fragments from L2 straight into registers two taps ahead
+    CP360_L1_STAGE1_HEAD()
+    CP360_L1_STAGE1_START()
     if constexpr (FIRST) {
         // conv1 on the patch, in place: pixel block b = patch pixels 16 b .. 16 b + 15 (wave w takes b = w, w + 4, ...); a lane reads the two
         // k-block pieces of its pixel and writes the two 8-channel pieces it ends up holding into the same two slots of that pixel
         u32x4 a0[4][2];
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                a0[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(w0f) + ((rb * 2 + kb) * 64 + lane) * 16);
+        CP360_LOAD_FRAGS(a0, 4, 2, reinterpret_cast<const unsigned char*>(w0f), fr_ * 2 + fk_)
         float b0[2][8];
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr)
@@ -204,11 +223,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(c[2 * pr][e] + b0[pr][e], 0.f);
-                    v[4 + e] = fmaxf(c[2 * pr + 1][e] + b0[pr][4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, c[2 * pr], c[2 * pr + 1], b0[pr][e_], b0[pr][4 + e_], CP360_RELU)
                 *reinterpret_cast<u32x4*>(px + (((pr * 4 + lchunk) ^ px_swz(q)) << 4)) = pack8(v, T());
             }
         }
@@ -216,26 +231,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
     }
     L1_STAMP(1)
 
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        if (tap + DEPTH < 9) load_a(tap + DEPTH, aq[(tap + DEPTH) % (DEPTH + 1)]);
-        const int ky = tap / 3, kx = tap - ky * 3;
-        const int pbase = (wrow + ky) * NP + kx + x0 + lrow;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            u32x4 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int p = pbase + 16 * j;
-                b[j] = *reinterpret_cast<const u32x4*>(lds + p * 128 + (((kk * 4 + lchunk) ^ px_swz(p)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    CP360_L1_CONV2_TAPS()
     L1_STAMP(2)
     // every wave is done with the patch: bring conv3's (and the next conv1's) fragments in
     __syncthreads();
@@ -257,23 +253,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
     }
     // ---- stage 2: t = relu(conv2 + b2), rounded once, as B fragments bt[k-block][pixel block]
     u32x4 bt[2][4];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-        const int n = pr * 32 + lchunk * 8;
-        float bb[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bb[e] = bias2 ? bias2[n + e] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = fmaxf(acc[2 * pr][j][e] + bb[e], 0.f);
-                v[4 + e] = fmaxf(acc[2 * pr + 1][j][e] + bb[4 + e], 0.f);
-            }
-            bt[pr][j] = pack8(v, T());
-        }
-    }
+    CP360_L1_T_FRAGS()
     // downsample source: x's fragments of this wave's pixels (k-block kb = channels 32 kb .. +31)
     u32x4 bx[2][4];
     if (DS) {
@@ -305,12 +285,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
     // is ~0.3 us of MFMA work, an HBM / L2 round trip several times that)
     u32x4 r[4], r1[4];
     auto load_wd = [&](int p, u32x4 (&a)[2][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                a[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(wdf) +
-                                                            (((p * 2 + rb) * 2 + kb) * 64 + lane) * 16);
+        CP360_LOAD_FRAGS(a, 2, 2, reinterpret_cast<const unsigned char*>(wdf), (p * 2 + fr_) * 2 + fk_)
     };
     u32x4 ad[2][2];
     if (!DS) {
@@ -339,11 +314,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
         if (!DS && p < 6) load_res(p + 2, r2);
         if (DS && p < 7) load_wd(p + 1, adn);
         u32x4 a3[2][2];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                a3[rb][kb] = *reinterpret_cast<const u32x4*>(W3s + (((p * 2 + rb) * 2 + kb) * 64 + lane) * 16);
+        CP360_LOAD_FRAGS(a3, 2, 2, W3s, (p * 2 + fr_) * 2 + fk_)
         const int n = p * 32 + lchunk * 8;
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias_s + n), b1v = *reinterpret_cast<const f32x4*>(bias_s + n + 4);
         f32x4 c3[2][4];
@@ -369,11 +340,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = c3[0][j][e] + b0[e];
-                v[4 + e] = c3[1][j][e] + b1v[e];
-            }
+            CP360_BIAS_ACT8(v, c3[0][j], c3[1][j], b0[e_], b1v[e_], CP360_NOACT)
             if (!DS) {
                 float rv[8];
                 unpack8(r[j], rv, T());
@@ -388,9 +355,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
         }
         if (NEXT) {     // out's channels 32p .. 32p+31 = k-block p of the next conv1
             u32x4 a1[4];
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
-                a1[rb] = *reinterpret_cast<const u32x4*>(W1s + ((p * 4 + rb) * 64 + lane) * 16);
+            CP360_LOAD_FRAGS1(a1, 4, W1s, p * 4 + fr_)
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
@@ -422,11 +387,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
             for (int j = 0; j < 4; ++j) {
                 const int xo = x0 + j * 16 + lrow;
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[2 * pr][j][e] + bb[e], 0.f);
-                    v[4 + e] = fmaxf(acc[2 * pr + 1][j][e] + bb[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[2 * pr][j], acc[2 * pr + 1][j], bb[e_], bb[4 + e_], CP360_RELU)
                 if (xo < N) *reinterpret_cast<u32x4*>(orow + (size_t)(j * 16 + lrow) * C + n) = pack8(v, T());
             }
         }
@@ -435,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void l1block_kernel(const T* __restrict__ x
 }
 
 // The last block of layer1 (identity residual) with the WIDE chained conv1 (256 -> 128 = layer2.0's conv1): stages 1-2
-// as l1block_kernel; stage 3 twice over half of the wave's pixel blocks (see the header).
+// are l1block_kernel's (CP360_L1_*); stage 3 twice over half of the wave's pixel blocks (see the header).
 template <typename T, int NV, int BANDV>
 __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restrict__ x, const T* __restrict__ wpk2,
                                                               const float* __restrict__ bias2, const T* __restrict__ w3f,
@@ -456,62 +417,12 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
     const int wrow = wave / WPR, x0 = (wave - wrow * WPR) * 64;
     const size_t row_px = ((size_t)img * N + band * BAND + wrow) * N + x0;
 
-    // ---- stage 1 (as l1block_kernel)
-    {
-        const T* xg = x + (size_t)grp * 6 * N * N * C;
-#pragma unroll 1
-        for (int inst = wave; inst < PATCH_INST; inst += 4) {
-            const int q = inst * 8 + (lane >> 3);
-            const void* src = g_zero16;
-            if (q < PATCH_PX) {
-                const int pr = q / NP, pc = q - pr * NP;
-                const int sp = cubepad_src(f, BAND * band + pr, pc, geom);
-                src = xg + (size_t)sp * C + (((lane & 7) ^ px_swz(q)) << 3);
-            }
-            glds16(src, __builtin_amdgcn_readfirstlane(lds_base + inst * 1024));
-        }
-    }
-    const unsigned char* wb = reinterpret_cast<const unsigned char*>(wpk2);
-    auto load_a = [&](int t, u32x4 (&a)[4][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-                a[i][kk] = *reinterpret_cast<const u32x4*>(wb + (size_t)t * W2_TAP + ((i * 2 + kk) * 64 + lane) * 16);
-    };
-    constexpr int DEPTH = 2;
+    // ---- stages 1 and 2
+    CP360_L1_STAGE1_HEAD()
     u32x4 bt[2][4];
     {
-        u32x4 aq[DEPTH + 1][4][2];
-#pragma unroll
-        for (int t = 0; t < DEPTH; ++t) load_a(t, aq[t]);
-        f32x4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            if (tap + DEPTH < 9) load_a(tap + DEPTH, aq[(tap + DEPTH) % (DEPTH + 1)]);
-            const int ky = tap / 3, kx = tap - ky * 3;
-            const int pbase = (wrow + ky) * NP + kx + x0 + lrow;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                u32x4 b[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int p = pbase + 16 * j;
-                    b[j] = *reinterpret_cast<const u32x4*>(lds + p * 128 + (((kk * 4 + lchunk) ^ px_swz(p)) << 4));
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) mma_chunk<T>(acc[i][j], aq[tap % (DEPTH + 1)][i][kk], b[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        CP360_L1_STAGE1_START()
+        CP360_L1_CONV2_TAPS()
         // every wave is done with the patch: bring the chained conv1's fragments in (64 KiB)
         __syncthreads();
         {
@@ -522,24 +433,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
                 glds16(s1 + inst * 1024 + lane * 16, __builtin_amdgcn_readfirstlane(lds_base + inst * 1024));
             }
         }
-        // ---- stage 2: t = relu(conv2 + b2), rounded once, as B fragments bt[k-block][pixel block]
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            const int n = pr * 32 + lchunk * 8;
-            float bb[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bb[e] = bias2 ? bias2[n + e] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[2 * pr][j][e] + bb[e], 0.f);
-                    v[4 + e] = fmaxf(acc[2 * pr + 1][j][e] + bb[4 + e], 0.f);
-                }
-                bt[pr][j] = pack8(v, T());
-            }
-        }
+        CP360_L1_T_FRAGS()
     }
     float* bias_s = reinterpret_cast<float*>(lds + W1W_BYTES);
     bias_s[tid] = bias3[tid];
@@ -552,11 +446,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
     const unsigned char* W1s = lds;
     const unsigned char* w3g = reinterpret_cast<const unsigned char*>(w3f);
     auto load_w3 = [&](int p, u32x4 (&a)[2][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                a[rb][kb] = *reinterpret_cast<const u32x4*>(w3g + (((p * 2 + rb) * 2 + kb) * 64 + lane) * 16);
+        CP360_LOAD_FRAGS(a, 2, 2, w3g, (p * 2 + fr_) * 2 + fk_)
     };
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -601,11 +491,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = 2 * h + jj;
                 float v[8], rv[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = c3[0][jj][e] + b0[e];
-                    v[4 + e] = c3[1][jj][e] + b1v[e];
-                }
+                CP360_BIAS_ACT8(v, c3[0][jj], c3[1][jj], b0[e_], b1v[e_], CP360_NOACT)
                 unpack8(r[jj], rv, T());
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e] + rv[e], 0.f);
@@ -617,9 +503,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 u32x4 a1[4];
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb)
-                    a1[rb] = *reinterpret_cast<const u32x4*>(W1s + ((p * 8 + half * 4 + rb) * 64 + lane) * 16);
+                CP360_LOAD_FRAGS1(a1, 4, W1s, p * 8 + half * 4 + fr_)
 #pragma unroll
                 for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
@@ -647,11 +531,7 @@ __global__ __launch_bounds__(256, 2) void l1block_wide_kernel(const T* __restric
                 const int j = 2 * h + jj;
                 const int xo = x0 + j * 16 + lrow;
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[2 * pr][jj][e] + bb[e], 0.f);
-                    v[4 + e] = fmaxf(acc[2 * pr + 1][jj][e] + bb[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[2 * pr][jj], acc[2 * pr + 1][jj], bb[e_], bb[4 + e_], CP360_RELU)
                 if (xo < N) *reinterpret_cast<u32x4*>(orow + (size_t)(j * 16 + lrow) * C1W + n) = pack8(v, T());
             }
         }
@@ -667,16 +547,11 @@ extern "C" int cp360_frag_pack_1x1(int dtype, const float* w, const float* scale
                                    int order, void* stream) {
     if (!w || !packed) return CP360_ERR_NULL;
     if (n_out <= 0 || k <= 0 || n_out % 32 != 0 || k % 32 != 0 || (order != 0 && order != 1)) return CP360_ERR_BAD_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((n_out * k + 255) / 256);
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((frag_pack_kernel<bf16_raw>), dim3(blocks), dim3(256), 0, st, w, scale, (bf16_raw*)packed, n_out, k, order);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((frag_pack_kernel<f16_raw>), dim3(blocks), dim3(256), 0, st, w, scale, (f16_raw*)packed, n_out, k, order);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((frag_pack_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, scale, (T*)packed, n_out, k, order);
+    });
 }
 
 extern "C" size_t cp360_l1block_conv2_bytes(int dtype) {
@@ -685,16 +560,11 @@ extern "C" size_t cp360_l1block_conv2_bytes(int dtype) {
 
 extern "C" int cp360_l1block_pack_conv2(int dtype, const float* w_oihw, const float* scale, void* packed, void* stream) {
     if (!w_oihw || !packed) return CP360_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (9 * C * C + 255) / 256;
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((l1_pack_conv2_kernel<bf16_raw>), dim3(blocks), dim3(256), 0, st, w_oihw, scale, (bf16_raw*)packed);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((l1_pack_conv2_kernel<f16_raw>), dim3(blocks), dim3(256), 0, st, w_oihw, scale, (f16_raw*)packed);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((l1_pack_conv2_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, scale, (T*)packed);
+    });
 }
 
 extern "C" int cp360_l1block_forward_wide(int dtype, const void* mid, const void* w2_packed, const float* bias2,
@@ -702,23 +572,17 @@ extern "C" int cp360_l1block_forward_wide(int dtype, const void* mid, const void
                                           const void* w1_frags, const float* bias1, void* out_next, int n_img, int face,
                                           void* stream) {
     if (!mid || !w2_packed || !w3_frags || !bias3 || !out || !residual || !w1_frags || !out_next) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (face != 56 && face != 128) return CP360_ERR_UNSUPPORTED;
-    if ((long long)n_img * face * face * CO >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
+    if (const int bad = check_faces(n_img, face == 56 || face == 128, face, CO)) return bad;
     hipStream_t st = (hipStream_t)stream;
-#define CP360_L1W(TT, NV, BV)                                                                                       \
+#define CP360_L1W(NV, BV)                                                                                           \
     hipLaunchKernelGGL((l1block_wide_kernel<TT, NV, BV>), dim3((unsigned)(n_img * (NV / BV))), dim3(256), 0, st,      \
                        (const TT*)mid, (const TT*)w2_packed, bias2, (const TT*)w3_frags, bias3, (const TT*)residual, \
                        (TT*)out, (const TT*)w1_frags, bias1, (TT*)out_next, cp360_launch_reverse())
-#define CP360_L1W_T(TT) { if (face == 56) CP360_L1W(TT, 56, 4); else CP360_L1W(TT, 128, 2); }
-    if (dtype == CP360_BF16) CP360_L1W_T(bf16_raw)
-    else if (dtype == CP360_F16) CP360_L1W_T(f16_raw)
-    else return CP360_ERR_BAD_DTYPE;
-#undef CP360_L1W_T
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (face == 56) CP360_L1W(56, 4); else CP360_L1W(128, 2);
+    });
 #undef CP360_L1W
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }
 
 extern "C" int cp360_l1block_forward(int dtype, const void* mid, const void* w2_packed, const float* bias2,
@@ -729,31 +593,25 @@ extern "C" int cp360_l1block_forward(int dtype, const void* mid, const void* w2_
     if ((residual != nullptr) == (x_ds != nullptr)) return CP360_ERR_NULL;        // exactly one of the two
     if (x_ds && !wd_frags) return CP360_ERR_NULL;
     if ((w1_frags != nullptr) != (out_next != nullptr)) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (face != 56 && face != 128) return CP360_ERR_UNSUPPORTED;                  // other sizes: the per-convolution path
-    if ((long long)n_img * face * face * CO >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
+    if (const int bad = check_faces(n_img, face == 56 || face == 128, face, CO)) return bad;   // other sizes: the per-convolution path
     hipStream_t st = (hipStream_t)stream;
-#define CP360_L1B(TT, DSV, NX, NV, BV)                                                                          \
+#define CP360_L1B(DSV, NX, NV, BV)                                                                              \
     hipLaunchKernelGGL((l1block_kernel<TT, DSV, NX, NV, BV>), dim3((unsigned)(n_img * (NV / BV))), dim3(256), 0, st, \
                        (const TT*)mid, (const TT*)w2_packed, bias2, (const TT*)w3_frags, bias3, (const TT*)residual, \
                        (const TT*)x_ds, (const TT*)wd_frags, (TT*)out, (const TT*)w1_frags, bias1, (TT*)out_next, cp360_launch_reverse())
-#define CP360_L1B_F(TT, NV, BV)                                 \
-    {                                                           \
-        if (x_ds && w1_frags) CP360_L1B(TT, true, true, NV, BV);  \
-        else if (x_ds) CP360_L1B(TT, true, false, NV, BV);        \
-        else if (w1_frags) CP360_L1B(TT, false, true, NV, BV);    \
-        else CP360_L1B(TT, false, false, NV, BV);                 \
+#define CP360_L1B_F(NV, BV)                                 \
+    {                                                       \
+        if (x_ds && w1_frags) CP360_L1B(true, true, NV, BV);  \
+        else if (x_ds) CP360_L1B(true, false, NV, BV);        \
+        else if (w1_frags) CP360_L1B(false, true, NV, BV);    \
+        else CP360_L1B(false, false, NV, BV);                 \
     }
-#define CP360_L1B_T(TT) { if (face == 56) CP360_L1B_F(TT, 56, 4) else CP360_L1B_F(TT, 128, 2) }
-    if (dtype == CP360_BF16) CP360_L1B_T(bf16_raw)
-    else if (dtype == CP360_F16) CP360_L1B_T(f16_raw)
-    else return CP360_ERR_BAD_DTYPE;
-#undef CP360_L1B_T
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (face == 56) CP360_L1B_F(56, 4) else CP360_L1B_F(128, 2)
+    });
 #undef CP360_L1B_F
 #undef CP360_L1B
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }
 
 // layer1.0 with its own conv1 inside (FIRST): x = the block input [n_img, 56, 56, 64] (conv1's input AND the downsample source),
@@ -764,22 +622,18 @@ extern "C" int cp360_l1block_forward_first(int dtype, const void* x, const void*
                                            const void* w1_frags, const float* bias1, void* out_next, int n_img, int face, void* stream) {
     if (!x || !w0_frags || !w2_packed || !w3_frags || !bias3 || !wd_frags || !out) return CP360_ERR_NULL;
     if ((w1_frags != nullptr) != (out_next != nullptr)) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (face != 56) return CP360_ERR_UNSUPPORTED;                                 // other sizes: conv1 as its own launch + cp360_l1block_forward
-    if ((long long)n_img * face * face * CO >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
+    if (const int bad = check_faces(n_img, face == 56, face, CO)) return bad;     // other sizes: conv1 as its own launch + cp360_l1block_forward
     hipStream_t st = (hipStream_t)stream;
-#define CP360_L1F(TT, NX)                                                                                        \
+#define CP360_L1F(NX)                                                                                            \
     hipLaunchKernelGGL((l1block_kernel<TT, true, NX, 56, 4, true>), dim3((unsigned)(n_img * 14)), dim3(256), 0, st,  \
                        (const TT*)x, (const TT*)w2_packed, bias2, (const TT*)w3_frags, bias3, (const TT*)nullptr,   \
                        (const TT*)x, (const TT*)wd_frags, (TT*)out, (const TT*)w1_frags, bias1, (TT*)out_next,      \
                        cp360_launch_reverse(), (const TT*)w0_frags, bias0)
-    if (dtype == CP360_BF16) { if (w1_frags) CP360_L1F(bf16_raw, true); else CP360_L1F(bf16_raw, false); }
-    else if (dtype == CP360_F16) { if (w1_frags) CP360_L1F(f16_raw, true); else CP360_L1F(f16_raw, false); }
-    else return CP360_ERR_BAD_DTYPE;
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (w1_frags) CP360_L1F(true); else CP360_L1F(false);
+    });
 #undef CP360_L1F
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }
 
 #ifdef L1_STAMPS

@@ -6,7 +6,7 @@
 // cube 224, 64x64 = cube 512) and layer3's blocks 1-5 (C = 256; 14x14 faces = cube 224).  The text below describes the
 // layer2 geometry; layer3's differences are listed at BtGeom.  Separately these are a
 // generic implicit GEMM that re-gathers its im2col rows once per tap (conv2, 0.15 ms per block for 64 frames) and
-// an HBM-bound 1x1 (conv3, 0.15 ms) with t making a round trip through HBM in between.  Here, as in l1block.hip:
+// an HBM-bound 1x1 (conv3, 0.15 ms) with t making a round trip through HBM in between.  Here, as in l1block.hip (shared pieces: band.h):
 //   * a workgroup of 4 waves owns a band of 4 output rows (112 pixels = 7 MFMA pixel blocks, no padding columns: a
 //     band's pixels are consecutive in memory), two workgroups per CU (NB = 2 - one workgroup of 8 waves with two
 //     bands - measured slower; every launch has NB = 1);
@@ -26,8 +26,10 @@
 //     slice per pass (see the NEXT branch).
 // HBM traffic per block (64 frames): mid 77 MB + residual 308 MB + out 308 MB; t (77 MB x 2) never leaves the CU.
 // Work-item order: cp360_set_launch_order (descending band order when `reverse`).
-// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
-#include "tile.h"
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h;
+// the band gather, the epilogue piece, the A-fragment fetch (load_a3 / load_a1, shared with lfirst.hip), the MFMAs over the t tile, the
+// phase stamp and the host-side dispatch / checks shared with the other fused kernels: band.h.
+#include "band.h"
 
 namespace {
 constexpr int W_STEP = 16 * 1024;                            // conv2 weights per step: 4 fragments for each of the 4 waves
@@ -83,8 +85,7 @@ __global__ __launch_bounds__(256) void bt_pack_kernel(const float* __restrict__ 
     const int n = row_chan(((hc * 4 + wv) * 2 + i) * 16 + (lane & 15));
     const int c = (sub * 2 + kk) * 32 + (lane >> 4) * 8 + e;
     const float v = w[((size_t)n * C + c) * 9 + tap] * (scale ? scale[n] : 1.f);
-    if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-    else packed[idx] = f32_to_bf16(v);
+    store_folded(packed, idx, v);
 }
 
 // Diagnostic build only (-DL2_STAMPS, tools/l2_stamps.sh): s_memtime stamps of wave 0 of every workgroup at the phase boundaries (0 start,
@@ -92,10 +93,7 @@ __global__ __launch_bounds__(256) void bt_pack_kernel(const float* __restrict__ 
 // product build executes no stamp.
 #ifdef L2_STAMPS
 __device__ unsigned long long g_l2_stamps[8192 * 16];
-#define L2_STAMP(k)                                                                                         \
-    { __builtin_amdgcn_sched_barrier(0);                                                                    \
-      if (wave == 0 && lane == 0 && blockIdx.x < 8192) g_l2_stamps[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-      __builtin_amdgcn_sched_barrier(0); }
+#define L2_STAMP(k) CP360_PHASE_STAMP(g_l2_stamps, k)
 #else
 #define L2_STAMP(k)
 #endif
@@ -131,17 +129,8 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
     L2_STAMP(0)
 
     // ---- stage 1: gather the band's padded pixels: instruction i = patch pixels PPI i .. PPI i + PPI - 1 (4 x 256 B / 2 x 512 B)
-    {
-        const T* xg = x + (size_t)grp * 6 * N * N * C;
-#pragma unroll 1
-        for (int inst = w4; inst < PATCH_INST; inst += 4) {
-            const int q = inst * G::PPI + lane / G::CH16;
-            const int pr = q / NP, pc = q - pr * NP;
-            const int sp = cubepad_src(f, BAND * band + pr, pc, geom);
-            const T* src = xg + (size_t)sp * C + (((lane & (G::CH16 - 1)) ^ ((pr * N + pc) & 15)) << 3);   // swizzle key: see the B reads
-            glds16(src, __builtin_amdgcn_readfirstlane(lds_base + half_wg * PATCH_LDS + inst * 1024));
-        }
-    }
+    CP360_GATHER_BAND_PATCH(x + (size_t)grp * 6 * N * N * C, C, f, BAND * band, NP, geom, G::PATCH_PX, PATCH_INST, G::PPI, (pr_ * N + pc_) & 15,
+                            lds_base + half_wg * PATCH_LDS, w4, lane)                   // swizzle key: see the B reads
     // conv2's A fragments come straight from L2 into registers, three steps ahead (a step = half a tap = 4
     // fragments of this wave's row pair): ~96 KiB in flight per CU and no barrier in the whole stage - a ring
     // in LDS (3 x 16 KiB, 2 steps ahead) left the stage waiting on L2 latency at every step (0.25 -> 0.17 ms)
@@ -163,11 +152,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
         u32x4 aq[DEPTH + 1][RBW][KK];
         const unsigned char* wh = wb + (size_t)hc * STEPS * W_STEP;
         auto load_a = [&](int s, u32x4 (&a)[RBW][KK]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < RBW; ++i)
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk)
-                    a[i][kk] = *reinterpret_cast<const u32x4*>(wh + (size_t)s * W_STEP + (((w4 * RBW + i) * KK + kk) * 64 + lane) * 16);
+            CP360_LOAD_FRAGS(a, RBW, KK, wh + (size_t)s * W_STEP, (w4 * RBW + fr_) * KK + fk_)
         };
 #pragma unroll
         for (int s = 0; s < DEPTH; ++s) load_a(s, aq[s]);
@@ -250,11 +235,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[0][j][e] + bb[e], 0.f);
-                    v[4 + e] = fmaxf(acc[1][j][e] + bb[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[0][j], acc[1][j], bb[e_], bb[4 + e_], CP360_RELU)
                 const u32x4 o = pack8(v, T());
                 if (hc < HC - 1) tkeep[j] = o;
                 else *reinterpret_cast<u32x4*>(patch + (j * 16 + lrow) * T_STRIDE + n * 2) = o;
@@ -267,15 +248,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
         for (int j = 0; j < PB; ++j) *reinterpret_cast<u32x4*>(patch + (j * 16 + lrow) * T_STRIDE + n * 2) = tkeep[j];
     }
     // ---- stage 3: conv3 (+ residual, ReLU): PASSES passes of 32 output channels per wave, each H3 half passes of 4 k-blocks
-    auto load_a3 = [&](int u, u32x4 (&a)[2][4]) __attribute__((always_inline)) {     // unit u = pass * H3 + half
-        const int p = w4 + 4 * (u / H3), h = u % H3;
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-                a[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(w3f) +
-                                                            ((size_t)((p * 2 + rb) * KB3 + h * 4 + kb) * 64 + lane) * 16);
-    };
+    CP360_DEF_LOAD_A3(w3f);                                    // load_a3(unit u = pass * H3 + half, a)
     // (stage 3's addresses are derived from an opaque copy of the lane's row: computed here, not hoisted above conv2 and
     // spilled across it)
     int lrow3 = lrow;
@@ -310,23 +283,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
 #pragma unroll
                 for (int j = 0; j < PB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-            for (int j0 = 0; j0 < PB; j0 += 4) {               // pixel blocks in two groups (4 + 3): fewer live fragments
-                u32x4 b[4];
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    if (j0 + v < PB)
-                        b[v] = *reinterpret_cast<const u32x4*>(patch + ((j0 + v) * 16 + lrow) * T_STRIDE + ((h * 4 + kb) * 4 + lchunk) * 16);
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (j0 + v < PB) mma_chunk<T>(acc[rb][j0 + v], a3[rb][kb], b[v]);
-                __builtin_amdgcn_sched_barrier(0);             // keep the next group's fragment reads from being hoisted (spills)
-            }
-        }
+        CP360_MMA_OVER_TILE(acc, a3, patch, T_STRIDE, h * 4, PB)   // pixel blocks in two groups (4 + 3): fewer live fragments
         if (h == H3 - 1) {
             if (q + 1 < PASSES) load_res(p + 4, rn);           // lands under the next pass's MFMAs
             const int n = p * 32 + lchunk * 8;
@@ -335,11 +292,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
             for (int j = 0; j < PB; ++j) {
                 float v[8], rv[8];
                 unpack8(r[j], rv, T());
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[0][j][e] + b0[e] + rv[e], 0.f);
-                    v[4 + e] = fmaxf(acc[1][j][e] + b1[e] + rv[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[0][j], acc[1][j], b0[e_] + rv[e_], b1[e_] + rv[4 + e_], CP360_RELU)
                 if (PXV % 16 == 0 || j * 16 + lrow3 < PXV)
                     *reinterpret_cast<u32x4*>(out + (pix0 + j * 16 + lrow3) * CO + n) = pack8(v, T());
             }
@@ -369,14 +322,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < PB; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto load_a1 = [&](int q, u32x4 (&a)[2][4]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-                    a[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(w1f) +
-                                                                ((size_t)((w4 * 2 + rb) * 16 + 4 * q + kb) * 64 + lane) * 16);
-        };
+        CP360_DEF_LOAD_A1(w1f);                                    // load_a1(K slice q, a)
 #pragma unroll 1
         for (int q = 0; q < 4; ++q) {
             const int p = w4 + 4 * q;
@@ -386,23 +332,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < PB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-                for (int j0 = 0; j0 < PB; j0 += 4) {
-                    u32x4 b[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (j0 + u < PB)
-                            b[u] = *reinterpret_cast<const u32x4*>(patch + ((j0 + u) * 16 + lrow) * T_STRIDE + (kb * 4 + lchunk) * 16);
-#pragma unroll
-                    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (j0 + u < PB) mma_chunk<T>(acc[rb][j0 + u], a3[rb][kb], b[u]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+            CP360_MMA_OVER_TILE(acc, a3, patch, T_STRIDE, 0, PB)
             if (q < 3) load_a3(q + 1, a3);                        // a3 is dead: the next pass's fragments land under the chained MFMAs
             const int n = p * 32 + lchunk * 8;
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias_s + C + n), b1 = *reinterpret_cast<const f32x4*>(bias_s + C + n + 4);
@@ -411,34 +341,14 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
             for (int j = 0; j < PB; ++j) {
                 float v[8], rv[8];
                 unpack8(r[j], rv, T());
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[0][j][e] + b0[e] + rv[e], 0.f);
-                    v[4 + e] = fmaxf(acc[1][j][e] + b1[e] + rv[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[0][j], acc[1][j], b0[e_] + rv[e_], b1[e_] + rv[4 + e_], CP360_RELU)
                 const u32x4 o = pack8(v, T());
                 *reinterpret_cast<u32x4*>(out + (pix0 + j * 16 + lrow3) * CO + n) = o;
                 *reinterpret_cast<u32x4*>(slice + (j * 16 + lrow) * T_STRIDE + (w4 * 32 + lchunk * 8) * 2) = o;
             }
             if (q < 3) load_res(p + 4, r);                         // r is dead too
             __syncthreads();                                       // the slice is complete
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-                for (int j0 = 0; j0 < PB; j0 += 4) {
-                    u32x4 b[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (j0 + u < PB)
-                            b[u] = *reinterpret_cast<const u32x4*>(slice + ((j0 + u) * 16 + lrow) * T_STRIDE + (kb * 4 + lchunk) * 16);
-#pragma unroll
-                    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (j0 + u < PB) mma_chunk<T>(acc1[rb][j0 + u], a1[rb][kb], b[u]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+            CP360_MMA_OVER_TILE(acc1, a1, slice, T_STRIDE, 0, PB)
         }
         // mid' = relu(conv1 + b1), one rounding, 16-byte stores ([px][128 ch])
         const int n1 = w4 * 32 + lchunk * 8;
@@ -446,11 +356,7 @@ __global__ __launch_bounds__(256 * NB, 2) void l2block_kernel(const T* __restric
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = fmaxf(acc1[0][j][e] + c0[e], 0.f);
-                v[4 + e] = fmaxf(acc1[1][j][e] + c1[e], 0.f);
-            }
+            CP360_BIAS_ACT8(v, acc1[0][j], acc1[1][j], c0[e_], c1[e_], CP360_RELU)
             *reinterpret_cast<u32x4*>(out_next + (pix0 + j * 16 + lrow3) * C + n1) = pack8(v, T());
         }
     }
@@ -480,16 +386,11 @@ static size_t bt_packed_bytes(int dtype, int c) {
 template <int C>
 static int bt_pack(int dtype, const float* w_oihw, const float* scale, void* packed, void* stream) {
     if (!w_oihw || !packed) return CP360_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (9 * C * C + 255) / 256;
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((bt_pack_kernel<bf16_raw, C>), dim3(blocks), dim3(256), 0, st, w_oihw, scale, (bf16_raw*)packed);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((bt_pack_kernel<f16_raw, C>), dim3(blocks), dim3(256), 0, st, w_oihw, scale, (f16_raw*)packed);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((bt_pack_kernel<T, C>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, scale, (T*)packed);
+    });
 }
 
 extern "C" size_t cp360_l2block_packed_bytes(int dtype) { return bt_packed_bytes(dtype, 128); }
@@ -506,33 +407,23 @@ static int bt_launch(int layer, int dtype, const void* mid, const void* w2_packe
                      const float* bias3, const void* residual, void* out, const void* w1_frags, const float* bias1,
                      void* out_next, int n_img, int face, void* stream) {
     if (!mid || !w2_packed || !w3_frags || !bias3 || !residual || !out) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (layer == 2 ? (face != 28 && face != 64) : (face != 14 && face != 32)) return CP360_ERR_UNSUPPORTED;
-    if (out_next && (layer != 2 || face != 28)) return CP360_ERR_UNSUPPORTED;   // the chained conv1: layer2, 28x28 faces
-    const int co = layer == 2 ? 512 : 1024;
-    if ((long long)n_img * face * face * co >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
+    // the chained conv1: layer2, 28x28 faces
+    const bool supported = (layer == 2 ? (face == 28 || face == 64) : (face == 14 || face == 32)) && (!out_next || (layer == 2 && face == 28));
+    if (const int bad = check_faces(n_img, supported, face, layer == 2 ? 512 : 1024)) return bad;
     hipStream_t st = (hipStream_t)stream;
-#define CP360_L2B(TT, CV, NBV, NV, BV, NX)                                                                           \
+#define CP360_L2B(CV, NBV, NV, BV, NX)                                                                               \
     hipLaunchKernelGGL((l2block_kernel<TT, CV, NBV, NV, BV, NX>), dim3((unsigned)(n_img * (NV / BV) / NBV)), dim3(256 * NBV), 0, st, \
                        (const TT*)mid, (const TT*)w2_packed, bias2, (const TT*)w3_frags, bias3, (const TT*)residual, (TT*)out, \
                        (const TT*)w1_frags, bias1, (TT*)out_next, cp360_launch_reverse())
-#define CP360_L2B_T(TT)                                                  \
-    {                                                                    \
-        if (layer == 3 && face == 32) CP360_L2B(TT, 256, 1, 32, 2, false);  \
-        else if (layer == 3) CP360_L2B(TT, 256, 1, 14, 7, false);        \
-        else if (out_next) CP360_L2B(TT, 128, 1, 28, 4, true);           \
-        else if (face == 64) CP360_L2B(TT, 128, 1, 64, 2, false);        \
-        else CP360_L2B(TT, 128, 1, 28, 4, false);                        \
-    }
-    if (dtype == CP360_BF16) CP360_L2B_T(bf16_raw)
-    else if (dtype == CP360_F16) CP360_L2B_T(f16_raw)
-#undef CP360_L2B_T
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (layer == 3 && face == 32) CP360_L2B(256, 1, 32, 2, false);
+        else if (layer == 3) CP360_L2B(256, 1, 14, 7, false);
+        else if (out_next) CP360_L2B(128, 1, 28, 4, true);
+        else if (face == 64) CP360_L2B(128, 1, 64, 2, false);
+        else CP360_L2B(128, 1, 28, 4, false);
+    });
 #undef CP360_L2B
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }
 
 extern "C" int cp360_l2block_forward(int dtype, const void* mid, const void* w2_packed, const float* bias2,

@@ -24,8 +24,10 @@
 //     convolution) also go to an LDS slice, and after a barrier each wave accumulates its 32 conv1 channels over it (8 A
 //     fragments from L2, 32 MFMAs): layer2.1's conv1 launch (96 us, 308 MB re-read) is gone.
 // HBM traffic (64 frames): mid 308 MB + x 154 MB (every other pixel and row: whole 512-byte pixels) + out 308 MB.
-// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
-#include "tile.h"
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h;
+// the band gather, the epilogue piece, the A-fragment fetch (load_a3 / load_a1, shared with l2block.hip) and the host-side dispatch /
+// checks shared with the other fused kernels: band.h.
+#include "band.h"
 
 namespace {
 constexpr int C = 128, CX = 256, CO = 512, K3 = C + CX;     // conv2 channels, block-input channels, outputs, stage 3's K
@@ -59,8 +61,7 @@ __global__ __launch_bounds__(256) void lf_pack_w3d_kernel(const float* __restric
     const int n = row_chan(rb * 16 + (lane & 15));
     const int kk = kb * 32 + (lane >> 4) * 8 + e;
     const float v = kk < C ? w3[(size_t)n * C + kk] * (s3 ? s3[n] : 1.f) : wd[(size_t)n * CX + (kk - C)] * (sd ? sd[n] : 1.f);
-    if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-    else packed[idx] = f32_to_bf16(v);
+    store_folded(packed, idx, v);
 }
 
 // (Round 6: a 56-pixel band streams 816 KB of conv2 / conv3 + downsample / next-conv1 fragments from L2 - 4.4 GB per 64-frame launch.  A form with
@@ -87,20 +88,8 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
     unsigned char* patch = lds;
 
     // ---- stage 1: gather the band's 5 x 58 padded input pixels (instruction i = patch pixels 4i .. 4i+3)
-    {
-        const T* xg = mid + (size_t)grp * 6 * NI * NI * C;
-#pragma unroll 1
-        for (int inst = w4; inst < PATCH_INST; inst += 4) {
-            const int q = inst * 4 + (lane >> 4);
-            const void* src = g_zero16;
-            if (q < PATCH_PX) {
-                const int pr = q / NPI, pc = q - pr * NPI;
-                const int sp = cubepad_src(f, 2 * BAND * band + pr, pc, geom);
-                src = xg + (size_t)sp * C + (((lane & 15) ^ (((pr >> 1) * N + (pc >> 1)) & 15)) << 3);
-            }
-            glds16(src, __builtin_amdgcn_readfirstlane(lds_base + inst * 1024));
-        }
-    }
+    CP360_GATHER_BAND_PATCH(mid + (size_t)grp * 6 * NI * NI * C, C, f, 2 * BAND * band, NPI, geom, PATCH_PX, PATCH_INST, 4,
+                            ((pr_ >> 1) * N + (pc_ >> 1)) & 15, lds_base, w4, lane)
     const unsigned char* wb = reinterpret_cast<const unsigned char*>(wpk2);
     constexpr int DEPTH = 3;
     int pbase[PB];                                             // patch pixel of tap (0, 0) of this lane's pixel in block j
@@ -115,11 +104,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
     if (NEXT && tid < C) bias_s[C + CO + tid] = bias1 ? bias1[tid] : 0.f;
     u32x4 aq[DEPTH + 1][2][2];
     auto load_a = [&](int s, u32x4 (&a)[2][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-                a[i][kk] = *reinterpret_cast<const u32x4*>(wb + (size_t)s * W_STEP + (((w4 * 2 + i) * 2 + kk) * 64 + lane) * 16);
+        CP360_LOAD_FRAGS(a, 2, 2, wb + (size_t)s * W_STEP, (w4 * 2 + fr_) * 2 + fk_)
     };
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s) load_a(s, aq[s]);
@@ -177,11 +162,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = fmaxf(acc[0][j][e] + bb[e], 0.f);
-                v[4 + e] = fmaxf(acc[1][j][e] + bb[4 + e], 0.f);
-            }
+            CP360_BIAS_ACT8(v, acc[0][j], acc[1][j], bb[e_], bb[4 + e_], CP360_RELU)
             *reinterpret_cast<u32x4*>(patch + (j * 16 + lrow) * T_STRIDE + n * 2) = pack8(v, T());
         }
 #pragma unroll
@@ -191,15 +172,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
         }
     }
     // ---- stage 3: out = relu([W3 | Wd] . [t | x] + b3 + bd): 4 passes of 32 output channels per wave, 3 half passes of 4 k-blocks
-    auto load_a3 = [&](int u, u32x4 (&a)[2][4]) __attribute__((always_inline)) {      // unit u = pass * H3 + half
-        const int p = w4 + 4 * (u / H3), h = u % H3;
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-                a[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(w3df) +
-                                                            ((size_t)((p * 2 + rb) * KB3 + h * 4 + kb) * 64 + lane) * 16);
-    };
+    CP360_DEF_LOAD_A3(w3df);                                   // load_a3(unit u = pass * H3 + half, a)
     u32x4 a3[2][4];
     load_a3(0, a3);
     __syncthreads();                                           // the tile is complete
@@ -217,14 +190,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
             for (int j = 0; j < PB; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    auto load_a1 = [&](int q, u32x4 (&a)[2][4]) __attribute__((always_inline)) {       // w1 [128, 512], order 0: K slice q
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-                a[rb][kb] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(w1f) +
-                                                            ((size_t)((w4 * 2 + rb) * 16 + 4 * q + kb) * 64 + lane) * 16);
-    };
+    CP360_DEF_LOAD_A1(w1f);                                    // load_a1(K slice q, a)
 #pragma unroll 1
     for (int q = 0; q < PASSES; ++q) {
         const int p = w4 + 4 * q;
@@ -264,29 +230,14 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = fmaxf(acc[0][j][e] + b0[e], 0.f);
-                v[4 + e] = fmaxf(acc[1][j][e] + b1[e], 0.f);
-            }
+            CP360_BIAS_ACT8(v, acc[0][j], acc[1][j], b0[e_], b1[e_], CP360_RELU)
             const u32x4 o = pack8(v, T());
             if (j * 16 + lrow < PXV) *reinterpret_cast<u32x4*>(out + (pix0 + j * 16 + lrow) * CO + n) = o;
             if (NEXT) *reinterpret_cast<u32x4*>(slice + (j * 16 + lrow) * S_STRIDE + (w4 * 32 + lchunk * 8) * 2) = o;
         }
         if (NEXT) {
             __syncthreads();                                   // the slice is complete
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) {
-                u32x4 b[PB];
-#pragma unroll
-                for (int j = 0; j < PB; ++j)
-                    b[j] = *reinterpret_cast<const u32x4*>(slice + (j * 16 + lrow) * S_STRIDE + (kb * 4 + lchunk) * 16);
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                    for (int j = 0; j < PB; ++j) mma_chunk<T>(acc1[rb][j], a1[rb][kb], b[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            CP360_MMA_OVER_TILE(acc1, a1, slice, S_STRIDE, 0, PB)
         }
     }
     if (NEXT) {     // mid' = relu(conv1 + b1), one rounding, 16-byte stores ([px][128 ch])
@@ -295,11 +246,7 @@ __global__ __launch_bounds__(256, 2) void l2first_kernel(const T* __restrict__ m
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = fmaxf(acc1[0][j][e] + c0[e], 0.f);
-                v[4 + e] = fmaxf(acc1[1][j][e] + c1[e], 0.f);
-            }
+            CP360_BIAS_ACT8(v, acc1[0][j], acc1[1][j], c0[e_], c1[e_], CP360_RELU)
             if (j * 16 + lrow < PXV) *reinterpret_cast<u32x4*>(out_next + (pix0 + j * 16 + lrow) * C + n1) = pack8(v, T());
         }
     }
@@ -312,16 +259,11 @@ extern "C" size_t cp360_l2first_w3d_bytes(int dtype) {
 extern "C" int cp360_l2first_pack_w3d(int dtype, const float* w3, const float* scale3, const float* wd, const float* scaled,
                                       void* packed, void* stream) {
     if (!w3 || !wd || !packed) return CP360_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (CO * K3 + 255) / 256;
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((lf_pack_w3d_kernel<bf16_raw>), dim3(blocks), dim3(256), 0, st, w3, scale3, wd, scaled, (bf16_raw*)packed);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((lf_pack_w3d_kernel<f16_raw>), dim3(blocks), dim3(256), 0, st, w3, scale3, wd, scaled, (f16_raw*)packed);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((lf_pack_w3d_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w3, scale3, wd, scaled, (T*)packed);
+    });
 }
 
 extern "C" int cp360_l2first_forward(int dtype, const void* mid, const void* w2_packed, const float* bias2, const void* w3d_frags,
@@ -329,21 +271,16 @@ extern "C" int cp360_l2first_forward(int dtype, const void* mid, const void* w2_
                                      void* out_next, int n_img, int face_out, void* stream) {
     if (!mid || !w2_packed || !w3d_frags || !bias3d || !x || !out) return CP360_ERR_NULL;
     if ((w1_frags != nullptr) != (out_next != nullptr)) return CP360_ERR_NULL;
-    if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
-    if (n_img % 6 != 0) return CP360_ERR_BATCH_NOT_6N;
-    if (face_out != N) return CP360_ERR_UNSUPPORTED;                          // other sizes: the per-convolution path
-    if ((long long)n_img * NI * NI * CX >= (1LL << 31)) return CP360_ERR_BAD_SHAPE;
+    if (const int bad = check_faces(n_img, face_out == N, NI, CX)) return bad;       // other sizes: the per-convolution path
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(n_img * (N / BAND)));
     const int rev = cp360_launch_reverse();
-#define CP360_LF(TT, NX)                                                                                              \
+#define CP360_LF(NX)                                                                                                  \
     hipLaunchKernelGGL((l2first_kernel<TT, NX>), grid, dim3(256), 0, st, (const TT*)mid, (const TT*)w2_packed, bias2,      \
                        (const TT*)w3d_frags, bias3d, (const TT*)x, (TT*)out, (const TT*)w1_frags, bias1, (TT*)out_next, rev)
-    if (dtype == CP360_BF16) { if (w1_frags) CP360_LF(bf16_raw, true); else CP360_LF(bf16_raw, false); }
-    else if (dtype == CP360_F16) { if (w1_frags) CP360_LF(f16_raw, true); else CP360_LF(f16_raw, false); }
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (w1_frags) CP360_LF(true); else CP360_LF(false);
+    });
 #undef CP360_LF
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }

@@ -14,8 +14,9 @@
 // Wave w computes output row w of the band: 112 pixels x 64 channels = 7 x 4 MFMA tiles, 7 k-steps.
 // Epilogue: bias + ReLU, one rounding, 16-byte pieces straight to global (acc_chan row order: a lane
 // holds 8 consecutive channels), 128 contiguous bytes per pixel.
-// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h.
-#include "tile.h"
+// The tile primitives used here (vector types, mma_chunk, glds16, swizzles, acc_chan / row_chan, pack8 / unpack8, g_zero16): tile.h;
+// the epilogue piece, the packers' final conversion and the 16-bit dtype dispatch shared with the other fused kernels: band.h.
+#include "band.h"
 
 namespace {
 // Geometry per cube size.  BAND output rows per workgroup, WPR waves per output row (8 waves in all): cube 224 ->
@@ -44,12 +45,11 @@ __global__ __launch_bounds__(256) void stem_pack_kernel(const float* __restrict_
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= 7 * 64 * 32) return;
     const int k = idx & 31, r = (idx >> 5) & 63, ky = idx >> 11;
-    const int n = (r & ~31) + ((r >> 2) & 3) * 8 + ((r >> 4) & 1) * 4 + (r & 3);
+    const int n = (r & ~31) + ((r >> 2) & 3) * 8 + ((r >> 4) & 1) * 4 + (r & 3);      // = row_chan(r), as in band3x3_pack_kernel
     const int kx = k >> 2, ch = k & 3;
     float v = 0.f;
     if (kx < 7 && ch < 3) v = w[((n * 3 + ch) * 7 + ky) * 7 + kx] * (scale ? scale[n] : 1.f);
-    if constexpr (__is_same(T, f16_raw)) packed[idx] = (f16_raw)v;
-    else packed[idx] = f32_to_bf16(v);
+    store_folded(packed, idx, v);
 }
 
 template <typename T, int CDV>
@@ -148,11 +148,7 @@ __global__ __launch_bounds__(512, 2) void stem_kernel(const T* __restrict__ xp, 
 #pragma unroll
             for (int j = 0; j < MJ; ++j) {
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[2 * pr][j][e] + bl[e];
-                    v[4 + e] = acc[2 * pr + 1][j][e] + bl[4 + e];
-                }
+                CP360_BIAS_ACT8(v, acc[2 * pr][j], acc[2 * pr + 1][j], bl[e_], bl[4 + e_], CP360_NOACT)
                 if (relu) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
@@ -300,11 +296,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool4_kernel(const T* __restrict_
 #pragma unroll
             for (int u = 0; u < 9; ++u) {
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[2 * pr][u][e] + bl[e], 0.f);
-                    v[4 + e] = fmaxf(acc[2 * pr + 1][u][e] + bl[4 + e], 0.f);
-                }
+                CP360_BIAS_ACT8(v, acc[2 * pr][u], acc[2 * pr + 1][u], bl[e_], bl[4 + e_], CP360_RELU)
                 o[u] = pack8(v, T());
             }
             if (srow == 0 || srow == WO - 1) {
@@ -416,20 +408,12 @@ extern "C" int cp360_stem_pool_forward(int dtype, const void* xp, const void* pa
     const int fix_blocks = (n_img * 111 * 8 + 255) / 256;
     const int ntiles = n_img * 28;                                 // bands of 4 stem rows
     const dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));
-#define CP360_SP(TT)                                                                                                   \
-    {                                                                                                                  \
-        hipLaunchKernelGGL((stem_pool4_kernel<TT>), grid, dim3(256), 0, st, (const TT*)xp, (const TT*)packed, bias, (TT*)y, \
-                           (TT*)border, n_img, rev);                                                                   \
-        hipLaunchKernelGGL((stem_pool_fix_kernel<TT>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (TT*)y,            \
-                           (const TT*)border, n_img);                                                                  \
-    }
-    if (dtype == CP360_BF16) CP360_SP(bf16_raw)
-    else if (dtype == CP360_F16) CP360_SP(f16_raw)
-#undef CP360_SP
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        hipLaunchKernelGGL((stem_pool4_kernel<TT>), grid, dim3(256), 0, st, (const TT*)xp, (const TT*)packed, bias, (TT*)y, (TT*)border,
+                           n_img, rev);
+        hipLaunchKernelGGL((stem_pool_fix_kernel<TT>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (TT*)y, (const TT*)border, n_img);
+    });
 }
 
 extern "C" size_t cp360_stem_packed_bytes(int dtype) {
@@ -438,15 +422,10 @@ extern "C" size_t cp360_stem_packed_bytes(int dtype) {
 
 extern "C" int cp360_stem_pack_weights(int dtype, const float* w_oihw, const float* scale, void* packed, void* stream) {
     if (!w_oihw || !packed) return CP360_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CP360_BF16)
-        hipLaunchKernelGGL((stem_pack_kernel<bf16_raw>), dim3(56), dim3(256), 0, st, w_oihw, scale, (bf16_raw*)packed);
-    else if (dtype == CP360_F16)
-        hipLaunchKernelGGL((stem_pack_kernel<f16_raw>), dim3(56), dim3(256), 0, st, w_oihw, scale, (f16_raw*)packed);
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    return with_elem16(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((stem_pack_kernel<T>), dim3(56), dim3(256), 0, (hipStream_t)stream, w_oihw, scale, (T*)packed);
+    });
 }
 
 extern "C" int cp360_stem_forward(int dtype, const void* xp, const void* packed, const float* bias, void* out, int n_img,
@@ -455,18 +434,16 @@ extern "C" int cp360_stem_forward(int dtype, const void* xp, const void* packed,
     if (n_img <= 0) return CP360_ERR_BAD_SHAPE;
     if (cube_dim != 224 && cube_dim != 512) return CP360_ERR_UNSUPPORTED;   // other cube sizes: the generic implicit GEMM
     hipStream_t st = (hipStream_t)stream;
-#define CP360_STEM(TT, CDV)                                                                                     \
+#define CP360_STEM(CDV)                                                                                         \
     {                                                                                                           \
         const int ntiles = n_img * (StemGeom<CDV>::WO / StemGeom<CDV>::BAND);                                   \
         const dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));                                               \
         hipLaunchKernelGGL((stem_kernel<TT, CDV>), grid, dim3(512), 0, st, (const TT*)xp, (const TT*)packed, bias, \
                            (TT*)out, n_img, relu, cp360_launch_reverse());                                      \
     }
-    if (dtype == CP360_BF16) { if (cube_dim == 224) CP360_STEM(bf16_raw, 224) else CP360_STEM(bf16_raw, 512) }
-    else if (dtype == CP360_F16) { if (cube_dim == 224) CP360_STEM(f16_raw, 224) else CP360_STEM(f16_raw, 512) }
+    return with_elem16(dtype, [&](auto tag) {
+        using TT = decltype(tag);
+        if (cube_dim == 224) CP360_STEM(224) else CP360_STEM(512)
+    });
 #undef CP360_STEM
-    else
-        return CP360_ERR_BAD_DTYPE;
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }

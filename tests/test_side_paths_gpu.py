@@ -357,3 +357,115 @@ def test_equi2cube_ragged_frame_groups(F):
         assert got.shape[0] == 6 * F
         for k in range(F):
             assert same_bits(got[6 * k:6 * k + 6], ops.equi2cube(ft[k:k + 1], e.grid, cd, F32, layout)), (layout, k)
+
+
+# ------------------------------------------------------------------ the fused kernels' weight packers
+# Each packer against a numpy restatement of the layout comment above its kernel (csrc/l1block.hip, l2block.hip, lfirst.hip,
+# band3x3.hip, stem.hip), bit for bit.  Scales are None or signed powers of two, so the f32 product with the BN scale is exact
+# and the expected bytes do not depend on whether a packer rounds that product before the 16-bit conversion.
+def row_chan(R):
+    """Packed row R of a 32-row group holds this channel (csrc/tile.h): row 32q + 16b + 4g + e <- channel 32q + 8g + 4b + e."""
+    return (R & ~31) + ((R >> 2) & 3) * 8 + ((R >> 4) & 1) * 4 + (R & 3)
+
+
+def frag_lane(idx):
+    """idx -> (fragment, row inside its 16-row block, first channel of the lane's k-group + e): a fragment is [lane 64][e 8],
+    lane l holds row l & 15, k-group l >> 4."""
+    e, lane = idx & 7, (idx >> 3) & 63
+    return idx >> 9, lane & 15, (lane >> 4) * 8 + e
+
+
+def want_frag_1x1(w, n_out, k, order):
+    frag, row, kc = frag_lane(np.arange(n_out * k))
+    KB, RB = k // 32, n_out // 16
+    rb, kb = (frag // KB, frag % KB) if order == 0 else (frag % RB, frag // RB)
+    return w[row_chan(rb * 16 + row), kb * 32 + kc]
+
+
+def want_l1_conv2(w):                                   # [tap 9][row block 4][kk 2][lane][8]
+    frag, row, kc = frag_lane(np.arange(9 * 64 * 64))
+    kk, rb, tap = frag & 1, (frag >> 1) & 3, frag >> 3
+    return w.reshape(64, 64, 9)[row_chan(rb * 16 + row), kk * 32 + kc, tap]
+
+
+def want_bt_conv2(w, c):                                # [channel half][step = tap * SPT + sub][wave 4][i 2][kk 2][lane][8]
+    spt = c // 64
+    frag, row, kc = frag_lane(np.arange(9 * c * c))
+    kk, i, wv, rest = frag & 1, (frag >> 1) & 1, (frag >> 2) & 3, frag >> 4
+    st, hc = rest % (9 * spt), rest // (9 * spt)
+    tap, sub = st // spt, st % spt
+    return w.reshape(c, c, 9)[row_chan(((hc * 4 + wv) * 2 + i) * 16 + row), (sub * 2 + kk) * 32 + kc, tap]
+
+
+def want_w3d(w3d):                                      # [W3 | Wd] [512, 384]: fragment (p * 2 + rb) * 12 + kb, 32-row pair p
+    frag, row, kc = frag_lane(np.arange(512 * 384))     # (written out from its own comment, not through want_frag_1x1)
+    kb, rb, p = frag % 12, (frag // 12) & 1, frag // 24
+    return w3d[row_chan(p * 32 + rb * 16 + row), kb * 32 + kc]
+
+
+def want_band3x3(w):                                    # [tap][row r][64 channels]
+    idx = np.arange(9 * 64 * 64)
+    return w.reshape(64, 64, 9)[row_chan((idx >> 6) & 63), idx & 63, idx >> 12]
+
+
+def want_stem(w):                                       # [ky][row r][k = kx * 4 + ch], kx < 7 and ch < 3, the rest zero
+    idx = np.arange(7 * 64 * 32)
+    k, r, ky = idx & 31, (idx >> 5) & 63, idx >> 11
+    kx, ch = k >> 2, k & 3
+    ok = (kx < 7) & (ch < 3)
+    return np.where(ok, w[row_chan(r), np.minimum(ch, 2), ky, np.minimum(kx, 6)], np.float32(0))
+
+
+def pow2_scale(seed, n):
+    """n signed powers of two in [2^-3, 2^3]."""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randint(0, 2, (n,), generator=g) * 2 - 1).float() * torch.exp2(torch.randint(-3, 4, (n,), generator=g).float())
+
+
+def packer_cases():
+    """(name, weight shapes, channels the scale runs over, call(L, code, weights, scales, out) -> status, restatement)."""
+    from cp_360_weakly_supervised_saliency_amd._lib import ptr, stream
+    cases = []
+    for n_out, k in ((32, 32), (64, 256)):
+        for order in (0, 1):
+            cases.append(('frag_%dx%d_o%d' % (n_out, k, order), [(n_out, k)],
+                          lambda L, c, w, s, o, n_out=n_out, k=k, order=order:
+                          L.cp360_frag_pack_1x1(c, ptr(w[0]), ptr(s[0]), ptr(o), n_out, k, order, stream()),
+                          lambda w, n_out=n_out, k=k, order=order: want_frag_1x1(w[0], n_out, k, order)))
+    simple = (('l1_conv2', (64, 64, 3, 3), 'cp360_l1block_pack_conv2', want_l1_conv2),
+              ('l2_conv2', (128, 128, 3, 3), 'cp360_l2block_pack_weights', lambda w: want_bt_conv2(w, 128)),
+              ('l3_conv2', (256, 256, 3, 3), 'cp360_l3block_pack_weights', lambda w: want_bt_conv2(w, 256)),
+              ('band3x3', (64, 64, 3, 3), 'cp360_band3x3_pack_weights', want_band3x3),
+              ('stem', (64, 3, 7, 7), 'cp360_stem_pack_weights', want_stem))
+    for name, shape, fn, want in simple:
+        cases.append((name, [shape], lambda L, c, w, s, o, fn=fn: getattr(L, fn)(c, ptr(w[0]), ptr(s[0]), ptr(o), stream()),
+                      lambda w, want=want: want(w[0])))
+    cases.append(('l2first_w3d', [(512, 128), (512, 256)],
+                  lambda L, c, w, s, o: L.cp360_l2first_pack_w3d(c, ptr(w[0]), ptr(s[0]), ptr(w[1]), ptr(s[1]), ptr(o), stream()),
+                  lambda w: want_w3d(np.concatenate([w[0], w[1]], axis=1))))
+    return cases
+
+
+@pytest.mark.gpu
+def test_fused_packers_layouts_bit_exact():
+    from cp_360_weakly_supervised_saliency_amd import _lib
+    L = _lib.lib()
+    BAD_DTYPE = -4                                      # CP360_ERR_BAD_DTYPE (include/cp360.h)
+    assert L.cp360_frag_packed_bytes(_lib.BF16, 48, 32) == 0 and L.cp360_frag_packed_bytes(_lib.F32, 32, 32) == 0
+    for ci, (name, shapes, call, want) in enumerate(packer_cases()):
+        g = torch.Generator().manual_seed(100 + ci)
+        ws = [torch.randn(s, generator=g) for s in shapes]
+        for scaled in (False, True):
+            scs = [pow2_scale(200 + ci + 50 * i, s[0]) if scaled else None for i, s in enumerate(shapes)]
+            # the folded weights in f32 (exact: the scales are powers of two), then the restated layout
+            folded = [(w if sc is None else w * sc.reshape(-1, *([1] * (w.dim() - 1)))).numpy() for w, sc in zip(ws, scs)]
+            flat = torch.from_numpy(np.ascontiguousarray(want(folded), dtype=np.float32))
+            dw = [w.to(DEV) for w in ws]
+            dsc = [None if sc is None else sc.to(DEV) for sc in scs]
+            for dt, code in ((BF16, _lib.BF16), (F16, _lib.F16)):
+                out = torch.full((flat.numel() * 2,), 0xA5, dtype=torch.uint8, device=DEV)
+                assert call(L, code, dw, dsc, out) == 0, (name, dt)
+                torch.cuda.synchronize()
+                assert torch.equal(out.cpu(), bits(flat.to(dt)).reshape(-1)), (name, dt, scaled)
+            out = torch.zeros(flat.numel() * 2, dtype=torch.uint8, device=DEV)
+            assert call(L, _lib.F32, dw, dsc, out) == BAD_DTYPE, name
