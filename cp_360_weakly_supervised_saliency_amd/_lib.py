@@ -55,6 +55,10 @@ PUBLIC_SYMBOLS = [
     'cp360_flow_loss_backward',
     # K5o: fused Adam
     'cp360_train_adam', 'cp360_train_adam_conv',
+    # K10: Farneback optical flow
+    'cp360_optflow_levels_host', 'cp360_optflow_gauss_host', 'cp360_optflow_poly_tables_host', 'cp360_optflow_gray',
+    'cp360_optflow_pyr_level', 'cp360_optflow_poly_exp', 'cp360_optflow_matrices', 'cp360_optflow_blur_solve',
+    'cp360_optflow_flow_upsample', 'cp360_optflow_work_bytes', 'cp360_optflow_farneback',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -239,6 +243,18 @@ def lib():
     dbl = C.c_double
     L.cp360_train_adam.argtypes = [vp, vp, vp, vp, C.c_longlong, dbl, dbl, dbl, dbl, dbl, dbl, dbl, vp]
     L.cp360_train_adam_conv.argtypes = [vp, vp, vp, vp, i, i, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i, vp, vp, vp, i, i, vp]
+    L.cp360_optflow_levels_host.argtypes = [i, i, dbl, i, i, vp, vp, vp, vp]
+    L.cp360_optflow_gauss_host.argtypes = [i, dbl, vp]
+    L.cp360_optflow_poly_tables_host.argtypes = [i, dbl, vp, vp, vp, vp]
+    L.cp360_optflow_gray.argtypes = [vp, vp, C.c_longlong, vp]
+    L.cp360_optflow_pyr_level.argtypes = [vp, i, i, i, i, dbl, vp, i, i, vp, vp]
+    L.cp360_optflow_poly_exp.argtypes = [vp, i, i, i, i, dbl, vp, vp]
+    L.cp360_optflow_matrices.argtypes = [vp, vp, sz, vp, vp, i, i, i, vp]
+    L.cp360_optflow_blur_solve.argtypes = [vp, vp, i, i, i, i, vp]
+    L.cp360_optflow_flow_upsample.argtypes = [vp, i, i, i, vp, i, i, f, vp]
+    L.cp360_optflow_work_bytes.restype = sz
+    L.cp360_optflow_work_bytes.argtypes = [i, i, i, dbl, i]
+    L.cp360_optflow_farneback.argtypes = [vp, i, i, i, dbl, i, i, i, i, dbl, i, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

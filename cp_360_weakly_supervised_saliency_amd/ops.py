@@ -1264,3 +1264,121 @@ def flow_loss_backward(maps, flow, grad_loss, mm_th):
     check(lib().cp360_flow_loss_backward(_lib.F32, ptr(maps), ptr(flow), ptr(grad_loss), B, L, w, h, wl, float(mm_th),
                                          ptr(dmaps), ptr(work), stream()))
     return dmaps
+
+
+# ----------------------------------------------------------------------------- K10: Farneback optical flow
+def optflow_levels(H, W, pyr_scale=0.5, levels=7):
+    """cp360_optflow_levels_host (no GPU needed): [(h, w, ksz, sigma)] of pyramid levels k = 0 (full size) .. L."""
+    L = lib().cp360_optflow_levels_host(int(H), int(W), float(pyr_scale), int(levels), 0, None, None, None, None)
+    if L < 0:
+        check(L)
+    hs, ws, ks = (np.empty(L + 1, dtype=np.int32) for _ in range(3))
+    sg = np.empty(L + 1, dtype=np.float64)
+    vp = C.c_void_p
+    rc = lib().cp360_optflow_levels_host(int(H), int(W), float(pyr_scale), int(levels), L + 1, hs.ctypes.data_as(vp),
+                                         ws.ctypes.data_as(vp), ks.ctypes.data_as(vp), sg.ctypes.data_as(vp))
+    if rc < 0:
+        check(rc)
+    return [(int(hs[k]), int(ws[k]), int(ks[k]), float(sg[k])) for k in range(L + 1)]
+
+
+def optflow_gauss_kernel(ksz, sigma):
+    """cp360_optflow_gauss_host (no GPU needed): the f32 taps of a pyramid level's Gaussian."""
+    taps = np.empty(max(int(ksz), 1), dtype=np.float32)
+    check(lib().cp360_optflow_gauss_host(int(ksz), float(sigma), taps.ctypes.data_as(C.c_void_p)))
+    return taps
+
+
+def optflow_poly_tables(poly_n=5, poly_sigma=1.2):
+    """cp360_optflow_poly_tables_host (no GPU needed): g, xg, xxg f32 [2n + 1] and ig f32 [4] = (ig11, ig03, ig33, ig55)."""
+    n = int(poly_n)
+    g, xg, xxg = (np.empty(2 * max(n, 0) + 1, dtype=np.float32) for _ in range(3))
+    ig = np.empty(4, dtype=np.float32)
+    vp = C.c_void_p
+    check(lib().cp360_optflow_poly_tables_host(n, float(poly_sigma), g.ctypes.data_as(vp), xg.ctypes.data_as(vp),
+                                               xxg.ctypes.data_as(vp), ig.ctypes.data_as(vp)))
+    return g, xg, xxg, ig
+
+
+def _optflow_images(name, t, trailing=()):
+    """A contiguous f32 [..., h, w] + trailing tensor seen as [N, h, w] + trailing: (N, h, w)."""
+    nd = 2 + len(trailing)
+    if t.dim() < nd or tuple(t.shape[t.dim() - len(trailing):]) != tuple(trailing):
+        raise ValueError("%s must be [..., h, w%s], got %s" % (name, ''.join(', %d' % s for s in trailing), tuple(t.shape)))
+    _check_buf(name, t, torch.float32)
+    h, w = int(t.shape[-nd]), int(t.shape[-nd + 1])
+    return int(t.numel() // max(h * w * int(np.prod(trailing, dtype=np.int64)), 1)), h, w
+
+
+def optflow_gray(rgb):
+    """cp360_optflow_gray: u8 [..., 3] resized frames as the video reader delivers them -> f32 [...] gray 0 .. 255 (channels
+    reversed, then cv2's BGR2GRAY integer arithmetic: the reference's quirk)."""
+    require_gpu(rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() < 1 or rgb.shape[-1] != 3 or rgb.numel() == 0:
+        raise ValueError("rgb must be a non-empty uint8 [..., 3] tensor")
+    rgb = rgb.contiguous()
+    out = torch.empty(rgb.shape[:-1], dtype=torch.float32, device=rgb.device)
+    check(lib().cp360_optflow_gray(ptr(rgb), ptr(out), out.numel(), stream()))
+    return out
+
+
+def optflow_pyr_level(gray, ksz, sigma, lh, lw):
+    """cp360_optflow_pyr_level: f32 [..., H, W] -> [..., lh, lw] = bilinear resize of the ksz x ksz Gaussian blur."""
+    require_gpu(gray)
+    N, H, W = _optflow_images('gray', gray)
+    out = torch.empty(tuple(gray.shape[:-2]) + (int(lh), int(lw)), dtype=torch.float32, device=gray.device)
+    tmp = torch.empty_like(gray)
+    check(lib().cp360_optflow_pyr_level(ptr(gray), N, H, W, int(ksz), float(sigma), ptr(out), int(lh), int(lw), ptr(tmp),
+                                        stream()))
+    return out
+
+
+def optflow_poly_exp(img, poly_n=5, poly_sigma=1.2):
+    """cp360_optflow_poly_exp: f32 [..., h, w] -> R [..., 5, h, w] (planar), the coefficients of [y, x, y^2, x^2, xy]."""
+    require_gpu(img)
+    N, h, w = _optflow_images('img', img)
+    R = torch.empty(tuple(img.shape[:-2]) + (5, h, w), dtype=torch.float32, device=img.device)
+    check(lib().cp360_optflow_poly_exp(ptr(img), N, h, w, int(poly_n), float(poly_sigma), ptr(R), stream()))
+    return R
+
+
+def optflow_matrices(R0, R1, flow):
+    """cp360_optflow_matrices: R0 (prev), R1 (next) f32 [P, 5, h, w] or [5, h, w], flow f32 [P, h, w, 2] or [h, w, 2]
+    -> M of R0's shape."""
+    require_gpu(R0, R1, flow)
+    if R0.shape != R1.shape or R0.dim() not in (3, 4) or R0.shape[-3] != 5:
+        raise ValueError("R0 and R1 must both be [P, 5, h, w] or [5, h, w], got %s and %s" % (tuple(R0.shape), tuple(R1.shape)))
+    h, w = int(R0.shape[-2]), int(R0.shape[-1])
+    P = int(R0.shape[0]) if R0.dim() == 4 else 1
+    _check_buf('R0', R0, torch.float32)
+    _check_buf('R1', R1, torch.float32)
+    _check_buf('flow', flow, torch.float32, numel=P * h * w * 2)
+    if tuple(flow.shape[-3:]) != (h, w, 2):
+        raise ValueError("flow must be [P, h, w, 2] for R [P, 5, h, w], got %s" % (tuple(flow.shape),))
+    M = torch.empty_like(R0)
+    check(lib().cp360_optflow_matrices(ptr(R0), ptr(R1), 5 * h * w, ptr(flow), ptr(M), P, h, w, stream()))
+    return M
+
+
+def optflow_blur_solve(M, winsize=15):
+    """cp360_optflow_blur_solve: M f32 [P, 5, h, w] or [5, h, w] -> flow [P, h, w, 2] or [h, w, 2]."""
+    require_gpu(M)
+    if M.dim() not in (3, 4) or M.shape[-3] != 5:
+        raise ValueError("M must be [P, 5, h, w] or [5, h, w], got %s" % (tuple(M.shape),))
+    if int(winsize) < 1 or int(winsize) % 2 == 0:
+        raise ValueError("winsize must be odd, got %s" % (winsize,))
+    _check_buf('M', M, torch.float32)
+    h, w = int(M.shape[-2]), int(M.shape[-1])
+    P = int(M.shape[0]) if M.dim() == 4 else 1
+    flow = torch.empty(tuple(M.shape[:-3]) + (h, w, 2), dtype=torch.float32, device=M.device)
+    check(lib().cp360_optflow_blur_solve(ptr(M), ptr(flow), P, h, w, int(winsize), stream()))
+    return flow
+
+
+def optflow_flow_upsample(flow, h_out, w_out, mul):
+    """cp360_optflow_flow_upsample: f32 [..., h, w, 2] -> [..., h_out, w_out, 2] = bilinear resize times mul."""
+    require_gpu(flow)
+    P, h, w = _optflow_images('flow', flow, (2,))
+    out = torch.empty(tuple(flow.shape[:-3]) + (int(h_out), int(w_out), 2), dtype=torch.float32, device=flow.device)
+    check(lib().cp360_optflow_flow_upsample(ptr(flow), P, h, w, ptr(out), int(h_out), int(w_out), float(mul), stream()))
+    return out

@@ -8,6 +8,8 @@ keeps these tensors in HBM).
 * ``<out>/<video>/{:05}.npy`` - float32 [2w, 4w]: the temporal model's equirectangular saliency map of
   the window ending at that frame (test_temporal.py:86-88); ground-truth fixation maps use the same
   naming under ``Wild360_GT/<video>.mp4/`` (:101-102).
+* ``<out>/<video>/motion/{:06}.npy`` - float32 [H, W, 2]: the optical flow (dx, dy) from one frame to the next, written by
+  dataset_feat_extractor.py:190-192 under the number of the EARLIER frame's ``cube_feat`` and read by data/dataset.py:31-34,55-57.
 """
 import os
 
@@ -16,6 +18,10 @@ import numpy as np
 
 def cube_feat_path(video_dir, frame_no):
     return os.path.join(video_dir, 'cube_feat', '{0:06}.npy'.format(int(frame_no)))
+
+
+def motion_path(video_dir, frame_no):
+    return os.path.join(video_dir, 'motion', '{0:06}.npy'.format(int(frame_no)))
 
 
 def saliency_path(out_dir, video, frame_no):
@@ -54,3 +60,15 @@ def save_saliency(out_dir, video, frame_no, sal):
     sal = sal.detach().cpu().numpy() if hasattr(sal, 'detach') else np.asarray(sal)
     os.makedirs(os.path.join(out_dir, video), exist_ok=True)
     np.save(saliency_path(out_dir, video, frame_no), sal.astype(np.float32))
+
+
+def save_motions(video_dir, flows, first_frame_no=2):
+    """flows [F, H, W, 2] (host or device; ``utils.optical_flow.FarnebackFlow``'s output) -> one .npy per pair.  The
+    extractor's index rule: the flow from frame i to frame i + 1 (counting from 0) is saved under i + first_frame_no, the
+    number of frame i's ``cube_feat`` file (``save_cube_feats`` with the same first_frame_no)."""
+    flows = flows.detach().cpu().numpy() if hasattr(flows, 'detach') else np.asarray(flows)
+    if flows.ndim != 4 or flows.shape[-1] != 2:
+        raise ValueError("flows must be [F, H, W, 2], got %s" % (flows.shape,))
+    os.makedirs(os.path.join(video_dir, 'motion'), exist_ok=True)
+    for t in range(flows.shape[0]):
+        np.save(motion_path(video_dir, first_frame_no + t), np.ascontiguousarray(flows[t], dtype=np.float32))

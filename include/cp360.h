@@ -452,6 +452,48 @@ int cp360_overlay_colorize(const float* heat, int h, int w, int square, const ui
 int cp360_overlay_blend_u8(const uint8_t* img, const uint8_t* heat_rgb, uint8_t* out, long long n_bytes,
                            float alpha, void* stream);
 
+/* ------------------------------------------------------------------ K10: Farneback optical flow
+ * cv2.calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, 0), the
+ * alternative the reference carries beneath its DeepFlow call (utils/optical_flow.py:32), batched over the F + 1 frames of a
+ * video: every frame's pyramid level and polynomial expansion is computed once, pair p uses frames p and p + 1.  The
+ * specification is DESIGN.md "K10"; tests/farneback_restate.py restates it in float64.  f32, no atomics, fixed-order sums:
+ * bit-reproducible and independent of the batch size.  Sign: prev(y, x) ~ next(y + flow[y, x, 1], x + flow[y, x, 0]).
+ *
+ * Layouts: images f32 [N, h, w]; R f32 [N, 5, h, w] and M f32 [P, 5, h, w] planar; flow f32 [P, h, w, 2] = (dx, dy).
+ *
+ * Host routines (no GPU):
+ *   levels_host        the pyramid of an H x W image: returns L (the number of coarser levels) or a negative status and fills
+ *                      h, w, ksz, sigma of levels k = 0 (full size) .. L where the pointers are not NULL (cap entries each;
+ *                      all four NULL: the count alone).  cvRound = round half to even.
+ *   gauss_host         the ksz taps (f32, normalised in double) of a level's Gaussian; sigma 0: ksz 3, {0.25, 0.5, 0.25}.
+ *   poly_tables_host   g, xg, xxg f32 [2n + 1] and ig = {ig11, ig03, ig33, ig55} of the polynomial expansion (n <= 7). */
+int cp360_optflow_levels_host(int H, int W, double pyr_scale, int levels, int cap, int* hs, int* ws, int* ksz, double* sigma);
+int cp360_optflow_gauss_host(int ksz, double sigma, float* taps);
+int cp360_optflow_poly_tables_host(int n, double sigma, float* g, float* xg, float* xxg, float* ig);
+/* The stages, one entry point each (device pointers):
+ *   gray           rgb u8 [n_pixels, 3] (a frame already resized, channels as the video reader delivers them) -> gray f32
+ *                  [n_pixels] = (c0 1868 + c1 9617 + c2 4899 + 8192) >> 14 on the REVERSED channels (c0 = rgb[2])
+ *   pyr_level      gray f32 [N, H, W] -> out f32 [N, lh, lw]: ksz x ksz Gaussian (reflect-101, folded as often as it takes),
+ *                  then the bilinear resize with the arithmetic of cp360_resize_linear_f32; tmp f32 [N, H, W] scratch; ksz <= 255
+ *   poly_exp       img f32 [N, h, w] -> R [N, 5, h, w] = the local coefficients of [y, x, y^2, x^2, xy]; replicate-clamped
+ *   matrices       pair p: R0 + p r_stride (prev), R1 + p r_stride (next), flow [P, h, w, 2] -> M [P, 5, h, w]
+ *   blur_solve     M [P, 5, h, w] -> flow [P, h, w, 2]: winsize^2 box mean (odd, <= 33; replicate-clamped) and the 2 x 2 solve
+ *   flow_upsample  flow [P, h, w, 2] -> out [P, h_out, w_out, 2] = bilinear resize times mul */
+int cp360_optflow_gray(const uint8_t* rgb, float* gray, long long n_pixels, void* stream);
+int cp360_optflow_pyr_level(const float* gray, int N, int H, int W, int ksz, double sigma, float* out, int lh, int lw, float* tmp,
+                            void* stream);
+int cp360_optflow_poly_exp(const float* img, int N, int h, int w, int poly_n, double poly_sigma, float* R, void* stream);
+int cp360_optflow_matrices(const float* R0, const float* R1, size_t r_stride, const float* flow, float* M, int P, int h, int w,
+                           void* stream);
+int cp360_optflow_blur_solve(const float* M, float* flow, int P, int h, int w, int winsize, void* stream);
+int cp360_optflow_flow_upsample(const float* flow, int P, int h, int w, float* out, int h_out, int w_out, float mul, void* stream);
+/* gray f32 [F + 1, H, W] (0 .. 255) -> flow f32 [F, H, W, 2] on the stream; work: 16-byte aligned device memory of at least
+ * the queried size (0: unsupported geometry), owned by the caller.  flags other than 0 (Gaussian window, initial flow):
+ * CP360_ERR_UNSUPPORTED; an even winsize: CP360_ERR_BAD_SHAPE. */
+size_t cp360_optflow_work_bytes(int F, int H, int W, double pyr_scale, int levels);
+int cp360_optflow_farneback(const float* gray, int F, int H, int W, double pyr_scale, int levels, int winsize, int iterations,
+                            int poly_n, double poly_sigma, int flags, float* flow, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
