@@ -246,30 +246,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
     auto set_tap = [&](int tap) __attribute__((always_inline)) {
         const int ky = tap / p.kw, kx = tap - ky * p.kw;
 #pragma unroll
-        for (int pb = 0; pb < B_PASSES; ++pb) {
-            const int m = m0 + row0 + 32 * pb;
-            int off = -1;
-            if (m < p.M) {
-                const int img = m / p.hw_out, rem = m - img * p.hw_out;
-                const int oy = rem / p.w_out, ox = rem - oy * p.w_out;
-                const int py = oy * p.sy + ky, px = ox * p.sx + kx;
-                int pix;
-                if (p.pad_mode) {
-                    const int grp = img / 6, f = img - grp * 6;
-                    pix = grp * 6 * p.h_in * p.w_in + cubepad_src(f, py, px, geom);
-                } else {
-                    pix = (img * p.h_in + py) * p.w_in + px;
-                }
-                off = pix * p.pix_stride;
-            }
-            roff[pb] = off;
-        }
+        for (int pb = 0; pb < B_PASSES; ++pb) CP360_SRC_PIXEL_OFF(roff[pb], false, m0 + row0 + 32 * pb, ky, kx, geom)
     };
 
     const int s_begin = split * p.steps_per_split;
     const int s_end = min(p.nsteps, s_begin + p.steps_per_split);
-    int tap = s_begin / p.steps_per_tap;
-    int c0 = (s_begin - tap * p.steps_per_tap) * BK;
+    int tap, c0;
+    CP360_SPLIT_START(tap, c0, false, s_begin, p.steps_per_tap, BK)
 
     const T* in = reinterpret_cast<const T*>(p.in);
     const T* wbase = reinterpret_cast<const T*>(p.w) + (size_t)(n0 + row0) * p.k_total + chunk * EPC;
@@ -302,14 +285,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
         _Pragma("unroll") for (int pb = 0; pb < B_PASSES; ++pb)                                          \
             *reinterpret_cast<u32x4*>(Bs_ + lds_swz(row0 + 32 * pb, chunk)) = RB[pb];                    \
     }
-    auto advance = [&]() __attribute__((always_inline)) {
-        c0 += BK;
-        if (c0 >= p.c_pad) {
-            c0 = 0;
-            ++tap;
-            set_tap(tap);
-        }
-    };
+    auto advance = [&]() __attribute__((always_inline)) { CP360_K_ADVANCE(tap, c0, BK, p.c_pad, true, set_tap) };
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -376,42 +352,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvK p) {
 #undef CP360_GLOAD
 #undef CP360_LDS_STORE
     // ---- epilogue: through LDS (full-line accesses) unless it is a split-K slab or misaligned
-    if (!p.partial && (p.c_out % EPC == 0) && (p.ld_out % EPC == 0) && (p.out_coff % EPC == 0) &&
-        (p.ld_res % EPC == 0)) {
+    if (CP360_VECTOR_EPILOGUE_OK(EPC)) {
         epilogue_lds<T, BN, BM, 4, 256, 2 * STAGE>(p, lds, acc, n0, m0, wn * 64, wm * 64, lane, tid);
         return;
     }
-    // ---- epilogue: lane holds channels n..n+3 of pixel m for every (i, j) sub-tile
+    // ---- element-wise epilogue (conv_common.h): lane holds channels n..n+3 of pixel m for every (i, j) sub-tile
     const int ml = lane & 15;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wn * 64 + acc_chan(i, lane);
-        if (n >= p.c_out) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = m0 + wm * 64 + j * 16 + ml;
-            if (m >= p.M) continue;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.partial) {
-                store4(p.partial + ((size_t)split * p.M + m) * p.c_out + (p.slab_rows ? slab_col(n) : n), v);
-            } else {
-                if (p.bias) {
-                    const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
-                    v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-                }
-                if (p.res) {
-                    float r[4];
-                    load4(reinterpret_cast<const T*>(p.res) + (size_t)m * p.ld_res + n, r);
-                    v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
-                }
-                if (p.relu) {
-                    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f);
-                    v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                }
-                store4(reinterpret_cast<T*>(p.out) + (size_t)m * p.ld_out + p.out_coff + n, v);
-            }
-        }
-    }
+    CP360_EPILOGUE_SCALAR(acc, 4, n0 + wn * 64, 0, m0 + wm * 64, p.M)
 }
 
 // ------------------------------------------------------------------ wide-tile LDS-DMA kernel
@@ -446,31 +393,14 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     auto set_tap = [&](int tap) __attribute__((always_inline)) {
         const int ky = tap / p.kw, kx = tap - ky * p.kw;
 #pragma unroll
-        for (int pb = 0; pb < B_PASSES; ++pb) {
-            const int m = m0 + drow + 64 * pb;
-            int off = -1;
-            if (m < p.M) {
-                const int img = m / p.hw_out, rem = m - img * p.hw_out;
-                const int oy = rem / p.w_out, ox = rem - oy * p.w_out;
-                const int py = oy * p.sy + ky, px = ox * p.sx + kx;
-                int pix;
-                if (p.pad_mode) {
-                    const int grp = img / 6, f = img - grp * 6;
-                    pix = grp * 6 * p.h_in * p.w_in + cubepad_src(f, py, px, geom);
-                } else {
-                    pix = (img * p.h_in + py) * p.w_in + px;
-                }
-                off = pix * p.pix_stride;
-            }
-            roff[pb] = off;
-        }
+        for (int pb = 0; pb < B_PASSES; ++pb) CP360_SRC_PIXEL_OFF(roff[pb], false, m0 + drow + 64 * pb, ky, kx, geom)
     };
 
     const int s_begin = split * p.steps_per_split;
     const int s_end = min(p.nsteps, s_begin + p.steps_per_split);
     const int nloc = s_end - s_begin;
-    int tap = s_begin / p.steps_per_tap;
-    int c0 = (s_begin - tap * p.steps_per_tap) * BK;
+    int tap, c0;
+    CP360_SPLIT_START(tap, c0, false, s_begin, p.steps_per_tap, BK)
 
     const T* in = reinterpret_cast<const T*>(p.in);
     const T* wbase = reinterpret_cast<const T*>(p.w) + (size_t)(n0 + drow) * p.k_total + dchunk * EPC;
@@ -495,14 +425,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
 #pragma unroll
         for (int q = 0; q < DMA_PER_STEP; ++q) issue_one(q, sbase);
     };
-    auto advance = [&]() __attribute__((always_inline)) {
-        c0 += BK;
-        if (c0 >= p.c_pad) {
-            c0 = 0;
-            ++tap;
-            set_tap(tap);
-        }
-    };
+    auto advance = [&]() __attribute__((always_inline)) { CP360_K_ADVANCE(tap, c0, BK, p.c_pad, true, set_tap) };
 
     f32x4 acc[4][MJ];
 #pragma unroll
@@ -563,43 +486,14 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_dma_kernel(const ConvK p) {
     }
 
     // ---- epilogue: through LDS (full-line accesses) unless it is a split-K slab or misaligned
-    const int ml = lane & 15;
-    const bool lds_epi = !p.partial && (p.c_out % EPC == 0) && (p.ld_out % EPC == 0) && (p.out_coff % EPC == 0) &&
-                         (p.ld_res % EPC == 0);
+    const int ml = lane & 15;                                  // (the element-wise nest's; where it is declared is part of the code)
+    const bool lds_epi = CP360_VECTOR_EPILOGUE_OK(EPC);
     if (lds_epi) {
         epilogue_lds<T, BN, BM, MJ, 512, (PIPE_BYTES > EPI_BYTES ? PIPE_BYTES : EPI_BYTES)>(
             p, lds, acc, n0, m0, wn * 64, wm * (16 * MJ), lane, tid);
         return;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wn * 64 + acc_chan(i, lane);
-        if (n >= p.c_out) continue;
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-            const int m = m0 + wm * (16 * MJ) + j * 16 + ml;
-            if (m >= p.M) continue;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.partial) {
-                store4(p.partial + ((size_t)split * p.M + m) * p.c_out + (p.slab_rows ? slab_col(n) : n), v);
-            } else {
-                if (p.bias) {
-                    const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
-                    v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-                }
-                if (p.res) {
-                    float r[4];
-                    load4(reinterpret_cast<const T*>(p.res) + (size_t)m * p.ld_res + n, r);
-                    v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
-                }
-                if (p.relu) {
-                    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f);
-                    v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                }
-                store4(reinterpret_cast<T*>(p.out) + (size_t)m * p.ld_out + p.out_coff + n, v);
-            }
-        }
-    }
+    CP360_EPILOGUE_SCALAR(acc, MJ, n0 + wn * 64, 0, m0 + wm * (16 * MJ), p.M)      // element-wise (conv_common.h)
 }
 
 // ------------------------------------------------------------------ 256 x {256, 304} tile, 4-stage ring
@@ -659,6 +553,9 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
 
     int roff[B_PASSES];
     const CubePadGeom geom{p.h_in, p.pad, p.pad, p.pad, p.pad};
+    // The source-pixel map of CP360_SRC_PIXEL_OFF (conv_common.h), WRITTEN OUT: with the macro - in either order of its second-source
+    // branch and with the partial-pass guard inside or around it - the 160 / 256 / 304-pixel ring kernels compiled to other code
+    // (DESIGN.md, section 3).  A change to the map is made in both places; test_conv_source_pixel_map_of_every_loader runs both.
     auto set_tap = [&](int tap) __attribute__((always_inline)) {
         const int ky = tap / p.kw, kx = tap - ky * p.kw;
         const bool sec = tap >= p.ntap;                        // the second source's tap (wave-uniform)
@@ -693,8 +590,8 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
     const int s_end = 2 * min(p.nsteps, (split + 1) * p.steps_per_split);
     const int nloc = s_end - s_begin;
     const int sub_per_tap = 2 * p.steps_per_tap;
-    int tap = min(s_begin / sub_per_tap, p.ntap);              // ntap = the second source's tap (if any)
-    int c0 = (s_begin - tap * sub_per_tap) * BKS;
+    int tap, c0;
+    CP360_SPLIT_START(tap, c0, true, s_begin, sub_per_tap, BKS)
 
     const T* in = reinterpret_cast<const T*>(p.in);
     const T* in2 = reinterpret_cast<const T*>(p.in2);
@@ -722,14 +619,8 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
         for (int q = 0; q < D0; ++q) issue_one(q, sbase);
         if (G::XWAVES > 0 && xw) issue_one(D0, sbase);
     };
-    auto advance = [&]() __attribute__((always_inline)) {
-        c0 += BKS;
-        if (c0 >= p.c_pad && tap < p.ntap) {                   // (the second source's tap is the last one)
-            c0 = 0;
-            ++tap;
-            set_tap(tap);
-        }
-    };
+    // (the second source's tap is the last one)
+    auto advance = [&]() __attribute__((always_inline)) { CP360_K_ADVANCE(tap, c0, BKS, p.c_pad, tap < p.ntap, set_tap) };
 
     f32x4 acc[4][MJ];
 #pragma unroll
@@ -812,45 +703,16 @@ __device__ __forceinline__ void ring_body(const ConvK& p, unsigned char* lds, co
 #undef CP360_RING_TAIL
     }
 
-    const int ml = lane & 15;
+    const int ml = lane & 15;                                  // (the element-wise nest's; where it is declared is part of the code)
     if (!p.partial && p.epi_direct) {
         epilogue_direct<T, MJ>(p, acc, n0, m0, wch0, wrow0, lane, BM);
         return;
     }
-    if (!p.partial && (p.c_out % EPC == 0) && (p.ld_out % EPC == 0) && (p.out_coff % EPC == 0) &&
-        (p.ld_res % EPC == 0)) {
+    if (CP360_VECTOR_EPILOGUE_OK(EPC)) {
         epilogue_lds<T, BN, BM, MJ, 512, G::template lds_bytes<T>()>(p, lds, acc, n0, m0, wch0, wrow0, lane, tid);
         return;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wch0 + acc_chan(i, lane);
-        if (n >= p.c_out) continue;
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-            const int m = m0 + wrow0 + j * 16 + ml;
-            if (m >= p.M) continue;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.partial) {
-                store4(p.partial + ((size_t)split * p.M + m) * p.c_out + (p.slab_rows ? slab_col(n) : n), v);
-            } else {
-                if (p.bias) {
-                    const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
-                    v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-                }
-                if (p.res) {
-                    float r[4];
-                    load4(reinterpret_cast<const T*>(p.res) + (size_t)m * p.ld_res + n, r);
-                    v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
-                }
-                if (p.relu) {
-                    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f);
-                    v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                }
-                store4(reinterpret_cast<T*>(p.out) + (size_t)m * p.ld_out + p.out_coff + n, v);
-            }
-        }
-    }
+    CP360_EPILOGUE_SCALAR(acc, MJ, n0 + wch0, 0, m0 + wrow0, p.M)                  // element-wise (conv_common.h)
 }
 
 template <typename T, int BM>
@@ -1160,42 +1022,12 @@ __device__ __forceinline__ void clip_body(const ConvK& p, unsigned char* lds, co
 #undef CP360_CLIP_TAIL
     }
 
-    const int ml = lane & 15;
-    if (!p.partial && (p.c_out % EPC == 0) && (p.ld_out % EPC == 0) && (p.out_coff % EPC == 0) &&
-        (p.ld_res % EPC == 0)) {
+    const int ml = lane & 15;                                  // (the element-wise nest's; where it is declared is part of the code)
+    if (CP360_VECTOR_EPILOGUE_OK(EPC)) {
         epilogue_lds<T, BN, BM, MJ, 512, G::LDS_BYTES>(p, lds, acc, n0, m0, wch0, wrow0, lane, tid, rows_valid);
         return;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wch0 + acc_chan(i, lane);
-        if (n >= p.c_out) continue;
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-            const int row = wrow0 + j * 16 + ml;
-            if (row >= rows_valid) continue;
-            const int m = m0 + row;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.partial) {
-                store4(p.partial + ((size_t)split * p.M + m) * p.c_out + (p.slab_rows ? slab_col(n) : n), v);
-            } else {
-                if (p.bias) {
-                    const float4 bb = *reinterpret_cast<const float4*>(p.bias + n);
-                    v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-                }
-                if (p.res) {
-                    float r[4];
-                    load4(reinterpret_cast<const T*>(p.res) + (size_t)m * p.ld_res + n, r);
-                    v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
-                }
-                if (p.relu) {
-                    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f);
-                    v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                }
-                store4(reinterpret_cast<T*>(p.out) + (size_t)m * p.ld_out + p.out_coff + n, v);
-            }
-        }
-    }
+    CP360_EPILOGUE_SCALAR(acc, MJ, n0 + wch0, m0, wrow0, rows_valid)               // element-wise: rows counted inside the clip
 }
 
 // ------------------------------------------------------------------ pointwise 64 -> 64 (16-bit): layer1.0's conv1

@@ -56,38 +56,9 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     const int chunk = tid & 7, row0 = tid >> 3;        // this thread's 16-byte chunk of weight row row0 AND of pixel row row0
 
     // ---- source-offset table: element offset of tile row r's input pixel for tap t, offtab[t * 64 + r] (-1: no such output
-    // pixel).  All divisions and the branchy cubepad_src() run HERE, once per (tap, row); inside the K loop a tap change is
-    // one LDS read per thread.  (Computed in the loop - as conv_igemm_kernel does - the divergent code and the waits the
-    // compiler merges at its join points cost more than the MFMAs of a 64 x 64 tile.)
+    // pixel), built once; inside the K loop a tap change is one LDS read per thread (CP360_BUILD_OFFTAB of conv_common.h)
     __shared__ int offtab[MAX_TAPS * BM];
-    {
-        const int ntap_all = p.ntap + (p.c_in2 > 0 ? 1 : 0);
-        const CubePadGeom geom{p.h_in, p.pad, p.pad, p.pad, p.pad};
-        for (int t = tid; t < ntap_all * BM; t += NT) {
-            const int tp = t >> 6, r = t & 63;
-            const int m = m0 + r;
-            int off = -1;
-            if (m < p.M) {
-                const int img = m / p.hw_out, rem = m - img * p.hw_out;
-                const int oy = rem / p.w_out, ox = rem - oy * p.w_out;
-                if (tp >= p.ntap) {
-                    off = ((img * p.h_in2 + oy * p.sy2) * p.w_in2 + ox * p.sx2) * p.pix_stride2;
-                } else {
-                    const int ky = tp / p.kw, kx = tp - ky * p.kw;
-                    const int py = oy * p.sy + ky, px = ox * p.sx + kx;
-                    int pix;
-                    if (p.pad_mode) {
-                        const int grp = img / 6, f = img - grp * 6;
-                        pix = grp * 6 * p.h_in * p.w_in + cubepad_src(f, py, px, geom);
-                    } else {
-                        pix = (img * p.h_in + py) * p.w_in + px;
-                    }
-                    off = pix * p.pix_stride;
-                }
-            }
-            offtab[t] = off;
-        }
-    }
+    CP360_BUILD_OFFTAB(offtab, m0, tid, NT)
     __syncthreads();
     const T* in = reinterpret_cast<const T*>(p.in);
     const T* in2 = reinterpret_cast<const T*>(p.in2);
@@ -106,6 +77,9 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
 
     const int s_begin = split * p.steps_per_split;
     const int s_end = min(p.nsteps, s_begin + p.steps_per_split);
+    // first (tap, c0) of this split: what CP360_SPLIT_START (conv_common.h) computes with a second source, WRITTEN OUT in the
+    // branch form both small-tile kernels were built with - the macro's min() form compiles all three to other code (same
+    // instruction and VGPR counts, another order and SGPR spill count)
     const int first_steps = p.ntap * p.steps_per_tap;
     int tap, c0;
     if (s_begin < first_steps) {
@@ -161,12 +135,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
     int issued = 0;                                       // K steps requested so far
     auto next_gload = [&](u32x4& sa, u32x4& sb, int& sm) __attribute__((always_inline)) {
         if (issued > 0 && issued < nloc) {                // (uniform) move on to the next step; past the end: repeat the last
-            c0 += BK;
-            if (c0 >= src_cpad) {
-                c0 = 0;
-                ++tap;
-                set_tap(tap);
-            }
+            CP360_K_ADVANCE(tap, c0, BK, src_cpad, true, set_tap)
         }
         ++issued;
         gload(sa, sb, sm);
@@ -250,57 +219,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
             for (int e = 0; e < 4; ++e) acc[i][j][e] += xch[((pair * 16) + (i * 2 + j) * 4 + e) * 64 + lane];
 
     // ---- epilogue: a lane owns channels n .. n+7 of pixel m for each of its two pixel blocks
-    const int ml = lane & 15;
-    const int n = n0 + wn * 32 + (lane >> 4) * 8;
-    if (n >= p.c_out) return;                              // c_out % 8 == 0 on this path
-    float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!p.partial && p.bias) {
-        const float4 t0 = *reinterpret_cast<const float4*>(p.bias + n);
-        const float4 t1 = *reinterpret_cast<const float4*>(p.bias + n + 4);
-        bb[0] = t0.x; bb[1] = t0.y; bb[2] = t0.z; bb[3] = t0.w; bb[4] = t1.x; bb[5] = t1.y; bb[6] = t1.z; bb[7] = t1.w;
-    }
-    const T* res = reinterpret_cast<const T*>(p.res);
-    T* outp = reinterpret_cast<T*>(p.out);
-    u32x4 rr[2];
-    if (!p.partial && res) {                               // both pixel blocks' residual pieces in flight together
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int m = m0 + wm * 32 + j * 16 + ml;
-            const T* s = m < p.M ? res + (size_t)m * p.ld_res + n : reinterpret_cast<const T*>(g_zero16);
-            rr[j] = *reinterpret_cast<const u32x4*>(s);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int m = m0 + wm * 32 + j * 16 + ml;
-        if (m >= p.M) continue;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = acc[0][j][e];
-            v[4 + e] = acc[1][j][e];
-        }
-        if (p.partial) {
-            float* dst = p.partial + ((size_t)split * p.M + m) * p.c_out;
-            store4(dst + (p.slab_rows ? slab_col(n) : n), v);
-            store4(dst + (p.slab_rows ? slab_col(n + 4) : n + 4), v + 4);
-            continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += bb[e];
-        if (res) {
-            float r[8];
-            unpack8(rr[j], r, T());
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += r[e];
-        }
-        if (p.relu) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        T* dst = outp + (size_t)m * p.ld_out + p.out_coff + n;
-        *reinterpret_cast<u32x4*>(dst) = pack8(v, T());
-    }
+    CP360_EPILOGUE_SMALL8(acc, n0 + wn * 32 + (lane >> 4) * 8, m0 + wm * 32, CP360_ADD_RES8_16BIT)
 }
 
 // ------------------------------------------------------------------ f32 form: one wave per SIMD, fillers inside the MFMA gaps
@@ -312,7 +231,8 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const ConvK p) {
 // here ONE wave per SIMD issues the step's 32 MFMAs and places one or two of the other instructions in each gap (the placement
 // is pinned with sched_barrier; cdna_hip_programming.md, 4-wave attention structure: "budget every MFMA gap to <= 5 issues"):
 // the next step's eight fragment reads, the staged chunks' LDS stores, the address update and the four global loads.
-// Everything else - tile, work mapping, source-offset table, epilogue, split-K, second source - is the kernel above.
+// Everything else - tile, work mapping, source-offset table, epilogue, split-K, second source - is the kernel above's (the table and
+// the epilogue are the same text: CP360_BUILD_OFFTAB, CP360_EPILOGUE_SMALL8 of conv_common.h).
 __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     typedef float T;
     constexpr int BN = 64, BM = 64, NT = 256;
@@ -328,35 +248,8 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     conv_tile_of(p, BN, BM, &n0, &m0, &split);
     const int chunk = tid & 7, row0 = tid >> 3;        // this thread's chunk of weight rows row0, row0 + 32 and pixel rows row0, row0 + 32
 
-    __shared__ int offtab[MAX_TAPS * BM];              // see conv_small_kernel
-    {
-        const int ntap_all = p.ntap + (p.c_in2 > 0 ? 1 : 0);
-        const CubePadGeom geom{p.h_in, p.pad, p.pad, p.pad, p.pad};
-        for (int t = tid; t < ntap_all * BM; t += NT) {
-            const int tp = t >> 6, r = t & 63;
-            const int m = m0 + r;
-            int off = -1;
-            if (m < p.M) {
-                const int img = m / p.hw_out, rem = m - img * p.hw_out;
-                const int oy = rem / p.w_out, ox = rem - oy * p.w_out;
-                if (tp >= p.ntap) {
-                    off = ((img * p.h_in2 + oy * p.sy2) * p.w_in2 + ox * p.sx2) * p.pix_stride2;
-                } else {
-                    const int ky = tp / p.kw, kx = tp - ky * p.kw;
-                    const int py = oy * p.sy + ky, px = ox * p.sx + kx;
-                    int pix;
-                    if (p.pad_mode) {
-                        const int grp = img / 6, f = img - grp * 6;
-                        pix = grp * 6 * p.h_in * p.w_in + cubepad_src(f, py, px, geom);
-                    } else {
-                        pix = (img * p.h_in + py) * p.w_in + px;
-                    }
-                    off = pix * p.pix_stride;
-                }
-            }
-            offtab[t] = off;
-        }
-    }
+    __shared__ int offtab[MAX_TAPS * BM];              // [tap][tile row] source offsets, as in the 16-bit form
+    CP360_BUILD_OFFTAB(offtab, m0, tid, NT)
     __syncthreads();
     const T* in = reinterpret_cast<const T*>(p.in);
     const T* in2 = reinterpret_cast<const T*>(p.in2);
@@ -376,6 +269,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     };
     const int s_begin = split * p.steps_per_split;
     const int s_end = min(p.nsteps, s_begin + p.steps_per_split);
+    // first (tap, c0) of this split, in the branch form (see the 16-bit kernel above)
     const int first_steps = p.ntap * p.steps_per_tap;
     int tap, c0;
     if (s_begin < first_steps) {
@@ -398,12 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
     const T* cur_a = src;
     auto advance = [&]() __attribute__((always_inline)) {  // (uniform) the next step to request; past the end: repeat the last
         if (issued > 0 && issued < nloc) {
-            c0 += BK;
-            if (c0 >= src_cpad) {
-                c0 = 0;
-                ++tap;
-                set_tap(tap);
-            }
+            CP360_K_ADVANCE(tap, c0, BK, src_cpad, true, set_tap)
         }
         ++issued;
         cur_w = wtile + (size_t)tap * p.c_pad + c0;
@@ -538,61 +427,8 @@ __global__ __launch_bounds__(256, 2) void conv_small_f32_kernel(const ConvK p) {
 #undef CP360_S4_LOADA
 #undef CP360_S4_LOADW
 
-    // ---- epilogue: a lane owns channels n .. n+7 of pixel m for each of its two pixel blocks (as conv_small_kernel)
-    const int ml = lane & 15;
-    const int n = n0 + wn * 32 + (lane >> 4) * 8;
-    if (n >= p.c_out) return;
-    float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!p.partial && p.bias) {
-        const float4 t0 = *reinterpret_cast<const float4*>(p.bias + n);
-        const float4 t1 = *reinterpret_cast<const float4*>(p.bias + n + 4);
-        bb[0] = t0.x; bb[1] = t0.y; bb[2] = t0.z; bb[3] = t0.w; bb[4] = t1.x; bb[5] = t1.y; bb[6] = t1.z; bb[7] = t1.w;
-    }
-    const T* res = reinterpret_cast<const T*>(p.res);
-    T* outp = reinterpret_cast<T*>(p.out);
-    u32x4 rr[2][2];
-    if (!p.partial && res) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int m = m0 + wm * 32 + j * 16 + ml;
-            const T* sp = m < p.M ? res + (size_t)m * p.ld_res + n : reinterpret_cast<const T*>(g_zero16);
-            rr[j][0] = *reinterpret_cast<const u32x4*>(sp);
-            rr[j][1] = *reinterpret_cast<const u32x4*>(m < p.M ? sp + 4 : sp);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int m = m0 + wm * 32 + j * 16 + ml;
-        if (m >= p.M) continue;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = acc[0][j][e];
-            v[4 + e] = acc[1][j][e];
-        }
-        if (p.partial) {
-            float* dst = p.partial + ((size_t)split * p.M + m) * p.c_out;
-            store4(dst + (p.slab_rows ? slab_col(n) : n), v);
-            store4(dst + (p.slab_rows ? slab_col(n + 4) : n + 4), v + 4);
-            continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += bb[e];
-        if (res) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] += __uint_as_float(rr[j][0][e]);
-                v[4 + e] += __uint_as_float(rr[j][1][e]);
-            }
-        }
-        if (p.relu) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        T* dst = outp + (size_t)m * p.ld_out + p.out_coff + n;
-        *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
+    // ---- epilogue: a lane owns channels n .. n+7 of pixel m for each of its two pixel blocks
+    CP360_EPILOGUE_SMALL8(acc, n0 + wn * 32 + (lane >> 4) * 8, m0 + wm * 32, CP360_ADD_RES8_F32)
 }
 
 }  // namespace

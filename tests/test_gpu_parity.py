@@ -951,6 +951,48 @@ def test_conv_element_wise_epilogue_of_every_kernel_family(family, prec):
         assert rel_err(sums.transpose(0, 3, 1, 2), want_raw) <= tol, (slab_rows, rel_err(sums.transpose(0, 3, 1, 2), want_raw))
 
 
+_SRC_MAP_GEOMS = {'cubepad_3x3_stride2': (3, 2, 1), 'plain_1x1_stride2': (1, 2, 0)}       # filter size, stride, CubePad width
+_SRC_MAP_REF = {}
+
+
+def _src_map_operands(prec, geom):
+    """One cube of 10x10 faces, 96 -> 256 channels, 5x5 output faces (M = 150): the operands and the torch-CPU reference on the
+    operands rounded to prec.  Computed once per (precision, geometry) and shared by every loader family."""
+    if (prec, geom) not in _SRC_MAP_REF:
+        k, stride, pad = _SRC_MAP_GEOMS[geom]
+        n_img, cin, cout, n = 6, 96, 256, 10
+        x = hashrng.normal(9700 + k, (n_img, cin, n, n))
+        w = hashrng.normal(9710 + k, (cout, cin, k, k), 0, (2.0 / (k * k * cin)) ** 0.5)
+        bias = hashrng.normal(9720, (cout,), 0, 0.1)
+        rb = (lambda a: torch.from_numpy(a).to(_TDT[prec]).float().numpy()) if prec != 'fp32' else (lambda a: a)
+        _SRC_MAP_REF[(prec, geom)] = (x, w, bias, _conv_ref(rb(x), rb(w), None, bias, stride, pad, False))
+    return _SRC_MAP_REF[(prec, geom)]
+
+
+# (tile_px = 160, the 160-pixel ring tile, exists for the 16-bit types only: check_desc refuses it in fp32, which
+# test_wide_conv_160_pixel_tile asserts - that one case is left out here)
+@pytest.mark.parametrize('tile_px,prec', [(t, p) for t in (64, 128, 256, 304, 160, 6464) for p in ('fp32', 'bf16') if (t, p) != (160, 'fp32')])
+def test_conv_source_pixel_map_of_every_loader(tile_px, prec):
+    """Output pixel, tap -> input pixel (CP360_SRC_PIXEL_OFF of csrc/conv_common.h and the ring body's own copy) and the
+    (tap, channel) at which a K split starts, in every loader family: the 128 x 128 register-staged kernel (tile_px 64), the
+    256 x 128 LDS-DMA kernel (128), the 256 / 304 / 160-pixel rings and the small tile's offset table (6464).  One cube of 10x10
+    faces, 96 -> 256 channels, stride 2 -> 5x5 output faces, M = 150 pixels: a ragged 64-pixel tile, one full and one ragged
+    128-pixel part; (a) CubePad(1) + 3x3, (b) an unpadded 1x1.  splits = 4: bf16 has two 128-byte steps per tap, 18 steps in
+    splits of 5 start at steps 5 and 15 = inside taps 2 and 7, the last split is 3 steps short; fp32 has three per tap, 27 steps
+    in splits of 7 start inside taps 2 and 4, the last split is one short (the 1x1 has fewer steps than splits: empty splits).  No ReLU, so that a wrong
+    source pixel is not clamped away.  Against torch-CPU on identically rounded operands."""
+    dt = _TDT[prec]
+    for geom, (k, stride, pad) in _SRC_MAP_GEOMS.items():
+        x, w, bias, want = _src_map_operands(prec, geom)
+        conv = ops.Conv(torch.from_numpy(w), None, torch.from_numpy(bias), stride, pad, False, dt, DEV)
+        xt = ops.nchw_to_nhwc(torch.from_numpy(x).to(DEV), out_dtype=dt)
+        for splits in (1, 4):
+            got = ops.nhwc_to_nchw(conv(xt, splits=splits, tile_px=tile_px), out_dtype=torch.float32).cpu().numpy()
+            err = rel_err(got, want)
+            print(tile_px, prec, geom, splits, err)
+            assert got.shape == want.shape and err <= _TOL[prec], (geom, splits, err)
+
+
 @pytest.mark.parametrize('prec', ['fp32', 'bf16', 'fp16'])
 def test_stem_conv_and_maxpool(prec):
     dt = _TDT[prec]
