@@ -59,6 +59,8 @@ PUBLIC_SYMBOLS = [
     'cp360_optflow_levels_host', 'cp360_optflow_gauss_host', 'cp360_optflow_poly_tables_host', 'cp360_optflow_gray',
     'cp360_optflow_pyr_level', 'cp360_optflow_poly_exp', 'cp360_optflow_matrices', 'cp360_optflow_blur_solve',
     'cp360_optflow_flow_upsample', 'cp360_optflow_work_bytes', 'cp360_optflow_farneback',
+    # K11: 360-degree stabilisation
+    'cp360_stab_work_bytes', 'cp360_stab_fit', 'cp360_stab_flow', 'cp360_stab_rotate',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -255,8 +257,13 @@ def lib():
     L.cp360_optflow_work_bytes.restype = sz
     L.cp360_optflow_work_bytes.argtypes = [i, i, i, dbl, i]
     L.cp360_optflow_farneback.argtypes = [vp, i, i, i, dbl, i, i, i, i, dbl, i, vp, vp, sz, vp]
+    L.cp360_stab_work_bytes.restype = sz
+    L.cp360_stab_work_bytes.argtypes = [i, i, i]
+    L.cp360_stab_fit.argtypes = [vp, i, i, i, i, dbl, vp, vp, vp, sz, vp]
+    L.cp360_stab_flow.argtypes = [vp, i, i, i, vp, vp, sz, vp]
+    L.cp360_stab_rotate.argtypes = [i, vp, vp, i, i, i, i, vp, vp, sz, vp]
     for name in SYMBOLS:
-        getattr(L, name)          # AttributeError here = header and library disagree
+        getattr(L, name)         # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):
         raise ImportError("%s is a stale build: version %d / cp360_conv_desc %d bytes, the binding expects %d / %d "
                           "- rebuild it (__graft_entry__.build())"

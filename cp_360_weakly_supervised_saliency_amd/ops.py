@@ -1382,3 +1382,73 @@ def optflow_flow_upsample(flow, h_out, w_out, mul):
     out = torch.empty(tuple(flow.shape[:-3]) + (int(h_out), int(w_out), 2), dtype=torch.float32, device=flow.device)
     check(lib().cp360_optflow_flow_upsample(ptr(flow), P, h, w, ptr(out), int(h_out), int(w_out), float(mul), stream()))
     return out
+
+
+# ----------------------------------------------------------------------------- K11: 360-degree stabilisation (csrc/stabilize.hip)
+def _stab_work(F, H, W, device, work=None):
+    """The workspace of one K11 call: `work` when it is large enough, else a new one (F = 0: the tables alone)."""
+    nbytes = lib().cp360_stab_work_bytes(int(F), int(H), int(W))
+    if nbytes == 0:
+        raise ValueError("stabilisation: unsupported geometry: %d x %d x %d" % (F, H, W))
+    if work is None or work.device != device or work.numel() * 8 < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
+def _stab_rotations(R, n=None):
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1 or (n is not None and R.shape[0] != n):
+        raise ValueError("R must be [%s, 3, 3], got %s" % ('F' if n is None else n, tuple(R.shape)))
+    _check_buf('R', R, torch.float32)
+
+
+def rotation_fit(flow, iters=8, c_min_px=0.25, work=None):
+    """cp360_stab_fit: flow f32 [F, H, W, 2] (K10's convention) -> (R f32 [F, 3, 3], diag f64 [F, 4]): the camera rotation of
+    every pair (a scene direction p of frame t is seen at R_t p in frame t + 1) and (final scale in px, sum of weights, weighted
+    RMS residual in px, |delta| of the last iteration)."""
+    require_gpu(flow)
+    if flow.dim() != 4 or flow.shape[3] != 2 or flow.numel() == 0:
+        raise ValueError("flow must be a non-empty [F, H, W, 2], got %s" % (tuple(flow.shape),))
+    _check_buf('flow', flow, torch.float32)
+    if int(iters) < 1 or not float(c_min_px) > 0.0:
+        raise ValueError("iters must be at least 1 and c_min_px positive, got %r, %r" % (iters, c_min_px))
+    F, H, W = (int(s) for s in flow.shape[:3])
+    work = _stab_work(F, H, W, flow.device, work)
+    R = torch.empty((F, 3, 3), dtype=torch.float32, device=flow.device)
+    diag = torch.empty((F, 4), dtype=torch.float64, device=flow.device)
+    check(lib().cp360_stab_fit(ptr(flow), F, H, W, int(iters), float(c_min_px), ptr(R), ptr(diag), ptr(work), work.numel() * 8,
+                               stream()))
+    return R, diag
+
+
+def rotation_flow(R, H, W, work=None):
+    """cp360_stab_flow: R f32 [F, 3, 3] -> G f32 [F, H, W, 2] = pix(R dir(x, y)) - (x, y), x wrapped into [-W / 2, W / 2)."""
+    require_gpu(R)
+    _stab_rotations(R)
+    F, H, W = int(R.shape[0]), int(H), int(W)
+    work = _stab_work(0, H, W, R.device, work)
+    G = torch.empty((F, H, W, 2), dtype=torch.float32, device=R.device)
+    check(lib().cp360_stab_flow(ptr(R), F, H, W, ptr(G), ptr(work), work.numel() * 8, stream()))
+    return G
+
+
+def equirect_rotate(frames, R, out=None, work=None):
+    """cp360_stab_rotate: out[n](x, y) = bilinear(frames[n], pix(R[n] dir(x, y))), columns wrap, rows clamp; frames u8
+    [N, H, W, 3] or f32 [N, H, W, C], C <= 4; R f32 [N, 3, 3]; the output has the frames' type and size."""
+    require_gpu(frames, R, out)
+    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3] or float32 [N, H, W, C], got %s %s"
+                         % (frames.dtype, tuple(frames.shape)))
+    N, H, W, C = (int(s) for s in frames.shape)
+    if C > 4 or (frames.dtype == torch.uint8 and C != 3):
+        raise ValueError("frames must have 3 channels (uint8) or at most 4 (float32), got %d" % C)
+    _check_buf('frames', frames, frames.dtype)
+    _stab_rotations(R, N)
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.shape != frames.shape or out.device != frames.device or out.data_ptr() == frames.data_ptr():
+        raise ValueError("out must be another tensor of the frames' shape on their device")
+    _check_buf('out', out, frames.dtype)
+    work = _stab_work(0, H, W, frames.device, work)
+    check(lib().cp360_stab_rotate(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, ptr(out), ptr(work),
+                                  work.numel() * 8, stream()))
+    return out

@@ -1,0 +1,96 @@
+"""360-degree stabilisation of an equirectangular video (K11, csrc/stabilize.hip): the reference trains its temporal model on
+"stationary videos (without camera motion)" only and leaves the rest to the user (README: "you might want to compensate camera
+motion and apply 360 stabilization").  For an equirectangular frame a camera rotation is a remapping of the sphere: it is fitted
+to the optical flow of every frame pair (K10 + ``ops.rotation_fit``) and removed by re-rendering the frames
+(``ops.equirect_rotate``).  The definition is the package's own (DESIGN.md "K11").
+
+``Stabilizer`` is the driver: ``rotations`` gives the per-pair and the cumulative camera rotations of F + 1 frames, ``stabilize``
+the frames in the first frame's orientation - the input of ``SaliencyEngine`` and ``FarnebackFlow`` alike - and ``from_frames``
+the flows of the stabilised video, which is what ``utils.npy_io.save_motions`` and ``train_step`` are fed for a moving camera.
+Translation and parallax of the camera stay in the flow.
+"""
+import numpy as np
+import torch
+
+from .. import ops
+from .optical_flow import FarnebackFlow
+
+
+def orthonormalise(M):
+    """The rows of a float64 [3, 3] near-rotation by Gram-Schmidt (exact on I)."""
+    r0 = M[0] / np.linalg.norm(M[0])
+    r1 = M[1] - (M[1] @ r0) * r0
+    r1 = r1 / np.linalg.norm(r1)
+    r2 = M[2] - (M[2] @ r0) * r0 - (M[2] @ r1) * r1
+    return np.stack([r0, r1, r2 / np.linalg.norm(r2)])
+
+
+def compose(R):
+    """R [F, 3, 3] (host) -> C float64 [F + 1, 3, 3]: C_0 = I, C_t+1 = R_t C_t, the chain in float64 and every C_t
+    re-orthonormalised once on the way out: a scene direction p of frame 0's camera is seen at C_t p in frame t."""
+    R = np.asarray(R, np.float64)
+    C, out = np.eye(3), [np.eye(3)]
+    for f in range(R.shape[0]):
+        C = R[f] @ C
+        out.append(orthonormalise(C))
+    return np.stack(out)
+
+
+class Stabilizer:
+    """``Stabilizer((H, W))``: the rotation fit runs on flows of H x W (the frames are resized for it as ``FarnebackFlow`` does),
+    the re-rendering at the frames' own resolution.  Holds the ``FarnebackFlow`` and the K11 workspaces."""
+
+    def __init__(self, hw=(480, 960), device='cuda', iters=8, c_min_px=0.25):
+        if int(iters) < 1 or not float(c_min_px) > 0.0:
+            raise ValueError("iters must be at least 1 and c_min_px positive, got %r, %r" % (iters, c_min_px))
+        self.hw = (int(hw[0]), int(hw[1]))
+        self.device = torch.device(device)
+        self.iters, self.c_min_px = int(iters), float(c_min_px)
+        self.flow = FarnebackFlow(self.hw, device=device)
+        self._fit_work = None
+        self._tab_work = {}
+        self.diag = None                         # f64 [F, 4] of the last fit (device)
+
+    def _frames(self, frames):
+        if not torch.is_tensor(frames):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 2:
+            raise ValueError("frames must be uint8 [F + 1, h, w, 3] with F >= 1, got %s %s" % (frames.dtype, tuple(frames.shape)))
+        return frames.to(self.device).contiguous()
+
+    def rotations(self, frames):
+        """frames u8 [F + 1, h, w, 3] -> (R f32 [F, 3, 3], C f32 [F + 1, 3, 3]) on the device."""
+        frames = self._frames(frames)
+        H, W = self.hw
+        flows = self.flow.from_frames(frames, res=(W, H))
+        F = int(flows.shape[0])
+        self._fit_work = ops._stab_work(F, H, W, flows.device, self._fit_work)
+        R, self.diag = ops.rotation_fit(flows, self.iters, self.c_min_px, work=self._fit_work)
+        C = compose(R.cpu().numpy())
+        return R, torch.from_numpy(C.astype(np.float32)).to(self.device)
+
+    def stabilize(self, frames):
+        """frames u8 [F + 1, h, w, 3] -> (the frames in frame 0's orientation, S_t(p) = frame_t(C_t p), u8 on the device; C).
+        Frame 0 is copied."""
+        frames = self._frames(frames)
+        _, C = self.rotations(frames)
+        out = torch.empty_like(frames)
+        out[0].copy_(frames[0])
+        self.render(frames[1:], C[1:], out=out[1:])
+        return out, C
+
+    def render(self, frames, C, out=None):
+        """frames u8 [N, h, w, 3] under the rotations C f32 [N, 3, 3] (for instance ``rotations``' C after a smoothing of the
+        caller's): out[n](p) = frames[n](C[n] p), at the frames' own resolution, on the device."""
+        if not torch.is_tensor(frames):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = frames.to(self.device).contiguous()
+        C = torch.as_tensor(C, dtype=torch.float32).to(self.device).contiguous()
+        h, w = int(frames.shape[1]), int(frames.shape[2])
+        work = self._tab_work[(h, w)] = ops._stab_work(0, h, w, frames.device, self._tab_work.get((h, w)))
+        return ops.equirect_rotate(frames, C, out=out, work=work)
+
+    def from_frames(self, frames):
+        """frames u8 [F + 1, h, w, 3] -> the flows f32 [F, H, W, 2] of the stabilised video, on the device."""
+        H, W = self.hw
+        return self.flow.from_frames(self.stabilize(frames)[0], res=(W, H))

@@ -494,6 +494,34 @@ size_t cp360_optflow_work_bytes(int F, int H, int W, double pyr_scale, int level
 int cp360_optflow_farneback(const float* gray, int F, int H, int W, double pyr_scale, int levels, int winsize, int iterations,
                             int poly_n, double poly_sigma, int flags, float* flow, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K11: 360-degree stabilisation
+ * The camera rotation between the frames of an equirectangular video, fitted to the flow K10 computes, and the frames re-rendered
+ * without it.  The reference has no counterpart (its README leaves moving cameras to the user): the specification is the
+ * package's own, DESIGN.md "K11", restated in float64 in tests/stabilize_restate.py.  Pixel (x, y) of an H x W image looks along
+ * dir(x, y) = (cos phi cos theta, sin phi, cos phi sin theta), theta = (2 (x + 1/2) / W - 1) pi, phi = (1 - 2 (y + 1/2) / H) pi / 2
+ * (utils/sph_utils.py); pix() is its inverse.  Rotations are f32 [.., 3, 3], row-major.
+ *
+ *   fit      flow f32 [F, H, W, 2] (K10's convention) -> R f32 [F, 3, 3]: a scene direction p of frame t's camera is seen at
+ *            R_t p in frame t + 1; diag f64 [F, 4] = {the scale c after the last update, in pixels; sum of weights, weighted RMS
+ *            residual in pixels and |delta| of the last iteration}.  Gauss-Newton on the robust Wahba problem: iteration 0 is
+ *            plain least squares with the solid-angle weight cos phi, later ones weigh by cos phi / (1 + r^2 / c^2)^2 with c
+ *            halved per iteration down to c_min_px pixels.  Per-pixel terms f32, sums f64 in a fixed order, no atomics: bit-
+ *            reproducible and independent of F.  Non-finite flow values weigh 0; a singular system (all weights 0, fewer than 3
+ *            independent directions) leaves R = I with the diagnostics' sum of weights 0.  2 + 2 iters launches, no
+ *            host synchronisation.
+ *   flow     R [F, 3, 3] -> G f32 [F, H, W, 2] = pix(R dir(x, y)) - (x, y), x wrapped into [-W / 2, W / 2): what fit inverts
+ *   rotate   out[n](x, y) = bilinear(frames[n], pix(R[n] dir(x, y))), columns wrap modulo W, rows clamp to 0 .. H - 1;
+ *            frames u8 [N, H, W, 3] (rintf, half to even) or f32 [N, H, W, C], C <= 4 (CP360_ERR_UNSUPPORTED above); not in place
+ * work: 16-byte aligned device memory of cp360_stab_work_bytes(F, H, W) bytes for fit, of cp360_stab_work_bytes(0, H, W) bytes
+ * for flow and rotate (the per-row and per-column sin / cos tables every call rebuilds); 0 = bad or unsupported sizes.  A
+ * workspace that is too small: CP360_ERR_BAD_SHAPE. */
+size_t cp360_stab_work_bytes(int F, int H, int W);
+int cp360_stab_fit(const float* flow, int F, int H, int W, int iters, double c_min_px, float* R, double* diag, void* work,
+                   size_t work_bytes, void* stream);
+int cp360_stab_flow(const float* R, int F, int H, int W, float* G, void* work, size_t work_bytes, void* stream);
+int cp360_stab_rotate(int dtype, const void* frames, const float* R, int N, int H, int W, int C, void* out, void* work,
+                      size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
