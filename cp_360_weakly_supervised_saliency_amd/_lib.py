@@ -61,6 +61,8 @@ PUBLIC_SYMBOLS = [
     'cp360_optflow_flow_upsample', 'cp360_optflow_work_bytes', 'cp360_optflow_farneback',
     # K11: 360-degree stabilisation
     'cp360_stab_work_bytes', 'cp360_stab_fit', 'cp360_stab_flow', 'cp360_stab_rotate',
+    # K12: the viewport pilot
+    'cp360_view_render', 'cp360_view_outline', 'cp360_view_smooth', 'cp360_view_peak',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -262,6 +264,10 @@ def lib():
     L.cp360_stab_fit.argtypes = [vp, i, i, i, i, dbl, vp, vp, vp, sz, vp]
     L.cp360_stab_flow.argtypes = [vp, i, i, i, vp, vp, sz, vp]
     L.cp360_stab_rotate.argtypes = [i, vp, vp, i, i, i, i, vp, vp, sz, vp]
+    L.cp360_view_render.argtypes = [i, vp, vp, i, i, i, i, dbl, vp, i, i, vp]
+    L.cp360_view_outline.argtypes = [vp, vp, i, i, i, dbl, i, i, dbl, vp, vp, vp, sz, vp]
+    L.cp360_view_smooth.argtypes = [vp, i, i, i, dbl, vp, vp, sz, vp]
+    L.cp360_view_peak.argtypes = [vp, vp, i, i, i, dbl, vp, vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)         # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

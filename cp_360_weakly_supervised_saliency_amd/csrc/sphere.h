@@ -1,0 +1,134 @@
+// The sphere geometry of an equirectangular image, shared by stabilize.hip (K11) and viewport.hip (K12): the one definition of
+// dir, pix, the rotation of a direction, the (cos, sin) tables of the pixel centres and the bilinear sample that wraps in x and
+// clamps in y (DESIGN.md "K11" geometry; tests/stabilize_restate.py restates it).
+//
+//     theta = (2 (x + 1/2) / W - 1) pi        phi = (1 - 2 (y + 1/2) / H) pi / 2        dir = (cos phi cos theta, sin phi, cos phi sin theta)
+//     pix(q): theta = atan2(q_z, q_x), phi = asin(clamp(q_y, -1, 1)), x = (theta / pi + 1) W / 2 - 1/2, y = (1 - phi / (pi / 2)) H / 2 - 1/2
+//
+// Every term is f32 with plain operators: the including file switches contraction off before it includes this header
+// (#pragma clang fp contract(off)), so that a float32 restatement follows the kernels operation by operation.  Everything here
+// has internal linkage: each file that includes it compiles its own copy.
+#pragma once
+#include "common.h"
+#include "../../include/cp360.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr float kInvPi = 0.318309886183790671538f;
+constexpr float kTwoOverPi = 0.636619772367581343076f;
+
+struct Rot {
+    float r00, r01, r02, r10, r11, r12, r20, r21, r22;
+};
+
+// direction of pixel centre (x, y) from its column's (cos, sin) theta and its row's (cos, sin) phi
+__device__ __forceinline__ void stab_dir(const float2 cs_theta, const float2 cs_phi, float& px, float& py, float& pz) {
+    px = cs_phi.x * cs_theta.x;
+    py = cs_phi.y;
+    pz = cs_phi.x * cs_theta.y;
+}
+
+__device__ __forceinline__ void stab_rotate(const Rot& R, float px, float py, float pz, float& qx, float& qy, float& qz) {
+    qx = R.r00 * px + R.r01 * py + R.r02 * pz;
+    qy = R.r10 * px + R.r11 * py + R.r12 * pz;
+    qz = R.r20 * px + R.r21 * py + R.r22 * pz;
+}
+
+// pix(q) in pixel-index units; half_w = W / 2, half_h = H / 2
+__device__ __forceinline__ void stab_pix(float qx, float qy, float qz, float half_w, float half_h, float& sx, float& sy) {
+    const float theta = atan2f(qz, qx);
+    const float phi = asinf(fminf(fmaxf(qy, -1.f), 1.f));
+    sx = (theta * kInvPi + 1.f) * half_w - 0.5f;
+    sy = (1.f - phi * kTwoOverPi) * half_h - 0.5f;
+}
+
+__device__ __forceinline__ Rot load_rot(const float* R) {
+    Rot r;
+    r.r00 = R[0]; r.r01 = R[1]; r.r02 = R[2];
+    r.r10 = R[3]; r.r11 = R[4]; r.r12 = R[5];
+    r.r20 = R[6]; r.r21 = R[7]; r.r22 = R[8];
+    return r;
+}
+
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(uint8_t v) { return (float)v; }
+__device__ __forceinline__ void store_px(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_px(uint8_t* p, float v) { *p = (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f); }
+
+// The C channels of the H x W image `img` at the real position (sx, sy), bilinear: four taps, columns wrap modulo W, rows
+// clamp to 0 .. H - 1, top + ty (bot - top).  A non-finite position (a non-finite R) samples inside the frame.
+template <typename T, int C>
+__device__ __forceinline__ void sphere_sample(const T* img, int H, int W, float sx, float sy, T* o) {
+    if (!(fabsf(sx) <= (float)W)) sx = 0.f;                            // a non-finite R: stay inside the frame
+    sy = fminf(fmaxf(sy, 0.f), (float)(H - 1));                        // fmaxf(NaN, 0) = 0
+    const float x0f = floorf(sx), y0f = floorf(sy);
+    const float tx = sx - x0f, ty = sy - y0f;
+    int x0 = (int)x0f % W;
+    if (x0 < 0) x0 += W;
+    const int x1 = x0 + 1 == W ? 0 : x0 + 1;
+    const int y0 = (int)y0f;
+    const int y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+    const T* p00 = img + ((size_t)y0 * W + x0) * C;
+    const T* p01 = img + ((size_t)y0 * W + x1) * C;
+    const T* p10 = img + ((size_t)y1 * W + x0) * C;
+    const T* p11 = img + ((size_t)y1 * W + x1) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float v00 = to_f32(p00[c]), v01 = to_f32(p01[c]), v10 = to_f32(p10[c]), v11 = to_f32(p11[c]);
+        const float top = v00 + tx * (v01 - v00);
+        const float bot = v10 + tx * (v11 - v10);
+        store_px(o + c, top + ty * (bot - top));
+    }
+}
+
+// ------------------------------------------------------------------ tables
+// tabx f32 [W][2] = (cos, sin) theta, taby f32 [H][2] = (cos, sin) phi: cospi / sinpi of the exact fraction in double
+__global__ __launch_bounds__(256) void stab_tables_kernel(float2* __restrict__ tabx, float2* __restrict__ taby, int H, int W) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < W) {
+        const double t = (double)(2 * i + 1) / (double)W - 1.0;              // theta / pi
+        tabx[i] = make_float2((float)cospi(t), (float)sinpi(t));
+    } else if (i < W + H) {
+        const int y = i - W;
+        const double t = 0.5 * (1.0 - (double)(2 * y + 1) / (double)H);      // phi / pi
+        taby[y] = make_float2((float)cospi(t), (float)sinpi(t));
+    }
+}
+
+// ------------------------------------------------------------------ host side
+bool bad_image(int N, int h, int w) {
+    return N <= 0 || h <= 0 || w <= 0;
+}
+// grid y = rows, grid z = images; the pixel index of one image stays an int
+bool big_image(int N, int h, int w) {
+    return N > 65535 || h > 65535 || (long long)h * w > (1LL << 28);
+}
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// the tables at the head of a workspace: byte offsets, and the bytes they take = cp360_stab_work_bytes(0, H, W)
+struct TabLayout {
+    size_t tabx, taby, total;
+};
+
+TabLayout tab_layout(int H, int W) {
+    TabLayout t;
+    t.tabx = 0;
+    t.taby = align16((size_t)W * sizeof(float2));
+    t.total = t.taby + align16((size_t)H * sizeof(float2));
+    return t;
+}
+
+int launch_tables(void* work, int H, int W, hipStream_t s) {
+    const TabLayout t = tab_layout(H, W);
+    hipLaunchKernelGGL(stab_tables_kernel, dim3((H + W + 255) / 256), dim3(256), 0, s, (float2*)((char*)work + t.tabx),
+                       (float2*)((char*)work + t.taby), H, W);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+}  // namespace

@@ -19,12 +19,9 @@
 // of 11 sums per workgroup (registers, wave shuffles, LDS across the 4 waves); one wave per pair adds the partials (lane l takes
 // l, l + 64, ... in order, then the shuffle tree), solves and updates the pair's state in the workspace.  No atomics, no host
 // synchronisation, results independent of the batch size.
-#include "common.h"
-#include "../../include/cp360.h"
-
-#include <math.h>
-
 #pragma clang fp contract(off)
+
+#include "sphere.h"
 
 namespace {
 
@@ -33,21 +30,8 @@ constexpr int kFitBlock = 256 * kFitPx;      // pixels per workgroup = per parti
 constexpr int kSums = 11;                    // Nxx Nxy Nxz Nyy Nyz Nzz bx by bz sum_w sum_w_r2
 constexpr int kPartial = 12;                 // doubles per partial (padded)
 constexpr int kState = 16;                   // doubles per pair: R[9], c, dead, 1 / c^2
-constexpr float kInvPi = 0.318309886183790671538f;
-constexpr float kTwoOverPi = 0.636619772367581343076f;
 
-struct Rot {
-    float r00, r01, r02, r10, r11, r12, r20, r21, r22;
-};
-
-// ------------------------------------------------------------------ geometry: the one definition
-// direction of pixel centre (x, y) from its column's (cos, sin) theta and its row's (cos, sin) phi
-__device__ __forceinline__ void stab_dir(const float2 cs_theta, const float2 cs_phi, float& px, float& py, float& pz) {
-    px = cs_phi.x * cs_theta.x;
-    py = cs_phi.y;
-    pz = cs_phi.x * cs_theta.y;
-}
-
+// ------------------------------------------------------------------ geometry: dir, pix, the rotation and the sampler are sphere.h's
 // direction of (x + dx, y + dy): the angle sums theta + dx 2 pi / W and phi - dy pi / H
 __device__ __forceinline__ void stab_dir_moved(const float2 cs_theta, const float2 cs_phi, float dx, float dy, float kx, float ky,
                                                float& px, float& py, float& pz) {
@@ -61,42 +45,6 @@ __device__ __forceinline__ void stab_dir_moved(const float2 cs_theta, const floa
     px = cp * ct;
     py = sp;
     pz = cp * st;
-}
-
-__device__ __forceinline__ void stab_rotate(const Rot& R, float px, float py, float pz, float& qx, float& qy, float& qz) {
-    qx = R.r00 * px + R.r01 * py + R.r02 * pz;
-    qy = R.r10 * px + R.r11 * py + R.r12 * pz;
-    qz = R.r20 * px + R.r21 * py + R.r22 * pz;
-}
-
-// pix(q) in pixel-index units; half_w = W / 2, half_h = H / 2
-__device__ __forceinline__ void stab_pix(float qx, float qy, float qz, float half_w, float half_h, float& sx, float& sy) {
-    const float theta = atan2f(qz, qx);
-    const float phi = asinf(fminf(fmaxf(qy, -1.f), 1.f));
-    sx = (theta * kInvPi + 1.f) * half_w - 0.5f;
-    sy = (1.f - phi * kTwoOverPi) * half_h - 0.5f;
-}
-
-__device__ __forceinline__ Rot load_rot(const float* R) {
-    Rot r;
-    r.r00 = R[0]; r.r01 = R[1]; r.r02 = R[2];
-    r.r10 = R[3]; r.r11 = R[4]; r.r12 = R[5];
-    r.r20 = R[6]; r.r21 = R[7]; r.r22 = R[8];
-    return r;
-}
-
-// ------------------------------------------------------------------ tables
-// tabx f32 [W][2] = (cos, sin) theta, taby f32 [H][2] = (cos, sin) phi: cospi / sinpi of the exact fraction in double
-__global__ __launch_bounds__(256) void stab_tables_kernel(float2* __restrict__ tabx, float2* __restrict__ taby, int H, int W) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < W) {
-        const double t = (double)(2 * i + 1) / (double)W - 1.0;              // theta / pi
-        tabx[i] = make_float2((float)cospi(t), (float)sinpi(t));
-    } else if (i < W + H) {
-        const int y = i - W;
-        const double t = 0.5 * (1.0 - (double)(2 * y + 1) / (double)H);      // phi / pi
-        taby[y] = make_float2((float)cospi(t), (float)sinpi(t));
-    }
 }
 
 // ------------------------------------------------------------------ K11a: fit
@@ -282,11 +230,6 @@ __global__ __launch_bounds__(256) void stab_flow_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------ K11c: the frame under a rotation
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(uint8_t v) { return (float)v; }
-__device__ __forceinline__ void store_px(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store_px(uint8_t* p, float v) { *p = (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f); }
-
 // grid (ceil(W / 256), H, N): one thread per output pixel, all C channels; wrap in x, clamp in y
 template <typename T, int C>
 __global__ __launch_bounds__(256) void stab_rotate_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
@@ -299,41 +242,10 @@ __global__ __launch_bounds__(256) void stab_rotate_kernel(const T* __restrict__ 
     stab_dir(tabx[x], taby[y], px, py, pz);
     stab_rotate(R, px, py, pz, qx, qy, qz);
     stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
-    if (!(fabsf(sx) <= (float)W)) sx = 0.f;                            // a non-finite R: stay inside the frame
-    sy = fminf(fmaxf(sy, 0.f), (float)(H - 1));                        // fmaxf(NaN, 0) = 0
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float tx = sx - x0f, ty = sy - y0f;
-    int x0 = (int)x0f % W;
-    if (x0 < 0) x0 += W;
-    const int x1 = x0 + 1 == W ? 0 : x0 + 1;
-    const int y0 = (int)y0f;
-    const int y1 = y0 + 1 < H ? y0 + 1 : H - 1;
-    const T* img = src + (size_t)blockIdx.z * H * W * C;
-    const T* p00 = img + ((size_t)y0 * W + x0) * C;
-    const T* p01 = img + ((size_t)y0 * W + x1) * C;
-    const T* p10 = img + ((size_t)y1 * W + x0) * C;
-    const T* p11 = img + ((size_t)y1 * W + x1) * C;
-    T* o = dst + (((size_t)blockIdx.z * H + y) * W + x) * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float v00 = to_f32(p00[c]), v01 = to_f32(p01[c]), v10 = to_f32(p10[c]), v11 = to_f32(p11[c]);
-        const float top = v00 + tx * (v01 - v00);
-        const float bot = v10 + tx * (v11 - v10);
-        store_px(o + c, top + ty * (bot - top));
-    }
+    sphere_sample<T, C>(src + (size_t)blockIdx.z * H * W * C, H, W, sx, sy, dst + (((size_t)blockIdx.z * H + y) * W + x) * C);
 }
 
 // ------------------------------------------------------------------ host side
-bool bad_image(int N, int h, int w) {
-    return N <= 0 || h <= 0 || w <= 0;
-}
-// grid y = rows, grid z = images; the pixel index of one image stays an int
-bool big_image(int N, int h, int w) {
-    return N > 65535 || h > 65535 || (long long)h * w > (1LL << 28);
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 struct WorkLayout {
     size_t tabx, taby, state, partials, total;   // byte offsets
     int nblk;
@@ -342,19 +254,13 @@ struct WorkLayout {
 WorkLayout work_layout(int F, int H, int W) {
     WorkLayout l;
     l.nblk = (int)(((long long)H * W + kFitBlock - 1) / kFitBlock);
-    l.tabx = 0;
-    l.taby = align16((size_t)W * sizeof(float2));
-    l.state = l.taby + align16((size_t)H * sizeof(float2));
+    const TabLayout t = tab_layout(H, W);
+    l.tabx = t.tabx;
+    l.taby = t.taby;
+    l.state = t.total;
     l.partials = l.state + (size_t)F * kState * sizeof(double);
     l.total = l.partials + (size_t)F * l.nblk * kPartial * sizeof(double);
     return l;
-}
-
-int launch_tables(void* work, const WorkLayout& l, int H, int W, hipStream_t s) {
-    hipLaunchKernelGGL(stab_tables_kernel, dim3((H + W + 255) / 256), dim3(256), 0, s, (float2*)((char*)work + l.tabx),
-                       (float2*)((char*)work + l.taby), H, W);
-    CP360_CHECK_HIP();
-    return CP360_OK;
 }
 
 template <typename T, int C>
@@ -389,7 +295,7 @@ extern "C" int cp360_stab_fit(const float* flow, int F, int H, int W, int iters,
     double* partials = (double*)((char*)work + l.partials);
     const double two_pi = 6.283185307179586476925;
     const double c_min = c_min_px * two_pi / (double)W;
-    int st = launch_tables(work, l, H, W, s);
+    int st = launch_tables(work, H, W, s);
     if (st != CP360_OK) return st;
     hipLaunchKernelGGL(stab_fit_init_kernel, dim3((F + 63) / 64), dim3(64), 0, s, state, F, c_min);
     CP360_CHECK_HIP();
@@ -413,7 +319,7 @@ extern "C" int cp360_stab_flow(const float* R, int F, int H, int W, float* G, vo
     const WorkLayout l = work_layout(0, H, W);
     if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    const int st = launch_tables(work, l, H, W, s);
+    const int st = launch_tables(work, H, W, s);
     if (st != CP360_OK) return st;
     hipLaunchKernelGGL(stab_flow_kernel, dim3((W + 255) / 256, H, F), dim3(256), 0, s, R, (const float2*)((char*)work + l.tabx),
                        (const float2*)((char*)work + l.taby), (float2*)G, H, W);
@@ -432,7 +338,7 @@ extern "C" int cp360_stab_rotate(int dtype, const void* frames, const float* R, 
     const WorkLayout l = work_layout(0, H, W);
     if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    const int st = launch_tables(work, l, H, W, s);
+    const int st = launch_tables(work, H, W, s);
     if (st != CP360_OK) return st;
     const float2* tabx = (const float2*)((char*)work + l.tabx);
     const float2* taby = (const float2*)((char*)work + l.taby);

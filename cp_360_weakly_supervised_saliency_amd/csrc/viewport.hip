@@ -1,0 +1,330 @@
+// K12: the viewport pilot - a saliency map turned into a camera: the perspective (gnomonic) view of an equirectangular frame
+// under a camera rotation (K12a), the view's frame drawn on the panorama (K12b), the saliency map smoothed on the sphere (K12c)
+// and its peak with one mean-shift step (K12d).  The reference's utils/fov_visual.py (box_proh, fov_module, draw_cube_fov_box)
+// has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12", and
+// tests/viewport_restate.py restates it in float64.  Geometry, tables and the bilinear sample are sphere.h's.
+//
+// Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
+// centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
+//   K12a  view pixel (i, j): u = ((2 i + 1) / w - 1) tx, v = (1 - (2 j + 1) / h) ty, r = 1 / sqrtf((1 + v v) + u u),
+//         d = (r, v r, u r), q = R d, out = bilinear(frame, pix(q)): columns wrap, rows clamp
+//   K12b  panorama pixel (x, y): p = dir(x, y), d = R^T p = (d_f, d_u, d_r), u = d_r / d_f, v = d_u / d_f, b = border_px 2 tx / w;
+//         border <=> d_f > 0, |u| <= tx, |v| <= ty and not (|u| <= tx - b and |v| <= ty - b)
+//   K12c  out_i = sum_j a_j s_j e_ij / sum_j a_j e_ij, e_ij = expf(kappa (p_i . p_j - 1)), kappa = 1 / sigma^2, a_j = cos phi_j
+//   K12d  idx = argmax of the smoothed map (lowest index on ties), p* = dir(idx), c = sum_j a_j s_j e(p*, p_j) p_j, dir = c / |c|
+// Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d are f64 in a fixed order.  No
+// atomics, no host synchronisation, results independent of the batch size.
+#pragma clang fp contract(off)
+
+#include "sphere.h"
+
+namespace {
+
+constexpr int kMaxMapPx = 16384;             // K12c is all pairs: P^2 terms per frame
+
+__device__ __forceinline__ bool rot_finite(const Rot& R) {
+    const float s = fabsf(R.r00) + fabsf(R.r01) + fabsf(R.r02) + fabsf(R.r10) + fabsf(R.r11) + fabsf(R.r12) + fabsf(R.r20) +
+                    fabsf(R.r21) + fabsf(R.r22);
+    return isfinite(s);
+}
+
+// ------------------------------------------------------------------ K12a: the view
+// grid (ceil(w / 256), h, N): one thread per view pixel, all C channels
+template <typename T, int C>
+__global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ src, const float* __restrict__ Rs, T* __restrict__ dst,
+                                                          int H, int W, int h, int w, float tx, float ty) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= w) return;
+    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
+    const float u = ((float)(2 * i + 1) / (float)w - 1.f) * tx;
+    const float v = (1.f - (float)(2 * j + 1) / (float)h) * ty;
+    const float r = 1.f / sqrtf((1.f + v * v) + u * u);
+    float qx, qy, qz, sx, sy;
+    stab_rotate(R, r, v * r, u * r, qx, qy, qz);
+    stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
+    sphere_sample<T, C>(src + (size_t)blockIdx.z * H * W * C, H, W, sx, sy, dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
+}
+
+// ------------------------------------------------------------------ K12b: the view's frame on the panorama
+// grid (ceil(W / 256), H, N); element-wise, so dst may be src
+__global__ __launch_bounds__(256) void view_outline_kernel(const uint8_t* src, const float* __restrict__ Rs,
+                                                           const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                           uint8_t* dst, int H, int W, float tx, float ty, float b, int cr, int cg,
+                                                           int cb) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
+    float px, py, pz;
+    stab_dir(tabx[x], taby[y], px, py, pz);
+    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
+    const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
+    const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
+    const float au = fabsf(dr / df), av = fabsf(du / df);
+    const bool inside = df > 0.f && au <= tx && av <= ty;
+    const bool inner = au <= tx - b && av <= ty - b;
+    const size_t o = (((size_t)blockIdx.z * H + y) * W + x) * 3;
+    if (inside && !inner && rot_finite(R)) {
+        dst[o] = (uint8_t)cr;
+        dst[o + 1] = (uint8_t)cg;
+        dst[o + 2] = (uint8_t)cb;
+    } else if (dst != src) {
+        const uint8_t v0 = src[o], v1 = src[o + 1], v2 = src[o + 2];
+        dst[o] = v0;
+        dst[o + 1] = v1;
+        dst[o + 2] = v2;
+    }
+}
+
+// ------------------------------------------------------------------ K12c: von Mises-Fisher smoothing, all pairs
+// grid (ceil(P / 256), F): a workgroup owns 256 output pixels of one frame and walks the frame in LDS tiles of 256 sources
+__global__ __launch_bounds__(256) void view_smooth_kernel(const float* __restrict__ maps, const float2* __restrict__ tabx,
+                                                          const float2* __restrict__ taby, float* __restrict__ out, int hm, int wm,
+                                                          float kappa) {
+    __shared__ float4 tile_p[256];                                      // p_j and a_j
+    __shared__ float tile_as[256];                                      // a_j s_j
+    const int P = hm * wm, tid = threadIdx.x;
+    const int i = blockIdx.x * 256 + tid;
+    const float* s = maps + (size_t)blockIdx.y * P;
+    float pix_x = 1.f, pix_y = 0.f, pix_z = 0.f;
+    if (i < P) {
+        const int y = i / wm, x = i - y * wm;
+        stab_dir(tabx[x], taby[y], pix_x, pix_y, pix_z);
+    }
+    double num = 0.0, den = 0.0;
+    for (int t0 = 0; t0 < P; t0 += 256) {
+        const int j = t0 + tid;
+        if (j < P) {
+            const int y = j / wm, x = j - y * wm;
+            const float2 csp = taby[y];
+            float qx, qy, qz;
+            stab_dir(tabx[x], csp, qx, qy, qz);
+            const float sj = s[j];
+            tile_p[tid] = make_float4(qx, qy, qz, csp.x);
+            tile_as[tid] = csp.x * (isfinite(sj) ? sj : 0.f);
+        }
+        __syncthreads();
+        const int n = P - t0 < 256 ? P - t0 : 256;
+        for (int k = 0; k < n; ++k) {
+            const float4 q = tile_p[k];
+            const float dot = pix_x * q.x + pix_y * q.y + pix_z * q.z;
+            const float e = expf(kappa * (dot - 1.f));
+            num += (double)(tile_as[k] * e);
+            den += (double)(q.w * e);
+        }
+        __syncthreads();
+    }
+    if (i < P) out[(size_t)blockIdx.y * P + i] = (float)(num / den);
+}
+
+// ------------------------------------------------------------------ K12d: the peak and one mean-shift step
+// grid F, 256 threads: thread t takes pixels t, t + 256, .. in order, then the shuffle tree, then the 4 waves in order
+__global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict__ smooth, const float* __restrict__ maps,
+                                                        const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                        float* __restrict__ dir_out, int* __restrict__ idx_out,
+                                                        float* __restrict__ val_out, int hm, int wm, float kappa) {
+    __shared__ float red_v[4];
+    __shared__ int red_i[4];
+    __shared__ int red_n[4];
+    __shared__ double red_c[4][3];
+    const int P = hm * wm, tid = threadIdx.x, f = blockIdx.x;
+    const float* sm = smooth + (size_t)f * P;
+    const float* s = maps + (size_t)f * P;
+    // the argmax of the finite smoothed values, lowest index on ties; the number of finite raw values
+    float best = 0.f;
+    int bi = -1, nfin = 0;
+    for (int j = tid; j < P; j += 256) {
+        const float v = sm[j];
+        if (isfinite(v) && (bi < 0 || v > best)) {
+            best = v;
+            bi = j;
+        }
+        nfin += isfinite(s[j]) ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_down(best, off, 64);
+        const int oi = __shfl_down(bi, off, 64);
+        nfin += __shfl_down(nfin, off, 64);
+        if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    if ((tid & 63) == 0) {
+        red_v[tid >> 6] = best;
+        red_i[tid >> 6] = bi;
+        red_n[tid >> 6] = nfin;
+    }
+    __syncthreads();
+    best = red_v[0];
+    bi = red_i[0];
+    nfin = red_n[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        const float ov = red_v[k];
+        const int oi = red_i[k];
+        nfin += red_n[k];
+        if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    if (bi < 0 || nfin == 0) {                                          // nothing finite: look ahead
+        if (tid == 0) {
+            dir_out[(size_t)f * 3] = 1.f;
+            dir_out[(size_t)f * 3 + 1] = 0.f;
+            dir_out[(size_t)f * 3 + 2] = 0.f;
+            idx_out[f] = -1;
+            val_out[f] = nanf("");
+        }
+        return;
+    }
+    float cx, cy, cz;
+    {
+        const int y = bi / wm, x = bi - y * wm;
+        stab_dir(tabx[x], taby[y], cx, cy, cz);
+    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int j = tid; j < P; j += 256) {
+        const int y = j / wm, x = j - y * wm;
+        const float2 csp = taby[y];
+        float qx, qy, qz;
+        stab_dir(tabx[x], csp, qx, qy, qz);
+        const float sj = s[j];
+        const float dot = cx * qx + cy * qy + cz * qz;
+        const float e = expf(kappa * (dot - 1.f));
+        const float wgt = (csp.x * (isfinite(sj) ? sj : 0.f)) * e;
+        acc[0] += (double)(wgt * qx);
+        acc[1] += (double)(wgt * qy);
+        acc[2] += (double)(wgt * qz);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+        acc[k] = v;
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) red_c[tid >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double sx = ((red_c[0][0] + red_c[1][0]) + red_c[2][0]) + red_c[3][0];
+    const double sy = ((red_c[0][1] + red_c[1][1]) + red_c[2][1]) + red_c[3][1];
+    const double sz = ((red_c[0][2] + red_c[1][2]) + red_c[2][2]) + red_c[3][2];
+    const double n = sqrt(sx * sx + sy * sy + sz * sz);
+    float ox = cx, oy = cy, oz = cz;
+    if (n > 0.0 && isfinite(n)) {
+        ox = (float)(sx / n);
+        oy = (float)(sy / n);
+        oz = (float)(sz / n);
+    }
+    dir_out[(size_t)f * 3] = ox;
+    dir_out[(size_t)f * 3 + 1] = oy;
+    dir_out[(size_t)f * 3 + 2] = oz;
+    idx_out[f] = bi;
+    val_out[f] = best;
+}
+
+// ------------------------------------------------------------------ host side
+const double kPi = 3.14159265358979323846;
+
+bool bad_hfov(double hfov) { return !(hfov > 0.0 && hfov < kPi); }
+bool bad_sigma(double sigma) { return !(sigma > 0.0) || !isfinite(sigma); }
+
+template <typename T, int C>
+int launch_render(const void* frames, const float* R, void* out, int N, int H, int W, int h, int w, float tx, float ty,
+                  hipStream_t s) {
+    hipLaunchKernelGGL((view_render_kernel<T, C>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R, (T*)out, H, W,
+                       h, w, tx, ty);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// the checks smooth and peak share; *kappa = 1 / sigma^2 rounded once
+int map_args(int F, int hm, int wm, double sigma_rad, const void* work, size_t work_bytes, float* kappa) {
+    if (bad_image(F, hm, wm) || bad_sigma(sigma_rad)) return CP360_ERR_BAD_SHAPE;
+    if ((long long)hm * wm > kMaxMapPx || F > 65535) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
+    if (work_bytes < tab_layout(hm, wm).total) return CP360_ERR_BAD_SHAPE;
+    *kappa = (float)(1.0 / (sigma_rad * sigma_rad));
+    return CP360_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI
+extern "C" int cp360_view_render(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad,
+                                 void* out, int h, int w, void* stream) {
+    if (!frames || !R || !out) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1 || bad_hfov(hfov_rad)) return CP360_ERR_BAD_SHAPE;
+    if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
+    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w)) return CP360_ERR_UNSUPPORTED;
+    if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
+    const double t = tan(0.5 * hfov_rad);
+    const float tx = (float)t, ty = (float)(t * (double)h / (double)w);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == CP360_U8) return launch_render<uint8_t, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
+    switch (C) {
+        case 1: return launch_render<float, 1>(frames, R, out, N, H, W, h, w, tx, ty, s);
+        case 2: return launch_render<float, 2>(frames, R, out, N, H, W, h, w, tx, ty, s);
+        case 3: return launch_render<float, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
+        default: return launch_render<float, 4>(frames, R, out, N, H, W, h, w, tx, ty, s);
+    }
+}
+
+extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, int H, int W, double hfov_rad, int h, int w,
+                                  double border_px, const uint8_t* rgb, uint8_t* out, void* work, size_t work_bytes, void* stream) {
+    if (!frames || !R || !rgb || !out || !work) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || bad_image(N, h, w) || bad_hfov(hfov_rad) || !(border_px > 0.0) || !isfinite(border_px))
+        return CP360_ERR_BAD_SHAPE;
+    if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
+    const TabLayout l = tab_layout(H, W);
+    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
+    const double t = tan(0.5 * hfov_rad);
+    const float tx = (float)t, ty = (float)(t * (double)h / (double)w), b = (float)(border_px * 2.0 * t / (double)w);
+    hipStream_t s = (hipStream_t)stream;
+    const int st = launch_tables(work, H, W, s);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R,
+                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, H, W, tx, ty, b,
+                       (int)rgb[0], (int)rgb[1], (int)rgb[2]);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_view_smooth(const float* maps, int F, int hm, int wm, double sigma_rad, float* out, void* work,
+                                 size_t work_bytes, void* stream) {
+    if (!maps || !out || !work) return CP360_ERR_NULL;
+    float kappa = 0.f;
+    int st = map_args(F, hm, wm, sigma_rad, work, work_bytes, &kappa);
+    if (st != CP360_OK) return st;
+    if (maps == out) return CP360_ERR_UNSUPPORTED;                     // every output reads every input
+    const TabLayout l = tab_layout(hm, wm);
+    hipStream_t s = (hipStream_t)stream;
+    st = launch_tables(work, hm, wm, s);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_smooth_kernel, dim3((hm * wm + 255) / 256, F), dim3(256), 0, s, maps,
+                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, hm, wm, kappa);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_view_peak(const float* smooth, const float* maps, int F, int hm, int wm, double sigma_rad, float* dir_out,
+                               int* idx_out, float* val_out, void* work, size_t work_bytes, void* stream) {
+    if (!smooth || !maps || !dir_out || !idx_out || !val_out || !work) return CP360_ERR_NULL;
+    float kappa = 0.f;
+    int st = map_args(F, hm, wm, sigma_rad, work, work_bytes, &kappa);
+    if (st != CP360_OK) return st;
+    const TabLayout l = tab_layout(hm, wm);
+    hipStream_t s = (hipStream_t)stream;
+    st = launch_tables(work, hm, wm, s);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_peak_kernel, dim3(F), dim3(256), 0, s, smooth, maps, (const float2*)((char*)work + l.tabx),
+                       (const float2*)((char*)work + l.taby), dir_out, idx_out, val_out, hm, wm, kappa);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}

@@ -1452,3 +1452,102 @@ def equirect_rotate(frames, R, out=None, work=None):
     check(lib().cp360_stab_rotate(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, ptr(out), ptr(work),
                                   work.numel() * 8, stream()))
     return out
+
+
+# ----------------------------------------------------------------------------- K12: the viewport pilot (csrc/viewport.hip)
+def _view_geometry(hw, hfov_deg):
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1 or not 0.0 < float(hfov_deg) < 180.0:
+        raise ValueError("a view needs h, w >= 1 and 0 < hfov_deg < 180, got %r, %r" % (hw, hfov_deg))
+    return h, w, math.radians(float(hfov_deg))
+
+
+def viewport_render(frames, R, hw, hfov_deg, out=None):
+    """cp360_view_render: the perspective view of hw = (h, w) pixels and hfov_deg degrees of every frame under its camera R[n]
+    (f32 [N, 3, 3], camera-to-world, columns forward / up / right; I looks at the panorama's centre): frames u8 [N, H, W, 3] or
+    f32 [N, H, W, C], C <= 4 -> [N, h, w, C] of the frames' type.  Bilinear, columns wrap, rows clamp, no anti-aliasing."""
+    require_gpu(frames, R, out)
+    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3] or float32 [N, H, W, C], got %s %s"
+                         % (frames.dtype, tuple(frames.shape)))
+    N, H, W, C = (int(s) for s in frames.shape)
+    if C > 4 or (frames.dtype == torch.uint8 and C != 3):
+        raise ValueError("frames must have 3 channels (uint8) or at most 4 (float32), got %d" % C)
+    _check_buf('frames', frames, frames.dtype)
+    _stab_rotations(R, N)
+    h, w, hfov = _view_geometry(hw, hfov_deg)
+    if out is None:
+        out = torch.empty((N, h, w, C), dtype=frames.dtype, device=frames.device)
+    elif tuple(out.shape) != (N, h, w, C) or out.device != frames.device or out.data_ptr() == frames.data_ptr():
+        raise ValueError("out must be another tensor of shape %s on the frames' device" % ((N, h, w, C),))
+    _check_buf('out', out, frames.dtype)
+    check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
+    return out
+
+
+def viewport_outline(frames, R, hw, hfov_deg, border_px=3, rgb=(0, 255, 0), out=None, work=None):
+    """cp360_view_outline: the frame of the view (hw, hfov_deg) of camera R[n], border_px view pixels wide, drawn in rgb on the
+    panorama: frames u8 [N, H, W, 3] -> u8 [N, H, W, 3]; out may be frames (every other pixel is copied)."""
+    require_gpu(frames, R, out)
+    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
+        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    N, H, W = (int(s) for s in frames.shape[:3])
+    _check_buf('frames', frames, torch.uint8)
+    _stab_rotations(R, N)
+    h, w, hfov = _view_geometry(hw, hfov_deg)
+    rgb = tuple(int(v) for v in rgb)
+    if not float(border_px) > 0.0 or len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise ValueError("border_px must be positive and rgb three values of 0 .. 255, got %r, %r" % (border_px, rgb))
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.shape != frames.shape or out.device != frames.device:
+        raise ValueError("out must have the frames' shape on their device")
+    _check_buf('out', out, torch.uint8)
+    work = _stab_work(0, H, W, frames.device, work)
+    colour = (C.c_ubyte * 3)(*rgb)
+    check(lib().cp360_view_outline(ptr(frames), ptr(R), N, H, W, hfov, h, w, float(border_px), C.cast(colour, C.c_void_p),
+                                   ptr(out), ptr(work), work.numel() * 8, stream()))
+    return out
+
+
+def _view_maps(maps, sigma_deg):
+    if maps.dim() != 3 or maps.numel() == 0:
+        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+    _check_buf('maps', maps, torch.float32)
+    if not float(sigma_deg) > 0.0 or not math.isfinite(float(sigma_deg)):
+        raise ValueError("sigma_deg must be positive, got %r" % (sigma_deg,))
+    F, hm, wm = (int(s) for s in maps.shape)
+    if hm * wm > 16384:
+        raise ValueError("maps of more than 16384 pixels are not supported (all pairs), got %d x %d" % (hm, wm))
+    return F, hm, wm, math.radians(float(sigma_deg))
+
+
+def sphere_smooth(maps, sigma_deg=15.0, work=None):
+    """cp360_view_smooth: maps f32 [F, hm, wm] smoothed on the sphere with a von Mises-Fisher kernel of sigma_deg degrees
+    (kappa = 1 / sigma^2), weighted by solid angle and normalised; non-finite values count as 0."""
+    require_gpu(maps)
+    F, hm, wm, sigma = _view_maps(maps, sigma_deg)
+    work = _stab_work(0, hm, wm, maps.device, work)
+    out = torch.empty_like(maps)
+    check(lib().cp360_view_smooth(ptr(maps), F, hm, wm, sigma, ptr(out), ptr(work), work.numel() * 8, stream()))
+    return out
+
+
+def sphere_peak(maps, sigma_deg=15.0, smooth=None, work=None):
+    """cp360_view_peak: maps f32 [F, hm, wm] -> (dirs f32 [F, 3], idx i32 [F], val f32 [F]): the argmax of the smoothed map
+    (``smooth``, default ``sphere_smooth(maps, sigma_deg)``; lowest index on ties), its value, and the unit direction after one
+    mean-shift step on the raw map.  A frame with no finite value: idx -1, dir (1, 0, 0), val NaN."""
+    require_gpu(maps, smooth)
+    F, hm, wm, sigma = _view_maps(maps, sigma_deg)
+    work = _stab_work(0, hm, wm, maps.device, work)
+    if smooth is None:
+        smooth = sphere_smooth(maps, sigma_deg, work=work)
+    elif smooth.shape != maps.shape or smooth.device != maps.device:
+        raise ValueError("smooth must have the maps' shape on their device")
+    _check_buf('smooth', smooth, torch.float32)
+    dirs = torch.empty((F, 3), dtype=torch.float32, device=maps.device)
+    idx = torch.empty((F,), dtype=torch.int32, device=maps.device)
+    val = torch.empty((F,), dtype=torch.float32, device=maps.device)
+    check(lib().cp360_view_peak(ptr(smooth), ptr(maps), F, hm, wm, sigma, ptr(dirs), ptr(idx), ptr(val), ptr(work),
+                                work.numel() * 8, stream()))
+    return dirs, idx, val

@@ -522,6 +522,41 @@ int cp360_stab_flow(const float* R, int F, int H, int W, float* G, void* work, s
 int cp360_stab_rotate(int dtype, const void* frames, const float* R, int N, int H, int W, int C, void* out, void* work,
                       size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K12: the viewport pilot
+ * What a 360-degree saliency map is used for: choosing where to look and rendering that view (the purpose of the reference's
+ * utils/fov_visual.py - box_proh, fov_module, draw_cube_fov_box - which does not compile).  The specification is the package's
+ * own, DESIGN.md "K12", restated in float64 in tests/viewport_restate.py; geometry, tables and the bilinear sample are K11's
+ * (csrc/sphere.h).  A camera is R f32 [3, 3] row-major, camera-to-world, with the columns (forward, up, right) of the view:
+ * R = I looks along dir of the panorama's centre, (1, 0, 0), with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w.
+ *
+ *   render   out[n](i, j) = bilinear(frames[n], pix(R[n] d)), d = (1, v, u) / sqrt(1 + v^2 + u^2), u = ((2 i + 1) / w - 1) tx,
+ *            v = (1 - (2 j + 1) / h) ty: the gnomonic view of h x w pixels; columns wrap, rows clamp, no anti-aliasing.  frames
+ *            u8 [N, H, W, 3] (rintf, half to even) or f32 [N, H, W, C], C <= 4 (CP360_ERR_UNSUPPORTED above) -> out [N, h, w, C]
+ *            of the same type; not in place; no workspace.  0 < hfov_rad < pi, else CP360_ERR_BAD_SHAPE.
+ *   outline  the view's frame drawn on the panorama, u8 [N, H, W, 3]; out may be frames.  Pixel (x, y): d = R[n]^T dir(x, y) =
+ *            (d_f, d_u, d_r), u = d_r / d_f, v = d_u / d_f, b = border_px 2 tx / w (border_px > 0).  The pixel takes rgb[0..2]
+ *            (three bytes of HOST memory, read during the call) where d_f > 0, |u| <= tx, |v| <= ty and not (|u| <= tx - b and
+ *            |v| <= ty - b); every other pixel is copied.  A non-finite R draws nothing.
+ *   smooth   maps f32 [F, hm, wm] -> out f32 [F, hm, wm]: out_i = sum_j a_j s_j e_ij / sum_j a_j e_ij, the von Mises-Fisher
+ *            kernel e_ij = expf(kappa (p_i . p_j - 1)), kappa = 1 / sigma_rad^2 (double, rounded once), a_j = cos phi_j, p = dir of
+ *            the map's pixel centres.  Terms f32, the two sums f64 in ascending j; non-finite s_j count as 0; a constant map
+ *            comes back constant.  All pairs: hm wm <= 16384 (CP360_ERR_UNSUPPORTED above).  Not in place.
+ *   peak     smooth, maps [F, hm, wm] -> idx i32 [F] = argmax of the finite values of smooth (lowest index on ties), val f32 [F]
+ *            = smooth there, dir f32 [F, 3] = c / |c| with c = sum_j a_j s_j e(p*, p_j) p_j on the raw map, p* = dir(idx): one
+ *            mean-shift step, the sub-pixel position (terms f32, sums f64 in a fixed order).  |c| = 0: dir = p*.  A frame with no
+ *            finite value: idx = -1, dir = (1, 0, 0), val = NaN.
+ * work (outline, smooth, peak): 16-byte aligned device memory of cp360_stab_work_bytes(0, H, W) bytes - of (0, hm, wm) for the
+ * maps - for K11's tables, which every call rebuilds; too small: CP360_ERR_BAD_SHAPE.  Asynchronous on the stream, no atomics,
+ * bit-reproducible, independent of N / F. */
+int cp360_view_render(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad, void* out, int h,
+                      int w, void* stream);
+int cp360_view_outline(const uint8_t* frames, const float* R, int N, int H, int W, double hfov_rad, int h, int w, double border_px,
+                       const uint8_t* rgb, uint8_t* out, void* work, size_t work_bytes, void* stream);
+int cp360_view_smooth(const float* maps, int F, int hm, int wm, double sigma_rad, float* out, void* work, size_t work_bytes,
+                      void* stream);
+int cp360_view_peak(const float* smooth, const float* maps, int F, int hm, int wm, double sigma_rad, float* dir_out, int* idx_out,
+                    float* val_out, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
