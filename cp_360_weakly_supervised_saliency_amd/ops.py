@@ -1551,3 +1551,66 @@ def sphere_peak(maps, sigma_deg=15.0, smooth=None, work=None):
     check(lib().cp360_view_peak(ptr(smooth), ptr(maps), F, hm, wm, sigma, ptr(dirs), ptr(idx), ptr(val), ptr(work),
                                 work.numel() * 8, stream()))
     return dirs, idx, val
+
+
+# ----------------------------------------------------------------------------- K13: shot detection (csrc/shots.hip)
+_SHOT_WEIGHTS = {}
+
+
+def shot_weights_host(H):
+    """cp360_shot_weights_host: (a int32 numpy [H], sum_y a_y): a_y = floor(cos(phi_y) 1024 + 1/2), the solid-angle weight of row
+    y of an H-row equirectangular image.  Host only: needs no GPU."""
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be at least 1, got %d" % H)
+    a = np.empty(H, np.int32)
+    total = C.c_longlong(0)
+    check(lib().cp360_shot_weights_host(H, a.ctypes.data_as(C.c_void_p), C.cast(C.byref(total), C.c_void_p)))
+    return a, int(total.value)
+
+
+def shot_weights(H, device):
+    """The weight table of H rows on `device`, uploaded once per (H, device)."""
+    key = (int(H), torch.device(device))
+    if key not in _SHOT_WEIGHTS:
+        _SHOT_WEIGHTS[key] = torch.from_numpy(shot_weights_host(H)[0]).to(key[1])
+    return _SHOT_WEIGHTS[key]
+
+
+def _shot_work(F, H, W, device, work=None):
+    """The workspace of one cp360_shot_signatures call: `work` when it is large enough, else a new one."""
+    nbytes = lib().cp360_shot_work_bytes(int(F), int(H), int(W))
+    if nbytes == 0:
+        raise ValueError("shot signatures: unsupported geometry: %d x %d x %d" % (F, H, W))
+    if work is None or work.device != device or work.numel() * 8 < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
+def shot_signatures(frames, work=None, weights=None):
+    """cp360_shot_signatures: frames u8 [F, H, W, 3] (contiguous; a slice may start at any byte) -> sig int64 [F, 3, 64] on the
+    device: sig[f, c, b] = the sum of the row weights a_y over the pixels with frames[f, y, x, c] >> 2 == b.  Exact integers:
+    bit-identical between runs and batch sizes."""
+    require_gpu(frames, work, weights)
+    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
+        raise ValueError("frames must be a non-empty uint8 [F, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    _check_buf('frames', frames, torch.uint8)
+    F, H, W = (int(s) for s in frames.shape[:3])
+    if weights is None:
+        weights = shot_weights(H, frames.device)
+    elif tuple(weights.shape) != (H,) or weights.device != frames.device:
+        raise ValueError("weights must be int32 [%d] on the frames' device" % H)
+    _check_buf('weights', weights, torch.int32)
+    work = _shot_work(F, H, W, frames.device, work)
+    sig = torch.empty((F, 3, 64), dtype=torch.int64, device=frames.device)
+    check(lib().cp360_shot_signatures(ptr(frames), F, H, W, ptr(weights), ptr(sig), ptr(work), work.numel() * 8, stream()))
+    return sig
+
+
+def shot_distances(sig):
+    """sig int64 [F, 3, 64] -> (sad int64 [F - 1], T int64 scalar), both on sig's device, without a synchronisation:
+    sad_t = sum_{c, b} |sig_t - sig_t+1| and T = the sum of one channel's histogram; d_t = sad_t / (6 T) lies in [0, 1]."""
+    if sig.dim() != 3 or tuple(sig.shape[1:]) != (3, 64) or sig.shape[0] < 1 or sig.dtype != torch.int64:
+        raise ValueError("sig must be int64 [F, 3, 64] with F >= 1, got %s %s" % (sig.dtype, tuple(sig.shape)))
+    sad = (sig[1:] - sig[:-1]).abs().sum(dim=(1, 2))
+    return sad, sig[0, 0].sum()

@@ -14,6 +14,7 @@ import torch
 
 from .. import ops
 from .optical_flow import FarnebackFlow
+from .shots import check_cuts, segments
 
 
 def orthonormalise(M):
@@ -25,12 +26,19 @@ def orthonormalise(M):
     return np.stack([r0, r1, r2 / np.linalg.norm(r2)])
 
 
-def compose(R):
+def compose(R, cuts=None):
     """R [F, 3, 3] (host) -> C float64 [F + 1, 3, 3]: C_0 = I, C_t+1 = R_t C_t, the chain in float64 and every C_t
-    re-orthonormalised once on the way out: a scene direction p of frame 0's camera is seen at C_t p in frame t."""
+    re-orthonormalised once on the way out: a scene direction p of frame 0's camera is seen at C_t p in frame t.
+    ``cuts`` (``utils.shots``: the first frame of every new shot) restarts the chain: C_t = I exactly for t in cuts, and the
+    R_t-1 of the pair that straddles the cut is not used; every shot is stabilised to its own first frame."""
     R = np.asarray(R, np.float64)
+    starts = set(check_cuts(cuts, R.shape[0] + 1))
     C, out = np.eye(3), [np.eye(3)]
     for f in range(R.shape[0]):
+        if f + 1 in starts:
+            C = np.eye(3)
+            out.append(np.eye(3))
+            continue
         C = R[f] @ C
         out.append(orthonormalise(C))
     return np.stack(out)
@@ -58,25 +66,34 @@ class Stabilizer:
             raise ValueError("frames must be uint8 [F + 1, h, w, 3] with F >= 1, got %s %s" % (frames.dtype, tuple(frames.shape)))
         return frames.to(self.device).contiguous()
 
-    def rotations(self, frames):
-        """frames u8 [F + 1, h, w, 3] -> (R f32 [F, 3, 3], C f32 [F + 1, 3, 3]) on the device."""
+    def rotations(self, frames, cuts=None):
+        """frames u8 [F + 1, h, w, 3] -> (R f32 [F, 3, 3], C f32 [F + 1, 3, 3]) on the device.  ``cuts`` (``utils.shots``: the
+        first frame of every new shot): the R of a pair that straddles a cut is I and its ``diag`` row zeros - the flow across
+        a cut means nothing -, C restarts at I there, and every other R and C is what the shot's own frames give."""
         frames = self._frames(frames)
+        cuts = check_cuts(cuts, int(frames.shape[0]))
         H, W = self.hw
         flows = self.flow.from_frames(frames, res=(W, H))
         F = int(flows.shape[0])
         self._fit_work = ops._stab_work(F, H, W, flows.device, self._fit_work)
         R, self.diag = ops.rotation_fit(flows, self.iters, self.c_min_px, work=self._fit_work)
-        C = compose(R.cpu().numpy())
+        if cuts:
+            pairs = torch.tensor([t - 1 for t in cuts], device=R.device)
+            R[pairs] = torch.eye(3, dtype=R.dtype, device=R.device)
+            self.diag[pairs] = 0.0
+        C = compose(R.cpu().numpy(), cuts)
         return R, torch.from_numpy(C.astype(np.float32)).to(self.device)
 
-    def stabilize(self, frames):
+    def stabilize(self, frames, cuts=None):
         """frames u8 [F + 1, h, w, 3] -> (the frames in frame 0's orientation, S_t(p) = frame_t(C_t p), u8 on the device; C).
-        Frame 0 is copied."""
+        Frame 0 is copied.  With ``cuts`` every shot is brought to the orientation of its own first frame, which is copied."""
         frames = self._frames(frames)
-        _, C = self.rotations(frames)
+        _, C = self.rotations(frames, cuts)
         out = torch.empty_like(frames)
-        out[0].copy_(frames[0])
-        self.render(frames[1:], C[1:], out=out[1:])
+        for lo, hi in segments(cuts, int(frames.shape[0])):
+            out[lo].copy_(frames[lo])
+            if hi - lo > 1:
+                self.render(frames[lo + 1:hi], C[lo + 1:hi], out=out[lo + 1:hi])
         return out, C
 
     def render(self, frames, C, out=None):
@@ -91,6 +108,9 @@ class Stabilizer:
         return ops.equirect_rotate(frames, C, out=out, work=work)
 
     def from_frames(self, frames):
-        """frames u8 [F + 1, h, w, 3] -> the flows f32 [F, H, W, 2] of the stabilised video, on the device."""
+        """frames u8 [F + 1, h, w, 3] -> the flows f32 [F, H, W, 2] of the stabilised video, on the device.  It takes no ``cuts``:
+        a flow across a cut has no meaning and must not reach ``npy_io.save_motions`` / ``train_step``.  For a video with cuts
+        call it on every shot of two frames or more: ``for lo, hi in utils.shots.segments(cuts, n): if hi - lo >= 2: ...
+        from_frames(frames[lo:hi])``."""
         H, W = self.hw
         return self.flow.from_frames(self.stabilize(frames)[0], res=(W, H))

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .shots import check_cuts, segments
 
 _Y = np.array([0.0, 1.0, 0.0])
 _Z = np.array([0.0, 0.0, 1.0])
@@ -60,15 +61,19 @@ def _one_pass(c, alpha, max_step):
     return out
 
 
-def smooth_path(c, alpha=0.85, max_step_deg=None):
+def smooth_path(c, alpha=0.85, max_step_deg=None, cuts=None):
     """c [F, 3] unit directions -> float64 [F, 3]: m_0 = c_0, m_t = the point on the great circle from m_t-1 towards c_t at
     the fraction 1 - alpha of their angle (at most max_step_deg degrees), then the same pass backwards over the result (zero
-    phase); re-normalised."""
+    phase); re-normalised.  ``cuts`` (``utils.shots``: the first frame of every new shot): both passes run shot by shot, so the
+    camera neither leaves for the next scene's peak before a cut nor is still arriving after it."""
     c = np.asarray(c, np.float64)
     if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1:
         raise ValueError("c must be [F, 3], got %s" % (c.shape,))
     if not 0.0 <= float(alpha) < 1.0 or (max_step_deg is not None and not float(max_step_deg) > 0.0):
         raise ValueError("alpha must be in [0, 1) and max_step_deg positive, got %r, %r" % (alpha, max_step_deg))
+    shots = segments(cuts, c.shape[0])
+    if len(shots) > 1:
+        return np.concatenate([smooth_path(c[lo:hi], alpha, max_step_deg) for lo, hi in shots])
     c = c / np.linalg.norm(c, axis=1, keepdims=True)
     max_step = None if max_step_deg is None else np.deg2rad(float(max_step_deg))
     fwd = _one_pass(c, float(alpha), max_step)
@@ -76,11 +81,14 @@ def smooth_path(c, alpha=0.85, max_step_deg=None):
     return out / np.linalg.norm(out, axis=1, keepdims=True)
 
 
-def cameras(path):
-    """path [F, 3] -> float64 [F, 3, 3]: ``look_at`` of every direction, each frame's right handed to the next one."""
+def cameras(path, cuts=None):
+    """path [F, 3] -> float64 [F, 3, 3]: ``look_at`` of every direction, each frame's right handed to the next one - within a
+    shot: the first frame of every shot (``cuts``) starts without one."""
+    path = np.asarray(path, np.float64)
+    starts = set(check_cuts(cuts, path.shape[0]))
     out, right = [], None
-    for p in np.asarray(path, np.float64):
-        R = look_at(p, right)
+    for t, p in enumerate(path):
+        R = look_at(p, None if t in starts else right)
         right = R[:, 2]
         out.append(R)
     return np.stack(out)
@@ -119,11 +127,12 @@ class ViewportPilot:
         maps = self._maps(maps)
         return ops.sphere_peak(maps, self.sigma_deg, work=self._tab_work(int(maps.shape[1]), int(maps.shape[2])))[0]
 
-    def path(self, maps):
+    def path(self, maps, cuts=None):
         """maps f32 [F, hm, wm] -> the cameras R f32 [F, 3, 3] on the device: the peaks, copied to the host (3 F floats, the one
-        synchronisation of a video), ``smooth_path`` and ``look_at`` with every frame's right chained, copied back."""
+        synchronisation of a video), ``smooth_path`` and ``look_at`` with every frame's right chained, copied back.  With
+        ``cuts`` (``utils.shots``) the path of every shot is its own: the concatenation of the shots' paths."""
         dirs = self.peaks(maps).cpu().numpy()
-        R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg))
+        R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg, cuts), cuts)
         return torch.from_numpy(R.astype(np.float32)).to(self.device)
 
     def render(self, frames, R, out=None):
@@ -138,11 +147,12 @@ class ViewportPilot:
         work = self._tab_work(int(frames.shape[1]), int(frames.shape[2]))
         return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=work)
 
-    def follow(self, frames, maps):
+    def follow(self, frames, maps, cuts=None):
         """frames u8 [F, H, W, 3], maps f32 [F, hm, wm] (one per frame, e.g. ``SaliencyEngine(.., return_all_steps=True)``'s
-        output) -> (views u8 [F, h, w, 3], R f32 [F, 3, 3]) on the device; the frames keep their own resolution."""
+        output) -> (views u8 [F, h, w, 3], R f32 [F, 3, 3]) on the device; the frames keep their own resolution.  ``cuts``: as
+        in ``path``."""
         frames = self._frames(frames)
         if frames.dim() != 4 or len(maps) != frames.shape[0]:
             raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
-        R = self.path(maps)
+        R = self.path(maps, cuts)
         return self.render(frames, R), R

@@ -557,6 +557,27 @@ int cp360_view_smooth(const float* maps, int F, int hm, int wm, double sigma_rad
 int cp360_view_peak(const float* smooth, const float* maps, int F, int hm, int wm, double sigma_rad, float* dir_out, int* idx_out,
                     float* val_out, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K13: shot detection
+ * Where the hard cuts of an equirectangular video are: K10 - K12 assume one continuous take.  The signature of a frame is the
+ * colour histogram of the whole sphere, every pixel weighted by the solid angle of its row: a camera rotation leaves it nearly
+ * unchanged, a cut does not.  The reference has no counterpart: the specification is the package's own, DESIGN.md "K13", restated
+ * in integers in tests/shots_restate.py.
+ *
+ *   weights_host  a int32 [H] (HOST memory): a_y = floor(cos(phi_y) 1024 + 1/2), phi_y = (1 - (2 y + 1) / H) pi / 2, the latitude of
+ *                 row y's pixel centres, in double from the exact fraction (rows y and H - 1 - y get the same weight);
+ *                 *total_per_width (optional) = sum_y a_y, so that T = W * total_per_width
+ *   signatures    frames u8 [F, H, W, 3], contiguous, at ANY byte address; weights = the table above in DEVICE memory ->
+ *                 sig int64 [F, 3, 64], sig[f, c, b] = sum of a_y over the pixels with frames[f, y, x, c] >> 2 == b.  Every
+ *                 sig[f, c, :] sums to T.  Integers only: bit-identical between runs, launch geometries and batch sizes.  Every byte
+ *                 is read once; two launches, no global atomics, no trigonometry, no host synchronisation.
+ * work: 16-byte aligned device memory of cp360_shot_work_bytes(F, H, W) bytes (the workgroups' u32 partial sums); 0 = bad or
+ * unsupported sizes; too small: CP360_ERR_BAD_SHAPE.  F, H or W < 1: CP360_ERR_BAD_SHAPE; F or H > 65535, H W > 2^28,
+ * W > 2^21 or T >= 2^62: CP360_ERR_UNSUPPORTED. */
+int cp360_shot_weights_host(int H, int32_t* a, long long* total_per_width);
+size_t cp360_shot_work_bytes(int F, int H, int W);
+int cp360_shot_signatures(const uint8_t* frames, int F, int H, int W, const int32_t* weights, long long* sig, void* work,
+                          size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with

@@ -1,0 +1,172 @@
+"""Shot detection on the GPU (K13, csrc/shots.hip) against the integer restatement of its specification
+(tests/shots_restate.py, whose own claims tests/test_shots_cpu.py pins): the signatures are integers, so every comparison is
+exact (torch.equal) - against the restatement, between runs, and between a batch and single-frame calls.  Then the driver
+(ShotDetector) and the consumers of its cuts on the device: Stabilizer and ViewportPilot shot by shot, bit for bit.
+
+No test depends on ShotDetector's defaults: thr, ratio and radius are passed."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import ops
+from cp_360_weakly_supervised_saliency_amd.utils import hashrng
+from cp_360_weakly_supervised_saliency_amd.utils.shots import ShotDetector, segments
+from cp_360_weakly_supervised_saliency_amd.utils.stabilize import Stabilizer, compose
+from cp_360_weakly_supervised_saliency_amd.utils.viewport import ViewportPilot
+from tests import shots_restate as rs
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+THR, RATIO, RADIUS = 0.25, 3, 8
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def clip(F, H, W):
+    """F hash-noise frames with a vertical ramp, so that rows differ and every bin occurs; (frames u8, restated signatures)."""
+    noise = hashrng.uniform(800 + H, (F, H, W, 3), 0.0, 255.0, dtype=np.float64)
+    ramp = np.linspace(0.0, 255.0, H)[None, :, None, None]
+    frames = np.rint(0.5 * noise + 0.5 * ramp).astype(np.uint8)
+    return frames, rs.signatures(frames)[0]
+
+
+# ----------------------------------------------------------------------------- the kernel
+@pytest.mark.parametrize('F,H,W', [(3, 8, 16), (3, 33, 66), (3, 64, 128), (2, 480, 960)])
+def test_signatures_match_the_restatement(F, H, W):
+    """8 x 16 is one workgroup per frame; 33 x 66 has rows of 198 bytes (no multiple of 16: every row has a masked first or last
+    vector) and frames that start 6534 bytes apart (no multiple of 4); 480 x 960 has 60 partials per frame."""
+    frames, want = clip(F, H, W)
+    sig = ops.shot_signatures(dev(frames))
+    assert sig.shape == (F, 3, 64) and sig.dtype == torch.int64 and sig.is_cuda
+    assert torch.equal(sig.cpu(), torch.from_numpy(want))
+    T = W * rs.weights(H)[1]
+    assert torch.equal(sig.sum(dim=2).cpu(), torch.full((F, 3), T, dtype=torch.int64))
+
+
+def test_signatures_of_an_unaligned_view():
+    """frames[1:] of the 33 x 66 clip starts 6534 bytes into the allocation: 6 bytes past a 16-byte boundary."""
+    frames, want = clip(3, 33, 66)
+    view = dev(frames)[1:]
+    assert view.is_contiguous() and view.data_ptr() % 16 == 6
+    assert torch.equal(ops.shot_signatures(view).cpu(), torch.from_numpy(want[1:]))
+    # ... and every other offset from a 16-byte boundary: a byte buffer holds one frame at 1 .. 15 bytes in
+    raw = torch.zeros(33 * 66 * 3 + 16, dtype=torch.uint8, device=DEV)
+    one = dev(frames[2])
+    for off in range(1, 16):
+        at = raw[off:off + one.numel()].view(1, 33, 66, 3)
+        at.copy_(one[None])
+        assert at.data_ptr() % 16 == (raw.data_ptr() + off) % 16
+        assert torch.equal(ops.shot_signatures(at).cpu(), torch.from_numpy(want[2:])), off
+
+
+@pytest.mark.parametrize('H,W,value', [(480, 960, 255), (8, 16, 0)])
+def test_constant_frames(H, W, value):
+    """Every pixel in one bin: all lanes of every LDS update meet on it, and the bin holds T itself (2.9e8 at 480 x 960): a lost
+    update or an overflowing u32 partial would show."""
+    frames = torch.full((2, H, W, 3), value, dtype=torch.uint8, device=DEV)
+    sig = ops.shot_signatures(frames).cpu()
+    T = W * rs.weights(H)[1]
+    want = torch.zeros(2, 3, 64, dtype=torch.int64)
+    want[:, :, value >> 2] = T
+    assert torch.equal(sig, want)
+
+
+def test_runs_and_batches_are_bit_identical():
+    frames, want = clip(3, 33, 66)
+    x = dev(frames)
+    first, second = ops.shot_signatures(x), ops.shot_signatures(x)
+    assert torch.equal(first, second)
+    singles = torch.cat([ops.shot_signatures(x[f:f + 1]) for f in range(3)])
+    assert torch.equal(first, singles)
+    # a caller's workspace and weight table
+    work = ops._shot_work(3, 33, 66, x.device)
+    assert torch.equal(ops.shot_signatures(x, work=work, weights=ops.shot_weights(33, x.device)), first)
+    # F = 1: a signature, and no distances
+    sad, T = ops.shot_distances(singles[:1])
+    assert tuple(sad.shape) == (0,) and int(T) == 66 * rs.weights(33)[1]
+    det = ShotDetector(thr=THR, ratio=RATIO, radius=RADIUS)
+    assert det.distances(frames[:1]).shape == (0,) and det.cuts(frames[:1]) == []
+    # the same frame twice: distance zero
+    assert np.array_equal(det.distances(np.stack([frames[0], frames[0]])), [0.0])
+
+
+def test_errors():
+    x = dev(clip(3, 8, 16)[0])
+    with pytest.raises(ValueError):
+        ops.shot_signatures(x[:, :, ::2])                              # not contiguous
+    with pytest.raises(ValueError):
+        ops.shot_signatures(x.float())                                 # wrong dtype
+    with pytest.raises(ValueError):
+        ops.shot_signatures(x[..., :2].contiguous())                   # C != 3
+    with pytest.raises(ValueError):
+        ops.shot_signatures(x[0])                                      # no frame axis
+    with pytest.raises(ValueError):
+        ops.shot_signatures(x, weights=ops.shot_weights(9, x.device))  # another geometry's table
+
+
+# ----------------------------------------------------------------------------- the driver
+@pytest.mark.parametrize('hw', [(32, 64), (33, 66)])
+def test_detector_on_the_three_shot_video(hw):
+    video = rs.three_shot_video(*hw)
+    det = ShotDetector(thr=THR, ratio=RATIO, radius=RADIUS)
+    assert torch.equal(det.signatures(video).cpu(), torch.from_numpy(rs.signatures(video)[0]))
+    d = det.distances(video)
+    assert d.dtype == np.float64 and np.array_equal(d, rs.distances(video))
+    assert det.cuts(video) == rs.THREE_SHOT_CUTS
+    assert det.cuts(dev(video)) == rs.THREE_SHOT_CUTS                  # frames already on the device
+
+
+# ----------------------------------------------------------------------------- the consumers
+def test_stabilizer_shot_by_shot():
+    """Two shots of 4 frames at 64 x 128, the camera turning within each.  With the detector's cuts the second shot is
+    stabilised as if it were a video of its own; without, the rotation fitted across the cut enters every later C."""
+    frames, cut = rs.two_shot_video()
+    det = ShotDetector(thr=THR, ratio=RATIO, radius=RADIUS)
+    cuts = det.cuts(frames)
+    assert cuts == [cut]
+    st = Stabilizer((64, 128))
+    out, C = st.stabilize(frames, cuts=cuts)
+    R, C2 = st.rotations(frames, cuts=cuts)
+    diag = st.diag.clone()
+    eye = torch.eye(3, device=DEV)
+    assert out.shape == frames.shape and out.dtype == torch.uint8 and torch.equal(C, C2)
+    assert torch.equal(C[cut], eye) and torch.equal(C[0], eye)
+    assert torch.equal(R[cut - 1], eye) and torch.equal(diag[cut - 1], torch.zeros(4, dtype=torch.float64, device=DEV))
+    assert torch.equal(out[cut], dev(frames[cut])) and torch.equal(out[0], dev(frames[0]))
+    for lo, hi in segments(cuts, frames.shape[0]):
+        out_s, C_s = st.stabilize(frames[lo:hi])
+        R_s, _ = st.rotations(frames[lo:hi])
+        assert torch.equal(out[lo:hi], out_s) and torch.equal(C[lo:hi], C_s)
+        assert torch.equal(R[lo:hi - 1], R_s) and torch.equal(diag[lo:hi - 1], st.diag)
+    # without cuts: the chain as it was - compose of the returned R, the straddling pair's included
+    out_n, C_n = st.stabilize(frames)
+    R_n, C_n2 = st.rotations(frames)
+    want = torch.from_numpy(compose(R_n.cpu().numpy()).astype(np.float32)).to(DEV)
+    assert torch.equal(C_n, want) and torch.equal(C_n2, want)
+    assert torch.equal(R_n[:cut - 1], R[:cut - 1]) and torch.equal(R_n[cut:], R[cut:])
+    assert not torch.equal(R_n[cut - 1], eye) and not torch.equal(C_n[cut], eye)      # the garbage the cuts keep out
+    assert torch.equal(out_n[1:], st.render(frames[1:], C_n[1:])) and torch.equal(out_n[0], dev(frames[0]))
+    with pytest.raises(ValueError):
+        st.stabilize(frames, cuts=[0])
+    with pytest.raises(ValueError):
+        st.rotations(frames, cuts=[8])
+
+
+def test_viewport_pilot_shot_by_shot():
+    maps = hashrng.uniform(990, (8, 14, 28), 0.0, 1.0, dtype=np.float64).astype(np.float32)
+    pilot = ViewportPilot((9, 16), hfov_deg=90.0)
+    got = pilot.path(maps, cuts=[4])
+    assert got.shape == (8, 3, 3) and got.is_cuda
+    assert torch.equal(got, torch.cat([pilot.path(maps[:4]), pilot.path(maps[4:])]))
+    assert not torch.equal(got, pilot.path(maps))
+    assert torch.equal(pilot.path(maps, cuts=None), pilot.path(maps))
+    frames = dev(rs.three_shot_video(32, 64)[:8])
+    views, R = pilot.follow(frames, maps, cuts=[4])
+    assert torch.equal(R, got) and torch.equal(views, pilot.render(frames, got))
+    with pytest.raises(ValueError):
+        pilot.path(maps, cuts=[4, 4])
