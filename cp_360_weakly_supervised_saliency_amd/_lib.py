@@ -65,6 +65,8 @@ PUBLIC_SYMBOLS = [
     'cp360_view_render', 'cp360_view_outline', 'cp360_view_smooth', 'cp360_view_peak',
     # K13: shot detection
     'cp360_shot_weights_host', 'cp360_shot_work_bytes', 'cp360_shot_signatures',
+    # K14: saliency metrics on the sphere
+    'cp360_seval_work_bytes', 'cp360_seval_resample', 'cp360_seval_scores',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -274,6 +276,10 @@ def lib():
     L.cp360_shot_work_bytes.restype = sz
     L.cp360_shot_work_bytes.argtypes = [i, i, i]
     L.cp360_shot_signatures.argtypes = [vp, i, i, i, vp, vp, vp, sz, vp]
+    L.cp360_seval_work_bytes.restype = sz
+    L.cp360_seval_work_bytes.argtypes = [i, i, i]
+    L.cp360_seval_resample.argtypes = [vp, i, i, i, vp, i, i, vp]
+    L.cp360_seval_scores.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)         # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

@@ -1614,3 +1614,78 @@ def shot_distances(sig):
         raise ValueError("sig must be int64 [F, 3, 64] with F >= 1, got %s %s" % (sig.dtype, tuple(sig.shape)))
     sad = (sig[1:] - sig[:-1]).abs().sum(dim=(1, 2))
     return sad, sig[0, 0].sum()
+
+
+# ----------------------------------------------------------------------------- K14: metrics on the sphere (csrc/sphere_eval.hip)
+_EVAL_WEIGHTS = {}
+
+
+def sphere_eval_weights(h, mode, device):
+    """The int32 [h] row weights of an h-row evaluation grid on `device`: K13's solid-angle table ('solid_angle') or 1024 in every
+    row ('uniform', a flat grid).  Uploaded once per (h, mode, device)."""
+    if mode not in ('solid_angle', 'uniform'):
+        raise ValueError("weights must be 'solid_angle' or 'uniform', got %r" % (mode,))
+    key = (int(h), mode, torch.device(device))
+    if key not in _EVAL_WEIGHTS:
+        a = shot_weights_host(h)[0] if mode == 'solid_angle' else np.full(int(h), 1024, np.int32)
+        _EVAL_WEIGHTS[key] = torch.from_numpy(a).to(key[2])
+    return _EVAL_WEIGHTS[key]
+
+
+def _eval_maps(name, t):
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError("%s must be a non-empty float32 [F, h, w], got %s" % (name, tuple(t.shape)))
+    _check_buf(name, t, torch.float32)
+    return tuple(int(s) for s in t.shape)
+
+
+def sphere_eval_work(F, h, w, device, work=None):
+    """The workspace of one cp360_seval_scores call: `work` when it is large enough, else a new one."""
+    nbytes = lib().cp360_seval_work_bytes(int(F), int(h), int(w))
+    if nbytes == 0:
+        raise ValueError("sphere_eval: unsupported geometry: %d x %d x %d (F <= 65535, h w <= 2^21)" % (F, h, w))
+    if work is None or work.device != device or work.dtype != torch.float64 or work.numel() * 8 < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
+def sphere_eval_resample(maps, hw, out=None):
+    """cp360_seval_resample: maps f32 [F, hs, ws] -> f32 [F, h, w], bilinear on the sphere's pixel centres (columns wrap, rows
+    clamp, no anti-aliasing); maps that are already h x w are copied bit for bit."""
+    require_gpu(maps, out)
+    F, hs, ws = _eval_maps('maps', maps)
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError("the grid must be at least 1 x 1, got %d x %d" % (h, w))
+    if out is None:
+        out = torch.empty((F, h, w), dtype=torch.float32, device=maps.device)
+    elif tuple(out.shape) != (F, h, w) or out.device != maps.device:
+        raise ValueError("out must be float32 [%d, %d, %d] on the maps' device" % (F, h, w))
+    _check_buf('out', out, torch.float32)
+    check(lib().cp360_seval_resample(ptr(maps), F, hs, ws, ptr(out), h, w, stream()))
+    return out
+
+
+def sphere_eval(S, G, weights, fixations=None, work=None):
+    """cp360_seval_scores: S, G f32 [F, h, w] on the evaluation grid, weights int32 [h] (``sphere_eval_weights``), fixations u8 /
+    bool [F, h, w] or None (the rule G > mean + 2 std, weighted) -> (scores f64 [F, 5] = (auc, nss, cc, sim, kl), n_fix int32
+    [F]), both on the device, without a synchronisation.  A frame's numbers do not depend on F or on its place in the batch."""
+    require_gpu(S, G, weights, fixations, work)
+    F, h, w = _eval_maps('S', S)
+    if _eval_maps('G', G) != (F, h, w) or G.device != S.device:
+        raise ValueError("G must have S's shape %s on its device, got %s" % ((F, h, w), tuple(G.shape)))
+    if tuple(weights.shape) != (h,) or weights.device != S.device:
+        raise ValueError("weights must be int32 [%d] on the maps' device" % h)
+    _check_buf('weights', weights, torch.int32)
+    if fixations is not None:
+        if fixations.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("fixations must be uint8 or bool, got %s" % fixations.dtype)
+        if tuple(fixations.shape) != (F, h, w) or fixations.device != S.device:
+            raise ValueError("fixations must be [%d, %d, %d] on the maps' device, got %s" % (F, h, w, tuple(fixations.shape)))
+        _check_buf('fixations', fixations, fixations.dtype)
+    work = sphere_eval_work(F, h, w, S.device, work)
+    scores = torch.empty((F, 5), dtype=torch.float64, device=S.device)
+    n_fix = torch.empty((F,), dtype=torch.int32, device=S.device)
+    check(lib().cp360_seval_scores(ptr(S), ptr(G), ptr(fixations), ptr(weights), F, h, w, ptr(scores), ptr(n_fix), ptr(work),
+                                   work.numel() * 8, stream()))
+    return scores, n_fix

@@ -578,6 +578,33 @@ size_t cp360_shot_work_bytes(int F, int H, int W);
 int cp360_shot_signatures(const uint8_t* frames, int F, int H, int W, const int32_t* weights, long long* sig, void* work,
                           size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K14: saliency metrics on the sphere, a video per call
+ * AUC-Judd, NSS, CC, SIM and KL of F saliency maps against F ground-truth maps on an h x w equirectangular grid, every pixel
+ * weighted by the solid angle of its row.  K8 below keeps the reference's flat, one-frame functions; the specification of these
+ * is the package's own, DESIGN.md "K14", restated in float64 and exact integers in tests/sphere_eval_restate.py.
+ *
+ *   resample  src f32 [F, hs, ws] -> dst f32 [F, h, w]: grid pixel (x, y) samples the source at sx = (float)((double)((2 x + 1)
+ *             ws) / (double)(2 w) - 0.5), sy alike, bilinear with K11's sample (columns wrap, rows clamp, no contraction, no
+ *             anti-aliasing); a source that is already h x w is copied bit for bit.  hs, ws as for K11's images.
+ *   scores    S, G f32 [F, h, w]; fixations u8 [F, h, w] (non-zero = fixated) or NULL: the rule G_i > mu_G + 2 sigma_G with the
+ *             weighted mean and deviation, compared in double; weights int32 [h] (DEVICE memory; cp360_shot_weights_host's table
+ *             for the solid angle, 1024 everywhere for a flat grid; values are clamped to 0 .. 1024) -> scores f64 [F, 5] = (auc,
+ *             nss, cc, sim, kl) and n_fix int32 [F].  With a_i the weight of pixel i's row and sums in double: CC the weighted
+ *             Pearson coefficient from centred sums; P_i = a_i (S_i - min S) / sum_j a_j (S_j - min S), Q_i alike from G, SIM =
+ *             sum_i min(P_i, Q_i), KL = sum_i Q_i log(eps + Q_i / (P_i + eps)), eps = 2^-52; NSS = the mean over the fixated pixels
+ *             of (S_i - mu_S) / sigma_S; AUC = the trapezoid sum over (0, 0), (A_i / A_neg, c_i / n_fix) by descending S_i, (1, 1),
+ *             c_i = #{fixated j: S_j >= S_i}, A_i = the weight of the pixels that are not fixated with S_j >= S_i, A_neg that of all
+ *             of them: an integer over 2 A_neg n_fix, rounded once, no jitter.  n_fix = 0 or h w: AUC and NSS are NaN; no variance:
+ *             CC and NSS are NaN; no mass above the minimum: SIM and KL are NaN; a non-finite value in a frame's S or G: all five
+ *             of that frame are NaN.  Three launches, no host synchronisation, no global atomics; a frame's numbers are
+ *             bit-identical between runs, batch sizes and places in the batch.
+ * work: 16-byte aligned device memory of cp360_seval_work_bytes(F, h, w) bytes (20 bytes per pixel); 0 = bad or unsupported sizes;
+ * too small: CP360_ERR_BAD_SHAPE.  F, h or w < 1: CP360_ERR_BAD_SHAPE; F > 65535 or h w > 2^21: CP360_ERR_UNSUPPORTED. */
+size_t cp360_seval_work_bytes(int F, int h, int w);
+int cp360_seval_resample(const float* src, int F, int hs, int ws, float* dst, int h, int w, void* stream);
+int cp360_seval_scores(const float* S, const float* G, const uint8_t* fixations, const int32_t* weights, int F, int h, int w,
+                       double* scores, int32_t* n_fix, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
