@@ -67,6 +67,8 @@ PUBLIC_SYMBOLS = [
     'cp360_shot_weights_host', 'cp360_shot_work_bytes', 'cp360_shot_signatures',
     # K14: saliency metrics on the sphere
     'cp360_seval_work_bytes', 'cp360_seval_resample', 'cp360_seval_scores',
+    # K15: fixations from scan-paths, shuffled AUC on the sphere
+    'cp360_fix_work_bytes', 'cp360_fix_counts', 'cp360_fix_density', 'cp360_fix_sauc',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -280,6 +282,11 @@ def lib():
     L.cp360_seval_work_bytes.argtypes = [i, i, i]
     L.cp360_seval_resample.argtypes = [vp, i, i, i, vp, i, i, vp]
     L.cp360_seval_scores.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.cp360_fix_work_bytes.restype = sz
+    L.cp360_fix_work_bytes.argtypes = [i, i, i]
+    L.cp360_fix_counts.argtypes = [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]
+    L.cp360_fix_density.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, vp, vp, sz, vp]
+    L.cp360_fix_sauc.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)         # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

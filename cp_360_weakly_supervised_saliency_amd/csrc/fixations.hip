@@ -1,0 +1,408 @@
+// K15: fixation ground truth from scan-paths, and shuffled AUC on the sphere.  A video's fixations are N points (longitude,
+// latitude in radians, float64) in CSR form: offsets int32 [F + 1], the points of frame f are offsets[f] .. offsets[f + 1] - 1.
+// The specification is the package's own, DESIGN.md "K15"; tests/fixations_restate.py restates it in float64 and exact integers.
+//
+//   bin      u = (lon / pi + 1) (w / 2), x = floor(u) mod w in 0 .. w - 1;  v = (1 - lat / (pi / 2)) (h / 2), y = clamp(floor(v), 0,
+//            h - 1): float64, one operation per step, no trigonometry - numpy gives the same integers.  A point with a non-finite
+//            coordinate contributes nothing anywhere; a finite longitude so large that u overflows lands in column 0.
+//   counts   counts[f, y, x] = the number of frame f's points in pixel (x, y), n_points[f] = the number of its finite points
+//   density  G[f, i] = sum_k e(p_i, q_k) over the frame's finite points in ascending k, e = expf(kappa (p_i . q_k - 1)), kappa =
+//            1 / sigma^2 rounded once (K12's convention), p_i from sphere.h's tables, q_k = dir(lon_k, lat_k) in double, rounded
+//            to f32; the sum is f32 in that order: a frame's map does not depend on F or on its place in the batch
+//   sAUC     K14's construction with multiplicities: positives pos_i (clamped to 0 .. 1023), negatives neg_i (0 .. 2^20, every
+//            pixel, fixated ones included), C_tot = sum pos, A_neg = sum neg.  For a pixel with pos_i > 0: C_i = sum_{pos_j > 0,
+//            S_j >= S_i} pos_j, A_i = sum_{S_j >= S_i} neg_j.  The ROC points are (0, 0), the distinct (A_i / A_neg, C_i / C_tot)
+//            by descending S_i, (1, 1); N = sum_k (A_k - A_k-1)(C_k + C_k-1) is an integer and AUC = N / (2 A_neg C_tot), rounded
+//            once.  C_tot = 0, A_neg = 0, a non-finite S or 2 A_neg C_tot >= 2^53: NaN.
+//
+// Launches, all on the caller's stream, no host synchronisation, integer atomics only (any order gives the same bits):
+//   K15a  counts: a clear, then one workgroup per frame, a vector atomicAdd per point
+//   K15b  density: grid (ceil(P / 256), F), a pixel per thread; the frame's q_k staged in LDS 256 at a time, every lane reads the
+//         same address (a broadcast), one expf per pair
+//   K15c  sAUC prepare: one 1024-thread workgroup per frame - the sums, the finiteness of S, the positives compacted as (S, pos)
+//   K15d  sAUC rank: grid (ceil(P / 256), F), sized for P positives in tiles of 256.  A thread owns one positive: a loop over the
+//         compacted list gives C_i, G_i (the same sum with >), the next higher positive value and whether it is the first of its
+//         ties in the list; a loop over pixels, (S_j, neg_j) staged in LDS 1024 at a time, gives A_i and the A of the next higher
+//         value (u32 per tile: 1024 * 2^20 < 2^32; 64 bits across tiles).  The first of each distinct value adds (A - A_prev)(C +
+//         G) to the frame's int64 sum, the lowest value also the segment to (1, 1).  A video has tens of positives per frame,
+//         not P: the workgroups that the positives leave over split the pixel loop (N is linear in A), the rest exit at once.
+//   K15e  sAUC finish: the quotient
+#pragma clang fp contract(off)
+#include "sphere.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int kFixTile = 256;                // K15b: points staged at a time
+constexpr int kPrepThreads = 1024;           // K15c
+constexpr int kPrepWaves = kPrepThreads / 64;
+constexpr int kRankThreads = 256;            // K15d: positives per workgroup
+constexpr int kRankTile = 1024;              // K15d: pixels staged at a time = the span over which a u32 cannot overflow
+constexpr int kMaxPos = 1023;
+constexpr int kMaxNeg = 1 << 20;
+constexpr int kFixMaxP = 1 << 21;            // 1023 P < 2^31: C_tot and every C_i fit a u32
+constexpr double kPi = 3.14159265358979323846;
+constexpr double kHalfPi = 1.57079632679489661923;
+
+struct SaucHdr {                             // per frame, K15c -> K15d, K15e
+    int n_rank;                              // the number of positive pixels, or 0 when the frame has no AUC
+    int pad;
+    long long c_tot, a_neg;
+    unsigned long long N;                    // sum (A_k - A_k-1)(C_k + C_k-1)
+};
+
+struct FixLayout {
+    size_t tabx, taby, hdr, cs, cp, total;
+};
+
+// F = 0: the tables alone (counts needs nothing, density the tables)
+FixLayout fix_layout(int F, int h, int w) {
+    FixLayout l;
+    const TabLayout t = tab_layout(h, w);
+    const size_t n = (size_t)F * (size_t)h * (size_t)w;
+    l.tabx = t.tabx;
+    l.taby = t.taby;
+    l.hdr = t.total;
+    l.cs = l.hdr + align16((size_t)F * sizeof(SaucHdr));
+    l.cp = l.cs + align16(n * sizeof(float));
+    l.total = l.cp + align16(n * sizeof(unsigned));
+    return l;
+}
+
+__device__ __forceinline__ bool fix_finite(double v) { return fabs(v) < INFINITY; }
+
+__device__ __forceinline__ int fix_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the pixel of (lon, lat); false for a point that contributes nothing
+__device__ __forceinline__ bool fix_bin(double lon, double lat, int h, int w, int& x, int& y) {
+    if (!fix_finite(lon) || !fix_finite(lat)) return false;
+    const double u = (lon / kPi + 1.0) * ((double)w / 2.0);
+    const double v = (1.0 - lat / kHalfPi) * ((double)h / 2.0);
+    double xf = fmod(floor(u), (double)w);                             // exact; NaN when u overflowed
+    if (xf < 0.0) xf += (double)w;
+    x = xf >= 0.0 && xf < (double)w ? (int)xf : 0;
+    const double yf = floor(v);
+    y = yf < 0.0 ? 0 : (yf > (double)(h - 1) ? h - 1 : (int)yf);
+    return true;
+}
+
+// the points of frame f, inside 0 .. N whatever the offsets hold
+__device__ __forceinline__ void fix_range(const int* __restrict__ offsets, int f, int N, int& k0, int& k1) {
+    k0 = fix_clamp(offsets[f], 0, N);
+    k1 = fix_clamp(offsets[f + 1], k0, N);
+}
+
+// ------------------------------------------------------------------ K15a: counts
+// grid F, 256 threads; counts cleared before
+__global__ __launch_bounds__(256) void fix_counts_kernel(const double* __restrict__ lonlat, const int* __restrict__ offsets, int N,
+                                                         int h, int w, int* __restrict__ counts, int* __restrict__ n_points) {
+    __shared__ int red[4];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    int k0, k1;
+    fix_range(offsets, f, N, k0, k1);
+    int* c = counts + (size_t)f * h * w;
+    int n = 0;
+    for (long long k = (long long)k0 + tid; k < k1; k += 256) {
+        int x, y;
+        if (fix_bin(lonlat[2 * k], lonlat[2 * k + 1], h, w, x, y)) {
+            atomicAdd(&c[y * w + x], 1);
+            ++n;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if ((tid & 63) == 0) red[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0) n_points[f] = red[0] + red[1] + red[2] + red[3];
+}
+
+// ------------------------------------------------------------------ K15b: density
+// grid (ceil(P / 256), F), 256 threads
+__global__ __launch_bounds__(256) void fix_density_kernel(const double* __restrict__ lonlat, const int* __restrict__ offsets, int N,
+                                                          const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                          float* __restrict__ out, int h, int w, float kappa) {
+    __shared__ float4 tile_q[kFixTile];                                // q_k, and 1 for a finite point, 0 for one that is dropped
+    const int P = h * w, tid = threadIdx.x, f = blockIdx.y;
+    const int i = blockIdx.x * 256 + tid;
+    int k0, k1;
+    fix_range(offsets, f, N, k0, k1);
+    float px = 1.f, py = 0.f, pz = 0.f;
+    if (i < P) {
+        const int y = i / w, x = i - y * w;
+        stab_dir(tabx[x], taby[y], px, py, pz);
+    }
+    float acc = 0.f;
+    for (long long t0 = k0; t0 < k1; t0 += kFixTile) {                 // k0, k1 are the workgroup's: the barriers are uniform
+        const long long k = t0 + tid;
+        if (k < k1) {
+            const double lon = lonlat[2 * k], lat = lonlat[2 * k + 1];
+            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (fix_finite(lon) && fix_finite(lat)) {
+                const double cl = cos(lat);
+                q = make_float4((float)(cl * cos(lon)), (float)sin(lat), (float)(cl * sin(lon)), 1.f);
+            }
+            tile_q[tid] = q;
+        }
+        __syncthreads();
+        const int n = k1 - t0 < kFixTile ? (int)(k1 - t0) : kFixTile;
+        for (int k = 0; k < n; ++k) {
+            const float4 q = tile_q[k];
+            const float dot = px * q.x + py * q.y + pz * q.z;
+            const float e = expf(kappa * (dot - 1.f));
+            acc += q.w != 0.f ? e : 0.f;                               // acc >= +0: adding +0 changes no bit
+        }
+        __syncthreads();
+    }
+    if (i < P) out[(size_t)f * P + i] = acc;                           // a frame without points: zeros
+}
+
+// ------------------------------------------------------------------ K15c: sums and the compacted positives
+// grid F, 1024 threads
+__global__ __launch_bounds__(kPrepThreads) void fix_sauc_prep_kernel(const float* __restrict__ S, const int* __restrict__ pos,
+                                                                     const int* __restrict__ neg, size_t neg_stride, int P,
+                                                                     double* __restrict__ auc, long long* __restrict__ c_tot_out,
+                                                                     long long* __restrict__ a_neg_out, SaucHdr* __restrict__ hdr,
+                                                                     float* __restrict__ cs, unsigned* __restrict__ cp) {
+    __shared__ long long sml[kPrepWaves * 3];
+    __shared__ int cnt;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, f = blockIdx.x;
+    S += (size_t)f * P;
+    pos += (size_t)f * P;
+    neg += (size_t)f * neg_stride;
+    cs += (size_t)f * P;
+    cp += (size_t)f * P;
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    long long acc[3] = {0, 0, 0};                                      // C_tot, A_neg, non-finite values
+    for (int i0 = 0; i0 < P; i0 += kPrepThreads) {                     // uniform: ballots need every lane
+        const int i = i0 + tid;
+        int m = 0;
+        float s = 0.f;
+        if (i < P) {
+            s = S[i];
+            m = fix_clamp(pos[i], 0, kMaxPos);
+            acc[0] += m;
+            acc[1] += fix_clamp(neg[i], 0, kMaxNeg);
+            acc[2] += !(fabsf(s) < INFINITY);
+        }
+        const bool fx = m > 0;
+        const unsigned long long b = __ballot(fx);
+        int base = 0;
+        if (lane == 0 && b) base = atomicAdd(&cnt, __popcll(b));
+        base = __shfl(base, 0);
+        if (fx) {
+            const int slot = base + __popcll(b & ((1ull << lane) - 1ull));
+            cs[slot] = s;
+            cp[slot] = (unsigned)m;
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[n] += __shfl_xor(acc[n], off);
+        if (lane == 0) sml[wave * 3 + n] = acc[n];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long c_tot = 0, a_neg = 0, bad = 0;
+        for (int k = 0; k < kPrepWaves; ++k) {
+            c_tot += sml[k * 3];
+            a_neg += sml[k * 3 + 1];
+            bad += sml[k * 3 + 2];
+        }
+        // 2 A_neg C_tot < 2^53  <=>  A_neg <= floor((2^52 - 1) / C_tot): the product itself may not fit 64 bits
+        const bool rank = bad == 0 && c_tot > 0 && a_neg > 0 && a_neg <= ((1LL << 52) - 1) / c_tot;
+        c_tot_out[f] = c_tot;
+        a_neg_out[f] = a_neg;
+        if (!rank) auc[f] = __longlong_as_double(0x7ff8000000000000LL);
+        hdr[f].n_rank = rank ? cnt : 0;
+        hdr[f].pad = 0;
+        hdr[f].c_tot = c_tot;
+        hdr[f].a_neg = a_neg;
+        hdr[f].N = 0ull;
+    }
+}
+
+// ------------------------------------------------------------------ K15d: the ROC segment of every distinct positive value
+// grid (ceil(P / 256), F), 256 threads
+__global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float* __restrict__ S, const int* __restrict__ neg,
+                                                                     size_t neg_stride, SaucHdr* __restrict__ hdr,
+                                                                     const float* __restrict__ cs, const unsigned* __restrict__ cp,
+                                                                     int P) {
+    __shared__ __attribute__((aligned(16))) float sv[kRankTile];
+    __shared__ __attribute__((aligned(16))) unsigned sp[kRankTile];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const int n = hdr[f].n_rank;
+    if (n == 0) return;                                                // the whole workgroup: before any barrier
+    // the grid holds ceil(P / 256) >= tiles workgroups: those that the positives leave over share the pixel loop - workgroup b
+    // owns tile b % tiles of the positives and every chunks-th pixel tile from b / tiles on; N is linear in A, so the parts add up
+    const int tiles = (n + kRankThreads - 1) / kRankThreads, chunks = (int)gridDim.x / tiles;
+    if ((int)blockIdx.x >= tiles * chunks) return;
+    const int chunk = (int)blockIdx.x / tiles;
+    const int k = ((int)blockIdx.x - chunk * tiles) * kRankThreads + tid;
+    S += (size_t)f * P;
+    neg += (size_t)f * neg_stride;
+    cs += (size_t)f * P;
+    cp += (size_t)f * P;
+    const bool own = k < n;
+    const bool busy = k - (tid & 63) < n;                              // the wave owns a positive: the others only stage and wait
+    const float v = own ? cs[k] : INFINITY;
+    // the positives alone: C, G, the next higher value, the first of the ties
+    unsigned Cge = 0u, Cgt = 0u;
+    float nv = INFINITY;
+    bool first = true;
+    for (int t0 = 0; t0 < n; t0 += kRankTile) {
+#pragma unroll
+        for (int q = 0; q < kRankTile / kRankThreads; ++q) {
+            const int jj = q * kRankThreads + tid, j = t0 + jj;
+            sv[jj] = j < n ? cs[j] : -INFINITY;                        // below every value: counts nothing
+            sp[jj] = j < n ? cp[j] : 0u;
+        }
+        __syncthreads();
+        const int lim = n - t0 < kRankTile ? n - t0 : kRankTile;
+        for (int jj = 0; busy && jj < lim; ++jj) {
+            const float s = sv[jj];
+            const unsigned m = sp[jj];
+            Cge += s >= v ? m : 0u;
+            Cgt += s > v ? m : 0u;
+            nv = s > v ? fminf(nv, s) : nv;
+            first = first && !(s == v && t0 + jj < k);
+        }
+        __syncthreads();
+    }
+    // this chunk's pixels: their share of A at v and at the next higher value
+    unsigned long long A = 0ull, Ap = 0ull;
+    for (int t0 = chunk * kRankTile; t0 < P; t0 += chunks * kRankTile) {         // chunks <= 2^13: t0 stays below 2^24
+#pragma unroll
+        for (int q = 0; q < kRankTile / kRankThreads; ++q) {
+            const int jj = q * kRankThreads + tid, j = t0 + jj;
+            const bool in = j < P;
+            sv[jj] = in ? S[j] : 0.f;
+            sp[jj] = in ? (unsigned)fix_clamp(neg[j], 0, kMaxNeg) : 0u;     // a pixel past the frame counts nothing
+        }
+        __syncthreads();
+        unsigned a = 0u, ap = 0u;
+#pragma unroll 4
+        for (int jj = 0; busy && jj < kRankTile; jj += 4) {
+            const float4 s = *reinterpret_cast<const float4*>(&sv[jj]);
+            const uint4 p = *reinterpret_cast<const uint4*>(&sp[jj]);
+            a += s.x >= v ? p.x : 0u;
+            a += s.y >= v ? p.y : 0u;
+            a += s.z >= v ? p.z : 0u;
+            a += s.w >= v ? p.w : 0u;
+            ap += s.x >= nv ? p.x : 0u;
+            ap += s.y >= nv ? p.y : 0u;
+            ap += s.z >= nv ? p.z : 0u;
+            ap += s.w >= nv ? p.w : 0u;
+        }
+        A += a;
+        Ap += ap;
+        __syncthreads();
+    }
+    unsigned long long part = 0ull;
+    if (own && first) {
+        const unsigned long long c_tot = (unsigned long long)hdr[f].c_tot, a_neg = (unsigned long long)hdr[f].a_neg;
+        part = (A - Ap) * (unsigned long long)(Cge + Cgt);             // the point before: (Ap, Cgt)
+        // the lowest value: on to (1, 1), (A_neg - A) 2 C_tot; a chunk other than 0 brings -A alone, modulo 2^64 - N itself is below 2^53
+        if ((unsigned long long)Cge == c_tot) part += ((chunk == 0 ? a_neg : 0ull) - A) * (2ull * c_tot);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    if ((tid & 63) == 0 && part) atomicAdd(&hdr[f].N, part);           // integers: no order
+}
+
+// ------------------------------------------------------------------ K15e: the AUC
+__global__ __launch_bounds__(256) void fix_sauc_finish_kernel(const SaucHdr* __restrict__ hdr, double* __restrict__ auc, int F) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F || hdr[f].n_rank == 0) return;                          // K15c wrote the NaN
+    auc[f] = (double)hdr[f].N / (2.0 * (double)hdr[f].a_neg * (double)hdr[f].c_tot);     // integers below 2^53: one rounding
+}
+
+// ------------------------------------------------------------------ host side
+int fix_args(int F, int h, int w) {
+    if (bad_image(F, h, w)) return CP360_ERR_BAD_SHAPE;
+    if (F > 65535 || (long long)h * w > kFixMaxP) return CP360_ERR_UNSUPPORTED;
+    return CP360_OK;
+}
+
+// the points: lonlat may be NULL when there are none
+int fix_points(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w) {
+    if (!offsets || (!lonlat && N > 0)) return CP360_ERR_NULL;
+    const int st = fix_args(F, h, w);
+    if (st != CP360_OK) return st;
+    if (N < 0) return CP360_ERR_BAD_SHAPE;
+    if (N >= (1LL << 31)) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)lonlat & 7) != 0 || ((uintptr_t)offsets & 3) != 0) return CP360_ERR_ALIGN;
+    return CP360_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI
+extern "C" size_t cp360_fix_work_bytes(int F, int h, int w) {
+    if (fix_args(F == 0 ? 1 : F, h, w) != CP360_OK) return 0;          // F = 0: what density needs, the tables alone
+    return fix_layout(F, h, w).total;
+}
+
+extern "C" int cp360_fix_counts(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w, int32_t* counts,
+                                int32_t* n_points, void* stream) {
+    if (!counts || !n_points) return CP360_ERR_NULL;
+    const int st = fix_points(lonlat, offsets, N, F, h, w);
+    if (st != CP360_OK) return st;
+    if ((((uintptr_t)counts | (uintptr_t)n_points) & 3) != 0) return CP360_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, (size_t)F * h * w * sizeof(int32_t), s) != hipSuccess) return CP360_ERR_HIP;
+    hipLaunchKernelGGL(fix_counts_kernel, dim3(F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N, h, w, (int*)counts,
+                       (int*)n_points);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_fix_density(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w, double sigma_rad,
+                                 float* out, void* work, size_t work_bytes, void* stream) {
+    if (!out || !work) return CP360_ERR_NULL;
+    int st = fix_points(lonlat, offsets, N, F, h, w);
+    if (st != CP360_OK) return st;
+    if (!(sigma_rad > 0.0) || !isfinite(sigma_rad)) return CP360_ERR_BAD_SHAPE;
+    if (((uintptr_t)work & 15) != 0 || ((uintptr_t)out & 3) != 0) return CP360_ERR_ALIGN;
+    const FixLayout l = fix_layout(0, h, w);
+    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
+    const float kappa = (float)(1.0 / (sigma_rad * sigma_rad));
+    hipStream_t s = (hipStream_t)stream;
+    st = launch_tables(work, h, w, s);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(fix_density_kernel, dim3((h * w + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N,
+                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, h, w, kappa);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t* neg, int Fn, int F, int h, int w, double* auc,
+                              long long* c_tot, long long* a_neg, void* work, size_t work_bytes, void* stream) {
+    if (!S || !pos || !neg || !auc || !c_tot || !a_neg || !work) return CP360_ERR_NULL;
+    const int st = fix_args(F, h, w);
+    if (st != CP360_OK) return st;
+    if (Fn != 1 && Fn != F) return CP360_ERR_BAD_SHAPE;
+    if (((uintptr_t)work & 15) != 0 || (((uintptr_t)auc | (uintptr_t)c_tot | (uintptr_t)a_neg) & 7) != 0 ||
+        (((uintptr_t)S | (uintptr_t)pos | (uintptr_t)neg) & 3) != 0)
+        return CP360_ERR_ALIGN;
+    const int P = h * w;
+    const FixLayout l = fix_layout(F, h, w);
+    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
+    char* wk = (char*)work;
+    SaucHdr* hdr = (SaucHdr*)(wk + l.hdr);
+    float* cs = (float*)(wk + l.cs);
+    unsigned* cp = (unsigned*)(wk + l.cp);
+    const size_t neg_stride = Fn == 1 ? 0 : (size_t)P;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fix_sauc_prep_kernel, dim3(F), dim3(kPrepThreads), 0, s, S, (const int*)pos, (const int*)neg, neg_stride, P,
+                       auc, c_tot, a_neg, hdr, cs, cp);
+    CP360_CHECK_HIP();
+    hipLaunchKernelGGL(fix_sauc_rank_kernel, dim3((P + kRankThreads - 1) / kRankThreads, F), dim3(kRankThreads), 0, s, S,
+                       (const int*)neg, neg_stride, hdr, (const float*)cs, (const unsigned*)cp, P);
+    CP360_CHECK_HIP();
+    hipLaunchKernelGGL(fix_sauc_finish_kernel, dim3((F + 255) / 256), dim3(256), 0, s, (const SaucHdr*)hdr, auc, F);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}

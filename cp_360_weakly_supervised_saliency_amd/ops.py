@@ -1689,3 +1689,76 @@ def sphere_eval(S, G, weights, fixations=None, work=None):
     check(lib().cp360_seval_scores(ptr(S), ptr(G), ptr(fixations), ptr(weights), F, h, w, ptr(scores), ptr(n_fix), ptr(work),
                                    work.numel() * 8, stream()))
     return scores, n_fix
+
+
+# ----------------------------------------------------------------------------- K15: fixations and shuffled AUC (csrc/fixations.hip)
+def _fix_points(lonlat, offsets, hw):
+    """The checks the three point ops share -> (N, F, h, w)."""
+    if lonlat.dim() != 2 or lonlat.shape[1] != 2:
+        raise ValueError("lonlat must be float64 [N, 2], got %s" % (tuple(lonlat.shape),))
+    _check_buf('lonlat', lonlat, torch.float64)
+    if offsets.dim() != 1 or offsets.shape[0] < 2 or offsets.device != lonlat.device:
+        raise ValueError("offsets must be int32 [F + 1] with F >= 1 on lonlat's device, got %s" % (tuple(offsets.shape),))
+    _check_buf('offsets', offsets, torch.int32)
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError("the grid must be at least 1 x 1, got %d x %d" % (h, w))
+    return int(lonlat.shape[0]), int(offsets.shape[0]) - 1, h, w
+
+
+def fixation_work(F, h, w, device, work=None):
+    """The workspace of cp360_fix_sauc for F frames (F = 0: of cp360_fix_density): `work` when it is large enough, else a new one."""
+    nbytes = lib().cp360_fix_work_bytes(int(F), int(h), int(w))
+    if nbytes == 0:
+        raise ValueError("fixations: unsupported geometry: %d x %d x %d (F <= 65535, h w <= 2^21)" % (F, h, w))
+    if work is None or work.device != device or work.dtype != torch.float64 or work.numel() * 8 < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
+def fixation_counts(lonlat, offsets, hw):
+    """cp360_fix_counts: lonlat f64 [N, 2] (longitude, latitude in radians), offsets int32 [F + 1] (CSR: frame f owns the points
+    offsets[f] .. offsets[f + 1] - 1) -> (counts int32 [F, h, w], n_points int32 [F]), both on the device, without a
+    synchronisation.  Longitudes wrap, latitudes clamp, points with a non-finite coordinate are dropped and not counted."""
+    require_gpu(lonlat, offsets)
+    N, F, h, w = _fix_points(lonlat, offsets, hw)
+    counts = torch.empty((F, h, w), dtype=torch.int32, device=lonlat.device)
+    n_points = torch.empty((F,), dtype=torch.int32, device=lonlat.device)
+    check(lib().cp360_fix_counts(ptr(lonlat), ptr(offsets), N, F, h, w, ptr(counts), ptr(n_points), stream()))
+    return counts, n_points
+
+
+def fixation_density(lonlat, offsets, hw, sigma_rad, work=None):
+    """cp360_fix_density: the points of ``fixation_counts`` -> f32 [F, h, w], per frame the sum over its points of the von
+    Mises-Fisher kernel exp((p . q - 1) / sigma_rad^2) on the sphere (``sphere_smooth``'s kernel), un-normalised.  A frame's map does
+    not depend on F or on its place in the batch; a frame without points is zero."""
+    require_gpu(lonlat, offsets, work)
+    N, F, h, w = _fix_points(lonlat, offsets, hw)
+    sigma_rad = float(sigma_rad)
+    if not (sigma_rad > 0.0 and math.isfinite(sigma_rad)):
+        raise ValueError("sigma_rad must be finite and positive, got %r" % (sigma_rad,))
+    work = fixation_work(0, h, w, lonlat.device, work)
+    out = torch.empty((F, h, w), dtype=torch.float32, device=lonlat.device)
+    check(lib().cp360_fix_density(ptr(lonlat), ptr(offsets), N, F, h, w, sigma_rad, ptr(out), ptr(work), work.numel() * 8, stream()))
+    return out
+
+
+def shuffled_auc(S, pos, neg, work=None):
+    """cp360_fix_sauc: S f32 [F, h, w], pos int32 [F, h, w] (the fixation counts of each frame, clamped to 0 .. 1023), neg int32
+    [1, h, w] or [F, h, w] (the counts the negatives are drawn from, clamped to 0 .. 2^20) -> (auc f64 [F], c_tot int64 [F], a_neg
+    int64 [F]) on the device, without a synchronisation.  An exact quotient of integers: no jitter, no random draw."""
+    require_gpu(S, pos, neg, work)
+    F, h, w = _eval_maps('S', S)
+    if pos.dim() != 3 or tuple(pos.shape) != (F, h, w) or pos.device != S.device:
+        raise ValueError("pos must be int32 %s on S's device, got %s" % ((F, h, w), tuple(pos.shape)))
+    if neg.dim() != 3 or tuple(neg.shape) not in ((1, h, w), (F, h, w)) or neg.device != S.device:
+        raise ValueError("neg must be int32 [1 or %d, %d, %d] on S's device, got %s" % (F, h, w, tuple(neg.shape)))
+    _check_buf('pos', pos, torch.int32)
+    _check_buf('neg', neg, torch.int32)
+    work = fixation_work(F, h, w, S.device, work)
+    auc = torch.empty((F,), dtype=torch.float64, device=S.device)
+    c_tot = torch.empty((F,), dtype=torch.int64, device=S.device)
+    a_neg = torch.empty((F,), dtype=torch.int64, device=S.device)
+    check(lib().cp360_fix_sauc(ptr(S), ptr(pos), ptr(neg), int(neg.shape[0]), F, h, w, ptr(auc), ptr(c_tot), ptr(a_neg), ptr(work),
+                               work.numel() * 8, stream()))
+    return auc, c_tot, a_neg

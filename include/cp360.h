@@ -605,6 +605,38 @@ int cp360_seval_resample(const float* src, int F, int hs, int ws, float* dst, in
 int cp360_seval_scores(const float* S, const float* G, const uint8_t* fixations, const int32_t* weights, int F, int h, int w,
                        double* scores, int32_t* n_fix, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K15: fixations from scan-paths, shuffled AUC on the sphere
+ * A video's fixations are N points in CSR form: lonlat f64 [N, 2] in radians (longitude = theta, latitude = phi of K11's
+ * geometry, north up; may be NULL when N = 0), offsets int32 [F + 1] ascending from 0 to N (DEVICE memory: an offset outside
+ * 0 .. N is clamped into it); the points of frame f are offsets[f] .. offsets[f + 1] - 1.  A point with a non-finite coordinate
+ * contributes nothing anywhere.  The specification is the package's own, DESIGN.md "K15", restated in tests/fixations_restate.py.
+ *
+ *   counts   counts int32 [F, h, w] = the number of frame f's points in each pixel, n_points int32 [F] = the number of its finite
+ *            points.  The pixel, in float64 with one operation per step: u = (lon / pi + 1) (w / 2), x = floor(u) mod w in 0 ..
+ *            w - 1 (longitudes wrap; a u that overflows: column 0); v = (1 - lat / (pi / 2)) (h / 2), y = clamp(floor(v), 0, h - 1)
+ *            (latitudes beyond the poles clamp).  No trigonometry: numpy gives the same integers.
+ *   density  out f32 [F, h, w]: G[f, i] = sum_k expf(kappa (p_i . q_k - 1)) over the frame's finite points in ascending k, kappa =
+ *            (float)(1 / sigma_rad^2) (cp360_view_smooth's kernel), p_i from K11's tables, q_k = dir(lon_k, lat_k) computed in double
+ *            and rounded to f32, the sum in f32 in that order: un-normalised, bit-identical whatever the batch and the frame's
+ *            place in it; a frame without points is zero.  sigma_rad finite and > 0, else CP360_ERR_BAD_SHAPE.
+ *   sauc     shuffled AUC: S f32 [F, h, w], pos int32 [F, h, w] (clamped to 0 .. 1023), neg int32 [Fn, h, w], Fn = 1 (one map for
+ *            every frame) or F (clamped to 0 .. 2^20; every pixel counts, fixated ones included) -> auc f64 [F], c_tot int64 [F] =
+ *            sum pos, a_neg int64 [F] = sum neg.  For a pixel with pos_i > 0: C_i = sum of pos_j over pos_j > 0, S_j >= S_i, A_i =
+ *            sum of neg_j over S_j >= S_i; AUC = the trapezoid sum over (0, 0), the distinct (A_i / A_neg, C_i / C_tot) by
+ *            descending S_i, (1, 1) = an integer over 2 A_neg C_tot, rounded once; no jitter, no random draw.  C_tot = 0, A_neg =
+ *            0, a non-finite value in the frame's S, or 2 A_neg C_tot >= 2^53: NaN for that frame.
+ * work: 16-byte aligned device memory of cp360_fix_work_bytes(F, h, w) bytes for sauc, of cp360_fix_work_bytes(0, h, w) bytes for
+ * density (K11's tables, which every call rebuilds); counts needs none; 0 = bad or unsupported sizes; too small:
+ * CP360_ERR_BAD_SHAPE.  F, h or w < 1, N < 0, Fn not 1 or F: CP360_ERR_BAD_SHAPE; F > 65535, h w > 2^21 or N >= 2^31:
+ * CP360_ERR_UNSUPPORTED.  Asynchronous on the stream; the only atomics add integers. */
+size_t cp360_fix_work_bytes(int F, int h, int w);
+int cp360_fix_counts(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w, int32_t* counts,
+                     int32_t* n_points, void* stream);
+int cp360_fix_density(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w, double sigma_rad, float* out,
+                      void* work, size_t work_bytes, void* stream);
+int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t* neg, int Fn, int F, int h, int w, double* auc,
+                   long long* c_tot, long long* a_neg, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
