@@ -13,35 +13,40 @@
 //            pixel, fixated ones included), C_tot = sum pos, A_neg = sum neg.  For a pixel with pos_i > 0: C_i = sum_{pos_j > 0,
 //            S_j >= S_i} pos_j, A_i = sum_{S_j >= S_i} neg_j.  The ROC points are (0, 0), the distinct (A_i / A_neg, C_i / C_tot)
 //            by descending S_i, (1, 1); N = sum_k (A_k - A_k-1)(C_k + C_k-1) is an integer and AUC = N / (2 A_neg C_tot), rounded
-//            once.  C_tot = 0, A_neg = 0, a non-finite S or 2 A_neg C_tot >= 2^53: NaN.
+//            once.  C_tot = 0, A_neg = 0, a non-finite S or 2 A_neg C_tot >= 2^53: NaN.  Summed by parts, with the distinct
+//            positive values v_1 > .. > v_m, mult_k = sum of pos_j over S_j = v_k and A_k = sum of neg_j over S_j >= v_k:
+//                N = 2 A_neg C_tot - T,   T = sum_{k = 1 .. m} A_k (mult_k + mult_k+1),   mult_m+1 = 0
+//            Every term needs the A of its own value alone, T is a sum of non-negative terms below 2^53 (it never wraps, any
+//            order gives the same bits) and it is linear in A.
 //
 // Launches, all on the caller's stream, no host synchronisation, integer atomics only (any order gives the same bits):
 //   K15a  counts: a clear, then one workgroup per frame, a vector atomicAdd per point
 //   K15b  density: grid (ceil(P / 256), F), a pixel per thread; the frame's q_k staged in LDS 256 at a time, every lane reads the
 //         same address (a broadcast), one expf per pair
 //   K15c  sAUC prepare: one 1024-thread workgroup per frame - the sums, the finiteness of S, the positives compacted as (S, pos)
-//   K15d  sAUC rank: grid (ceil(P / 256), F), sized for P positives in tiles of 256.  A thread owns one positive: a loop over the
-//         compacted list gives C_i, G_i (the same sum with >), the next higher positive value and whether it is the first of its
-//         ties in the list; a loop over pixels, (S_j, neg_j) staged in LDS 1024 at a time, gives A_i and the A of the next higher
-//         value (u32 per tile: 1024 * 2^20 < 2^32; 64 bits across tiles).  The first of each distinct value adds (A - A_prev)(C +
-//         G) to the frame's int64 sum, the lowest value also the segment to (1, 1).  A video has tens of positives per frame,
-//         not P: the workgroups that the positives leave over split the pixel loop (N is linear in A), the rest exit at once.
+//   K15d  sAUC rank: grid (ceil(P / 256), F), sized for P positives in tiles of 256.  A thread owns one positive, value v: a loop
+//         over the compacted list gives meq = the sum of pos_j at v, whether the thread is the first of its ties in the list, and
+//         (nl, mlow) = the largest value below v and the sum of pos_j at it, tracked online in the one pass; a loop over pixels,
+//         (S_j, neg_j) staged in LDS 1024 at a time, gives A with one compare-select-add per pair (u32 per tile: 1024 * 2^20 <
+//         2^32; 64 bits across tiles).  The first of each distinct value adds A (meq + mlow) to the frame's T.  A video has tens
+//         of positives per frame, not P: the workgroups that the positives leave over split the pixel loop (T is linear in A)
+//         as far as kSplit allows, the rest exit at once.
 //   K15e  sAUC finish: the quotient
 #pragma clang fp contract(off)
-#include "sphere.h"
+#include "roc.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int kFixTile = 256;                // K15b: points staged at a time
-constexpr int kPrepThreads = 1024;           // K15c
-constexpr int kPrepWaves = kPrepThreads / 64;
-constexpr int kRankThreads = 256;            // K15d: positives per workgroup
-constexpr int kRankTile = 1024;              // K15d: pixels staged at a time = the span over which a u32 cannot overflow
 constexpr int kMaxPos = 1023;
 constexpr int kMaxNeg = 1 << 20;
-constexpr int kFixMaxP = 1 << 21;            // 1023 P < 2^31: C_tot and every C_i fit a u32
+// K15d: a workgroup that shares a tile's pixel loop repeats the tile's list loop (n entries), so it takes a share only while the
+// share is at least kSplit n pixels.  Measured on one MI355X, cp360_fix_sauc alone at the bench shape (256 frames of 120 x 240,
+// n = 25 .. 32, 29 pixel tiles; three runs each): kSplit 4 (113 chunks) 0.162 / 0.164 / 0.162 ms, 16 (60 chunks) 0.138 / 0.138 /
+// 0.139 ms, 64 (15 chunks of two pixel tiles) 0.132 / 0.134 / 0.132 ms.
+constexpr int kSplit = 64;
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kHalfPi = 1.57079632679489661923;
 
@@ -49,7 +54,7 @@ struct SaucHdr {                             // per frame, K15c -> K15d, K15e
     int n_rank;                              // the number of positive pixels, or 0 when the frame has no AUC
     int pad;
     long long c_tot, a_neg;
-    unsigned long long N;                    // sum (A_k - A_k-1)(C_k + C_k-1)
+    unsigned long long T;                    // sum_k A_k (mult_k + mult_k+1)
 };
 
 struct FixLayout {
@@ -159,14 +164,14 @@ __global__ __launch_bounds__(256) void fix_density_kernel(const double* __restri
 
 // ------------------------------------------------------------------ K15c: sums and the compacted positives
 // grid F, 1024 threads
-__global__ __launch_bounds__(kPrepThreads) void fix_sauc_prep_kernel(const float* __restrict__ S, const int* __restrict__ pos,
-                                                                     const int* __restrict__ neg, size_t neg_stride, int P,
-                                                                     double* __restrict__ auc, long long* __restrict__ c_tot_out,
-                                                                     long long* __restrict__ a_neg_out, SaucHdr* __restrict__ hdr,
-                                                                     float* __restrict__ cs, unsigned* __restrict__ cp) {
-    __shared__ long long sml[kPrepWaves * 3];
+__global__ __launch_bounds__(kRocThreads) void fix_sauc_prep_kernel(const float* __restrict__ S, const int* __restrict__ pos,
+                                                                    const int* __restrict__ neg, size_t neg_stride, int P,
+                                                                    double* __restrict__ auc, long long* __restrict__ c_tot_out,
+                                                                    long long* __restrict__ a_neg_out, SaucHdr* __restrict__ hdr,
+                                                                    float* __restrict__ cs, unsigned* __restrict__ cp) {
+    __shared__ long long sml[kRocWaves * 3];
     __shared__ int cnt;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, f = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, f = blockIdx.x;
     S += (size_t)f * P;
     pos += (size_t)f * P;
     neg += (size_t)f * neg_stride;
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(kPrepThreads) void fix_sauc_prep_kernel(const float
     if (tid == 0) cnt = 0;
     __syncthreads();
     long long acc[3] = {0, 0, 0};                                      // C_tot, A_neg, non-finite values
-    for (int i0 = 0; i0 < P; i0 += kPrepThreads) {                     // uniform: ballots need every lane
+    for (int i0 = 0; i0 < P; i0 += kRocThreads) {                      // uniform: ballots need every lane
         const int i = i0 + tid;
         int m = 0;
         float s = 0.f;
@@ -197,20 +202,9 @@ __global__ __launch_bounds__(kPrepThreads) void fix_sauc_prep_kernel(const float
             cp[slot] = (unsigned)m;
         }
     }
-#pragma unroll
-    for (int n = 0; n < 3; ++n) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[n] += __shfl_xor(acc[n], off);
-        if (lane == 0) sml[wave * 3 + n] = acc[n];
-    }
-    __syncthreads();
+    roc_reduce(acc, sml, RocAdd());
     if (tid == 0) {
-        long long c_tot = 0, a_neg = 0, bad = 0;
-        for (int k = 0; k < kPrepWaves; ++k) {
-            c_tot += sml[k * 3];
-            a_neg += sml[k * 3 + 1];
-            bad += sml[k * 3 + 2];
-        }
+        const long long c_tot = acc[0], a_neg = acc[1], bad = acc[2];
         // 2 A_neg C_tot < 2^53  <=>  A_neg <= floor((2^52 - 1) / C_tot): the product itself may not fit 64 bits
         const bool rank = bad == 0 && c_tot > 0 && a_neg > 0 && a_neg <= ((1LL << 52) - 1) / c_tot;
         c_tot_out[f] = c_tot;
@@ -220,11 +214,11 @@ __global__ __launch_bounds__(kPrepThreads) void fix_sauc_prep_kernel(const float
         hdr[f].pad = 0;
         hdr[f].c_tot = c_tot;
         hdr[f].a_neg = a_neg;
-        hdr[f].N = 0ull;
+        hdr[f].T = 0ull;
     }
 }
 
-// ------------------------------------------------------------------ K15d: the ROC segment of every distinct positive value
+// ------------------------------------------------------------------ K15d: T of every frame
 // grid (ceil(P / 256), F), 256 threads
 __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float* __restrict__ S, const int* __restrict__ neg,
                                                                      size_t neg_stride, SaucHdr* __restrict__ hdr,
@@ -235,9 +229,10 @@ __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float
     const int f = blockIdx.y, tid = threadIdx.x;
     const int n = hdr[f].n_rank;
     if (n == 0) return;                                                // the whole workgroup: before any barrier
-    // the grid holds ceil(P / 256) >= tiles workgroups: those that the positives leave over share the pixel loop - workgroup b
-    // owns tile b % tiles of the positives and every chunks-th pixel tile from b / tiles on; N is linear in A, so the parts add up
-    const int tiles = (n + kRankThreads - 1) / kRankThreads, chunks = (int)gridDim.x / tiles;
+    // the grid holds ceil(P / 256) >= tiles workgroups: workgroup b owns tile b % tiles of the positives and every chunks-th
+    // pixel tile from b / tiles on; T is linear in A, so the parts add up
+    const int tiles = (n + kRankThreads - 1) / kRankThreads, share = P / (kSplit * n);                 // kSplit n <= 2^27
+    const int spare = (int)gridDim.x / tiles, chunks = share < 1 ? 1 : (share < spare ? share : spare);
     if ((int)blockIdx.x >= tiles * chunks) return;
     const int chunk = (int)blockIdx.x / tiles;
     const int k = ((int)blockIdx.x - chunk * tiles) * kRankThreads + tid;
@@ -248,15 +243,15 @@ __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float
     const bool own = k < n;
     const bool busy = k - (tid & 63) < n;                              // the wave owns a positive: the others only stage and wait
     const float v = own ? cs[k] : INFINITY;
-    // the positives alone: C, G, the next higher value, the first of the ties
-    unsigned Cge = 0u, Cgt = 0u;
-    float nv = INFINITY;
+    // the positives alone: the multiplicity at v, the first of the ties, the next lower value and the multiplicity at it
+    unsigned meq = 0u, mlow = 0u;
+    float nl = -INFINITY;
     bool first = true;
     for (int t0 = 0; t0 < n; t0 += kRankTile) {
 #pragma unroll
         for (int q = 0; q < kRankTile / kRankThreads; ++q) {
             const int jj = q * kRankThreads + tid, j = t0 + jj;
-            sv[jj] = j < n ? cs[j] : -INFINITY;                        // below every value: counts nothing
+            sv[jj] = j < n ? cs[j] : -INFINITY;                        // padding: below every value, multiplicity 0
             sp[jj] = j < n ? cp[j] : 0u;
         }
         __syncthreads();
@@ -264,16 +259,19 @@ __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float
         for (int jj = 0; busy && jj < lim; ++jj) {
             const float s = sv[jj];
             const unsigned m = sp[jj];
-            Cge += s >= v ? m : 0u;
-            Cgt += s > v ? m : 0u;
-            nv = s > v ? fminf(nv, s) : nv;
-            first = first && !(s == v && t0 + jj < k);
+            const bool eq = s == v;
+            meq += eq ? m : 0u;
+            first = first && !(eq && t0 + jj < k);
+            const float c = s < v ? s : -INFINITY;
+            mlow = c > nl ? m : mlow + (c == nl ? m : 0u);             // while nl = -inf this gathers every m: the first c > nl drops it
+            nl = fmaxf(nl, c);
         }
         __syncthreads();
     }
-    // this chunk's pixels: their share of A at v and at the next higher value
-    unsigned long long A = 0ull, Ap = 0ull;
-    for (int t0 = chunk * kRankTile; t0 < P; t0 += chunks * kRankTile) {         // chunks <= 2^13: t0 stays below 2^24
+    if (nl == -INFINITY) mlow = 0u;                                    // the lowest value: nothing below it
+    // this chunk's pixels: their share of A
+    unsigned long long A = 0ull;
+    for (int t0 = chunk * kRankTile; t0 < P; t0 += chunks * kRankTile) {          // chunks <= 2^13: t0 stays below 2^24
 #pragma unroll
         for (int q = 0; q < kRankTile / kRankThreads; ++q) {
             const int jj = q * kRankThreads + tid, j = t0 + jj;
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float
             sp[jj] = in ? (unsigned)fix_clamp(neg[j], 0, kMaxNeg) : 0u;     // a pixel past the frame counts nothing
         }
         __syncthreads();
-        unsigned a = 0u, ap = 0u;
+        unsigned a = 0u;
 #pragma unroll 4
         for (int jj = 0; busy && jj < kRankTile; jj += 4) {
             const float4 s = *reinterpret_cast<const float4*>(&sv[jj]);
@@ -291,45 +289,30 @@ __global__ __launch_bounds__(kRankThreads) void fix_sauc_rank_kernel(const float
             a += s.y >= v ? p.y : 0u;
             a += s.z >= v ? p.z : 0u;
             a += s.w >= v ? p.w : 0u;
-            ap += s.x >= nv ? p.x : 0u;
-            ap += s.y >= nv ? p.y : 0u;
-            ap += s.z >= nv ? p.z : 0u;
-            ap += s.w >= nv ? p.w : 0u;
         }
         A += a;
-        Ap += ap;
         __syncthreads();
     }
-    unsigned long long part = 0ull;
-    if (own && first) {
-        const unsigned long long c_tot = (unsigned long long)hdr[f].c_tot, a_neg = (unsigned long long)hdr[f].a_neg;
-        part = (A - Ap) * (unsigned long long)(Cge + Cgt);             // the point before: (Ap, Cgt)
-        // the lowest value: on to (1, 1), (A_neg - A) 2 C_tot; a chunk other than 0 brings -A alone, modulo 2^64 - N itself is below 2^53
-        if ((unsigned long long)Cge == c_tot) part += ((chunk == 0 ? a_neg : 0ull) - A) * (2ull * c_tot);
-    }
+    unsigned long long part = own && first ? A * (unsigned long long)(meq + mlow) : 0ull;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if ((tid & 63) == 0 && part) atomicAdd(&hdr[f].N, part);           // integers: no order
+    if ((tid & 63) == 0 && part) atomicAdd(&hdr[f].T, part);           // integers: no order
 }
 
 // ------------------------------------------------------------------ K15e: the AUC
 __global__ __launch_bounds__(256) void fix_sauc_finish_kernel(const SaucHdr* __restrict__ hdr, double* __restrict__ auc, int F) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F || hdr[f].n_rank == 0) return;                          // K15c wrote the NaN
-    auc[f] = (double)hdr[f].N / (2.0 * (double)hdr[f].a_neg * (double)hdr[f].c_tot);     // integers below 2^53: one rounding
+    const unsigned long long a_neg = (unsigned long long)hdr[f].a_neg, c_tot = (unsigned long long)hdr[f].c_tot;
+    const unsigned long long N = 2ull * a_neg * c_tot - hdr[f].T;      // integers below 2^53: one rounding
+    auc[f] = (double)N / (2.0 * (double)a_neg * (double)c_tot);
 }
 
 // ------------------------------------------------------------------ host side
-int fix_args(int F, int h, int w) {
-    if (bad_image(F, h, w)) return CP360_ERR_BAD_SHAPE;
-    if (F > 65535 || (long long)h * w > kFixMaxP) return CP360_ERR_UNSUPPORTED;
-    return CP360_OK;
-}
-
 // the points: lonlat may be NULL when there are none
 int fix_points(const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w) {
     if (!offsets || (!lonlat && N > 0)) return CP360_ERR_NULL;
-    const int st = fix_args(F, h, w);
+    const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
     if (N < 0) return CP360_ERR_BAD_SHAPE;
     if (N >= (1LL << 31)) return CP360_ERR_UNSUPPORTED;
@@ -341,7 +324,7 @@ int fix_points(const double* lonlat, const int32_t* offsets, long long N, int F,
 
 // ------------------------------------------------------------------ C ABI
 extern "C" size_t cp360_fix_work_bytes(int F, int h, int w) {
-    if (fix_args(F == 0 ? 1 : F, h, w) != CP360_OK) return 0;          // F = 0: what density needs, the tables alone
+    if (roc_args(F == 0 ? 1 : F, h, w) != CP360_OK) return 0;          // F = 0: what density needs, the tables alone
     return fix_layout(F, h, w).total;
 }
 
@@ -381,7 +364,7 @@ extern "C" int cp360_fix_density(const double* lonlat, const int32_t* offsets, l
 extern "C" int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t* neg, int Fn, int F, int h, int w, double* auc,
                               long long* c_tot, long long* a_neg, void* work, size_t work_bytes, void* stream) {
     if (!S || !pos || !neg || !auc || !c_tot || !a_neg || !work) return CP360_ERR_NULL;
-    const int st = fix_args(F, h, w);
+    const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
     if (Fn != 1 && Fn != F) return CP360_ERR_BAD_SHAPE;
     if (((uintptr_t)work & 15) != 0 || (((uintptr_t)auc | (uintptr_t)c_tot | (uintptr_t)a_neg) & 7) != 0 ||
@@ -396,7 +379,7 @@ extern "C" int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t*
     unsigned* cp = (unsigned*)(wk + l.cp);
     const size_t neg_stride = Fn == 1 ? 0 : (size_t)P;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fix_sauc_prep_kernel, dim3(F), dim3(kPrepThreads), 0, s, S, (const int*)pos, (const int*)neg, neg_stride, P,
+    hipLaunchKernelGGL(fix_sauc_prep_kernel, dim3(F), dim3(kRocThreads), 0, s, S, (const int*)pos, (const int*)neg, neg_stride, P,
                        auc, c_tot, a_neg, hdr, cs, cp);
     CP360_CHECK_HIP();
     hipLaunchKernelGGL(fix_sauc_rank_kernel, dim3((P + kRankThreads - 1) / kRankThreads, F), dim3(kRankThreads), 0, s, S,

@@ -29,20 +29,25 @@
 //         compacted list (n_fix^2 compares, not n_fix P).  The point of fixation i goes to slot c_i - 1; tied fixations write the
 //         same words to the same slot.  The grid is sized for n_fix = P; a tile past the frame's n_fix exits at once.
 //   K14c  one workgroup per frame adds N over the filled slots (integers: no order) and writes the AUC.
-#include "sphere.h"
+//
+// This AUC is fixations.hip's shuffled AUC (K15) with pos_i = [i in M], neg_i = [i not in M] a_i: the tests hold the two entries
+// to the same bits, and the limits, their check and the workgroup reduction are shared (roc.h).  K14b and K14c stay beside K15d
+// because unit positives and weights <= 1024 let c ride in the packed word for nothing and make the slot index a rank: K15d, which
+// has neither, finds each value's neighbour in a list loop of about 17 instructions per entry where K14b spends 2, and on it this
+// file's bench call took 1.81 ms instead of 1.29 ms (DESIGN.md "K14 and K15: one ROC").
+#include "roc.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int kEvalThreads = 1024;           // K14a
-constexpr int kEvalWaves = kEvalThreads / 64;
-constexpr int kRankThreads = 256;            // K14b: fixations per workgroup
-constexpr int kRankTile = 1024;              // K14b: pixels staged at a time = the span over which the packed word cannot overflow
+constexpr int kEvalThreads = kRocThreads;    // K14a
+constexpr int kEvalWaves = kRocWaves;
+// kRankThreads (K14b: fixations per workgroup) and kRankTile (K14b: pixels staged at a time = the span over which the packed
+// word cannot overflow) are roc.h's
 constexpr int kFixShift = 21;                // pk = 1 << 21 for a fixated pixel; weights <= 1024, 1024 * 1024 < 2^21
 constexpr unsigned kWeightMask = (1u << kFixShift) - 1u;
-constexpr int kEvalMaxP = 1 << 21;           // 1024 P < 2^31: A and every A_i fit a u32
-constexpr int kMaxWeight = 1024;
+constexpr int kMaxWeight = 1024;             // 1024 P <= 2^31 (roc.h's kRocMaxP): A and every A_i fit a u32
 constexpr double kEvalEps = 2.220446049250313e-16;             // 2^-52
 
 struct EvalHdr {                             // per frame, K14a -> K14b, K14c
@@ -67,30 +72,7 @@ EvalLayout eval_layout(int F, int P) {
     return l;
 }
 
-// ---- workgroup reductions of K14a: 16 waves, each value through a xor butterfly (every lane ends with the same bits: a + b =
-// b + a), then the 16 wave results through a second butterfly in every wave: one fixed tree
-struct EvAdd { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
 struct EvMin { __device__ float operator()(float a, float b) const { return fminf(a, b); } };
-
-template <typename T, int N, typename Op>
-__device__ __forceinline__ void eval_reduce(T (&v)[N], T* sm, Op op) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[n] = op(v[n], __shfl_xor(v[n], off));
-        if (lane == 0) sm[wave * N + n] = v[n];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        T r = sm[(lane & (kEvalWaves - 1)) * N + n];                   // lane l holds wave l % 16's result
-#pragma unroll
-        for (int off = kEvalWaves / 2; off > 0; off >>= 1) r = op(r, __shfl_xor(r, off));
-        v[n] = r;
-    }
-    __syncthreads();
-}
 
 __device__ __forceinline__ int eval_weight(const int* __restrict__ wrow, int y) {
     const int a = wrow[y];
@@ -152,12 +134,12 @@ __global__ __launch_bounds__(kEvalThreads) void seval_moments_kernel(const float
     }
     {
         double t[5] = {s1[0], s1[1], 0.0, 0.0, 0.0};
-        eval_reduce(t, smd, EvAdd());
+        roc_reduce(t, smd, RocAdd());
         s1[0] = t[0];
         s1[1] = t[1];
     }
-    eval_reduce(mn, smf, EvMin());
-    eval_reduce(ia, sml, EvAdd());
+    roc_reduce(mn, smf, EvMin());
+    roc_reduce(ia, sml, RocAdd());
     const double A = (double)ia[0];
     const bool bad = ia[1] != 0;
     const double mu_s = s1[0] / A, mu_g = s1[1] / A;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(kEvalThreads) void seval_moments_kernel(const float
         s2[3] += a * (s - min_s);
         s2[4] += a * (g - min_g);
     }
-    eval_reduce(s2, smd, EvAdd());
+    roc_reduce(s2, smd, RocAdd());
     const double sig_s = sqrt(s2[0] / A), sig_g = sqrt(s2[1] / A);
     const double thr = mu_g + 2.0 * sig_g;
     const double mass_s = s2[3], mass_g = s2[4];
@@ -206,8 +188,8 @@ __global__ __launch_bounds__(kEvalThreads) void seval_moments_kernel(const float
         base = __shfl(base, 0);
         if (fx) fixs[base + __popcll(m & ((1ull << lane) - 1ull))] = sf;
     }
-    eval_reduce(s3, smd, EvAdd());
-    eval_reduce(i3, sml, EvAdd());
+    roc_reduce(s3, smd, RocAdd());
+    roc_reduce(i3, sml, RocAdd());
     const int n_fix = (int)i3[0];
     const long long a_neg = i3[1];
     const bool rank = !bad && n_fix > 0 && n_fix < P && a_neg > 0;
@@ -324,25 +306,18 @@ __global__ __launch_bounds__(256) void seval_auc_kernel(const EvalHdr* __restric
     }
 }
 
-// ------------------------------------------------------------------ host side
-int eval_args(int F, int h, int w) {
-    if (bad_image(F, h, w)) return CP360_ERR_BAD_SHAPE;
-    if (F > 65535 || (long long)h * w > kEvalMaxP) return CP360_ERR_UNSUPPORTED;
-    return CP360_OK;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
 extern "C" size_t cp360_seval_work_bytes(int F, int h, int w) {
-    if (eval_args(F, h, w) != CP360_OK) return 0;
+    if (roc_args(F, h, w) != CP360_OK) return 0;
     return eval_layout(F, h * w).total;
 }
 
 extern "C" int cp360_seval_resample(const float* src, int F, int hs, int ws, float* dst, int h, int w, void* stream) {
     if (!src || !dst) return CP360_ERR_NULL;
     if (bad_image(F, hs, ws) || bad_image(F, h, w)) return CP360_ERR_BAD_SHAPE;
-    const int st = eval_args(F, h, w);
+    const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
     if (big_image(F, hs, ws)) return CP360_ERR_UNSUPPORTED;
     if (((uintptr_t)src & 3) != 0 || ((uintptr_t)dst & 3) != 0) return CP360_ERR_ALIGN;
@@ -354,7 +329,7 @@ extern "C" int cp360_seval_resample(const float* src, int F, int hs, int ws, flo
 extern "C" int cp360_seval_scores(const float* S, const float* G, const uint8_t* fixations, const int32_t* weights, int F, int h, int w,
                                   double* scores, int32_t* n_fix, void* work, size_t work_bytes, void* stream) {
     if (!S || !G || !weights || !scores || !n_fix || !work) return CP360_ERR_NULL;
-    const int st = eval_args(F, h, w);
+    const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
     if (((uintptr_t)work & 15) != 0 || ((uintptr_t)scores & 7) != 0 || (((uintptr_t)S | (uintptr_t)G | (uintptr_t)weights | (uintptr_t)n_fix) & 3) != 0)
         return CP360_ERR_ALIGN;

@@ -9,6 +9,7 @@ density, the scan-path interpolation, and the synthetic points and maps that the
     sAUC     pos clamped to 0 .. 1023, neg to 0 .. 2^20; C_tot = sum pos, A_neg = sum neg (every pixel); for pos_i > 0: C_i = sum of
              pos_j over pos_j > 0, S_j >= S_i, A_i = sum of neg_j over S_j >= S_i; the trapezoid rule over (0, 0), the distinct
              (A_i / A_neg, C_i / C_tot) by descending S_i, (1, 1).  NaN: C_tot = 0, A_neg = 0, a non-finite S, 2 A_neg C_tot >= 2^53
+             sauc_exact is the specification; sauc_numerator_by_parts restates the form that K15d adds up
 """
 import numpy as np
 
@@ -149,16 +150,32 @@ def sauc_trapezoid(A, C, a_neg, c_tot):
     return rs.auc_trapezoid(np.asarray(A), np.asarray(C), a_neg, c_tot)
 
 
+def sauc_numerator(A, C, a_neg, c_tot):
+    """N = sum (A_k - A_k-1)(C_k + C_k-1) over (0, 0), the points, (A_neg, C_tot): a Python integer."""
+    xs = [0] + [int(v) for v in A] + [a_neg]
+    ys = [0] + [int(v) for v in C] + [c_tot]
+    return sum((xs[k + 1] - xs[k]) * (ys[k + 1] + ys[k]) for k in range(len(xs) - 1))
+
+
 def sauc_exact(S, pos, neg):
     """The shuffled AUC of one frame as one quotient of Python integers, rounded once; NaN in the degenerate cases."""
     S = np.asarray(S)
     A, C, a_neg, c_tot = sauc_points(S, pos, neg)
     if c_tot == 0 or a_neg == 0 or not np.all(np.isfinite(S)) or 2 * a_neg * c_tot >= 1 << 53:
         return float('nan')
-    xs = [0] + [int(v) for v in A] + [a_neg]
-    ys = [0] + [int(v) for v in C] + [c_tot]
-    N = sum((xs[k + 1] - xs[k]) * (ys[k + 1] + ys[k]) for k in range(len(xs) - 1))
-    return N / (2 * a_neg * c_tot)
+    return sauc_numerator(A, C, a_neg, c_tot) / (2 * a_neg * c_tot)
+
+
+def sauc_numerator_by_parts(S, pos, neg):
+    """The same N summed by parts, the form K15d adds up: with the distinct values v_1 > .. > v_m of S at the positive
+    pixels, mult_k = the sum of pos over S = v_k and A_k = the sum of neg over S >= v_k, N = 2 A_neg C_tot - T, T = sum_k A_k
+    (mult_k + mult_k+1), mult_m+1 = 0.  No sorting of the pixels, no running C: every term from its own value alone."""
+    S = np.asarray(S).astype(np.float64).reshape(-1)
+    pos, neg = _clamped(pos, neg)
+    vals = sorted(set(S[pos > 0].tolist()), reverse=True)
+    mult = [int(pos[S == v].sum()) for v in vals] + [0]
+    T = sum(int(neg[S >= v].sum()) * (mult[k] + mult[k + 1]) for k, v in enumerate(vals))
+    return 2 * int(neg.sum()) * int(pos.sum()) - T
 
 
 def sauc_video(S, pos, neg):

@@ -133,6 +133,49 @@ def test_sauc_exact_agrees_with_the_float64_trapezoid_to_2e16():
     assert abs(fr.sauc_exact(S, pos, neg) - fr.sauc_trapezoid(A, Cc, a_neg, c_tot)) <= 2e-16
 
 
+def by_parts_frames():
+    """(name, S, pos, neg): quantised (8 levels) and unquantised maps at 8 x 16 and 33 x 66 with multiplicities up to 1023 and
+    negatives up to 2^20 on every pixel class (positive or not, tied or not), a frame with a single positive, and a frame whose
+    lowest positive value ties with negatives."""
+    out = []
+    for h, w in ((8, 16), (33, 66)):
+        for levels in (8, None):
+            seed = 1900 + 10 * h + (levels or 0)
+            S, pos, _ = sauc_case(seed, h, w, levels=levels, n_pos=max(6, h * w // 20))
+            pos = pos * hashrng.integers(seed + 5, (h, w), 1, 342)     # 3 * 341 = 1023; sauc_case gives 1 .. 4 and sums of them
+            pos.reshape(-1)[np.flatnonzero(pos.reshape(-1))[:2]] = [1023, 2000]            # at the clamp and above it
+            neg = hashrng.integers(seed + 6, (h, w), 0, (1 << 20) + 1) * (hashrng.integers(seed + 7, (h, w), 0, 3) > 0)
+            neg.reshape(-1)[:2] = [1 << 20, 1 << 22]
+            out.append(('%dx%d levels %s' % (h, w, levels), S, pos, neg))
+            one = np.zeros_like(pos)
+            one[h // 2, w // 3] = 7
+            out.append(('%dx%d levels %s, a single positive' % (h, w, levels), S, one, neg))
+        S, pos, neg = (a.copy() for a in out[-4][1:])                  # the quantised frame of this size
+        low = np.flatnonzero(S.reshape(-1) == S.min())
+        pos.reshape(-1)[low[0]] = 5
+        neg.reshape(-1)[low[1:4]] = [3, 1 << 20, 0]
+        assert S.reshape(-1)[np.flatnonzero(pos.reshape(-1))].min() == S.min() and np.any((pos == 0) & (neg > 0) & (S == S.min()))
+        out.append(('%dx%d, the lowest positive ties with negatives' % (h, w), S, pos, neg))
+    return out
+
+
+def test_sauc_summed_by_parts_is_the_same_integer():
+    """K15d adds up N = 2 A_neg C_tot - sum_k A_k (mult_k + mult_k+1); sauc_exact, the specification, divides the sum of
+    (A_k - A_k-1)(C_k + C_k-1) over the points of sauc_points.  The two are the same Python integer."""
+    frames = by_parts_frames()
+    assert len(frames) == 10
+    for name, S, pos, neg in frames:
+        A, Cc, a_neg, c_tot = fr.sauc_points(S, pos, neg)
+        want = fr.sauc_numerator(A, Cc, a_neg, c_tot)
+        got = fr.sauc_numerator_by_parts(S, pos, neg)
+        assert got == want and 0 < want < 2 * a_neg * c_tot, name
+        assert fr.sauc_exact(S, pos, neg) == want / (2 * a_neg * c_tot)
+    cl = [fr._clamped(pos, neg) for _, _, pos, neg in frames]
+    assert max(int(p.max()) for p, _ in cl) == 1023 and max(int(n.max()) for _, n in cl) == 1 << 20
+    assert any(len(fr.sauc_points(S, pos, neg)[0]) == 1 for _, S, pos, neg in frames)
+    assert any(len(fr.sauc_points(S, pos, neg)[0]) < int((pos > 0).sum()) for _, S, pos, neg in frames)       # tied positives
+
+
 def test_sauc_exact_halves():
     S, pos, neg = sauc_case(1680, 8, 16)
     assert fr.sauc_exact(np.full((8, 16), 0.25, np.float32), pos, neg) == 0.5          # a constant map

@@ -213,6 +213,83 @@ def test_sauc_degenerate_frames_and_exact_halves():
     assert auc[1] == 0.5 and auc[2] == 0.5 and math.isnan(auc[3])
 
 
+@pytest.mark.parametrize('hw', [(8, 16), (33, 66)])
+def test_auc_judd_and_shuffled_auc_are_one_engine(hw):
+    """K14's AUC-Judd of a mask M is K15's shuffled AUC with pos = M and neg = a (1 - M): K14's packed-word kernels and K15's
+    sum by parts give the same bits.  Frame 0 is continuous, frame 1 quantised (ties inside and across the mask), frame
+    2 has an empty mask: the NaN of both."""
+    h, w = hw
+    S = hashrng.uniform(1880 + h, (3, h, w), 0.0, 1.0, dtype=np.float64).astype(np.float32)
+    S[1] = fr.quantised(1881 + h, 1, h, w, 8)[0]
+    M = hashrng.uniform(1882 + h, (3, h, w), 0.0, 1.0, dtype=np.float64) > 0.6
+    M[2] = False
+    assert set(S[1][M[1]].tolist()) == set(S[1][~M[1]].tolist()) and len(set(S[1][M[1]].tolist())) == 8 < M[1].sum() // 4
+    G = hashrng.uniform(1883 + h, (3, h, w), 0.0, 1.0, dtype=np.float64).astype(np.float32)
+    for mode in ('solid_angle', 'uniform'):
+        wt = ops.sphere_eval_weights(h, mode, torch.device(DEV, torch.cuda.current_device()))
+        pos = M.astype(np.int32)
+        neg = (wt.cpu().numpy()[None, :, None] * (1 - pos)).astype(np.int32)
+        scores, n_fix = ops.sphere_eval(dev(S), dev(G), wt, fixations=dev(M.astype(np.uint8)))
+        got = ops.shuffled_auc(dev(S), dev(pos), dev(neg))
+        auc = assert_sauc(got, S, pos, neg)                            # ... and both are the exact quotient
+        assert np.isnan(auc).tolist() == [False, False, True] and n_fix.tolist() == M.sum(axis=(1, 2)).tolist()
+        judd = scores[:, 0].contiguous()
+        assert torch.equal(judd.view(torch.int64), got[0].view(torch.int64)), (mode, judd.tolist(), got[0].tolist())
+        assert torch.equal(judd[:2], got[0][:2]) and bool(torch.isnan(judd[2])) and bool(torch.isnan(got[0][2]))
+
+
+def rank_split(n, P):
+    """K15d's launch rule, restated: the grid has ceil(P / 256) workgroups per frame, a frame's n positives fill
+    `tiles` of them, and the pixel loop is split over chunks = min(grid / tiles, max(1, P / (kSplit n))) workgroups per tile
+    -> (tiles, chunks, the workgroups that return at once).  kSplit is read from the source: tuning it must not move the
+    test's frames off the branches unnoticed."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(ops.__file__), 'csrc', 'fixations.hip')).read()
+    k_split = int(re.search(r'constexpr int kSplit = (\d+);', src).group(1))
+    grid, tiles = -(-P // 256), -(-n // 256)
+    chunks = min(grid // tiles, max(1, P // (k_split * n)))
+    return tiles, chunks, grid - tiles * chunks
+
+
+def split_inputs(hw, counts):
+    """One frame per entry of `counts`, with exactly that many positive pixels (multiplicities 1 .. 3), quantised and
+    continuous maps in turn, negatives 0 .. 4 on every pixel."""
+    h, w = hw
+    F, P = len(counts), h * w
+    S = hashrng.uniform(1890 + h, (F, h, w), 0.0, 1.0, dtype=np.float64).astype(np.float32)
+    S[::2] = fr.quantised(1891 + h, F, h, w, 8)[::2]
+    pos = np.zeros((F, P), np.int32)
+    for f, n in enumerate(counts):
+        where = np.argsort(hashrng.uniform(1892 + h + f, (P,), 0.0, 1.0, dtype=np.float64))[:n]
+        pos[f, where] = hashrng.integers(1895 + h + f, (n,), 1, 4)
+    neg = hashrng.integers(1898 + h, (F, h, w), 0, 5).astype(np.int32)
+    return S, pos.reshape(F, h, w), neg
+
+
+def test_sauc_on_every_branch_of_the_split_rule():
+    """33 x 66: P = 2178, 9 workgroups per frame, 3 pixel tiles.  n = 1 and 3: one tile of positives, the pixel loop split over
+    the spare workgroups (more chunks than pixel tiles: the last ones add nothing); n = 8: the split held back by kSplit, the
+    rest return; n = 30: one tile and no split; n = 300: two tiles, no split, spare workgroups return; n = P - 1: every workgroup
+    owns a tile.  8 x 16: one workgroup, nothing to split."""
+    hw, P = (33, 66), 33 * 66
+    counts = [1, 3, 8, 30, 300, P - 1]
+    splits = [rank_split(n, P) for n in counts]
+    print('split rule at 33 x 66 (tiles, chunks, returning):', splits)
+    assert all(t == 1 and c > 1 for t, c, _ in splits[:2])
+    assert splits[4][0] == 2 and splits[4][1] == 1 and splits[4][2] > 0
+    assert splits[5] == (9, 1, 0)
+    assert any(t == 1 and c == 1 for t, c, _ in splits) and any(t == 1 and c > 1 and r > 0 for t, c, r in splits)
+    S, pos, neg = split_inputs(hw, counts)
+    assert (pos > 0).sum(axis=(1, 2)).tolist() == counts
+    auc = assert_sauc(ops.shuffled_auc(dev(S), dev(pos), dev(neg)), S, pos, neg)
+    assert not np.isnan(auc).any()
+    assert rank_split(1, 8 * 16) == (1, 1, 0)
+    S, pos, neg = split_inputs((8, 16), [1])
+    auc = assert_sauc(ops.shuffled_auc(dev(S), dev(pos), dev(neg)), S, pos, neg)
+    assert not np.isnan(auc).any()
+
+
 # ----------------------------------------------------------------------------- end to end
 def test_fixation_maps_end_to_end(tmp_path):
     F, fps, viewers = 3, 10.0, 12

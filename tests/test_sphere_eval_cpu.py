@@ -112,6 +112,22 @@ def test_quantised_maps_tie_inside_and_across_the_mask():
         assert ci == (S[M] >= lvl).sum() and Ai == aw[(~M) & (S >= lvl)].sum()
 
 
+@pytest.mark.parametrize('mode', ['solid_angle', 'uniform'])
+def test_auc_judd_is_the_shuffled_auc_of_the_mask_and_the_unfixated_weights(mode):
+    """K14's AUC is K15's shuffled AUC with pos = M and neg = a (1 - M): the quotients are bit-equal, on
+    continuous maps and on quantised ones whose ties straddle the mask."""
+    from tests import fixations_restate as fr
+    for h, w in ((8, 16), (33, 66)):
+        a = rs.weights(h, mode)
+        M = noise(1470 + h, h, w) > 0.85
+        neg = np.repeat(a[:, None], w, 1) * ~M
+        for S in (noise(1471 + h, h, w), (np.floor(noise(1471 + h, h, w) * 8.0) / 8.0).astype(np.float32)):
+            A, c, a_neg = rs.roc_points(S, M, a)
+            want = fr.sauc_exact(S, M.astype(np.int64), neg)
+            assert rs.auc_exact(A, c, a_neg, int(M.sum())) == want and 0.0 < want < 1.0
+            assert rs.frame_scores(S, noise(1472, h, w), a, M, exact_auc=True)[0]['auc'] == want
+
+
 def test_degenerate_frames():
     h, w = 8, 16
     a = rs.weights(h)
