@@ -63,7 +63,8 @@ struct OpAdd { __device__ double operator()(double a, double b) const { return a
 struct OpMin { __device__ double operator()(double a, double b) const { return a < b ? a : b; } };
 struct OpMax { __device__ double operator()(double a, double b) const { return a > b ? a : b; } };
 
-// Workspace layout (doubles): [0] n_fix, [1] unused, then S [n] (normalised saliency, f64), Sth [n] (values at
+// Workspace layout (doubles): [0] n_fix, [1] status (0: the normalisation is defined; 1: it is not - a non-finite value, or a
+// range max - min that is zero or not finite: every S would be NaN), then S [n] (normalised saliency, f64), Sth [n] (values at
 // fixated pixels, compacted), pts [2 * (n + 2)] (fp, tp by rank).
 // mode 0 (AUC_Judd): S = sal (+ jitter); S = (S - min) / (max - min) - in float64 with the (float64) jitter, in float32
 //   without it, as numpy's type promotion does                                                          :104-116
@@ -84,6 +85,7 @@ __global__ __launch_bounds__(1024) void auc_prepare_kernel(const float* __restri
     for (int i = tid; i < n; i += 1024) { const double d = (double)fix[i] - fmean; s2 += d * d; }
     const double fstd = sqrt(block_reduce(s2, OpAdd(), sm) / n);
     const float fthr = (float)(fmean + 2.0 * fstd);
+    int bad = 0;                                                  // this thread saw what leaves the normalisation undefined
     if (mode == 1) {
         double a1 = 0.0;
         for (int i = tid; i < n; i += 1024) a1 += (double)sal[i];
@@ -94,10 +96,12 @@ __global__ __launch_bounds__(1024) void auc_prepare_kernel(const float* __restri
         double mn = 1e300, mx = -1e300;
         for (int i = tid; i < n; i += 1024) {
             const float v = sal[i] > sthr ? 1.0f : sal[i];
+            bad |= !isfinite(v);
             mn = fmin(mn, (double)v);
             mx = fmax(mx, (double)v);
         }
         const float fmn = (float)block_reduce(mn, OpMin(), sm), fmx = (float)block_reduce(mx, OpMax(), sm);
+        bad |= !(fmx > fmn) || !isfinite(fmx - fmn);
         for (int i = tid; i < n; i += 1024) {
             const float v = sal[i] > sthr ? 1.0f : sal[i];
             S[i] = (double)((v - fmn) / (fmx - fmn));
@@ -106,30 +110,34 @@ __global__ __launch_bounds__(1024) void auc_prepare_kernel(const float* __restri
         // jitter=False: the reference normalises the float32 map in float32 (no float64 randn term promotes it, :104-116)
         double mn = 1e300, mx = -1e300;
         for (int i = tid; i < n; i += 1024) {
+            bad |= !isfinite(sal[i]);
             mn = fmin(mn, (double)sal[i]);
             mx = fmax(mx, (double)sal[i]);
         }
         const float fmn = (float)block_reduce(mn, OpMin(), sm), fmx = (float)block_reduce(mx, OpMax(), sm);
+        bad |= !(fmx > fmn) || !isfinite(fmx - fmn);
         for (int i = tid; i < n; i += 1024) S[i] = (double)((sal[i] - fmn) / (fmx - fmn));
     } else {
         double mn = 1e300, mx = -1e300;
         for (int i = tid; i < n; i += 1024) {
             const double v = (double)sal[i] + (jitter ? jitter[i] : 0.0);
+            bad |= !isfinite(v);
             mn = fmin(mn, v);
             mx = fmax(mx, v);
         }
         const double gmn = block_reduce(mn, OpMin(), sm), gmx = block_reduce(mx, OpMax(), sm);
+        bad |= !(gmx > gmn) || !isfinite(gmx - gmn);
         for (int i = tid; i < n; i += 1024) {
             const double v = (double)sal[i] + (jitter ? jitter[i] : 0.0);
             S[i] = (v - gmn) / (gmx - gmn);
         }
     }
     if (tid == 0) cnt = 0;
-    __syncthreads();
+    const int status = __syncthreads_or(bad);
     for (int i = tid; i < n; i += 1024)
         if (fix[i] > fthr) Sth[atomicAdd(&cnt, 1)] = S[i];       // order is irrelevant: ranks are recomputed
     __syncthreads();
-    if (tid == 0) work[0] = (double)cnt;
+    if (tid == 0) { work[0] = (double)cnt; work[1] = status ? 1.0 : 0.0; }
 }
 
 // ROC point of every fixated value (:126-141): rank i among the fixated values (descending; ties by position),
@@ -141,6 +149,7 @@ __global__ __launch_bounds__(256) void auc_judd_rank_kernel(int n, double* __res
     double* fp = const_cast<double*>(Sth) + n;
     double* tp = fp + (n + 2);
     const int j = blockIdx.x * 256 + threadIdx.x;
+    if (work[1] != 0.0) return;                                  // S is NaN: no rank exists, auc_trapz_kernel reports NaN
     if (j == 0) {
         fp[0] = 0.0; tp[0] = 0.0;
         fp[n_fix + 1] = 1.0; tp[n_fix + 1] = 1.0;
@@ -160,6 +169,10 @@ __global__ __launch_bounds__(1024) void auc_trapz_kernel(int n, const double* __
     const int n_fix = (int)work[0];
     const double* fp = work + 2 + 2 * (size_t)n;
     const double* tp = fp + (n + 2);
+    if (work[1] != 0.0) {                                        // the rank tables were not written
+        if (threadIdx.x == 0) { out[0] = nan(""); out[1] = (double)n_fix; }
+        return;
+    }
     double s = 0.0;
     for (int k = threadIdx.x; k < n_fix + 1; k += 1024) s += (fp[k + 1] - fp[k]) * (tp[k + 1] + tp[k]) * 0.5;
     const double r = block_reduce(s, OpAdd(), sm);
@@ -175,10 +188,19 @@ __global__ __launch_bounds__(256) void auc_borji_kernel(int n, int n_splits, con
     const double* S = work + 2;
     const double* Sth = S + n;
     const int ss = blockIdx.x, tid = threadIdx.x;
+    if (work[1] != 0.0 || n_fix <= 0) {                          // NaN map, or no fixation to draw a split for: no ROC
+        if (tid == 0) aucs[ss] = nan("");
+        return;
+    }
     double mx = -1e300;
     for (int k = tid; k < n_fix; k += 256) mx = fmax(mx, fmax(Sth[k], S[rr[(size_t)k * n_splits + ss]]));
     const double top = block_reduce(mx, OpMax(), sm);
-    const int nthr = (int)ceil(top / step);                  // len(np.arange(0.0, top, step)); S in [0, 1]: <= 101
+    const double cnt = ceil(top / step);                     // len(np.arange(0.0, top, step)); S in [0, 1]: <= 102
+    if (!(cnt >= 0.0 && cnt <= 126.0)) {                     // tpv / fpv hold nthr + 2 entries (the same for every thread)
+        if (tid == 0) aucs[ss] = nan("");
+        return;
+    }
+    const int nthr = (int)cnt;
     // thresholds descending: t_i = (nthr - 1 - i) * step; tp[i + 1] = #(Sth >= t_i) / n_fix, fp likewise on curfix
     for (int i = 0; i < nthr; ++i) {
         const double t = (double)(nthr - 1 - i) * step;
@@ -234,8 +256,11 @@ __global__ __launch_bounds__(1024) void cc_sim_kernel(const float* __restrict__ 
     c = block_reduce(c, OpAdd(), sm); d = block_reduce(d, OpAdd(), sm); e = block_reduce(e, OpAdd(), sm);
     na = block_reduce(na, OpAdd(), sm); nb = block_reduce(nb, OpAdd(), sm);
     double sim = 0;
-    for (int i = tid; i < n; i += 1024)
-        sim += fmin((a[i] - mna) / (mxa - mna) / na, (b[i] - mnb) / (mxb - mnb) / nb);
+    for (int i = tid; i < n; i += 1024) {
+        // np.minimum propagates NaN (a flat map is 0 / 0 everywhere); fmin would return the other operand
+        const double x = (a[i] - mna) / (mxa - mna) / na, y = (b[i] - mnb) / (mxb - mnb) / nb;
+        sim += (x != x || y != y) ? nan("") : fmin(x, y);
+    }
     sim = block_reduce(sim, OpAdd(), sm);
     if (tid == 0) { out[0] = c / sqrt(d * e); out[1] = sim; }
 }

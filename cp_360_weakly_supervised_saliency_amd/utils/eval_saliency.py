@@ -13,6 +13,14 @@ Types: the maps the path produces are float32 and are resized in float32 (cv2.re
 input (e.g. a ground-truth map stored as float64) is cast to float32 first - the only consumer of its values is the
 ``F > mean(F) + 2 std(F)`` fixation threshold, evaluated in float64 from those float32 values.  AUC_Judd normalises in
 float64 with jitter (the float64 ``randn`` term promotes the map, as in numpy) and in float32 with ``jitter=False``.
+
+Refusals: where the min-max normalisation of the saliency map is undefined - a flat map (``max == min``; with AUC_Judd's
+default jitter a flat finite map stays legal, the jitter breaks the ties), a non-finite pixel, a range that overflows - the
+reference prints ``NaN saliency_map`` and exits (:42-44, :116-118); AUC_Judd and AUC_Borji raise ``ValueError('NaN
+saliency_map')``.  The kernel records the condition in its workspace and the C entry points answer NaN on their own.
+AUC_Borji also raises ValueError when no pixel of the fixation map passes ``mean + 2 std`` (the reference fails inside numpy
+there) and for a ``stepSize`` below 0.0099 (the C entry refuses it: its threshold table is fixed); AUC_Judd returns 0.5 for such a fixation map, as the reference does.  CorrCoeff
+and similarity return NaN for a flat map, as numpy does.
 """
 import ctypes as C
 
@@ -54,13 +62,16 @@ def _prepare(saliency_map, fixation_map, jitter, mode):
     if jitter is not None:
         jit = torch.from_numpy(np.ascontiguousarray(jitter, dtype=np.float64)).to(S.device)
     check(lib().cp360_metric_auc_prepare(ptr(S), ptr(F), ptr(jit), n, mode, ptr(work), stream()))
-    return n, work
+    n_fix, status = work[:16].view(torch.float64).tolist()
+    if status != 0.0:                                             # the reference prints this and exit()s (:42-44, :116-118)
+        raise ValueError('NaN saliency_map')
+    return n, work, int(n_fix)
 
 
 def AUC_Judd(saliency_map, fixation_map, jitter=True, to_plot=False):
     """eval_saliency.py:90-146."""
     jit = np.random.randn(SIZE[1], SIZE[0]) / 1e7 if jitter else None      # drawn where the reference draws it (:106-109)
-    n, work = _prepare(saliency_map, fixation_map, jit, 0)
+    n, work, _ = _prepare(saliency_map, fixation_map, jit, 0)
     out = torch.empty(2, dtype=torch.float64, device=work.device)
     check(lib().cp360_metric_auc_judd(n, ptr(work), ptr(out), stream()))
     return float(out[0].item())
@@ -68,8 +79,9 @@ def AUC_Judd(saliency_map, fixation_map, jitter=True, to_plot=False):
 
 def AUC_Borji(saliency_map, fixation_map, Nsplits=100, stepSize=0.01, to_plot=False):
     """eval_saliency.py:14-87."""
-    n, work = _prepare(saliency_map, fixation_map, None, 1)
-    n_fix = int(work[:8].view(torch.float64).item())               # the splits' shape depends on it (:53)
+    n, work, n_fix = _prepare(saliency_map, fixation_map, None, 1)  # the splits' shape depends on n_fix (:53)
+    if n_fix == 0:                                                 # the reference fails inside numpy (max of an empty array)
+        raise ValueError('no pixel of fixation_map is above mean + 2 std: AUC_Borji has no fixation to score')
     rr = np.random.randint(0, high=n, size=(n_fix, Nsplits))
     rr_d = torch.from_numpy(np.ascontiguousarray(rr, dtype=np.int32)).to(work.device)
     aucs = torch.empty(Nsplits, dtype=torch.float64, device=work.device)

@@ -73,13 +73,13 @@ def overlay(img, heatmap, cmap='jet', alpha=0.5, square=False):
         require_gpu(img)
         im = img
     else:
-        im = torch.from_numpy(np.ascontiguousarray(np.asarray(img.convert('RGB') if hasattr(img, 'convert') else img))).cuda()
+        im = torch.from_numpy(np.array(img.convert('RGB')) if hasattr(img, 'convert') else np.ascontiguousarray(img)).cuda()
     if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
         raise ValueError("img must be uint8 [H, W, 3]")
     im = im.contiguous()
     H, W = im.shape[:2]
     if hasattr(heatmap, 'convert'):
-        hm = torch.from_numpy(np.ascontiguousarray(np.asarray(heatmap.convert('RGB')))).to(im.device)
+        hm = torch.from_numpy(np.array(heatmap.convert('RGB'))).to(im.device)         # a copy: a PIL image's own array is read-only
     elif torch.is_tensor(heatmap) and heatmap.dtype == torch.uint8:
         hm = heatmap.to(im.device)
     elif isinstance(heatmap, np.ndarray) and heatmap.dtype == np.uint8 and heatmap.ndim == 3:

@@ -125,6 +125,7 @@ def overlay(img_u8, heat, lut, alpha=0.5):
     bad = np.isnan(xa)
     with np.errstate(invalid='ignore'):
         idx = np.clip(xa, 0, 255).astype(int)
+    idx[bad] = 0                                       # NaN casts to an arbitrary integer; its colour is set below
     rgb = lut[idx]
     rgb[bad] = 0
     up = resize_u8(rgb.astype(np.uint8), img_u8.shape[:2], 'bicubic')

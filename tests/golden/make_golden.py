@@ -6,7 +6,7 @@ reference is imported in memory with the shims listed in SURVEY.md section 8(c);
 nothing of its source is written to this repo - the fixtures are inputs (or their
 hash-RNG seeds) and the reference's outputs.
 
-    python tests/golden/make_golden.py [--only cubepad,e2c,c2e,resnet,clstm,resize,metrics,overlay]
+    python tests/golden/make_golden.py [--only cubepad,e2c,c2e,resnet,clstm,resize,metrics,overlay,cam_visual]
 
 Shims (all in memory):
   * ``np.int = int``  (alias removed in numpy >= 1.24; cube_pad.py:13,64)
@@ -351,9 +351,42 @@ def gen_overlay(out):
     print('overlay fixtures written')
 
 
+# --------------------------------------------------------------------------- cam_visual (f4)
+CAM_VISUAL_CASES = [((7, 14), (48, 96), 'float32'), ((14, 28), (48, 96), 'float64'), ((7, 14), (48, 96), 'int64')]
+
+
+def cam_visual_inputs(k):
+    """(image uint8 [H, W, 3], CAM [h, w]) of case k: a float32 / float64 CAM of either sign, or integer class scores."""
+    (h, w), (H, W), dtype = CAM_VISUAL_CASES[k]
+    cam = hashrng.normal(8700 + k, (h, w), 0.0, 40.0, dtype=np.float64)
+    cam = np.rint(cam).astype(np.int64) if dtype == 'int64' else cam.astype(dtype)
+    img = hashrng.uniform(8800 + k, (H, W, 3), 0.0, 256.0).astype(np.uint8)
+    return img, cam
+
+
+def gen_cam_visual(out):
+    """utils/utils.py:40-45 executed from the reference, with gen_overlay's shim."""
+    import importlib
+    import warnings
+    import matplotlib
+    from PIL import Image
+    matplotlib.use('Agg')
+    if not hasattr(Image, 'CUBIC'):
+        Image.CUBIC = Image.BICUBIC
+    warnings.simplefilter('ignore')
+    sys.path.insert(0, REF)
+    uu = importlib.import_module('utils.utils')
+    arrs = {}
+    for k in range(len(CAM_VISUAL_CASES)):
+        img, cam = cam_visual_inputs(k)
+        arrs['y%d' % k] = np.array(uu.cam_visual(img.copy(), cam.copy()))
+    np.savez_compressed(os.path.join(out, 'cam_visual.npz'), **arrs)
+    print('cam_visual fixtures written')
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', default='cubepad,e2c,c2e,resnet,clstm,resize,metrics,overlay')
+    ap.add_argument('--only', default='cubepad,e2c,c2e,resnet,clstm,resize,metrics,overlay,cam_visual')
     args = ap.parse_args()
     parts = args.only.split(',')
     if 'resize' in parts:                      # Pillow only: the reference itself is not needed
@@ -362,6 +395,9 @@ def main():
     if 'overlay' in parts:
         gen_overlay(HERE)
         parts.remove('overlay')
+    if 'cam_visual' in parts:
+        gen_cam_visual(HERE)
+        parts.remove('cam_visual')
     if not parts:
         return
     R = import_reference()

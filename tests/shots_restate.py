@@ -38,6 +38,21 @@ def signatures(frames):
     return sig, W * total
 
 
+def shot_rows(F, H, W):
+    """Rows of a frame per workgroup of K13a: 16 (two per wave) once a video gives the chip F ceil(H / 16) >= 1024 workgroups,
+    else 8; halved while a workgroup's u32 partial sums could overflow (R W 1024 > 2^31)."""
+    R = 16 if F * -(-H // 16) >= 1024 else 8
+    while R > 1 and R * W > 2 ** 21:
+        R //= 2
+    return R
+
+
+def work_bytes(F, H, W):
+    """cp360_shot_work_bytes: u32 [F, ceil(H / R), 3, 64] partial histograms, to a multiple of 16 bytes.  The size tells which R
+    the library chose."""
+    return -(-(F * -(-H // shot_rows(F, H, W)) * 192 * 4) // 16) * 16
+
+
 def sad(sig):
     """sig int64 [F, 3, 64] -> int64 [F - 1]."""
     sig = np.asarray(sig, np.int64)

@@ -58,3 +58,203 @@ def test_hip_overlay_equals_reference_golden(golden_dir):
     assert np.array_equal(colorize(torch.from_numpy(root).cuda(), square=True).cpu().numpy(),
                           colorize(torch.from_numpy(root * root).cuda()).cpu().numpy())
     assert int(colorize(torch.zeros((4, 8), device='cuda')).max()) == 0
+
+
+# ======================================================================================================================
+# K9 at its edges: colorize, the blend (every byte pair, every byte of an 8K frame), overlay's input paths and cam_visual.
+# Everything is bit-exact; expected values come from the oracle (oracle/o_resize.py), matplotlib, Pillow and
+# tests/golden/cam_visual.npz (the reference's own cam_visual on the seeded inputs of make_golden.py).
+# ======================================================================================================================
+import functools
+
+from tests.golden.make_golden import CAM_VISUAL_CASES, cam_visual_inputs
+
+
+def _cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def oracle_colors(heat):
+    """The oracle's colour step alone: o_resize.overlay on a black image of the map's size (no resize) with alpha = 1 (the
+    blend x + 1 * (y - x) of two bytes is y exactly)."""
+    heat = np.asarray(heat)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return o_resize.overlay(np.zeros(heat.shape + (3,), np.uint8), heat, jet_lut(), 1.0)
+
+
+def matplotlib_colors(heat):
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    with np.errstate(invalid='ignore', divide='ignore'):
+        heat = heat - np.min(heat)
+        heat = heat / np.max(heat)
+        return plt.get_cmap('jet')(heat, bytes=True)[:, :, :3]
+
+
+@functools.lru_cache(maxsize=None)
+def colorize_cases():
+    """name -> float32 map.  Sizes of 1, 2, 63, 1024, 1025 and 2178 pixels (the kernel is one workgroup of 1024 threads)."""
+    out = {}
+    for n, shape in ((1, (1, 1)), (2, (1, 2)), (63, (7, 9)), (1024, (32, 32)), (1025, (25, 41)), (2178, (33, 66))):
+        out['noise_%d' % n] = hashrng.uniform(8900 + n, shape, -2.0, 5.0)
+    k = hashrng.integers(8960, (33, 66), 0, 257).astype(np.float32)
+    k.flat[0], k.flat[1] = 0.0, 256.0
+    out['x256_is_an_integer'] = k / np.float32(256.0)            # normalised value k / 256 exactly: x * 256 = k, and 256 -> 255
+    z = hashrng.uniform(8961, (7, 9))
+    z[z < 0.4] = 0.0
+    z.flat[5], z.flat[6] = -0.0, 0.0
+    out['negative_zero'] = z
+    out['range_1e30'] = hashrng.uniform(8962, (25, 41), -0.5, 0.5) * np.float32(1e30)
+    out['subnormals'] = hashrng.integers(8963, (33, 66), 0, 5000).astype(np.int32).view(np.float32)   # k 2^-149
+    one_nan = hashrng.uniform(8964, (33, 66))
+    one_nan[20, 11] = np.nan
+    out['one_nan'] = one_nan
+    assert np.signbit(out['negative_zero'].flat[5]) and out['subnormals'].max() < 1e-41
+    return out
+
+
+def test_colorize_cases_oracle_equals_matplotlib():
+    pytest.importorskip('matplotlib')
+    for name, heat in colorize_cases().items():
+        want = oracle_colors(heat)
+        assert np.array_equal(want, matplotlib_colors(heat)), name
+        with np.errstate(over='ignore'):
+            sq = heat * heat                                                     # range_1e30 overflows: inf / inf = NaN there
+        assert sq.dtype == np.float32
+        assert np.array_equal(oracle_colors(sq), matplotlib_colors(sq)), name
+    assert not oracle_colors(colorize_cases()['one_nan']).any()                 # NaN min: every pixel is the "bad" colour
+    assert not oracle_colors(colorize_cases()['noise_1']).any()                 # 1 x 1: 0 / 0
+    assert len(np.unique(oracle_colors(colorize_cases()['x256_is_an_integer']).reshape(-1, 3), axis=0)) > 200
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(colorize_cases()))
+def test_hip_colorize_equals_oracle_and_matplotlib(name):
+    pytest.importorskip('matplotlib')
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import colorize
+    heat = colorize_cases()[name]
+    got = colorize(_cuda(heat)).cpu().numpy()
+    assert got.dtype == np.uint8 and got.shape == heat.shape + (3,)
+    assert np.array_equal(got, oracle_colors(heat)) and np.array_equal(got, matplotlib_colors(heat))
+    with np.errstate(over='ignore', invalid='ignore'):
+        sq = heat * heat                                                         # float32, one rounded product
+    got = colorize(_cuda(heat), square=True).cpu().numpy()
+    assert np.array_equal(got, oracle_colors(sq)) and np.array_equal(got, matplotlib_colors(sq))
+    if name in ('one_nan', 'noise_1'):
+        assert not got.any()
+
+
+def all_byte_pairs():
+    """Two uint8 [256, 256, 3] images whose bytes hold, between them, every (x, y) pair."""
+    i = np.arange(256 * 256 * 3)
+    x, y = ((i // 256) % 256).astype(np.uint8).reshape(256, 256, 3), (i % 256).astype(np.uint8).reshape(256, 256, 3)
+    assert len(np.unique(x.reshape(-1).astype(np.int64) * 256 + y.reshape(-1))) == 65536
+    return x, y
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('alpha', [0.0, 1.0 / 3.0, 0.3, 0.5, 0.999, 1.0])
+def test_hip_blend_equals_pillow_on_every_byte_pair(alpha):
+    from PIL import Image
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import overlay
+    x, y = all_byte_pairs()
+    want = np.array(Image.blend(Image.fromarray(x), Image.fromarray(y), alpha))
+    got = overlay(_cuda(x), _cuda(y), alpha=alpha)                   # a uint8 map of the image's size: the blend alone
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('alpha', [-0.1, 1.5, float('nan'), float('inf')])
+def test_hip_blend_refuses_alphas_outside_the_unit_interval(alpha):
+    """Pillow clips for those; the kernel has no clipping path, and the entry point says so."""
+    from cp_360_weakly_supervised_saliency_amd._lib import Cp360Error
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import overlay
+    x, y = all_byte_pairs()
+    with pytest.raises((ValueError, Cp360Error)):
+        overlay(_cuda(x), _cuda(y), alpha=alpha)
+
+
+@pytest.mark.gpu
+def test_hip_blend_covers_every_byte_of_an_8k_frame():
+    """4320 x 7680 x 3 = 99 532 800 bytes > 65535 * 4 * 256: the grid is capped and the grid-stride loop runs.  Against the same
+    arithmetic in torch float32, one rounded operation at a time (the test above pins that arithmetic against Pillow)."""
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import overlay
+    H, W, alpha = 4320, 7680, 0.3
+    assert H * W * 3 > 65535 * 4 * 256
+    g = torch.Generator(device='cuda')
+    g.manual_seed(8970)
+    x = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device='cuda', generator=g)
+    y = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device='cuda', generator=g)
+    got = overlay(x, y, alpha=alpha)
+    assert got.shape == x.shape and got.dtype == torch.uint8
+    a = torch.tensor(alpha, dtype=torch.float32, device='cuda')
+    for r in range(0, H, 540):                                       # in slices: the float32 copies stay small
+        xf, yf = x[r:r + 540].float(), y[r:r + 540].float()
+        want = (xf + a * (yf - xf)).to(torch.uint8)
+        assert torch.equal(got[r:r + 540], want), r
+    assert not torch.equal(got, x) and not torch.equal(got, y)
+
+
+@pytest.mark.gpu
+def test_hip_overlay_input_paths():
+    """A PIL image in; a uint8 RGB heat map (skips colorize), as an array, a tensor and a PIL image; a heat map already of the
+    image's size (skips the resize); a device image and a host image - each against o_resize.overlay."""
+    from PIL import Image
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import overlay
+    img, heat, alpha = overlay_inputs(2)
+    want = o_resize.overlay(img, heat, jet_lut(), alpha)
+    rgb = oracle_colors(heat)
+    got = overlay(Image.fromarray(img), heat, alpha=alpha)
+    assert isinstance(got, Image.Image) and got.mode == 'RGB' and np.array_equal(np.array(got), want)
+    assert np.array_equal(np.array(overlay(img, rgb, alpha=alpha)), want)
+    assert np.array_equal(np.array(overlay(img, Image.fromarray(rgb), alpha=alpha)), want)
+    assert np.array_equal(np.array(overlay(Image.fromarray(img), Image.fromarray(rgb), alpha=alpha)), want)
+    on_device = overlay(_cuda(img), _cuda(rgb), alpha=alpha)
+    assert torch.is_tensor(on_device) and on_device.is_cuda and np.array_equal(on_device.cpu().numpy(), want)
+    assert np.array_equal(overlay(_cuda(img), heat, alpha=alpha).cpu().numpy(), want)      # a host map on a device image
+    full = hashrng.uniform(8980, img.shape[:2])
+    want_full = o_resize.overlay(img, full, jet_lut(), alpha)
+    assert np.array_equal(np.array(overlay(img, full, alpha=alpha)), want_full)
+    assert np.array_equal(overlay(_cuda(img), _cuda(full), alpha=alpha).cpu().numpy(), want_full)
+
+
+def cam_visual_oracle(img, cam):
+    """utils/utils.py:40-45 on the repository's oracle: min-max normalise in the input's dtype (true division for integers),
+    np.uint8(255 * cam), then the overlay of that uint8 array."""
+    cam = np.asarray(cam)
+    cam = cam - np.min(cam)
+    cam = cam / np.max(cam)
+    return o_resize.overlay(img, np.uint8(255 * cam), jet_lut(), 0.5)
+
+
+def cam_cases():
+    out = [cam_visual_inputs(k) for k in range(len(CAM_VISUAL_CASES))]
+    img = out[0][0]
+    for k, (shape, dtype) in enumerate((((14, 28), np.float32), ((7, 14), np.float64), ((14, 28), np.int32))):
+        cam = hashrng.normal(8990 + k, shape, 3.0, 25.0, dtype=np.float64)
+        out.append((img, np.rint(cam).astype(dtype) if np.issubdtype(dtype, np.integer) else cam.astype(dtype)))
+    return out
+
+
+def test_oracle_cam_visual_equals_reference_golden(golden_dir):
+    g = np.load(os.path.join(golden_dir, 'cam_visual.npz'))
+    for k, (shape, size, dtype) in enumerate(CAM_VISUAL_CASES):
+        img, cam = cam_visual_inputs(k)
+        assert cam.shape == shape and img.shape == size + (3,) and cam.dtype == np.dtype(dtype)
+        assert g['y%d' % k].shape == img.shape and np.array_equal(cam_visual_oracle(img, cam), g['y%d' % k]), k
+    kinds = sorted(str(cam.dtype) + str(cam.shape) for _, cam in cam_cases())
+    assert len(set(kinds)) == 6                                      # float32, float64 and integers, each at 7 x 14 and 14 x 28
+
+
+@pytest.mark.gpu
+def test_hip_cam_visual(golden_dir):
+    from PIL import Image
+    from cp_360_weakly_supervised_saliency_amd.utils.utils import cam_visual
+    g = np.load(os.path.join(golden_dir, 'cam_visual.npz'))
+    for k, (img, cam) in enumerate(cam_cases()):
+        got = cam_visual(img, cam)
+        assert isinstance(got, Image.Image) and np.array_equal(np.array(got), cam_visual_oracle(img, cam)), k
+        if k < len(CAM_VISUAL_CASES):
+            assert np.array_equal(np.array(got), g['y%d' % k]), k
+        assert np.array_equal(cam_visual(_cuda(img), cam).cpu().numpy(), np.array(got)), k

@@ -75,6 +75,25 @@ def test_status_codes_without_gpu():
         assert nblk >= 1 and rows * W * 1024 < 2 ** 32, (F, H, W, nblk)
 
 
+# (F, H, W) -> R: both sides of the switch to 16 rows (F ceil(H / 16) = 1024 | 1008 | 1023), and of every halving for wide rows
+ROW_RULE = [((64, 250, 22), 16), ((63, 250, 22), 8), ((1, 5, 262145), 4), ((1, 3, 1048577), 1),
+            ((64, 256, 22), 16), ((1023, 16, 8), 8), ((1024, 16, 8), 16), ((1024, 1, 8), 16), ((2, 480, 960), 8),
+            ((16, 960, 1920), 8), ((18, 960, 1920), 16), ((1024, 16, 131072), 16), ((1024, 16, 131073), 8),
+            ((1, 5, 262144), 8), ((1, 5, 524288), 4), ((1, 5, 524289), 2), ((1, 3, 1048576), 2), ((1, 3, 1 << 21), 1),
+            ((1024, 16, 1 << 21), 1), ((3, 33, 66), 8), ((3, 8, 16), 8)]
+
+
+@pytest.mark.parametrize('shape,R', ROW_RULE)
+def test_work_bytes_prove_the_rows_per_workgroup(shape, R):
+    """shot_rows() of csrc/shots.hip, restated in tests/shots_restate.py and held to the library without a launch: the workspace
+    is F ceil(H / R) partial histograms, so its size tells R wherever ceil(H / R) differs between the candidates."""
+    F, H, W = shape
+    assert rs.shot_rows(F, H, W) == R
+    assert _lib.lib().cp360_shot_work_bytes(F, H, W) == rs.work_bytes(F, H, W) == -(-(F * -(-H // R) * 768) // 16) * 16
+    if shape in ROW_RULE[:4]:                                          # the shapes tests/test_shots_gpu.py launches
+        assert all(-(-H // r) != -(-H // R) for r in (1, 2, 4, 8, 16) if r != R)
+
+
 def test_ops_refuse_cpu_tensors_and_bad_arguments():
     with pytest.raises(RuntimeError, match='GPU only'):
         ops.shot_signatures(torch.zeros(2, 8, 16, 3, dtype=torch.uint8))
