@@ -172,6 +172,13 @@ def _check_buf(name, t, dtype, min_shape=None, numel=None):
         raise ValueError("%s holds %d elements, needs %d" % (name, t.numel(), numel))
 
 
+def _shares_bytes(a, b):
+    """Whether the storage byte ranges data_ptr() .. + numel * element_size of two contiguous tensors intersect: a destination
+    that starts elsewhere in its operand's buffer (two overlapping views) is an alias that comparing data_ptr() misses."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
 # Optional launch timer (bench.py installs one): an object with
 # ``wrap(tag, flops, fn)`` that brackets the conv_forward launch with HIP events on the
 # current stream.  None = no instrumentation (default).
@@ -1445,9 +1452,11 @@ def equirect_rotate(frames, R, out=None, work=None):
     _stab_rotations(R, N)
     if out is None:
         out = torch.empty_like(frames)
-    elif out.shape != frames.shape or out.device != frames.device or out.data_ptr() == frames.data_ptr():
+    elif out.shape != frames.shape or out.device != frames.device:
         raise ValueError("out must be another tensor of the frames' shape on their device")
     _check_buf('out', out, frames.dtype)
+    if _shares_bytes(out, frames):
+        raise ValueError("out must not share memory with frames (a gather: not in place)")
     work = _stab_work(0, H, W, frames.device, work)
     check(lib().cp360_stab_rotate(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, ptr(out), ptr(work),
                                   work.numel() * 8, stream()))
@@ -1478,9 +1487,11 @@ def viewport_render(frames, R, hw, hfov_deg, out=None):
     h, w, hfov = _view_geometry(hw, hfov_deg)
     if out is None:
         out = torch.empty((N, h, w, C), dtype=frames.dtype, device=frames.device)
-    elif tuple(out.shape) != (N, h, w, C) or out.device != frames.device or out.data_ptr() == frames.data_ptr():
+    elif tuple(out.shape) != (N, h, w, C) or out.device != frames.device:
         raise ValueError("out must be another tensor of shape %s on the frames' device" % ((N, h, w, C),))
     _check_buf('out', out, frames.dtype)
+    if _shares_bytes(out, frames):
+        raise ValueError("out must not share memory with frames (a gather: not in place)")
     check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
     return out
 
@@ -1503,6 +1514,8 @@ def viewport_outline(frames, R, hw, hfov_deg, border_px=3, rgb=(0, 255, 0), out=
     elif out.shape != frames.shape or out.device != frames.device:
         raise ValueError("out must have the frames' shape on their device")
     _check_buf('out', out, torch.uint8)
+    if out.data_ptr() != frames.data_ptr() and _shares_bytes(out, frames):
+        raise ValueError("out must be frames themselves or share no memory with them (pixels are copied in no order across frames)")
     work = _stab_work(0, H, W, frames.device, work)
     colour = (C.c_ubyte * 3)(*rgb)
     check(lib().cp360_view_outline(ptr(frames), ptr(R), N, H, W, hfov, h, w, float(border_px), C.cast(colour, C.c_void_p),

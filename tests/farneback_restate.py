@@ -191,8 +191,9 @@ def matrices(R0, R1, flow, dtype=np.float64):
     h, w = flow.shape[:2]
     dx, dy = flow[..., 0], flow[..., 1]
     fx, fy, inside = sample_positions(flow, dtype)
-    x1 = np.clip(np.floor(fx), 0, max(w - 2, 0)).astype(np.int64)
-    y1 = np.clip(np.floor(fy), 0, max(h - 2, 0)).astype(np.int64)
+    # a NaN position compares false with every bound, so it is outside and its taps are never used: any valid index serves
+    x1 = np.clip(np.nan_to_num(np.floor(fx), nan=0.0), 0, max(w - 2, 0)).astype(np.int64)
+    y1 = np.clip(np.nan_to_num(np.floor(fy), nan=0.0), 0, max(h - 2, 0)).astype(np.int64)
     x2, y2 = np.minimum(x1 + 1, w - 1), np.minimum(y1 + 1, h - 1)
     ax, ay = fx - np.floor(fx), fy - np.floor(fy)
     one, half, quarter = dtype(1), dtype(0.5), dtype(0.25)

@@ -69,6 +69,10 @@ def test_gray_is_bit_exact():
 def test_pyramid_level(hw, ksz, sigma, lhw):
     """Two ksz-term passes on weights that sum to 1, then the bilinear tap: (2 (ksz + 1) + 8) u max|image|.  5 x 7 with ksz 9
     folds reflect-101 more than once (period 2 (n - 1)); sigma 0 is the fixed {0.25, 0.5, 0.25} kernel at equal size."""
+    check_pyramid_level(hw, ksz, sigma, lhw)
+
+
+def check_pyramid_level(hw, ksz, sigma, lhw):
     img = (127.5 + 60.0 * smooth(11, (2,) + hw)).astype(np.float32)
     got = ops.optflow_pyr_level(dev(img), ksz, sigma, *lhw).cpu().numpy()
     want = np.stack([fb.pyr_level(i, ksz, sigma, lhw[0], lhw[1]) for i in img])
@@ -86,11 +90,17 @@ def test_reflect101_folds_more_than_once():
 
 def test_flow_upsample():
     """Bilinear resize times 1 / pyr_scale: 8 roundings of the tap and one of the scale."""
-    flow = np.stack([smooth(21, (2, 34, 66), 3.0), smooth(22, (2, 34, 66), 3.0)], -1)
-    got = ops.optflow_flow_upsample(dev(flow), 67, 131, 2.0).cpu().numpy()
-    want = np.stack([fb.flow_upsample(f, 67, 131, 2.0) for f in flow])
-    assert got.shape == (2, 67, 131, 2)
-    assert float(np.max(np.abs(got - want))) <= 9 * U * 2.0 * float(np.max(np.abs(flow)))
+    check_flow_upsample((34, 66), (67, 131), 2.0)
+
+
+def check_flow_upsample(hw, nhw, mul):
+    flow = np.stack([smooth(21, (2,) + hw, 3.0), smooth(22, (2,) + hw, 3.0)], -1)
+    got = ops.optflow_flow_upsample(dev(flow), nhw[0], nhw[1], mul).cpu().numpy()
+    want = np.stack([fb.flow_upsample(f, nhw[0], nhw[1], mul) for f in flow])
+    assert got.shape == (2,) + nhw + (2,)
+    err, tol = float(np.max(np.abs(got - want))), 9 * U * mul * float(np.max(np.abs(flow)))
+    print('flow upsample %s -> %s: max|d| = %.3e (bound %.3e)' % (hw, nhw, err, tol))
+    assert err <= tol
 
 
 # ----------------------------------------------------------------------------- expansion
@@ -101,6 +111,10 @@ def test_expansion(hw, n, sigma):
     remainders in both axes, 16 x 64 is exactly one tile (16-byte stores).  Elementwise bound: two (2n + 1)-term passes and
     the combination with the ig constants are 2 (2n + 2) + 4 roundings of S = the same expansion of |image| with the
     absolute values of the tables."""
+    check_expansion(hw, n, sigma)
+
+
+def check_expansion(hw, n, sigma):
     img = (127.5 + 60.0 * smooth(31 + n, (3,) + hw)).astype(np.float32)
     got = ops.optflow_poly_exp(dev(img), n, sigma).cpu().numpy()
     tabs = tuple(np.abs(t) for t in fb.poly_tables(n, sigma))
@@ -138,6 +152,18 @@ def matrices_case(hw, kind):
     return R0, R1, away_from_the_edges(flow)
 
 
+def matrices_bound(R0, R1, D, sampled=True):
+    """The bound of test_matrices for a flow of magnitude at most D.  sampled=False: for pixels that take the outside branch,
+    where no sample is taken and e_S is 0."""
+    h, w = R0.shape[-2:]
+    A = float(max(np.max(np.abs(R0)), np.max(np.abs(R1))))
+    B = A * (1 + 2 * D)
+    Gx, Gy = float(np.max(np.abs(np.diff(R1, axis=2)))), float(np.max(np.abs(np.diff(R1, axis=1))))
+    e_S = U * (Gx * (w + D) + Gy * (h + D) + 8 * A) if sampled else 0.0
+    e_4, e_2 = e_S + 3 * U * A, (0.5 + 2 * D) * e_S + 8 * U * B
+    return 2 * (A * e_2 + B * e_4) + 4 * U * A * B
+
+
 @pytest.mark.parametrize('hw,kind', [((33, 70), 'out'), ((8, 9), 'out'), ((33, 70), 'zero'), ((8, 9), 'zero')])
 def test_matrices(hw, kind):
     """With A = max|R|, D = max|flow|, B = A (1 + 2 D) >= |r2|, |r3|, Gx / Gy = the largest difference of horizontal /
@@ -159,13 +185,7 @@ def test_matrices(hw, kind):
         assert np.array_equal(inside, fb.sample_positions(flow, np.float32)[2])
     got = ops.optflow_matrices(dev(R0), dev(R1), dev(flow)).cpu().numpy()
     want = fb.matrices(R0, R1, flow)
-    A = float(max(np.max(np.abs(R0)), np.max(np.abs(R1))))
-    D = float(np.max(np.abs(flow)))
-    B = A * (1 + 2 * D)
-    Gx, Gy = float(np.max(np.abs(np.diff(R1, axis=2)))), float(np.max(np.abs(np.diff(R1, axis=1))))
-    e_S = U * (Gx * (w + D) + Gy * (h + D) + 8 * A)
-    e_4, e_2 = e_S + 3 * U * A, (0.5 + 2 * D) * e_S + 8 * U * B
-    tol = 2 * (A * e_2 + B * e_4) + 4 * U * A * B
+    tol = matrices_bound(R0, R1, float(np.max(np.abs(flow))))
     err = float(np.max(np.abs(got - want)))
     print('matrices %s %s: max|d| = %.3e (bound %.3e, max|M| = %.3e)' % (hw, kind, err, tol, np.max(np.abs(want))))
     assert got.shape == (5, h, w) and err <= tol
@@ -198,6 +218,10 @@ def test_blur_and_solve(hw, winsize):
     the scale); E propagates through det = g11 g22 - g12^2 + 1e-3 and the numerators (3 more roundings each on the sums of
     absolute products) and through the division (2 more) - so a badly conditioned pixel is allowed exactly what its
     conditioning |g11 g22| / |det + 1e-3| costs.  x 1.5 for the second-order terms.  9 x 11: the window is wider than the image."""
+    check_blur_and_solve(hw, winsize)
+
+
+def check_blur_and_solve(hw, winsize):
     M = solve_case(hw)
     got = ops.optflow_blur_solve(dev(M), winsize).cpu().numpy()
     want, cond, _ = fb.blur_solve(M, winsize, want_cond=True)
@@ -226,7 +250,8 @@ def test_blur_and_solve_of_zero_is_exactly_zero():
 
 
 # ----------------------------------------------------------------------------- end to end
-PATCH = {(64, 128): (slice(16, 32), slice(42, 74)), (67, 131): (slice(16, 32), slice(43, 75))}
+PATCH = {(64, 128): (slice(16, 32), slice(42, 74)), (67, 131): (slice(16, 32), slice(43, 75)),
+         (67, 129): (slice(16, 32), slice(42, 74))}
 
 
 @functools.lru_cache(maxsize=None)
@@ -264,17 +289,21 @@ def scene_device(hw):
     return FarnebackFlow(hw)(dev(scene(hw))).cpu().numpy()
 
 
+def assert_well_conditioned(hw, trace):
+    ys, xs = PATCH[hw]
+    for k, p, it, (g11, g12, g22) in trace:
+        out = np.ones(g11.shape, bool)
+        out[ys.start >> k:-(-ys.stop >> k), xs.start >> k:-(-xs.stop >> k)] = False
+        assert np.min(((g11 * g22 - g12 * g12) / (g11 * g22))[out]) >= 0.1, (k, p, it)
+
+
 @pytest.mark.parametrize('hw', [(64, 128), (67, 131)])
 def test_end_to_end(hw):
     """F = 3 pairs of 4 frames, two pyramid levels: within 8 d32 + 2^-22 max|flow| of the float64 restatement."""
     want, d32, trace = scene_reference(hw)
     assert len(fb.level_geometry(*hw)) == 2 and len(trace) == 2 * 3 * 3
     # asserted on the CPU first: every 2 x 2 system outside the flat patch is well conditioned at every level
-    ys, xs = PATCH[hw]
-    for k, p, it, (g11, g12, g22) in trace:
-        out = np.ones(g11.shape, bool)
-        out[ys.start >> k:-(-ys.stop >> k), xs.start >> k:-(-xs.stop >> k)] = False
-        assert np.min(((g11 * g22 - g12 * g12) / (g11 * g22))[out]) >= 0.1, (k, p, it)
+    assert_well_conditioned(hw, trace)
     got = scene_device(hw)
     assert got.shape == (3,) + hw + (2,) and got.dtype == np.float32
     err, tol = float(np.max(np.abs(got - want))), 8 * d32 + 2.0 ** -22 * float(np.max(np.abs(want)))

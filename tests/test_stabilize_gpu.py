@@ -125,21 +125,44 @@ def circular(d, W):
 def test_rotation_flow(hw):
     """The identity, a small generic rotation, 40 degrees about the vertical axis (pixels cross the seam) and 25 degrees about
     the x axis (pixels go over a pole, where theta jumps by pi)."""
+    check_rotation_flow(hw)
+
+
+def flow_rotations():
+    return np.stack([np.eye(3), sr.rot(sr.AXIS, 0.05), sr.rot((0, 1, 0), np.deg2rad(40.0)), sr.rot((1, 0, 0), np.deg2rad(25.0))])
+
+
+def leaves_through_the_seam(G):
+    """Whether a pixel of the flow G [H, W, 2] lands beyond the first or the last column's centre."""
+    x = np.arange(G.shape[1])[None, :]
+    return bool(((x + G[..., 0] < -0.5) | (x + G[..., 0] >= G.shape[1] - 0.5)).any())
+
+
+def goes_over_a_pole(G):
+    """Whether a pixel of the flow G [H, W, 2] moves more than a quarter turn in x, as only a path over a pole does."""
+    return bool((np.abs(G[..., 0]) > G.shape[1] / 4).any())
+
+
+def check_rotation_flow(hw, R=None, crossings=True, floor=0.0):
+    """R defaults to flow_rotations(); crossings: assert that R[2] leaves through the seam and R[3] goes over a pole; floor: the
+    share of the result's scale (max|G|) added to 8 d32, for the rounding of the stored float32."""
     H, W = hw
-    R = np.stack([np.eye(3), sr.rot(sr.AXIS, 0.05), sr.rot((0, 1, 0), np.deg2rad(40.0)), sr.rot((1, 0, 0), np.deg2rad(25.0))])
+    R = flow_rotations() if R is None else R
     want = sr.rotation_flow(R, H, W)
     d32 = float(np.max(np.abs(circular(sr.rotation_flow(R, H, W, np.float32) - want, W))))
-    # the cases do what they are for: columns leave through the seam, rows through a pole
-    x = np.arange(W)[None, :]
-    assert ((x + want[2, ..., 0] < -0.5) | (x + want[2, ..., 0] >= W - 0.5)).any()
-    assert (np.abs(want[3, ..., 0]) > W / 4).any()
+    if crossings:
+        # the cases do what they are for: columns leave through the seam, rows through a pole
+        assert leaves_through_the_seam(want[2])
+        assert goes_over_a_pole(want[3])
     got = ops.rotation_flow(dev(R.astype(np.float32)), H, W).cpu().numpy()
-    assert got.shape == (4, H, W, 2) and got.dtype == np.float32
+    assert got.shape == (R.shape[0], H, W, 2) and got.dtype == np.float32
     assert np.all(got[..., 0] >= -W / 2) and np.all(got[..., 0] <= W / 2)
     err = float(np.max(np.abs(circular(got - want, W))))
-    print('rotation flow %s: max|d| = %.2e, d32 = %.2e' % (hw, err, d32))
-    assert err <= 8 * d32
-    assert float(np.max(np.abs(got[0]))) <= 8 * d32
+    tol = 8 * d32 + floor * float(np.max(np.abs(want)))
+    print('rotation flow %s: max|d| = %.2e, d32 = %.2e (bound %.2e)' % (hw, err, d32, tol))
+    assert err <= tol
+    assert float(np.max(np.abs(got[0]))) <= tol
+    return got
 
 
 # ----------------------------------------------------------------------------- resample
@@ -152,9 +175,15 @@ def rotations_for(N):
 @pytest.mark.parametrize('C', [1, 3, 4])
 def test_equirect_rotate_f32(hw, N, C):
     """A box-blurred hash texture; 64 x 128 carries N = 3 frames with a rotation each (generic, across the seam, over a pole)."""
-    H, W = hw
-    frames = np.stack([3.0 * sr.texture(300 + n, H, W, C) - 1.0 for n in range(N)])
-    R = rotations_for(N)
+    check_equirect_rotate_f32(hw, rotations_for(N), C)
+
+
+def f32_frames(hw, N, C):
+    return np.stack([3.0 * sr.texture(300 + n, hw[0], hw[1], C) - 1.0 for n in range(N)])
+
+
+def check_equirect_rotate_f32(hw, R, C):
+    frames = f32_frames(hw, R.shape[0], C)
     want = sr.equirect_rotate(frames, R)
     d32 = float(np.max(np.abs(sr.equirect_rotate(frames, R, np.float32) - want)))
     got = ops.equirect_rotate(dev(frames), dev(R.astype(np.float32))).cpu().numpy()
@@ -162,29 +191,41 @@ def test_equirect_rotate_f32(hw, N, C):
     err, tol = float(np.max(np.abs(got - want))), 8 * d32 + FLOOR * float(np.max(np.abs(frames)))
     print('rotate f32 %s C %d: max|d| = %.2e (d32 %.2e, bound %.2e)' % (hw, C, err, d32, tol))
     assert err <= tol
+    return got
 
 
 @pytest.mark.parametrize('hw,N', [((33, 66), 1), ((64, 128), 3)])
 def test_equirect_rotate_u8(hw, N):
     """At most one level everywhere, and a pixel may differ only where the float64 value before rounding lies within 8 d32 of
     a rounding boundary."""
-    H, W = hw
-    frames = np.stack([np.rint(255.0 * sr.texture(400 + n, H, W, 3)).astype(np.uint8) for n in range(N)])
-    R = rotations_for(N)
+    frames, R = check_equirect_rotate_u8(hw, rotations_for(N))
+    with pytest.raises(ValueError):
+        ops.equirect_rotate(dev(frames), dev(R.astype(np.float32)), out=dev(frames)[..., :2])
+
+
+def u8_frames(hw, N):
+    return np.stack([np.rint(255.0 * sr.texture(400 + n, hw[0], hw[1], 3)).astype(np.uint8) for n in range(N)])
+
+
+def check_u8_against_the_restatement(frames, R, got, what):
+    """got u8 = the device's equirect_rotate(frames, R): the two assertions of test_equirect_rotate_u8."""
     raw = sr.equirect_rotate(frames, R, raw=True)
     want = sr.equirect_rotate(frames, R)
     d32 = float(np.max(np.abs(sr.equirect_rotate(frames, R, np.float32, raw=True) - raw)))
+    diff = got.astype(np.int32) - want.astype(np.int32)
+    to_boundary = np.abs(raw - np.floor(raw) - 0.5)
+    print('rotate u8 %s: %d of %d values differ, d32 = %.2e' % (what, np.count_nonzero(diff), diff.size, d32))
+    assert np.max(np.abs(diff)) <= 1
+    assert np.all(to_boundary[diff != 0] <= 8 * d32)
+
+
+def check_equirect_rotate_u8(hw, R):
+    frames = u8_frames(hw, R.shape[0])
     out = torch.empty(frames.shape, dtype=torch.uint8, device=DEV)
     got = ops.equirect_rotate(dev(frames), dev(R.astype(np.float32)), out=out)
     assert got is out
-    got = got.cpu().numpy()
-    diff = got.astype(np.int32) - want.astype(np.int32)
-    to_boundary = np.abs(raw - np.floor(raw) - 0.5)
-    print('rotate u8 %s: %d of %d values differ, d32 = %.2e' % (hw, np.count_nonzero(diff), diff.size, d32))
-    assert np.max(np.abs(diff)) <= 1
-    assert np.all(to_boundary[diff != 0] <= 8 * d32)
-    with pytest.raises(ValueError):
-        ops.equirect_rotate(dev(frames), dev(R.astype(np.float32)), out=dev(frames)[..., :2])
+    check_u8_against_the_restatement(frames, R, got.cpu().numpy(), hw)
+    return frames, R
 
 
 def test_identity_rotations_copy_bit_exactly_through_the_stabilizer():

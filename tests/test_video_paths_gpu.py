@@ -1,0 +1,481 @@
+"""Launch paths of the flow, stabilisation and viewport kernels (csrc/optflow.hip "K10", csrc/stabilize.hip "K11",
+csrc/viewport.hip "K12" and the sampler they share, csrc/sphere.h) that the shapes of their own tests never reach: rows wider
+than one 256-thread block, the two-channel instantiations, K10's scalar stores at a row that is a multiple of 4, the second
+pass of the gray kernel's grid-stride loop, the guard for a non-finite flow, the ends of the parameter ranges, K11a's batch
+paths, a caller's dirty workspace, a non-finite rotation, panoramas of one row or one column, and destinations that overlap
+their operands.  Every test calls a kernel through ``ops`` or the driver ``FarnebackFlow`` and compares with the float64
+restatements (tests/farneback_restate.py, stabilize_restate.py, viewport_restate.py), never with another path of the library -
+except where bit-equality of two paths is the claim, and then one of the two is held to the restatement as well.
+
+Bounds: no new numbers.  Each kernel keeps the rule of its own test file, through the ``check_*`` functions those files share:
+tests/test_optflow_gpu.py counts roundings per stage (u = 2^-24), tests/test_stabilize_gpu.py and tests/test_viewport_gpu.py
+allow 8 d32 + 2^-22 of the result's scale, d32 = max|restate(f32) - restate(f64)| on the same input (the flow of a rotation is
+stored as float32 too: here it gets the 2^-22 max|G| that test_rotation_flow does without).  Every comparison prints its observed
+error beside its bound.
+
+Conditions on the inputs (level geometry, workspace alignment, seam and pole crossings, the outline's undecided pixels, the
+in-bounds masks) are functions without a GPU call, asserted here before the device runs and again by
+tests/test_video_paths_cpu.py where no GPU is present."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import ops
+from cp_360_weakly_supervised_saliency_amd.utils import hashrng
+from cp_360_weakly_supervised_saliency_amd.utils.optical_flow import FarnebackFlow
+from tests import farneback_restate as fb
+from tests import stabilize_restate as sr
+from tests import test_optflow_gpu as k10
+from tests import test_stabilize_gpu as k11
+from tests import test_viewport_gpu as k12
+from tests import viewport_restate as vr
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+FLOOR = 2.0 ** -22
+dev = k10.dev
+
+
+# ============================================================================= K10: Farneback flow
+@pytest.mark.parametrize('hw,ksz,sigma,lhw', [((9, 600), 9, 1.5, (5, 300)), ((9, 600), 3, 0.0, (9, 600)),
+                                              ((40, 70), 19, 3.5, (5, 9)), ((40, 70), 39, 7.5, (5, 9))])
+def test_pyramid_level_wide_rows_and_long_kernels(hw, ksz, sigma, lhw):
+    """9 x 600: the source spans three blocks of pyr_hblur_kernel and the level two or three of pyr_vresize_kernel; reflect-101
+    folds at x < 4 in block 0 and at x > 595 in block 2.  40 x 70 with 19 and 39 taps: the kernels of the driver's levels 3 and
+    4, which the driver tests compare only with the stage entry points."""
+    k10.check_pyramid_level(hw, ksz, sigma, lhw)
+
+
+def test_flow_upsample_wide_rows():
+    """5 x 150 -> 9 x 300: the second block of flow_upsample_kernel taps the source's last columns, edge clamp included."""
+    k10.check_flow_upsample((5, 150), (9, 300), 2.0)
+
+
+HW129 = (67, 129)
+GEOMETRY129 = [(67, 129, 3, 0.0), (34, 64, 3, 0.5)]
+
+
+def scalar_store_conditions(F=1):
+    """67 x 129 has a level of 34 x 64, a row of a multiple of 4 pixels, and the driver's workspace puts that level's R at
+    (F + 1) H W floats and its flow at (11 F + 6) H W floats (images | R | M | odd levels' flow: F + 1, 5 (F + 1) and 5 F
+    planes of H W floats).  Neither is a multiple of 4 floats, so both stores take the scalar branch.  Returns the two
+    offsets in bytes modulo 16."""
+    H, W = HW129
+    assert fb.level_geometry(H, W) == GEOMETRY129
+    r_off, fl_off = (F + 1) * H * W, (11 * F + 6) * H * W
+    assert r_off % 4 != 0 and fl_off % 4 != 0
+    return 4 * r_off % 16, 4 * fl_off % 16
+
+
+@functools.lru_cache(maxsize=None)
+def pair129_reference():
+    """Two frames of test_optflow_gpu's scene at 67 x 129: (gray, float64 flow [1, 67, 129, 2], d32, trace)."""
+    gray = k10.scene(HW129)[:2]
+    trace = []
+    f64 = fb.farneback(gray, trace=trace)
+    d32 = float(np.max(np.abs(fb.farneback(gray, dtype=np.float32).astype(np.float64) - f64)))
+    return gray, f64, d32, trace
+
+
+def test_driver_scalar_stores_at_a_row_that_is_a_multiple_of_4():
+    """The driver's level 1 (34 x 64) goes through the scalar branch of poly_exp_kernel and blur_solve_kernel; through ``ops``
+    the same level lands in fresh allocations and takes the 16-byte branch.  The driver's flow is held to the float64
+    restatement at the end-to-end bound and, bit for bit, to the stage entry points."""
+    assert scalar_store_conditions() == (8, 12)
+    gray, want, d32, trace = pair129_reference()
+    assert len(trace) == 2 * 1 * 3
+    k10.assert_well_conditioned(HW129, trace)
+    ff = FarnebackFlow(HW129)
+    assert ff.geometry == GEOMETRY129
+    got = ff(dev(gray))
+    assert got.shape == (1,) + HW129 + (2,) and got.dtype == torch.float32
+    err = float(np.max(np.abs(got.cpu().numpy() - want)))
+    tol = 8 * d32 + FLOOR * float(np.max(np.abs(want)))
+    print('driver %s, one pair: d32 = %.3e, device max|d| = %.3e (bound %.3e), max|flow| = %.3f'
+          % (HW129, d32, err, tol, np.max(np.abs(want))))
+    assert err <= tol
+    cur = None
+    for h, w, ksz, sigma in reversed(ff.geometry):
+        R = ops.optflow_poly_exp(ops.optflow_pyr_level(dev(gray), ksz, sigma, h, w))
+        cur = torch.zeros(1, h, w, 2, device=DEV) if cur is None else ops.optflow_flow_upsample(cur, h, w, 2.0)
+        for _ in range(3):
+            cur = ops.optflow_blur_solve(ops.optflow_matrices(R[:-1], R[1:], cur), 15)
+            assert R.data_ptr() % 16 == 0 and cur.data_ptr() % 16 == 0          # the stage path stores 16-byte pieces at w = 64
+    differ = int(np.count_nonzero(got.cpu().numpy() != cur.cpu().numpy()))
+    print('driver against the stage entry points: %d of %d values differ (0 allowed)' % (differ, got.numel()))
+    assert differ == 0
+
+
+GRAY_SHAPE = (2, 2049, 4097, 3)
+
+
+def gray_second_pass_pixels():
+    n = int(np.prod(GRAY_SHAPE[:-1]))
+    assert n > 65536 * 256                       # the grid is capped at 65536 blocks of 256 threads
+    return n
+
+
+def test_gray_grid_stride_second_pass():
+    """16 789 506 pixels: the last 12 290 are the second pass of the capped grid's threads.  Seven hash bytes per word."""
+    n = gray_second_pass_pixels()
+    words = hashrng.integers(91, ((3 * n + 6) // 7,), 0, 1 << 56).astype('<i8')
+    rgb = np.ascontiguousarray(words.view(np.uint8).reshape(-1, 8)[:, :7]).reshape(-1)[:3 * n].reshape(GRAY_SHAPE)
+    got = ops.optflow_gray(dev(rgb)).cpu().numpy()
+    want = fb.gray_from_rgb(rgb)
+    assert got.shape == GRAY_SHAPE[:-1] and got.dtype == np.float32
+    wrong = got != want
+    print('gray %s: %d of %d pixels differ (0 allowed), %d of them in the second pass'
+          % (GRAY_SHAPE, wrong.sum(), n, wrong.reshape(-1)[65536 * 256:].sum()))
+    assert not wrong.any()
+
+
+GUARD_HW = (33, 70)
+GUARD_VALUES = (np.nan, np.inf, -np.inf, 1e30, -1e30)
+GUARD_SPOTS = ((0, 0), (5, 9), (16, 35), (32, 69), (20, 3), (7, 64), (31, 1), (12, 50), (25, 25), (2, 40))
+
+
+@functools.lru_cache(maxsize=None)
+def guarded_flow_case():
+    """test_matrices' outward flow at 33 x 70 and a copy with every value of GUARD_VALUES written once into dx and once into
+    dy of ten pixels (corners, borders, interior).  Asserts what the comparison rests on: no clean sample within 1e-3 of an
+    in-bounds switch, float32 and float64 agree on the mask, and every touched pixel is outside in the restatement.
+    Returns (R0, R1, clean, dirty, touched bool [h, w])."""
+    h, w = GUARD_HW
+    R0, R1, clean = k10.matrices_case(GUARD_HW, 'out')
+    fx, fy, inside = fb.sample_positions(clean)
+    for pos, n in ((fx, w), (fy, h)):
+        assert np.min(np.abs(pos)) >= 1e-3 and np.min(np.abs(pos - (n - 1))) >= 1e-3
+    assert np.array_equal(inside, fb.sample_positions(clean, np.float32)[2])
+    dirty, touched = clean.copy(), np.zeros(GUARD_HW, bool)
+    for k, (y, x) in enumerate(GUARD_SPOTS):
+        dirty[y, x, k % 2] = GUARD_VALUES[k // 2]
+        touched[y, x] = True
+    with np.errstate(invalid='ignore'):
+        for dtype in (np.float64, np.float32):
+            mask = fb.sample_positions(dirty, dtype)[2]
+            assert not mask[touched].any() and np.array_equal(mask[~touched], inside[~touched])
+    assert inside[touched].any()                                # some of them were inside before
+    return R0, R1, clean, dirty, touched
+
+
+def test_matrices_guard_for_a_non_finite_or_huge_flow():
+    """NaN, +-inf and +-1e30 take the outside branch and never become an index: every other pixel is bit-equal to the run on
+    the clean flow (itself held to test_matrices' bound), and a touched pixel equals the restatement's outside branch - NaN and
+    inf where it has them, its finite values within test_matrices' bound without the sample's term (no sample is taken), D
+    being the pixel's own finite displacement (the sums M[0 .. 2] do not involve the flow: D = 0)."""
+    R0, R1, clean, dirty, touched = guarded_flow_case()
+    got_clean = ops.optflow_matrices(dev(R0), dev(R1), dev(clean)).cpu().numpy()
+    got = ops.optflow_matrices(dev(R0), dev(R1), dev(dirty)).cpu().numpy()
+    torch.cuda.synchronize()
+    err, tol = float(np.max(np.abs(got_clean - fb.matrices(R0, R1, clean)))), k10.matrices_bound(R0, R1, float(np.max(np.abs(clean))))
+    print('matrices %s, clean flow: max|d| = %.3e (bound %.3e)' % (GUARD_HW, err, tol))
+    assert err <= tol
+    differ = int(np.count_nonzero(got[:, ~touched] != got_clean[:, ~touched]))
+    print('matrices %s, guarded flow: %d values of untouched pixels differ from the clean run (0 allowed)' % (GUARD_HW, differ))
+    assert differ == 0
+    with np.errstate(invalid='ignore', over='ignore'):
+        want = fb.matrices(R0, R1, dirty)
+    for k, (y, x) in enumerate(GUARD_SPOTS):
+        v, g, wv = GUARD_VALUES[k // 2], got[:, y, x].astype(np.float64), want[:, y, x]
+        assert np.array_equal(np.isnan(g), np.isnan(wv)) and np.array_equal(np.isinf(g), np.isinf(wv)), (y, x, g, wv)
+        assert np.array_equal(g[np.isinf(wv)], wv[np.isinf(wv)])
+        assert np.isfinite(wv[:3]).all()
+        fin = np.isfinite(wv)
+        tol = np.where(np.arange(5) < 3, k10.matrices_bound(R0, R1, 0.0, sampled=False),
+                       k10.matrices_bound(R0, R1, abs(v), sampled=False) if np.isfinite(v) else 0.0)
+        ratio = float(np.max(np.abs(g[fin] - wv[fin]) / tol[fin]))
+        print('matrices at (%d, %d) with d%s = %g: %d finite sums, max|d| / bound = %.3f' % (y, x, 'xy'[k % 2], v, fin.sum(), ratio))
+        assert ratio <= 1.0
+
+
+@pytest.mark.parametrize('hw', [(33, 70), (16, 64)])
+def test_blur_and_solve_with_a_window_of_one_pixel(hw):
+    """winsize 1 is m = 0: one tap, no halo; 16 x 64 is one tile stored in 16-byte pieces."""
+    k10.check_blur_and_solve(hw, 1)
+
+
+@pytest.mark.parametrize('n', [1, 3])
+@pytest.mark.parametrize('hw', [(33, 70), (16, 64)])
+def test_expansion_with_the_shortest_windows(hw, n):
+    """poly_n 1 and 3 (3 and 7 taps) at the default poly_sigma."""
+    k10.check_expansion(hw, n, 1.2)
+
+
+# ============================================================================= K11: stabilisation
+def wide_flow_rotations(hw):
+    """test_rotation_flow's four rotations.  3 x 600 has its rows at +-60 and 0 degrees, which 25 degrees about the x axis do
+    not carry over a pole: there a fifth rotation, 40 degrees about the same axis, does.  Asserts that a rotation leaves
+    through the seam and one goes over a pole."""
+    R = k11.flow_rotations()
+    if hw[0] < 5:
+        R = np.concatenate([R, sr.rot((1, 0, 0), np.deg2rad(40.0))[None]])
+    want = sr.rotation_flow(R, hw[0], hw[1])
+    assert k11.leaves_through_the_seam(want[2])
+    assert k11.goes_over_a_pole(want[-1])
+    return R
+
+
+def rotate_rotations(hw=None):
+    """rotations_for(3) (generic, across the seam, over a pole) and the identity.  With hw: asserts that at this size the second
+    one has a tap pair (W - 1, 0) astride the seam and the third one clamps rows at a pole and moves pixels by more than a
+    quarter turn."""
+    R = np.concatenate([k11.rotations_for(3), np.eye(3)[None]])
+    if hw is not None:
+        H, W = hw
+        sx, _ = sr.sample_positions(R[1], H, W)
+        assert (np.mod(np.floor(sx), W) == W - 1).any()
+        sx, sy = sr.sample_positions(R[2], H, W)
+        assert (sy == 0).any() and (sy == H - 1).any()
+        assert (np.abs(np.mod(sx - np.arange(W)[None, :] + 0.5 * W, W) - 0.5 * W) > W / 4).any()
+    return R
+
+
+@pytest.mark.parametrize('hw', [(5, 300), (3, 600)])
+def test_rotation_flow_wide_rows(hw):
+    """Two and three blocks of stab_flow_kernel: the table lookup and the wrap into [-W / 2, W / 2) beyond x = 255."""
+    k11.check_rotation_flow(hw, wide_flow_rotations(hw), crossings=False, floor=FLOOR)
+
+
+@pytest.mark.parametrize('hw,N', [((9, 300), 4), ((5, 600), 4), ((16, 32), 1), ((64, 128), 3)])
+def test_equirect_rotate_two_channels(hw, N):
+    """stab_rotate_kernel<float, 2>, the layout of a flow field, at the tested sizes and at rows of two and three blocks (there
+    with the identity as a fourth frame)."""
+    k11.check_equirect_rotate_f32(hw, rotate_rotations(hw) if N == 4 else k11.rotations_for(N), 2)
+
+
+def test_equirect_rotate_u8_wide_rows():
+    k11.check_equirect_rotate_u8((9, 300), rotate_rotations((9, 300)))
+
+
+@pytest.mark.parametrize('hw', [(1, 8), (8, 1)])
+def test_degenerate_panoramas(hw):
+    """One row: every row tap clamps onto row 0.  One column: every column tap wraps onto column 0."""
+    k11.check_rotation_flow(hw, crossings=False, floor=FLOOR)
+    k11.check_equirect_rotate_f32(hw, rotate_rotations(), 3)
+    k11.check_equirect_rotate_u8(hw, rotate_rotations())
+
+
+def broken_rotations(clean):
+    """clean [3, 3, 3] twice, the middle one all NaN, then the identity with one entry +inf."""
+    nan, inf = clean.copy(), clean.copy()
+    nan[1] = np.nan
+    inf[1] = np.eye(3)
+    inf[1, 0, 0] = np.inf
+    return nan, inf
+
+
+def test_a_non_finite_rotation_stays_in_its_frame():
+    """sphere_sample's guard through K11: the calls return, the frames beside the broken one are bit-equal to the clean run
+    (itself held to the restatement), and the broken frame holds values of its source (a sample inside the frame)."""
+    hw = (33, 66)
+    clean = k11.rotations_for(3)
+    f32 = k11.f32_frames(hw, 3, 3)
+    got_f32 = k11.check_equirect_rotate_f32(hw, clean, 3)
+    u8 = k11.u8_frames(hw, 3)
+    got_u8 = ops.equirect_rotate(dev(u8), dev(clean.astype(np.float32))).cpu().numpy()
+    k11.check_u8_against_the_restatement(u8, clean, got_u8, '%s, clean' % (hw,))
+    flow_clean = k11.flow_rotations()[:3]
+    got_flow = k11.check_rotation_flow(hw, flow_clean, crossings=False, floor=FLOOR)
+    for what, bad, bad_flow in zip(('NaN', 'inf'), broken_rotations(clean), broken_rotations(flow_clean)):
+        R = dev(bad.astype(np.float32))
+        a = ops.equirect_rotate(dev(f32), R).cpu().numpy()
+        b = ops.equirect_rotate(dev(u8), R).cpu().numpy()
+        c = ops.rotation_flow(dev(bad_flow.astype(np.float32)), hw[0], hw[1]).cpu().numpy()
+        torch.cuda.synchronize()
+        differ = [int(np.count_nonzero(x[[0, 2]] != y[[0, 2]])) for x, y in ((a, got_f32), (b, got_u8), (c, got_flow))]
+        print('middle R %s: values of the outer frames that differ from the clean run: f32 %d, u8 %d, flow %d (0 allowed)'
+              % ((what,) + tuple(differ)))
+        assert differ == [0, 0, 0]
+        slack = FLOOR * float(np.max(np.abs(f32[1])))
+        assert f32[1].min() - slack <= a[1].min() and a[1].max() <= f32[1].max() + slack
+        assert u8[1].min() <= b[1].min() and b[1].max() <= u8[1].max()
+
+
+@functools.lru_cache(maxsize=None)
+def fit65_case():
+    """65 pairs of 16 x 32, 0.5 + 0.1 i degrees: (flow, R64, D64, dR, dD) as test_stabilize_gpu.fit_case."""
+    flow = np.stack([sr.noisy_outlier_flow(sr.rot(sr.AXIS, np.deg2rad(0.5 + 0.1 * i)), 16, 32, 200 + i) for i in range(65)])
+    R64, D64 = sr.rotation_fit(flow)
+    R32, D32 = sr.rotation_fit(flow, dtype=np.float32)
+    return flow, R64, D64, float(np.max(np.abs(R32 - R64))), np.max(np.abs(D32 - D64), 0)
+
+
+def fit_numpy(R, D):
+    return R.cpu().numpy().astype(np.float64), D.cpu().numpy()
+
+
+def test_fit_of_65_pairs():
+    """Pair 64 is the first of the second block of stab_fit_init_kernel: its state is I and c_min like every other's."""
+    flow, R64, D64, dR, dD = fit65_case()
+    fl = dev(flow)
+    R, D = ops.rotation_fit(fl)
+    assert R.shape == (65, 3, 3) and D.shape == (65, 4)
+    k11.check_fit(*fit_numpy(R, D), R64, D64, dR, dD, 'fit of 65 pairs of 16 x 32')
+    for p in (0, 63, 64):
+        R1, D1 = ops.rotation_fit(fl[p:p + 1])
+        assert torch.equal(R1[0], R[p]) and torch.equal(D1[0], D[p]), p
+
+
+def test_fit_with_one_iteration():
+    """iters = 1: the unweighted iteration alone, whose scale is max(c_min, 2 s)."""
+    flow = k11.fit_case((33, 66))[0]
+    R64, D64 = sr.rotation_fit(flow, iters=1)
+    R32, D32 = sr.rotation_fit(flow, iters=1, dtype=np.float32)
+    R, D = ops.rotation_fit(dev(flow), iters=1)
+    k11.check_fit(*fit_numpy(R, D), R64, D64, float(np.max(np.abs(R32 - R64))), np.max(np.abs(D32 - D64), 0),
+                  'fit (33, 66), 1 iteration')
+
+
+def test_a_dead_pair_between_live_pairs():
+    """[live, all NaN, live]: the dead pair gives I with sum of weights 0 and leaves its neighbours alone."""
+    flow = k11.fit_case((33, 66))[0].copy()
+    flow[1] = np.nan
+    R64, D64 = sr.rotation_fit(flow)
+    R32, D32 = sr.rotation_fit(flow, dtype=np.float32)
+    assert np.array_equal(R64[1], np.eye(3)) and D64[1, 1] == 0.0
+    fl = dev(flow)
+    R, D = ops.rotation_fit(fl)
+    k11.check_fit(*fit_numpy(R, D), R64, D64, float(np.max(np.abs(R32 - R64))), np.max(np.abs(D32 - D64), 0),
+                  'fit (33, 66), live / dead / live')
+    assert np.array_equal(R[1].cpu().numpy(), np.eye(3, dtype=np.float32)) and float(D[1, 1]) == 0.0
+    for p in (0, 2):
+        R1, D1 = ops.rotation_fit(fl[p:p + 1])
+        assert torch.equal(R1[0], R[p]) and torch.equal(D1[0], D[p]), p
+
+
+def test_a_dirty_workspace_larger_than_needed():
+    """One workspace sized for 8 pairs of 64 x 128, full of NaN, passed from call to call: every result is bit-equal to the call
+    that allocates its own, which is held to the restatement."""
+    flow, R64, D64, dR, dD = k11.fit_case((33, 66))
+    fl = dev(flow)
+    work = ops._stab_work(8, 64, 128, fl.device)
+    work.fill_(float('nan'))
+    for F, H, W in ((3, 33, 66), (0, 16, 32), (0, 64, 128)):
+        assert ops._stab_work(F, H, W, fl.device, work) is work            # large enough: the calls below do use it
+    fit = ops.rotation_fit(fl)
+    k11.check_fit(*fit_numpy(*fit), R64, D64, dR, dD, 'fit (33, 66), own workspace')
+    Rf = dev(k11.flow_rotations().astype(np.float32))
+    G = torch.from_numpy(k11.check_rotation_flow((16, 32))).to(DEV)
+    Rr = dev(k11.rotations_for(3).astype(np.float32))
+    frames = dev(k11.f32_frames((64, 128), 3, 3))
+    rot = torch.from_numpy(k11.check_equirect_rotate_f32((64, 128), k11.rotations_for(3), 3)).to(DEV)
+
+    def fit_again():
+        R, D = ops.rotation_fit(fl, work=work)
+        assert torch.equal(R, fit[0]) and torch.equal(D, fit[1])
+
+    def flow_again():
+        assert torch.equal(ops.rotation_flow(Rf, 16, 32, work=work), G)
+
+    def rotate_again():
+        assert torch.equal(ops.equirect_rotate(frames, Rr, work=work), rot)
+
+    for step in (fit_again, flow_again, rotate_again, flow_again, fit_again):
+        step()
+    print('fit, flow, rotate, flow, fit on one dirty workspace of %d bytes: bit-equal to the calls with their own' % (work.numel() * 8))
+
+
+# ============================================================================= K12: the viewport pilot
+@pytest.mark.parametrize('hfov', [60.0, 120.0])
+@pytest.mark.parametrize('HW,hw', [((16, 32), (9, 16)), ((33, 66), (5, 300))])
+def test_render_f32_two_channels(HW, hw, hfov):
+    """view_render_kernel<float, 2> at test_render_f32's first and last shapes."""
+    k12.check_the_cameras_do_what_they_are_for(HW, hw, hfov)
+    k12.check_render_f32(HW, hw, hfov, 2)
+
+
+WIDE_PANORAMAS = [(20, 600), (33, 520)]
+
+
+def outline_blocks(HW, border_px):
+    """The 256-column blocks of view_outline_kernel that hold border pixels of the identity camera and of the 180-degree yaw;
+    asserts test_outline's condition on the inputs (undecided pixels at most 1 % of the border pixels, every camera draws)."""
+    masks, undecided = k12.outline_case(HW, border_px)
+    assert all(m.any() for m in masks)
+    assert int(undecided.sum()) <= 0.01 * int(masks.sum())
+    blocks = [sorted(set((np.nonzero(m.any(0))[0] // 256).tolist())) for m in masks[:2]]
+    # 600 columns: the yaw's border lies in blocks 0 and 2; 520 columns: block 2 has 8 columns, the border starts in block 1
+    assert blocks[0] == [0, 1] and blocks[1][0] == 0 and blocks[1][-1] >= 1 and (HW[1] != 600 or blocks[1] == [0, 2])
+    return blocks
+
+
+@pytest.mark.parametrize('alias', [False, True])
+@pytest.mark.parametrize('border_px', [1, 3])
+@pytest.mark.parametrize('HW', WIDE_PANORAMAS)
+def test_outline_on_wide_panoramas(HW, border_px, alias):
+    """The identity camera's border lies in blocks 0 and 1 of a row, the 180-degree yaw's astride the seam in the first and the
+    last block."""
+    outline_blocks(HW, border_px)
+    k12.check_outline(HW, border_px, alias)
+
+
+# ============================================================================= destinations that overlap their operands
+def test_overlapping_views_of_one_buffer_are_refused():
+    """frames = buf[:-1] with out = buf[1:] share all but one frame of storage and start apart: refused by the two gathers and
+    by the outline, whose copy runs in no order across frames.  The buffers stay as they were."""
+    hw = (16, 32)
+    u8 = k11.u8_frames(hw, 4)
+    f32 = k11.f32_frames(hw, 4, 3)
+    R = dev(k11.rotations_for(3).astype(np.float32))
+    for frames in (u8, f32):
+        buf = dev(frames)
+        with pytest.raises(ValueError):
+            ops.equirect_rotate(buf[:-1], R, out=buf[1:])
+        with pytest.raises(ValueError):
+            ops.equirect_rotate(buf[1:], R, out=buf[:-1])
+        with pytest.raises(ValueError):
+            ops.viewport_render(buf[:-1], R, hw, 90.0, out=buf[1:])
+        with pytest.raises(ValueError):
+            ops.viewport_render(buf[1:], R, hw, 90.0, out=buf[:-1])
+        with pytest.raises(ValueError):
+            ops.equirect_rotate(buf[:3], R, out=buf[:3])
+        with pytest.raises(ValueError):
+            ops.viewport_render(buf[:3], R, hw, 90.0, out=buf[:3])
+        assert np.array_equal(buf.cpu().numpy(), frames)
+    buf = dev(u8)
+    with pytest.raises(ValueError):
+        ops.viewport_outline(buf[:-1], R, (9, 16), 90.0, out=buf[1:])
+    with pytest.raises(ValueError):
+        ops.viewport_outline(buf[1:], R, (9, 16), 90.0, out=buf[:-1])
+    assert np.array_equal(buf.cpu().numpy(), u8)
+
+
+def test_disjoint_slices_of_one_buffer_still_work():
+    """How Stabilizer.stabilize calls the resampler: operand and destination are slices of one buffer that share no byte.  Each
+    result is held to the restatement as the kernel's own test does."""
+    hw = (33, 66)
+    # K11c, u8
+    R = k11.rotations_for(3)
+    frames = k11.u8_frames(hw, 3)
+    buf = dev(np.concatenate([frames, np.zeros_like(frames)]))
+    got = ops.equirect_rotate(buf[:3], dev(R.astype(np.float32)), out=buf[3:])
+    assert got.data_ptr() == buf[3:].data_ptr() and np.array_equal(buf[:3].cpu().numpy(), frames)
+    k11.check_u8_against_the_restatement(frames, R, buf[3:].cpu().numpy(), '%s into a slice of the frames\' buffer' % (hw,))
+    # K12a, f32: a view of the panorama's own size
+    frames, R, want, d32 = k12.render_case(hw, hw, 90.0, 3)
+    buf = dev(np.concatenate([frames, np.zeros_like(frames)]))
+    ops.viewport_render(buf[:4], dev(R.astype(np.float32)), hw, 90.0, out=buf[4:])
+    err, tol = float(np.max(np.abs(buf[4:].cpu().numpy() - want))), 8 * d32 + FLOOR * float(np.max(np.abs(frames)))
+    print('render f32 %s -> %s into a slice of the frames\' buffer: max|d| = %.2e (d32 %.2e, bound %.2e)' % (hw, hw, err, d32, tol))
+    assert err <= tol and np.array_equal(buf[:4].cpu().numpy(), frames)
+    # K12b: into a disjoint slice, onto the frames themselves, and onto another view of exactly the frames
+    view, hfov = k12.OUTLINE_VIEW
+    masks, undecided = k12.outline_case(hw, 3)
+    frames = np.stack([np.rint(255.0 * vr.texture(730 + n, hw[0], hw[1], 3)).astype(np.uint8) for n in range(4)])
+    rgb = (0, 255, 0)
+    Rc = dev(k12.cameras4().astype(np.float32))
+    buf = dev(np.concatenate([frames, np.zeros_like(frames)]))
+    ops.viewport_outline(buf[:4], Rc, view, hfov, 3, rgb, out=buf[4:])
+    ops.viewport_outline(buf[:4], Rc, view, hfov, 3, rgb, out=buf[:4])
+    assert torch.equal(buf[:4], buf[4:])
+    again = dev(frames)
+    assert ops.viewport_outline(again, Rc, view, hfov, 3, rgb, out=again[:]).data_ptr() == again.data_ptr()
+    assert torch.equal(again, buf[:4])
+    got = buf[4:].cpu().numpy()
+    drawn = np.all(got == np.asarray(rgb, np.uint8), -1)
+    print('outline %s into a slice of the frames\' buffer: %d pixels differ from float64, %d undecided'
+          % (hw, int((drawn != masks).sum()), int(undecided.sum())))
+    assert not ((drawn != masks) & ~undecided).any()
+    assert np.array_equal(got[~drawn], frames[~drawn])

@@ -72,12 +72,16 @@ def test_render_f32(HW, hw, hfov):
     """Views of odd sizes with one partial block, and 5 x 300, which crosses the 256-thread block boundary."""
     check_the_cameras_do_what_they_are_for(HW, hw, hfov)
     for C in (1, 3, 4):
-        frames, R, want, d32 = render_case(HW, hw, hfov, C)
-        got = ops.viewport_render(dev(frames), dev(R.astype(np.float32)), hw, hfov).cpu().numpy()
-        assert got.shape == (4,) + hw + (C,) and got.dtype == np.float32
-        err, tol = float(np.max(np.abs(got - want))), 8 * d32 + FLOOR * float(np.max(np.abs(frames)))
-        print('render f32 %s -> %s hfov %g C %d: max|d| = %.2e (d32 %.2e, bound %.2e)' % (HW, hw, hfov, C, err, d32, tol))
-        assert err <= tol
+        check_render_f32(HW, hw, hfov, C)
+
+
+def check_render_f32(HW, hw, hfov, C):
+    frames, R, want, d32 = render_case(HW, hw, hfov, C)
+    got = ops.viewport_render(dev(frames), dev(R.astype(np.float32)), hw, hfov).cpu().numpy()
+    assert got.shape == (4,) + hw + (C,) and got.dtype == np.float32
+    err, tol = float(np.max(np.abs(got - want))), 8 * d32 + FLOOR * float(np.max(np.abs(frames)))
+    print('render f32 %s -> %s hfov %g C %d: max|d| = %.2e (d32 %.2e, bound %.2e)' % (HW, hw, hfov, C, err, d32, tol))
+    assert err <= tol
 
 
 @pytest.mark.parametrize('hfov', [60.0, 120.0])
@@ -160,6 +164,10 @@ def outline_case(HW, border_px):
 @pytest.mark.parametrize('border_px', [1, 3])
 @pytest.mark.parametrize('HW', [(33, 66), (64, 128)])
 def test_outline(HW, border_px, alias):
+    check_outline(HW, border_px, alias)
+
+
+def check_outline(HW, border_px, alias):
     H, W = HW
     hw, hfov = OUTLINE_VIEW
     masks, undecided = outline_case(HW, border_px)
