@@ -184,7 +184,7 @@ bool make_consts(double lr, double beta1, double beta2, double eps, double wd, d
 }
 
 bool aligned16(const void* a, const void* b, const void* c, const void* d) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+    return ::aligned16(a) && ::aligned16(b) && ::aligned16(c) && ::aligned16(d);    // common.h's
 }
 
 }  // namespace

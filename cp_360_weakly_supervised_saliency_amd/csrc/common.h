@@ -91,6 +91,19 @@ __host__ __device__ __forceinline__ int cubepad_src(int f, int i, int j, const C
     return (sf * n + row) * n + col;
 }
 
+// ---------------------------------------------------------------------------------
+// Shape and alignment checks of the host entry points (K10 - K15, adam.hip).
+// ---------------------------------------------------------------------------------
+static inline bool bad_image(int N, int h, int w) {
+    return N <= 0 || h <= 0 || w <= 0;
+}
+// grid y = rows or row tiles, grid z = images; the pixel index of one image stays an int
+static inline bool big_image(int N, int h, int w) {
+    return N > 65535 || h > 65535 || (long long)h * w > (1LL << 28);
+}
+static inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // Traversal order of the launch being issued by this host thread (cp360_set_launch_order, include/cp360.h): 0 = work
 // items in ascending order, 1 = descending; in the alternating mode every call flips it.  Results never depend on it.
 // Defined in cubepad.hip; called once per launch by the kernels that honour it.

@@ -58,17 +58,14 @@ struct SaucHdr {                             // per frame, K15c -> K15d, K15e
 };
 
 struct FixLayout {
-    size_t tabx, taby, hdr, cs, cp, total;
+    size_t hdr, cs, cp, total;                   // byte offsets, behind sphere.h's tables
 };
 
 // F = 0: the tables alone (counts needs nothing, density the tables)
 FixLayout fix_layout(int F, int h, int w) {
     FixLayout l;
-    const TabLayout t = tab_layout(h, w);
     const size_t n = (size_t)F * (size_t)h * (size_t)w;
-    l.tabx = t.tabx;
-    l.taby = t.taby;
-    l.hdr = t.total;
+    l.hdr = tab_bytes(h, w);
     l.cs = l.hdr + align16((size_t)F * sizeof(SaucHdr));
     l.cp = l.cs + align16(n * sizeof(float));
     l.total = l.cp + align16(n * sizeof(unsigned));
@@ -115,11 +112,10 @@ __global__ __launch_bounds__(256) void fix_counts_kernel(const double* __restric
             ++n;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    n = wave_sum_down(n);
     if ((tid & 63) == 0) red[tid >> 6] = n;
     __syncthreads();
-    if (tid == 0) n_points[f] = red[0] + red[1] + red[2] + red[3];
+    if (tid == 0) n_points[f] = waves4_sum(red, 1);
 }
 
 // ------------------------------------------------------------------ K15b: density
@@ -153,8 +149,7 @@ __global__ __launch_bounds__(256) void fix_density_kernel(const double* __restri
         const int n = k1 - t0 < kFixTile ? (int)(k1 - t0) : kFixTile;
         for (int k = 0; k < n; ++k) {
             const float4 q = tile_q[k];
-            const float dot = px * q.x + py * q.y + pz * q.z;
-            const float e = expf(kappa * (dot - 1.f));
+            const float e = vmf(kappa, px, py, pz, q.x, q.y, q.z);
             acc += q.w != 0.f ? e : 0.f;                               // acc >= +0: adding +0 changes no bit
         }
         __syncthreads();
@@ -171,7 +166,7 @@ __global__ __launch_bounds__(kRocThreads) void fix_sauc_prep_kernel(const float*
                                                                     float* __restrict__ cs, unsigned* __restrict__ cp) {
     __shared__ long long sml[kRocWaves * 3];
     __shared__ int cnt;
-    const int tid = threadIdx.x, lane = tid & 63, f = blockIdx.x;
+    const int tid = threadIdx.x, f = blockIdx.x;
     S += (size_t)f * P;
     pos += (size_t)f * P;
     neg += (size_t)f * neg_stride;
@@ -192,12 +187,8 @@ __global__ __launch_bounds__(kRocThreads) void fix_sauc_prep_kernel(const float*
             acc[2] += !(fabsf(s) < INFINITY);
         }
         const bool fx = m > 0;
-        const unsigned long long b = __ballot(fx);
-        int base = 0;
-        if (lane == 0 && b) base = atomicAdd(&cnt, __popcll(b));
-        base = __shfl(base, 0);
+        const int slot = roc_slot(fx, &cnt);
         if (fx) {
-            const int slot = base + __popcll(b & ((1ull << lane) - 1ull));
             cs[slot] = s;
             cp[slot] = (unsigned)m;
         }
@@ -348,15 +339,14 @@ extern "C" int cp360_fix_density(const double* lonlat, const int32_t* offsets, l
     int st = fix_points(lonlat, offsets, N, F, h, w);
     if (st != CP360_OK) return st;
     if (!(sigma_rad > 0.0) || !isfinite(sigma_rad)) return CP360_ERR_BAD_SHAPE;
-    if (((uintptr_t)work & 15) != 0 || ((uintptr_t)out & 3) != 0) return CP360_ERR_ALIGN;
-    const FixLayout l = fix_layout(0, h, w);
-    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
-    const float kappa = (float)(1.0 / (sigma_rad * sigma_rad));
+    if (((uintptr_t)out & 3) != 0) return CP360_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
-    st = launch_tables(work, h, w, s);
+    SphereTabs t;
+    st = open_tabs(work, work_bytes, tab_bytes(h, w), h, w, s, &t);
     if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(fix_density_kernel, dim3((h * w + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N,
-                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, h, w, kappa);
+    const float kappa = (float)(1.0 / (sigma_rad * sigma_rad));
+    hipLaunchKernelGGL(fix_density_kernel, dim3((h * w + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N, t.x,
+                       t.y, out, h, w, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -367,7 +357,7 @@ extern "C" int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t*
     const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
     if (Fn != 1 && Fn != F) return CP360_ERR_BAD_SHAPE;
-    if (((uintptr_t)work & 15) != 0 || (((uintptr_t)auc | (uintptr_t)c_tot | (uintptr_t)a_neg) & 7) != 0 ||
+    if (!aligned16(work) || (((uintptr_t)auc | (uintptr_t)c_tot | (uintptr_t)a_neg) & 7) != 0 ||
         (((uintptr_t)S | (uintptr_t)pos | (uintptr_t)neg) & 3) != 0)
         return CP360_ERR_ALIGN;
     const int P = h * w;

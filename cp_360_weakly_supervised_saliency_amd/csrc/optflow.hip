@@ -359,8 +359,6 @@ __global__ __launch_bounds__(256) void blur_solve_kernel(const float* __restrict
 // ------------------------------------------------------------------ host side
 int cv_round(double v) { return (int)nearbyint(v); }              // round half to even (the default rounding mode)
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int gauss_taps(int ksz, double sigma, GaussTaps* t) {
     if (ksz < 1 || ksz > kMaxKsz || !(ksz & 1)) return CP360_ERR_UNSUPPORTED;
     for (int i = 0; i <= kMaxKsz; ++i) t->v[i] = 0.f;
@@ -377,14 +375,6 @@ int poly_tabs(int n, double sigma, PolyTabs* t) {
     t->ig33 = ig[2];
     t->ig55 = ig[3];
     return CP360_OK;
-}
-
-bool bad_image(int N, int h, int w) {
-    return N <= 0 || h <= 0 || w <= 0;
-}
-// grid y = rows or row tiles, grid z = images; the pixel index of one plane stays an int
-bool big_image(int N, int h, int w) {
-    return N > 65535 || h > 65535 || (long long)h * w > (1LL << 28);
 }
 
 int launch_pyr_level(const float* gray, int N, int H, int W, const GaussTaps& taps, int ksz, float* out, int lh, int lw,

@@ -1,8 +1,8 @@
 // What the two files that compute a ROC on the sphere share: sphere_eval.hip (K14, AUC-Judd) and fixations.hip (K15, shuffled
 // AUC).  Both take the exact integer ROC sum of a map against weighted positives and weighted negatives and divide once; K14 is
 // K15 with pos_i = [i in M], neg_i = [i not in M] a_i, and the tests hold the two entries to the same bits (DESIGN.md "K14 and
-// K15: one ROC").  Shared here: the launch shapes, the limits and their check, and the fixed-tree workgroup reduction of the two
-// prepare kernels.  The rank kernels stay apart, for a measured reason (same place).
+// K15: one ROC").  Shared here: the launch shapes, the limits and their check, and the fixed-tree workgroup reduction and the
+// wave compaction of the two prepare kernels.  The rank kernels stay apart, for a measured reason (same place).
 // Everything here has internal linkage: each file that includes it compiles its own copy.
 #pragma once
 #include "sphere.h"
@@ -43,6 +43,18 @@ __device__ __forceinline__ void roc_reduce(T (&v)[N], T* sm, Op op) {
         v[n] = r;
     }
     __syncthreads();
+}
+
+// ---- wave compaction of the prepare kernels: the slot of a kept lane in the workgroup's list, counted by the LDS counter *cnt.
+// A wave's kept lanes take consecutive slots in lane order, the waves in the order their atomics land.  Every lane of the wave
+// calls it (the ballot needs them all); the result means something for a kept lane alone.
+__device__ __forceinline__ int roc_slot(bool keep, int* cnt) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long m = __ballot(keep);
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(cnt, __popcll(m));
+    base = __shfl(base, 0);
+    return base + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 }  // namespace

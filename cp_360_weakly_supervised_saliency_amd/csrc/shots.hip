@@ -173,7 +173,7 @@ extern "C" int cp360_shot_signatures(const uint8_t* frames, int F, int H, int W,
     if (!frames || !weights || !sig || !work) return CP360_ERR_NULL;
     const int st = shot_args(F, H, W);
     if (st != CP360_OK) return st;
-    if (((uintptr_t)work & 15) != 0 || ((uintptr_t)sig & 7) != 0 || ((uintptr_t)weights & 3) != 0) return CP360_ERR_ALIGN;
+    if (!aligned16(work) || ((uintptr_t)sig & 7) != 0 || ((uintptr_t)weights & 3) != 0) return CP360_ERR_ALIGN;
     if (work_bytes < cp360_shot_work_bytes(F, H, W)) return CP360_ERR_BAD_SHAPE;
     const int R = shot_rows(F, H, W), nblk = (H + R - 1) / R;
     hipStream_t s = (hipStream_t)stream;

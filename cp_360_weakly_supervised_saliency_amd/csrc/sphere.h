@@ -1,6 +1,8 @@
-// The sphere geometry of an equirectangular image, shared by stabilize.hip (K11) and viewport.hip (K12): the one definition of
-// dir, pix, the rotation of a direction, the (cos, sin) tables of the pixel centres and the bilinear sample that wraps in x and
-// clamps in y (DESIGN.md "K11" geometry; tests/stabilize_restate.py restates it).
+// The sphere geometry of an equirectangular image, shared by stabilize.hip (K11), viewport.hip (K12), sphere_eval.hip (K14) and
+// fixations.hip (K15): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables of the pixel centres
+// and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry; tests/stabilize_restate.py restates it);
+// and what their kernels and entry points repeat: the von Mises-Fisher term, the ordered sum of a 256-thread workgroup, how a
+// caller's workspace is opened and the dispatch on the pixel type (DESIGN.md "What the sphere kernels share").
 //
 //     theta = (2 (x + 1/2) / W - 1) pi        phi = (1 - 2 (y + 1/2) / H) pi / 2        dir = (cos phi cos theta, sin phi, cos phi sin theta)
 //     pix(q): theta = atan2(q_z, q_x), phi = asin(clamp(q_y, -1, 1)), x = (theta / pi + 1) W / 2 - 1/2, y = (1 - phi / (pi / 2)) H / 2 - 1/2
@@ -13,6 +15,7 @@
 #include "../../include/cp360.h"
 
 #include <math.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -99,36 +102,68 @@ __global__ __launch_bounds__(256) void stab_tables_kernel(float2* __restrict__ t
     }
 }
 
+// ------------------------------------------------------------------ the von Mises-Fisher term of K12c, K12d and K15b
+__device__ __forceinline__ float vmf(float kappa, float px, float py, float pz, float qx, float qy, float qz) {
+    const float dot = px * qx + py * qy + pz * qz;
+    return expf(kappa * (dot - 1.f));
+}
+
+// ------------------------------------------------------------------ the ordered sum of a 256-thread workgroup
+// One fixed tree, whose bits the callers see: a wave's 64 values by __shfl_down with offsets 32, 16, .. 1 (lane 0 ends with the
+// sum), then lane 0 of each of the four waves leaves it in LDS and the slots add up as ((r0 + r1) + r2) + r3.
+template <typename T>
+__device__ __forceinline__ T wave_sum_down(T v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// slot[k * stride] = wave k's sum
+template <typename T>
+__device__ __forceinline__ T waves4_sum(const T* slot, int stride) {
+    return ((slot[0] + slot[stride]) + slot[2 * stride]) + slot[3 * stride];
+}
+
 // ------------------------------------------------------------------ host side
-bool bad_image(int N, int h, int w) {
-    return N <= 0 || h <= 0 || w <= 0;
-}
-// grid y = rows, grid z = images; the pixel index of one image stays an int
-bool big_image(int N, int h, int w) {
-    return N > 65535 || h > 65535 || (long long)h * w > (1LL << 28);
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// the tables at the head of a workspace: byte offsets, and the bytes they take = cp360_stab_work_bytes(0, H, W)
-struct TabLayout {
-    size_t tabx, taby, total;
+// The tables at the head of a workspace: tab_bytes = cp360_stab_work_bytes(0, H, W).  open_tabs is how an entry point takes the
+// caller's workspace: a misaligned one is CP360_ERR_ALIGN, one below `need` bytes CP360_ERR_BAD_SHAPE, then the tables are
+// launched and t points at them.  An entry point with a check between the two halves calls them itself.
+struct SphereTabs {
+    const float2 *x, *y;
 };
 
-TabLayout tab_layout(int H, int W) {
-    TabLayout t;
-    t.tabx = 0;
-    t.taby = align16((size_t)W * sizeof(float2));
-    t.total = t.taby + align16((size_t)H * sizeof(float2));
-    return t;
+size_t tab_bytes(int H, int W) { return align16((size_t)W * sizeof(float2)) + align16((size_t)H * sizeof(float2)); }
+
+int check_work(const void* work, size_t work_bytes, size_t need) {
+    if (!aligned16(work)) return CP360_ERR_ALIGN;
+    return work_bytes < need ? CP360_ERR_BAD_SHAPE : CP360_OK;
 }
 
-int launch_tables(void* work, int H, int W, hipStream_t s) {
-    const TabLayout t = tab_layout(H, W);
-    hipLaunchKernelGGL(stab_tables_kernel, dim3((H + W + 255) / 256), dim3(256), 0, s, (float2*)((char*)work + t.tabx),
-                       (float2*)((char*)work + t.taby), H, W);
+int launch_tables(void* work, int H, int W, hipStream_t s, SphereTabs* t) {
+    float2* x = (float2*)work;
+    float2* y = (float2*)((char*)work + align16((size_t)W * sizeof(float2)));
+    hipLaunchKernelGGL(stab_tables_kernel, dim3((H + W + 255) / 256), dim3(256), 0, s, x, y, H, W);
     CP360_CHECK_HIP();
+    t->x = x;
+    t->y = y;
     return CP360_OK;
+}
+
+int open_tabs(void* work, size_t work_bytes, size_t need, int H, int W, hipStream_t s, SphereTabs* t) {
+    const int st = check_work(work, work_bytes, need);
+    return st != CP360_OK ? st : launch_tables(work, H, W, s, t);
+}
+
+// f(T(), integral_constant<int, C>()) for the pixel types of K11c and K12a: u8 x 3 or f32 x 1 .. 4 (the caller has checked)
+template <typename F>
+int dispatch_pixels(int dtype, int C, F f) {
+    if (dtype == CP360_U8) return f(uint8_t(), std::integral_constant<int, 3>());
+    switch (C) {
+        case 1: return f(float(), std::integral_constant<int, 1>());
+        case 2: return f(float(), std::integral_constant<int, 2>());
+        case 3: return f(float(), std::integral_constant<int, 3>());
+        default: return f(float(), std::integral_constant<int, 4>());
+    }
 }
 
 }  // namespace

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kEvalThreads) void seval_moments_kernel(const float
     __shared__ long long sml[kEvalWaves * 3];
     __shared__ float smf[kEvalWaves * 2];
     __shared__ int cnt;
-    const int tid = threadIdx.x, lane = tid & 63, f = blockIdx.x, P = h * w;
+    const int tid = threadIdx.x, f = blockIdx.x, P = h * w;
     S += (size_t)f * P;
     G += (size_t)f * P;
     if (fix) fix += (size_t)f * P;
@@ -182,11 +182,8 @@ __global__ __launch_bounds__(kEvalThreads) void seval_moments_kernel(const float
             i3[1] += fx ? 0 : ai;
             pk[i] = fx ? (1u << kFixShift) : (unsigned)ai;
         }
-        const unsigned long long m = __ballot(fx);
-        int base = 0;
-        if (lane == 0 && m) base = atomicAdd(&cnt, __popcll(m));
-        base = __shfl(base, 0);
-        if (fx) fixs[base + __popcll(m & ((1ull << lane) - 1ull))] = sf;
+        const int slot = roc_slot(fx, &cnt);
+        if (fx) fixs[slot] = sf;
     }
     roc_reduce(s3, smd, RocAdd());
     roc_reduce(i3, sml, RocAdd());
@@ -331,7 +328,7 @@ extern "C" int cp360_seval_scores(const float* S, const float* G, const uint8_t*
     if (!S || !G || !weights || !scores || !n_fix || !work) return CP360_ERR_NULL;
     const int st = roc_args(F, h, w);
     if (st != CP360_OK) return st;
-    if (((uintptr_t)work & 15) != 0 || ((uintptr_t)scores & 7) != 0 || (((uintptr_t)S | (uintptr_t)G | (uintptr_t)weights | (uintptr_t)n_fix) & 3) != 0)
+    if (!aligned16(work) || ((uintptr_t)scores & 7) != 0 || (((uintptr_t)S | (uintptr_t)G | (uintptr_t)weights | (uintptr_t)n_fix) & 3) != 0)
         return CP360_ERR_ALIGN;
     const int P = h * w;
     const EvalLayout l = eval_layout(F, P);

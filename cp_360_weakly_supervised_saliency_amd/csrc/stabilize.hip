@@ -110,21 +110,13 @@ __global__ __launch_bounds__(256) void stab_fit_accum_kernel(const float2* __res
         acc[10] += (double)(w * r2);
     }
 #pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-        acc[k] = v;
-    }
+    for (int k = 0; k < kSums; ++k) acc[k] = wave_sum_down(acc[k]);
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < kSums; ++k) red[tid >> 6][k] = acc[k];
     }
     __syncthreads();
-    if (tid < kSums) {
-        const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        partials[((size_t)pair * gridDim.x + blockIdx.x) * kPartial + tid] = v;
-    }
+    if (tid < kSums) partials[((size_t)pair * gridDim.x + blockIdx.x) * kPartial + tid] = waves4_sum(&red[0][tid], kSums);
 }
 
 // grid F, one wave: the ordered pass over the pair's partials, the 3 x 3 solve, Rodrigues and the scale update in f64
@@ -141,12 +133,7 @@ __global__ __launch_bounds__(64) void stab_fit_finish_kernel(const double* __res
         for (int k = 0; k < kSums; ++k) acc[k] += P[(size_t)b * kPartial + k];
     }
 #pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-        acc[k] = v;
-    }
+    for (int k = 0; k < kSums; ++k) acc[k] = wave_sum_down(acc[k]);
     if (lane != 0) return;
     const double Nxx = acc[0], Nxy = acc[1], Nxz = acc[2], Nyy = acc[3], Nyz = acc[4], Nzz = acc[5];
     const double bx = acc[6], by = acc[7], bz = acc[8], sw = acc[9], swr2 = acc[10];
@@ -247,17 +234,14 @@ __global__ __launch_bounds__(256) void stab_rotate_kernel(const T* __restrict__ 
 
 // ------------------------------------------------------------------ host side
 struct WorkLayout {
-    size_t tabx, taby, state, partials, total;   // byte offsets
+    size_t state, partials, total;               // byte offsets, behind sphere.h's tables
     int nblk;
 };
 
 WorkLayout work_layout(int F, int H, int W) {
     WorkLayout l;
     l.nblk = (int)(((long long)H * W + kFitBlock - 1) / kFitBlock);
-    const TabLayout t = tab_layout(H, W);
-    l.tabx = t.tabx;
-    l.taby = t.taby;
-    l.state = t.total;
+    l.state = tab_bytes(H, W);
     l.partials = l.state + (size_t)F * kState * sizeof(double);
     l.total = l.partials + (size_t)F * l.nblk * kPartial * sizeof(double);
     return l;
@@ -285,23 +269,20 @@ extern "C" int cp360_stab_fit(const float* flow, int F, int H, int W, int iters,
     if (!flow || !R || !diag || !work) return CP360_ERR_NULL;
     if (bad_image(F, H, W) || iters < 1 || !(c_min_px > 0.0) || !isfinite(c_min_px)) return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
-    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
     const WorkLayout l = work_layout(F, H, W);
-    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    const float2* tabx = (const float2*)((char*)work + l.tabx);
-    const float2* taby = (const float2*)((char*)work + l.taby);
+    SphereTabs t;
+    const int st = open_tabs(work, work_bytes, l.total, H, W, s, &t);
+    if (st != CP360_OK) return st;
     double* state = (double*)((char*)work + l.state);
     double* partials = (double*)((char*)work + l.partials);
     const double two_pi = 6.283185307179586476925;
     const double c_min = c_min_px * two_pi / (double)W;
-    int st = launch_tables(work, H, W, s);
-    if (st != CP360_OK) return st;
     hipLaunchKernelGGL(stab_fit_init_kernel, dim3((F + 63) / 64), dim3(64), 0, s, state, F, c_min);
     CP360_CHECK_HIP();
     const float kx = (float)(two_pi / (double)W), ky = (float)(0.5 * two_pi / (double)H);
     for (int k = 0; k < iters; ++k) {
-        hipLaunchKernelGGL(stab_fit_accum_kernel, dim3(l.nblk, F), dim3(256), 0, s, (const float2*)flow, tabx, taby,
+        hipLaunchKernelGGL(stab_fit_accum_kernel, dim3(l.nblk, F), dim3(256), 0, s, (const float2*)flow, t.x, t.y,
                            (const double*)state, partials, H, W, kx, ky, k == 0 ? 1 : 0);
         CP360_CHECK_HIP();
         hipLaunchKernelGGL(stab_fit_finish_kernel, dim3(F), dim3(64), 0, s, (const double*)partials, l.nblk, state, R, diag,
@@ -315,14 +296,11 @@ extern "C" int cp360_stab_flow(const float* R, int F, int H, int W, float* G, vo
     if (!R || !G || !work) return CP360_ERR_NULL;
     if (bad_image(F, H, W)) return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
-    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
-    const WorkLayout l = work_layout(0, H, W);
-    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    const int st = launch_tables(work, H, W, s);
+    SphereTabs t;
+    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &t);
     if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(stab_flow_kernel, dim3((W + 255) / 256, H, F), dim3(256), 0, s, R, (const float2*)((char*)work + l.tabx),
-                       (const float2*)((char*)work + l.taby), (float2*)G, H, W);
+    hipLaunchKernelGGL(stab_flow_kernel, dim3((W + 255) / 256, H, F), dim3(256), 0, s, R, t.x, t.y, (float2*)G, H, W);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -334,19 +312,12 @@ extern "C" int cp360_stab_rotate(int dtype, const void* frames, const float* R, 
     if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
     if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
-    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
-    const WorkLayout l = work_layout(0, H, W);
-    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    const int st = launch_tables(work, H, W, s);
+    SphereTabs t;
+    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &t);
     if (st != CP360_OK) return st;
-    const float2* tabx = (const float2*)((char*)work + l.tabx);
-    const float2* taby = (const float2*)((char*)work + l.taby);
-    if (dtype == CP360_U8) return launch_rotate<uint8_t, 3>(frames, R, tabx, taby, out, N, H, W, s);
-    switch (C) {
-        case 1: return launch_rotate<float, 1>(frames, R, tabx, taby, out, N, H, W, s);
-        case 2: return launch_rotate<float, 2>(frames, R, tabx, taby, out, N, H, W, s);
-        case 3: return launch_rotate<float, 3>(frames, R, tabx, taby, out, N, H, W, s);
-        default: return launch_rotate<float, 4>(frames, R, tabx, taby, out, N, H, W, s);
-    }
+    return dispatch_pixels(dtype, C, [&](auto px, auto c) {
+        return launch_rotate<decltype(px), decltype(c)::value>(frames, R, t.x, t.y, out, N, H, W, s);
+    });
 }
+

@@ -28,6 +28,15 @@ __device__ __forceinline__ bool rot_finite(const Rot& R) {
     return isfinite(s);
 }
 
+// K12d's argmax, one step of its tree (the tree of sphere.h's ordered sum): the candidate (ov, oi) replaces (best, bi) when it
+// has the larger value, or the same value at a lower index; an index below 0 is no candidate
+__device__ __forceinline__ void peak_take(float ov, int oi, float& best, int& bi) {
+    if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
+        best = ov;
+        bi = oi;
+    }
+}
+
 // ------------------------------------------------------------------ K12a: the view
 // grid (ceil(w / 256), h, N): one thread per view pixel, all C channels
 template <typename T, int C>
@@ -106,8 +115,7 @@ __global__ __launch_bounds__(256) void view_smooth_kernel(const float* __restric
         const int n = P - t0 < 256 ? P - t0 : 256;
         for (int k = 0; k < n; ++k) {
             const float4 q = tile_p[k];
-            const float dot = pix_x * q.x + pix_y * q.y + pix_z * q.z;
-            const float e = expf(kappa * (dot - 1.f));
+            const float e = vmf(kappa, pix_x, pix_y, pix_z, q.x, q.y, q.z);
             num += (double)(tile_as[k] * e);
             den += (double)(q.w * e);
         }
@@ -141,15 +149,8 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
         nfin += isfinite(s[j]) ? 1 : 0;
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_down(best, off, 64);
-        const int oi = __shfl_down(bi, off, 64);
-        nfin += __shfl_down(nfin, off, 64);
-        if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
-            best = ov;
-            bi = oi;
-        }
-    }
+    for (int off = 32; off >= 1; off >>= 1) peak_take(__shfl_down(best, off, 64), __shfl_down(bi, off, 64), best, bi);
+    nfin = wave_sum_down(nfin);
     if ((tid & 63) == 0) {
         red_v[tid >> 6] = best;
         red_i[tid >> 6] = bi;
@@ -158,17 +159,9 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
     __syncthreads();
     best = red_v[0];
     bi = red_i[0];
-    nfin = red_n[0];
 #pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        const float ov = red_v[k];
-        const int oi = red_i[k];
-        nfin += red_n[k];
-        if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
-            best = ov;
-            bi = oi;
-        }
-    }
+    for (int k = 1; k < 4; ++k) peak_take(red_v[k], red_i[k], best, bi);
+    nfin = waves4_sum(red_n, 1);
     if (bi < 0 || nfin == 0) {                                          // nothing finite: look ahead
         if (tid == 0) {
             dir_out[(size_t)f * 3] = 1.f;
@@ -191,29 +184,21 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
         float qx, qy, qz;
         stab_dir(tabx[x], csp, qx, qy, qz);
         const float sj = s[j];
-        const float dot = cx * qx + cy * qy + cz * qz;
-        const float e = expf(kappa * (dot - 1.f));
+        const float e = vmf(kappa, cx, cy, cz, qx, qy, qz);
         const float wgt = (csp.x * (isfinite(sj) ? sj : 0.f)) * e;
         acc[0] += (double)(wgt * qx);
         acc[1] += (double)(wgt * qy);
         acc[2] += (double)(wgt * qz);
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-        acc[k] = v;
-    }
+    for (int k = 0; k < 3; ++k) acc[k] = wave_sum_down(acc[k]);
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) red_c[tid >> 6][k] = acc[k];
     }
     __syncthreads();
     if (tid != 0) return;
-    const double sx = ((red_c[0][0] + red_c[1][0]) + red_c[2][0]) + red_c[3][0];
-    const double sy = ((red_c[0][1] + red_c[1][1]) + red_c[2][1]) + red_c[3][1];
-    const double sz = ((red_c[0][2] + red_c[1][2]) + red_c[2][2]) + red_c[3][2];
+    const double sx = waves4_sum(&red_c[0][0], 3), sy = waves4_sum(&red_c[0][1], 3), sz = waves4_sum(&red_c[0][2], 3);
     const double n = sqrt(sx * sx + sy * sy + sz * sz);
     float ox = cx, oy = cy, oz = cz;
     if (n > 0.0 && isfinite(n)) {
@@ -247,10 +232,8 @@ int launch_render(const void* frames, const float* R, void* out, int N, int H, i
 int map_args(int F, int hm, int wm, double sigma_rad, const void* work, size_t work_bytes, float* kappa) {
     if (bad_image(F, hm, wm) || bad_sigma(sigma_rad)) return CP360_ERR_BAD_SHAPE;
     if ((long long)hm * wm > kMaxMapPx || F > 65535) return CP360_ERR_UNSUPPORTED;
-    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
-    if (work_bytes < tab_layout(hm, wm).total) return CP360_ERR_BAD_SHAPE;
     *kappa = (float)(1.0 / (sigma_rad * sigma_rad));
-    return CP360_OK;
+    return check_work(work, work_bytes, tab_bytes(hm, wm));
 }
 
 }  // namespace
@@ -266,13 +249,9 @@ extern "C" int cp360_view_render(int dtype, const void* frames, const float* R, 
     const double t = tan(0.5 * hfov_rad);
     const float tx = (float)t, ty = (float)(t * (double)h / (double)w);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CP360_U8) return launch_render<uint8_t, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
-    switch (C) {
-        case 1: return launch_render<float, 1>(frames, R, out, N, H, W, h, w, tx, ty, s);
-        case 2: return launch_render<float, 2>(frames, R, out, N, H, W, h, w, tx, ty, s);
-        case 3: return launch_render<float, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
-        default: return launch_render<float, 4>(frames, R, out, N, H, W, h, w, tx, ty, s);
-    }
+    return dispatch_pixels(dtype, C, [&](auto px, auto c) {
+        return launch_render<decltype(px), decltype(c)::value>(frames, R, out, N, H, W, h, w, tx, ty, s);
+    });
 }
 
 extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, int H, int W, double hfov_rad, int h, int w,
@@ -281,17 +260,14 @@ extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, 
     if (bad_image(N, H, W) || bad_image(N, h, w) || bad_hfov(hfov_rad) || !(border_px > 0.0) || !isfinite(border_px))
         return CP360_ERR_BAD_SHAPE;
     if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
-    if (((uintptr_t)work & 15) != 0) return CP360_ERR_ALIGN;
-    const TabLayout l = tab_layout(H, W);
-    if (work_bytes < l.total) return CP360_ERR_BAD_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs tabs;
+    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
+    if (st != CP360_OK) return st;
     const double t = tan(0.5 * hfov_rad);
     const float tx = (float)t, ty = (float)(t * (double)h / (double)w), b = (float)(border_px * 2.0 * t / (double)w);
-    hipStream_t s = (hipStream_t)stream;
-    const int st = launch_tables(work, H, W, s);
-    if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R,
-                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, H, W, tx, ty, b,
-                       (int)rgb[0], (int)rgb[1], (int)rgb[2]);
+    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, tabs.x, tabs.y, out, H, W, tx,
+                       ty, b, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -303,12 +279,11 @@ extern "C" int cp360_view_smooth(const float* maps, int F, int hm, int wm, doubl
     int st = map_args(F, hm, wm, sigma_rad, work, work_bytes, &kappa);
     if (st != CP360_OK) return st;
     if (maps == out) return CP360_ERR_UNSUPPORTED;                     // every output reads every input
-    const TabLayout l = tab_layout(hm, wm);
     hipStream_t s = (hipStream_t)stream;
-    st = launch_tables(work, hm, wm, s);
+    SphereTabs t;
+    st = launch_tables(work, hm, wm, s, &t);
     if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(view_smooth_kernel, dim3((hm * wm + 255) / 256, F), dim3(256), 0, s, maps,
-                       (const float2*)((char*)work + l.tabx), (const float2*)((char*)work + l.taby), out, hm, wm, kappa);
+    hipLaunchKernelGGL(view_smooth_kernel, dim3((hm * wm + 255) / 256, F), dim3(256), 0, s, maps, t.x, t.y, out, hm, wm, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -319,12 +294,11 @@ extern "C" int cp360_view_peak(const float* smooth, const float* maps, int F, in
     float kappa = 0.f;
     int st = map_args(F, hm, wm, sigma_rad, work, work_bytes, &kappa);
     if (st != CP360_OK) return st;
-    const TabLayout l = tab_layout(hm, wm);
     hipStream_t s = (hipStream_t)stream;
-    st = launch_tables(work, hm, wm, s);
+    SphereTabs t;
+    st = launch_tables(work, hm, wm, s, &t);
     if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(view_peak_kernel, dim3(F), dim3(256), 0, s, smooth, maps, (const float2*)((char*)work + l.tabx),
-                       (const float2*)((char*)work + l.taby), dir_out, idx_out, val_out, hm, wm, kappa);
+    hipLaunchKernelGGL(view_peak_kernel, dim3(F), dim3(256), 0, s, smooth, maps, t.x, t.y, dir_out, idx_out, val_out, hm, wm, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
 }

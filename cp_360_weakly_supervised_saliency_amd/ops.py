@@ -179,6 +179,49 @@ def _shares_bytes(a, b):
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
+def _out_for(out, shape, dtype, device, src, same_ok=False):
+    """The destination of a kernel that reads `src`: a new tensor, or the caller's `out` when it has this shape and dtype on this
+    device and shares no byte with src (same_ok: or is src itself, for an element-wise kernel)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.shape != shape or out.device != device:                     # torch.Size is a tuple
+        raise ValueError("out must be another tensor of shape %s on the frames' device" % (tuple(shape),))
+    _check_buf('out', out, dtype)
+    if _shares_bytes(out, src) and not (same_ok and out.data_ptr() == src.data_ptr()):
+        raise ValueError("out must be frames themselves or share no memory with them (pixels are copied in no order across frames)"
+                         if same_ok else "out must not share memory with frames (a gather: not in place)")
+    return out
+
+
+def _frames_nhwc(frames, u8_only, n='N'):
+    """The frame checks of K11c, K12a, K12b and K13 -> (N, H, W, C): a non-empty contiguous [N, H, W, C], uint8 with 3 channels
+    or (unless u8_only) float32 with at most 4."""
+    if u8_only:
+        if frames.dim() != 4 or frames.numel() == 0 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
+            raise ValueError("frames must be a non-empty uint8 [%s, H, W, 3], got %s %s" % (n, frames.dtype, tuple(frames.shape)))
+    else:
+        if frames.dim() != 4 or frames.numel() == 0 or frames.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("frames must be a non-empty uint8 [N, H, W, 3] or float32 [N, H, W, C], got %s %s"
+                             % (frames.dtype, tuple(frames.shape)))
+        if frames.shape[3] > 4 or (frames.dtype == torch.uint8 and frames.shape[3] != 3):
+            raise ValueError("frames must have 3 channels (uint8) or at most 4 (float32), got %d" % frames.shape[3])
+    _check_buf('frames', frames, frames.dtype)
+    return tuple(int(s) for s in frames.shape)
+
+
+def _work(bytes_fn, what, F, h, w, device, work, limits=''):
+    """The workspace of one call of the library, bytes_fn(F, h, w) bytes: `work` when it is a contiguous float64 tensor on
+    `device` that holds as many, else a new one.  The callers hand the library work.numel() * 8 as the byte count, so a tensor
+    of another element size must not pass."""
+    nbytes = bytes_fn(int(F), int(h), int(w))
+    if nbytes == 0:
+        raise ValueError("%s: unsupported geometry: %d x %d x %d%s" % (what, F, h, w, limits))
+    if work is None or work.device != device or work.dtype != torch.float64 or not work.is_contiguous() \
+            or work.numel() * 8 < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
 # Optional launch timer (bench.py installs one): an object with
 # ``wrap(tag, flops, fn)`` that brackets the conv_forward launch with HIP events on the
 # current stream.  None = no instrumentation (default).
@@ -1394,12 +1437,7 @@ def optflow_flow_upsample(flow, h_out, w_out, mul):
 # ----------------------------------------------------------------------------- K11: 360-degree stabilisation (csrc/stabilize.hip)
 def _stab_work(F, H, W, device, work=None):
     """The workspace of one K11 call: `work` when it is large enough, else a new one (F = 0: the tables alone)."""
-    nbytes = lib().cp360_stab_work_bytes(int(F), int(H), int(W))
-    if nbytes == 0:
-        raise ValueError("stabilisation: unsupported geometry: %d x %d x %d" % (F, H, W))
-    if work is None or work.device != device or work.numel() * 8 < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return work
+    return _work(lib().cp360_stab_work_bytes, "stabilisation", F, H, W, device, work)
 
 
 def _stab_rotations(R, n=None):
@@ -1442,21 +1480,9 @@ def equirect_rotate(frames, R, out=None, work=None):
     """cp360_stab_rotate: out[n](x, y) = bilinear(frames[n], pix(R[n] dir(x, y))), columns wrap, rows clamp; frames u8
     [N, H, W, 3] or f32 [N, H, W, C], C <= 4; R f32 [N, 3, 3]; the output has the frames' type and size."""
     require_gpu(frames, R, out)
-    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3] or float32 [N, H, W, C], got %s %s"
-                         % (frames.dtype, tuple(frames.shape)))
-    N, H, W, C = (int(s) for s in frames.shape)
-    if C > 4 or (frames.dtype == torch.uint8 and C != 3):
-        raise ValueError("frames must have 3 channels (uint8) or at most 4 (float32), got %d" % C)
-    _check_buf('frames', frames, frames.dtype)
+    N, H, W, C = _frames_nhwc(frames, u8_only=False)
     _stab_rotations(R, N)
-    if out is None:
-        out = torch.empty_like(frames)
-    elif out.shape != frames.shape or out.device != frames.device:
-        raise ValueError("out must be another tensor of the frames' shape on their device")
-    _check_buf('out', out, frames.dtype)
-    if _shares_bytes(out, frames):
-        raise ValueError("out must not share memory with frames (a gather: not in place)")
+    out = _out_for(out, (N, H, W, C), frames.dtype, frames.device, frames)
     work = _stab_work(0, H, W, frames.device, work)
     check(lib().cp360_stab_rotate(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, ptr(out), ptr(work),
                                   work.numel() * 8, stream()))
@@ -1476,22 +1502,10 @@ def viewport_render(frames, R, hw, hfov_deg, out=None):
     (f32 [N, 3, 3], camera-to-world, columns forward / up / right; I looks at the panorama's centre): frames u8 [N, H, W, 3] or
     f32 [N, H, W, C], C <= 4 -> [N, h, w, C] of the frames' type.  Bilinear, columns wrap, rows clamp, no anti-aliasing."""
     require_gpu(frames, R, out)
-    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3] or float32 [N, H, W, C], got %s %s"
-                         % (frames.dtype, tuple(frames.shape)))
-    N, H, W, C = (int(s) for s in frames.shape)
-    if C > 4 or (frames.dtype == torch.uint8 and C != 3):
-        raise ValueError("frames must have 3 channels (uint8) or at most 4 (float32), got %d" % C)
-    _check_buf('frames', frames, frames.dtype)
+    N, H, W, C = _frames_nhwc(frames, u8_only=False)
     _stab_rotations(R, N)
     h, w, hfov = _view_geometry(hw, hfov_deg)
-    if out is None:
-        out = torch.empty((N, h, w, C), dtype=frames.dtype, device=frames.device)
-    elif tuple(out.shape) != (N, h, w, C) or out.device != frames.device:
-        raise ValueError("out must be another tensor of shape %s on the frames' device" % ((N, h, w, C),))
-    _check_buf('out', out, frames.dtype)
-    if _shares_bytes(out, frames):
-        raise ValueError("out must not share memory with frames (a gather: not in place)")
+    out = _out_for(out, (N, h, w, C), frames.dtype, frames.device, frames)
     check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
     return out
 
@@ -1500,22 +1514,13 @@ def viewport_outline(frames, R, hw, hfov_deg, border_px=3, rgb=(0, 255, 0), out=
     """cp360_view_outline: the frame of the view (hw, hfov_deg) of camera R[n], border_px view pixels wide, drawn in rgb on the
     panorama: frames u8 [N, H, W, 3] -> u8 [N, H, W, 3]; out may be frames (every other pixel is copied)."""
     require_gpu(frames, R, out)
-    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
-        raise ValueError("frames must be a non-empty uint8 [N, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
-    N, H, W = (int(s) for s in frames.shape[:3])
-    _check_buf('frames', frames, torch.uint8)
+    N, H, W, _ = _frames_nhwc(frames, u8_only=True)
     _stab_rotations(R, N)
     h, w, hfov = _view_geometry(hw, hfov_deg)
     rgb = tuple(int(v) for v in rgb)
     if not float(border_px) > 0.0 or len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
         raise ValueError("border_px must be positive and rgb three values of 0 .. 255, got %r, %r" % (border_px, rgb))
-    if out is None:
-        out = torch.empty_like(frames)
-    elif out.shape != frames.shape or out.device != frames.device:
-        raise ValueError("out must have the frames' shape on their device")
-    _check_buf('out', out, torch.uint8)
-    if out.data_ptr() != frames.data_ptr() and _shares_bytes(out, frames):
-        raise ValueError("out must be frames themselves or share no memory with them (pixels are copied in no order across frames)")
+    out = _out_for(out, (N, H, W, 3), torch.uint8, frames.device, frames, same_ok=True)
     work = _stab_work(0, H, W, frames.device, work)
     colour = (C.c_ubyte * 3)(*rgb)
     check(lib().cp360_view_outline(ptr(frames), ptr(R), N, H, W, hfov, h, w, float(border_px), C.cast(colour, C.c_void_p),
@@ -1592,12 +1597,7 @@ def shot_weights(H, device):
 
 def _shot_work(F, H, W, device, work=None):
     """The workspace of one cp360_shot_signatures call: `work` when it is large enough, else a new one."""
-    nbytes = lib().cp360_shot_work_bytes(int(F), int(H), int(W))
-    if nbytes == 0:
-        raise ValueError("shot signatures: unsupported geometry: %d x %d x %d" % (F, H, W))
-    if work is None or work.device != device or work.numel() * 8 < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return work
+    return _work(lib().cp360_shot_work_bytes, "shot signatures", F, H, W, device, work)
 
 
 def shot_signatures(frames, work=None, weights=None):
@@ -1605,10 +1605,7 @@ def shot_signatures(frames, work=None, weights=None):
     device: sig[f, c, b] = the sum of the row weights a_y over the pixels with frames[f, y, x, c] >> 2 == b.  Exact integers:
     bit-identical between runs and batch sizes."""
     require_gpu(frames, work, weights)
-    if frames.dim() != 4 or frames.numel() == 0 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
-        raise ValueError("frames must be a non-empty uint8 [F, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
-    _check_buf('frames', frames, torch.uint8)
-    F, H, W = (int(s) for s in frames.shape[:3])
+    F, H, W, _ = _frames_nhwc(frames, u8_only=True, n='F')
     if weights is None:
         weights = shot_weights(H, frames.device)
     elif tuple(weights.shape) != (H,) or weights.device != frames.device:
@@ -1654,12 +1651,7 @@ def _eval_maps(name, t):
 
 def sphere_eval_work(F, h, w, device, work=None):
     """The workspace of one cp360_seval_scores call: `work` when it is large enough, else a new one."""
-    nbytes = lib().cp360_seval_work_bytes(int(F), int(h), int(w))
-    if nbytes == 0:
-        raise ValueError("sphere_eval: unsupported geometry: %d x %d x %d (F <= 65535, h w <= 2^21)" % (F, h, w))
-    if work is None or work.device != device or work.dtype != torch.float64 or work.numel() * 8 < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return work
+    return _work(lib().cp360_seval_work_bytes, "sphere_eval", F, h, w, device, work, " (F <= 65535, h w <= 2^21)")
 
 
 def sphere_eval_resample(maps, hw, out=None):
@@ -1721,12 +1713,7 @@ def _fix_points(lonlat, offsets, hw):
 
 def fixation_work(F, h, w, device, work=None):
     """The workspace of cp360_fix_sauc for F frames (F = 0: of cp360_fix_density): `work` when it is large enough, else a new one."""
-    nbytes = lib().cp360_fix_work_bytes(int(F), int(h), int(w))
-    if nbytes == 0:
-        raise ValueError("fixations: unsupported geometry: %d x %d x %d (F <= 65535, h w <= 2^21)" % (F, h, w))
-    if work is None or work.device != device or work.dtype != torch.float64 or work.numel() * 8 < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return work
+    return _work(lib().cp360_fix_work_bytes, "fixations", F, h, w, device, work, " (F <= 65535, h w <= 2^21)")
 
 
 def fixation_counts(lonlat, offsets, hw):

@@ -19,6 +19,7 @@ import torch
 
 from .. import ops
 from . import npy_io
+from ._device import host_tensor
 
 METRICS = ('auc_judd', 'nss', 'cc', 'sim', 'kl')       # the columns of ops.sphere_eval's scores
 
@@ -57,8 +58,7 @@ class SphereEval:
         return self._weights
 
     def _maps(self, name, maps):
-        if not torch.is_tensor(maps):
-            maps = torch.from_numpy(np.ascontiguousarray(maps, dtype=np.float32))
+        maps = host_tensor(maps, np.float32)
         if maps.dim() != 3 or maps.shape[0] < 1 or not maps.dtype.is_floating_point:
             raise ValueError("%s must be floating-point [F, h, w] with F >= 1, got %s %s" % (name, maps.dtype, tuple(maps.shape)))
         return maps.detach().to(self.device, torch.float32).contiguous()
@@ -74,8 +74,7 @@ class SphereEval:
         if S.shape[0] != G.shape[0]:
             raise ValueError("sal and gt must have as many frames, got %d and %d" % (S.shape[0], G.shape[0]))
         if fixations is not None:
-            if not torch.is_tensor(fixations):
-                fixations = torch.from_numpy(np.ascontiguousarray(fixations))
+            fixations = host_tensor(fixations)
             if fixations.dtype not in (torch.uint8, torch.bool):
                 fixations = fixations != 0
             fixations = fixations.to(self.device).contiguous()

@@ -20,6 +20,7 @@ import torch
 
 from .. import ops
 from . import npy_io
+from ._device import host_tensor, on_device
 
 
 def _unit(lon, lat):
@@ -88,9 +89,7 @@ class FixationMaps:
     def _points(self, lonlat, offsets):
         if not torch.is_tensor(lonlat):
             lonlat = torch.from_numpy(np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2))
-        if not torch.is_tensor(offsets):
-            offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32))
-        return lonlat.to(self.device, torch.float64).contiguous(), offsets.to(self.device, torch.int32).contiguous()
+        return on_device(lonlat, self.device, torch.float64), on_device(offsets, self.device, torch.int32)
 
     def _workspace(self, F, device):
         """The workspace for F frames on `device` (a tensor's, with its index); kept while it is large enough."""
@@ -127,13 +126,11 @@ class FixationMaps:
         """sal [F, ., .] (numpy or tensor, any size: resampled to the grid as ``SphereEval`` does), counts int32 [F, h, w] ->
         (auc float64 [F], c_tot int64 [F], a_neg int64 [F]) on the device.  negatives: 'other_frames' (frame f draws its negatives
         from the fixations of every other frame of the video) or an [h, w] count map for every frame."""
-        if not torch.is_tensor(sal):
-            sal = torch.from_numpy(np.ascontiguousarray(sal, dtype=np.float32))
+        sal = host_tensor(sal, np.float32)
         if sal.dim() != 3 or sal.shape[0] < 1 or not sal.dtype.is_floating_point:
             raise ValueError("sal must be floating-point [F, h, w] with F >= 1, got %s %s" % (sal.dtype, tuple(sal.shape)))
         S = ops.sphere_eval_resample(sal.detach().to(self.device, torch.float32).contiguous(), self.grid_hw)
-        if not torch.is_tensor(counts):
-            counts = torch.from_numpy(np.ascontiguousarray(counts))
+        counts = host_tensor(counts)
         F, (h, w) = int(S.shape[0]), self.grid_hw
         if tuple(counts.shape) != (F, h, w) or counts.dtype.is_floating_point:
             raise ValueError("counts must be integers [%d, %d, %d], got %s %s" % (F, h, w, counts.dtype, tuple(counts.shape)))
@@ -143,8 +140,7 @@ class FixationMaps:
                 raise ValueError("negatives must be 'other_frames' or an [h, w] count map, got %r" % (negatives,))
             neg = (pos.sum(dim=0, keepdim=True, dtype=torch.int64) - pos).clamp(max=1 << 20).to(torch.int32)
         else:
-            if not torch.is_tensor(negatives):
-                negatives = torch.from_numpy(np.ascontiguousarray(negatives))
+            negatives = host_tensor(negatives)
             if tuple(negatives.shape) != (h, w) or negatives.dtype.is_floating_point:
                 raise ValueError("negatives must be integers [%d, %d], got %s %s" % (h, w, negatives.dtype, tuple(negatives.shape)))
             neg = negatives.to(self.device, torch.int32).reshape(1, h, w).contiguous()

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ._device import host_tensor
 from .._lib import check, lib, ptr, require_gpu, stream
 from .resize import LanczosResize
 
@@ -68,8 +69,7 @@ class FarnebackFlow:
     def gray_from_frames(self, frames, res=None):
         """frames u8 [N, h, w, 3] as the video reader delivers them (host or device) -> gray f32 [N, H, W] on the device:
         the preamble of ``calcOpticalFlow`` (resize to ``res`` = (width, height), reversed channels, BGR2GRAY arithmetic)."""
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = host_tensor(frames)
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError("frames must be uint8 [N, h, w, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
         res = (self.hw[1], self.hw[0]) if res is None else (int(res[0]), int(res[1]))

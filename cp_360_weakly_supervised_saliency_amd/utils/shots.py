@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ._device import host_tensor
 
 
 def check_cuts(cuts, n):
@@ -72,8 +73,7 @@ class ShotDetector:
         self._geom = {}                          # (H, W) -> [weights (device), T, workspace]
 
     def _frames(self, frames):
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = host_tensor(frames)
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
             raise ValueError("frames must be uint8 [F, H, W, 3] with F >= 1, got %s %s" % (frames.dtype, tuple(frames.shape)))
         return frames.to(self.device).contiguous()

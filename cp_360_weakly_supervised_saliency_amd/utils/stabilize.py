@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ._device import TabWork, host_tensor, on_device
 from .optical_flow import FarnebackFlow
 from .shots import check_cuts, segments
 
@@ -56,12 +57,11 @@ class Stabilizer:
         self.iters, self.c_min_px = int(iters), float(c_min_px)
         self.flow = FarnebackFlow(self.hw, device=device)
         self._fit_work = None
-        self._tab_work = {}
+        self._tab_work = TabWork()
         self.diag = None                         # f64 [F, 4] of the last fit (device)
 
     def _frames(self, frames):
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = host_tensor(frames)
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 2:
             raise ValueError("frames must be uint8 [F + 1, h, w, 3] with F >= 1, got %s %s" % (frames.dtype, tuple(frames.shape)))
         return frames.to(self.device).contiguous()
@@ -99,13 +99,8 @@ class Stabilizer:
     def render(self, frames, C, out=None):
         """frames u8 [N, h, w, 3] under the rotations C f32 [N, 3, 3] (for instance ``rotations``' C after a smoothing of the
         caller's): out[n](p) = frames[n](C[n] p), at the frames' own resolution, on the device."""
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        frames = frames.to(self.device).contiguous()
-        C = torch.as_tensor(C, dtype=torch.float32).to(self.device).contiguous()
-        h, w = int(frames.shape[1]), int(frames.shape[2])
-        work = self._tab_work[(h, w)] = ops._stab_work(0, h, w, frames.device, self._tab_work.get((h, w)))
-        return ops.equirect_rotate(frames, C, out=out, work=work)
+        frames, C = on_device(frames, self.device), on_device(C, self.device, torch.float32)
+        return ops.equirect_rotate(frames, C, out=out, work=self._tab_work(frames))
 
     def from_frames(self, frames):
         """frames u8 [F + 1, h, w, 3] -> the flows f32 [F, H, W, 2] of the stabilised video, on the device.  It takes no ``cuts``:

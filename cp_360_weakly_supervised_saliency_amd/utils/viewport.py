@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ._device import TabWork, on_device
 from .shots import check_cuts, segments
 
 _Y = np.array([0.0, 1.0, 0.0])
@@ -106,26 +107,12 @@ class ViewportPilot:
         self.hfov_deg, self.sigma_deg, self.alpha = float(hfov_deg), float(sigma_deg), float(alpha)
         self.max_step_deg = None if max_step_deg is None else float(max_step_deg)
         self.device = torch.device(device)
-        self._work = {}
-
-    def _tab_work(self, h, w):
-        work = self._work[(h, w)] = ops._stab_work(0, h, w, self.device, self._work.get((h, w)))
-        return work
-
-    def _maps(self, maps):
-        if not torch.is_tensor(maps):
-            maps = torch.from_numpy(np.ascontiguousarray(maps))
-        return maps.to(self.device, torch.float32).contiguous()
-
-    def _frames(self, frames):
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        return frames.to(self.device).contiguous()
+        self._tab_work = TabWork()
 
     def peaks(self, maps):
         """maps f32 [F, hm, wm] -> the direction of every map's peak, f32 [F, 3] on the device."""
-        maps = self._maps(maps)
-        return ops.sphere_peak(maps, self.sigma_deg, work=self._tab_work(int(maps.shape[1]), int(maps.shape[2])))[0]
+        maps = on_device(maps, self.device, torch.float32)
+        return ops.sphere_peak(maps, self.sigma_deg, work=self._tab_work(maps))[0]
 
     def path(self, maps, cuts=None):
         """maps f32 [F, hm, wm] -> the cameras R f32 [F, 3, 3] on the device: the peaks, copied to the host (3 F floats, the one
@@ -137,21 +124,19 @@ class ViewportPilot:
 
     def render(self, frames, R, out=None):
         """frames u8 [N, H, W, 3] or f32 [N, H, W, C] under the cameras R [N, 3, 3] -> the views [N, h, w, C] on the device."""
-        R = torch.as_tensor(R, dtype=torch.float32).to(self.device).contiguous()
-        return ops.viewport_render(self._frames(frames), R, self.hw, self.hfov_deg, out=out)
+        R = on_device(R, self.device, torch.float32)
+        return ops.viewport_render(on_device(frames, self.device), R, self.hw, self.hfov_deg, out=out)
 
     def outline(self, frames, R, border_px=3, rgb=(0, 255, 0), out=None):
         """frames u8 [N, H, W, 3] -> the panoramas with every view's frame drawn in rgb, on the device."""
-        frames = self._frames(frames)
-        R = torch.as_tensor(R, dtype=torch.float32).to(self.device).contiguous()
-        work = self._tab_work(int(frames.shape[1]), int(frames.shape[2]))
-        return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=work)
+        frames, R = on_device(frames, self.device), on_device(R, self.device, torch.float32)
+        return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=self._tab_work(frames))
 
     def follow(self, frames, maps, cuts=None):
         """frames u8 [F, H, W, 3], maps f32 [F, hm, wm] (one per frame, e.g. ``SaliencyEngine(.., return_all_steps=True)``'s
         output) -> (views u8 [F, h, w, 3], R f32 [F, 3, 3]) on the device; the frames keep their own resolution.  ``cuts``: as
         in ``path``."""
-        frames = self._frames(frames)
+        frames = on_device(frames, self.device)
         if frames.dim() != 4 or len(maps) != frames.shape[0]:
             raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
         R = self.path(maps, cuts)

@@ -193,6 +193,32 @@ def test_status_codes_without_gpu():
     assert rot(_lib.F32, one, one, 1, 16, 32, 3, two, one, 8 * 48 - 1) == -1         # workspace too small
 
 
+@pytest.mark.parametrize('name, size', [('_stab_work', 'cp360_stab_work_bytes'), ('_shot_work', 'cp360_shot_work_bytes'),
+                                        ('sphere_eval_work', 'cp360_seval_work_bytes'), ('fixation_work', 'cp360_fix_work_bytes')])
+def test_a_workspace_is_kept_only_when_it_owns_the_bytes_the_library_is_told(name, size):
+    """The ops hand the library work.numel() * 8 as the workspace's byte count.  So, of a caller's tensors, only a float64 one of
+    at least the needed bytes is used as it is; one 8 bytes short, and a float32 or a uint8 one of the same numel() (which own a
+    half and an eighth of the bytes that count claims), are replaced by a float64 tensor that is large enough.  The sizes come
+    from the host functions cp360_*_work_bytes: no GPU."""
+    import torch
+    from cp_360_weakly_supervised_saliency_amd import ops
+    get, cpu = getattr(ops, name), torch.device('cpu')
+    F, h, w = 1, 16, 32
+    need = getattr(_lib.lib(), size)(F, h, w)
+    assert need > 0 and need % 8 == 0
+    fresh = get(F, h, w, cpu)
+    assert fresh.dtype == torch.float64 and fresh.device == cpu and fresh.numel() * 8 == need
+    exact = torch.empty(need // 8, dtype=torch.float64)
+    assert get(F, h, w, cpu, exact) is exact
+    for bad in (torch.empty(need // 8 - 1, dtype=torch.float64), torch.empty(need // 8, dtype=torch.float32),
+                torch.empty(need // 8, dtype=torch.uint8)):
+        got = get(F, h, w, cpu, bad)
+        assert got is not bad and got.dtype == torch.float64 and got.device == cpu and got.is_contiguous()
+        assert got.numel() * got.element_size() >= need
+    with pytest.raises(ValueError, match='unsupported geometry'):
+        get(70000, h, w, cpu)
+
+
 def test_ops_refuse_bad_arguments_without_gpu():
     import torch
     from cp_360_weakly_supervised_saliency_amd import ops

@@ -377,6 +377,17 @@ def test_a_dirty_workspace_larger_than_needed():
     print('fit, flow, rotate, flow, fit on one dirty workspace of %d bytes: bit-equal to the calls with their own' % (work.numel() * 8))
 
 
+def test_a_float32_workspace_is_not_taken_for_float64():
+    """16 x 32, F = 2: a float32 tensor with the numel() of the float64 workspace owns half the bytes that the ops would claim
+    for it (numel() * 8).  It is replaced, not used: every result is exactly the call's with work=None."""
+    R = dev(k11.rotations_for(2).astype(np.float32))
+    frames = dev(k11.u8_frames((16, 32), 2))
+    half = lambda get, F: torch.empty(get(F, 16, 32, R.device).numel(), dtype=torch.float32, device=R.device)
+    assert torch.equal(ops.rotation_flow(R, 16, 32, work=half(ops._stab_work, 0)), ops.rotation_flow(R, 16, 32))
+    assert torch.equal(ops.equirect_rotate(frames, R, work=half(ops._stab_work, 0)), ops.equirect_rotate(frames, R))
+    assert torch.equal(ops.shot_signatures(frames, work=half(ops._shot_work, 2)), ops.shot_signatures(frames))
+
+
 # ============================================================================= K12: the viewport pilot
 @pytest.mark.parametrize('hfov', [60.0, 120.0])
 @pytest.mark.parametrize('HW,hw', [((16, 32), (9, 16)), ((33, 66), (5, 300))])
