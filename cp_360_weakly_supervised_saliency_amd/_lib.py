@@ -69,6 +69,8 @@ PUBLIC_SYMBOLS = [
     'cp360_seval_work_bytes', 'cp360_seval_resample', 'cp360_seval_scores',
     # K15: fixations from scan-paths, shuffled AUC on the sphere
     'cp360_fix_work_bytes', 'cp360_fix_counts', 'cp360_fix_density', 'cp360_fix_sauc',
+    # K16: the camera path by dynamic programming
+    'cp360_path_table_bytes', 'cp360_path_table_host', 'cp360_path_work_bytes', 'cp360_view_path', 'cp360_view_refine',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -287,8 +289,15 @@ def lib():
     L.cp360_fix_counts.argtypes = [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]
     L.cp360_fix_density.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, vp, vp, sz, vp]
     L.cp360_fix_sauc.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]
+    L.cp360_path_table_bytes.restype = sz
+    L.cp360_path_table_bytes.argtypes = [i, i]
+    L.cp360_path_table_host.argtypes = [i, i, dbl, dbl, vp]
+    L.cp360_path_work_bytes.restype = sz
+    L.cp360_path_work_bytes.argtypes = [i, i, i]
+    L.cp360_view_path.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, sz, vp]
+    L.cp360_view_refine.argtypes = [vp, vp, i, i, i, dbl, vp, vp, sz, vp]
     for name in SYMBOLS:
-        getattr(L, name)         # AttributeError here = header and library disagree
+        getattr(L, name)        # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):
         raise ImportError("%s is a stale build: version %d / cp360_conv_desc %d bytes, the binding expects %d / %d "
                           "- rebuild it (__graft_entry__.build())"

@@ -1,8 +1,10 @@
 // K12: the viewport pilot - a saliency map turned into a camera: the perspective (gnomonic) view of an equirectangular frame
 // under a camera rotation (K12a), the view's frame drawn on the panorama (K12b), the saliency map smoothed on the sphere (K12c)
-// and its peak with one mean-shift step (K12d).  The reference's utils/fov_visual.py (box_proh, fov_module, draw_cube_fov_box)
-// has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12", and
-// tests/viewport_restate.py restates it in float64.  Geometry, tables and the bilinear sample are sphere.h's.
+// and its peak with one mean-shift step (K12d); and the camera path that collects the most saliency under a turn limit and a turn
+// cost, by dynamic programming over the map's pixels (K16a - K16c).  The reference's utils/fov_visual.py (box_proh, fov_module,
+// draw_cube_fov_box) has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12" and "K16";
+// tests/viewport_restate.py restates K12 in float64, tests/campath_restate.py K16 in integers.  Geometry, tables and the
+// bilinear sample are sphere.h's.
 //
 // Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
 // centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
@@ -12,11 +14,17 @@
 //         border <=> d_f > 0, |u| <= tx, |v| <= ty and not (|u| <= tx - b and |v| <= ty - b)
 //   K12c  out_i = sum_j a_j s_j e_ij / sum_j a_j e_ij, e_ij = expf(kappa (p_i . p_j - 1)), kappa = 1 / sigma^2, a_j = cos phi_j
 //   K12d  idx = argmax of the smoothed map (lowest index on ties), p* = dir(idx), c = sum_j a_j s_j e(p*, p_j) p_j, dir = c / |c|
-// Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d are f64 in a fixed order.  No
-// atomics, no host synchronisation, results independent of the batch size.
+//   K16a  q[t][j] = (int)rintf(min(max(s[t][j] g[t], 0), 4096)), 0 where the product is not finite; acc[lo] = q[lo],
+//         acc[t][j] = q[t][j] + max_i (acc[t-1][i] - cost(i, j)) over the allowed i, back[t][j] = that i (lowest on ties)
+//   K16b  idx[hi-1] = argmax acc[hi-1] (lowest on ties), idx[t-1] = back[t][idx[t]], dir = dir(idx), score = acc[hi-1][idx[hi-1]]
+//   K16c  K12d's mean-shift step about p* = dir(idx[t]) for given indices
+// Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d / K16c are f64 in a fixed order;
+// K16a / K16b are integers.  No atomics, no host synchronisation, results independent of the batch size.
 #pragma clang fp contract(off)
 
 #include "sphere.h"
+
+#include <atomic>
 
 namespace {
 
@@ -30,7 +38,8 @@ __device__ __forceinline__ bool rot_finite(const Rot& R) {
 
 // K12d's argmax, one step of its tree (the tree of sphere.h's ordered sum): the candidate (ov, oi) replaces (best, bi) when it
 // has the larger value, or the same value at a lower index; an index below 0 is no candidate
-__device__ __forceinline__ void peak_take(float ov, int oi, float& best, int& bi) {
+template <typename V>
+__device__ __forceinline__ void peak_take(V ov, int oi, V& best, int& bi) {
     if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
         best = ov;
         bi = oi;
@@ -124,6 +133,52 @@ __global__ __launch_bounds__(256) void view_smooth_kernel(const float* __restric
     if (i < P) out[(size_t)blockIdx.y * P + i] = (float)(num / den);
 }
 
+// K12d's mean-shift step, which K16c repeats for given indices: c = sum_j a_j s_j e(p*, p_j) p_j about p* = dir(bi) on the raw map
+// s, dir = c / |c| (p* when |c| is 0 or not finite), written by thread 0.  256 threads, all of which call it; thread t takes
+// pixels t, t + 256, .. in order, then sphere.h's ordered sum.  red_c is the caller's LDS.
+__device__ __forceinline__ void mean_shift_step(const float* __restrict__ s, const float2* __restrict__ tabx,
+                                                const float2* __restrict__ taby, int hm, int wm, float kappa, int bi,
+                                                double (*red_c)[3], float* __restrict__ dir) {
+    const int P = hm * wm, tid = threadIdx.x;
+    float cx, cy, cz;
+    {
+        const int y = bi / wm, x = bi - y * wm;
+        stab_dir(tabx[x], taby[y], cx, cy, cz);
+    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int j = tid; j < P; j += 256) {
+        const int y = j / wm, x = j - y * wm;
+        const float2 csp = taby[y];
+        float qx, qy, qz;
+        stab_dir(tabx[x], csp, qx, qy, qz);
+        const float sj = s[j];
+        const float e = vmf(kappa, cx, cy, cz, qx, qy, qz);
+        const float wgt = (csp.x * (isfinite(sj) ? sj : 0.f)) * e;
+        acc[0] += (double)(wgt * qx);
+        acc[1] += (double)(wgt * qy);
+        acc[2] += (double)(wgt * qz);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = wave_sum_down(acc[k]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) red_c[tid >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double sx = waves4_sum(&red_c[0][0], 3), sy = waves4_sum(&red_c[0][1], 3), sz = waves4_sum(&red_c[0][2], 3);
+    const double n = sqrt(sx * sx + sy * sy + sz * sz);
+    float ox = cx, oy = cy, oz = cz;
+    if (n > 0.0 && isfinite(n)) {
+        ox = (float)(sx / n);
+        oy = (float)(sy / n);
+        oz = (float)(sz / n);
+    }
+    dir[0] = ox;
+    dir[1] = oy;
+    dir[2] = oz;
+}
+
 // ------------------------------------------------------------------ K12d: the peak and one mean-shift step
 // grid F, 256 threads: thread t takes pixels t, t + 256, .. in order, then the shuffle tree, then the 4 waves in order
 __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict__ smooth, const float* __restrict__ maps,
@@ -172,45 +227,157 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
         }
         return;
     }
-    float cx, cy, cz;
-    {
-        const int y = bi / wm, x = bi - y * wm;
-        stab_dir(tabx[x], taby[y], cx, cy, cz);
+    mean_shift_step(s, tabx, taby, hm, wm, kappa, bi, red_c, dir_out + (size_t)f * 3);
+    if (tid == 0) {
+        idx_out[f] = bi;
+        val_out[f] = best;
     }
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int j = tid; j < P; j += 256) {
-        const int y = j / wm, x = j - y * wm;
-        const float2 csp = taby[y];
-        float qx, qy, qz;
-        stab_dir(tabx[x], csp, qx, qy, qz);
-        const float sj = s[j];
-        const float e = vmf(kappa, cx, cy, cz, qx, qy, qz);
-        const float wgt = (csp.x * (isfinite(sj) ? sj : 0.f)) * e;
-        acc[0] += (double)(wgt * qx);
-        acc[1] += (double)(wgt * qy);
-        acc[2] += (double)(wgt * qz);
+}
+
+// ------------------------------------------------------------------ K16: the camera path by dynamic programming
+// The table (cp360_path_table_host): cost int32 [hm][hm][wm / 2 + 1] by (row of i, row of j, column difference folded to
+// 0 .. wm / 2), -1 = forbidden; behind it span int32 [hm][hm], the largest allowed column difference of the row pair, -1 = none.
+constexpr int kPathVoteMax = 4096;
+constexpr int kPathThreads = 1024;
+constexpr int kPathNone = -(1 << 30);        // below every acc - cost: acc >= 0, cost <= 4096 * 180
+
+__device__ __forceinline__ int path_vote(float s, float g) {
+    const float p = s * g;
+    return isfinite(p) ? (int)rintf(fminf(fmaxf(p, 0.f), (float)kPathVoteMax)) : 0;
+}
+
+__device__ __forceinline__ int path_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// K16a.  grid S, blockDim.x <= 1024 threads and 2 P ints of dynamic LDS: one workgroup walks one sequence, thread k owns the
+// states k, k + blockDim.x, ..; the previous and the current frame's scores alternate between the two halves of the LDS, one
+// barrier per frame, which every thread reaches: lo and hi are the workgroup's, and no thread leaves early.  A predecessor
+// replaces the best so far when acc - cost is larger, or equal at a lower index: the order of the visit does not matter.  The
+// table's contents decide no address beyond their own range: spans are clamped to wm / 2, a cost below 0 is skipped, and a state
+// that finds no predecessor keeps itself.  The tail is K16b's argmax of the last frame: idx[hi - 1] and score[s].
+__global__ __launch_bounds__(kPathThreads) void path_dp_kernel(const float* __restrict__ smooth, const float* __restrict__ gain,
+                                                               const int* __restrict__ table, const int* __restrict__ starts,
+                                                               uint16_t* __restrict__ back, int* __restrict__ idx_out,
+                                                               int* __restrict__ score_out, int F, int hm, int wm) {
+    extern __shared__ int path_acc[];                                   // [2][P]
+    __shared__ int red_v[kPathThreads / 64];
+    __shared__ int red_i[kPathThreads / 64];
+    const int P = hm * wm, tid = threadIdx.x, nt = blockDim.x, half = wm / 2 + 1;
+    const int* span = table + (size_t)hm * hm * half;
+    const int lo = path_clamp(starts[blockIdx.x], 0, F), hi = path_clamp(starts[blockIdx.x + 1], 0, F);
+    int* prev = path_acc;
+    int* cur = path_acc + P;
+    for (int t = lo; t < hi; ++t) {
+        const float* s = smooth + (size_t)t * P;
+        uint16_t* bk = back + (size_t)t * P;
+        const float g = gain[t];
+        for (int j = tid; j < P; j += nt) {
+            const int q = path_vote(s[j], g);
+            const int rj = j / wm, cj = j - rj * wm;
+            int best = kPathNone, bi = j;
+            if (t == lo) best = 0;
+            else {
+                // the allowed rows are one interval about rj (the angle grows with the rows' distance): find its first row
+                int r0 = rj;
+                while (r0 > 0 && span[(r0 - 1) * hm + rj] >= 0) --r0;
+                int Dn = span[r0 * hm + rj];
+                for (int ri = r0; ri < hm; ++ri) {
+                    int D = Dn;
+                    Dn = ri + 1 < hm ? span[(ri + 1) * hm + rj] : -1;    // the next row's, in flight behind this row's columns
+                    if (D < 0) {
+                        if (ri > rj) break;
+                        continue;
+                    }
+                    D = D > wm / 2 ? wm / 2 : D;
+                    const bool all = 2 * D + 1 >= wm;                   // every column once: the pole rows
+                    const int n = all ? wm : 2 * D + 1;
+                    int c = all ? 0 : (cj - D < 0 ? cj - D + wm : cj - D);
+                    const int* cost = table + ((size_t)ri * hm + rj) * half;
+                    const int* row = prev + ri * wm;
+#pragma unroll 4
+                    for (int k = 0; k < n; ++k) {
+                        int d = c > cj ? c - cj : cj - c;
+                        d = d > wm - d ? wm - d : d;
+                        const int cst = cost[d], i = ri * wm + c;
+                        const int v = row[c] - cst;
+                        if (cst >= 0 && (v > best || (v == best && i < bi))) {
+                            best = v;
+                            bi = i;
+                        }
+                        c = c + 1 == wm ? 0 : c + 1;
+                    }
+                }
+                if (best == kPathNone) best = 0;                        // a table without the state itself: keep it
+            }
+            cur[j] = q + best;
+            bk[j] = (uint16_t)bi;
+        }
+        __syncthreads();
+        int* const swap = prev;
+        prev = cur;
+        cur = swap;
+    }
+    if (lo >= hi) return;                                               // the whole workgroup: lo and hi are uniform
+    // prev holds the last frame's scores: their argmax, lowest index on ties
+    int best = 0, bi = -1;
+    for (int j = tid; j < P; j += nt) {
+        const int v = prev[j];
+        if (bi < 0 || v > best) {
+            best = v;
+            bi = j;
+        }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = wave_sum_down(acc[k]);
+    for (int off = 32; off >= 1; off >>= 1) peak_take(__shfl_down(best, off, 64), __shfl_down(bi, off, 64), best, bi);
     if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) red_c[tid >> 6][k] = acc[k];
+        red_v[tid >> 6] = best;
+        red_i[tid >> 6] = bi;
     }
     __syncthreads();
     if (tid != 0) return;
-    const double sx = waves4_sum(&red_c[0][0], 3), sy = waves4_sum(&red_c[0][1], 3), sz = waves4_sum(&red_c[0][2], 3);
-    const double n = sqrt(sx * sx + sy * sy + sz * sz);
-    float ox = cx, oy = cy, oz = cz;
-    if (n > 0.0 && isfinite(n)) {
-        ox = (float)(sx / n);
-        oy = (float)(sy / n);
-        oz = (float)(sz / n);
+    for (int k = 1; k < nt / 64; ++k) peak_take(red_v[k], red_i[k], best, bi);
+    idx_out[hi - 1] = bi;
+    score_out[blockIdx.x] = best;
+}
+
+// K16b.  One thread per sequence, behind K16a on the stream: from idx[hi - 1] back along the back-pointers, hi - lo dependent
+// loads; dir = the pixel centre.
+__global__ __launch_bounds__(64) void path_trace_kernel(const uint16_t* __restrict__ back, const int* __restrict__ starts,
+                                                        const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                        int* __restrict__ idx_out, float* __restrict__ dir_out, int S, int F,
+                                                        int hm, int wm) {
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= S) return;
+    const int P = hm * wm;
+    const int lo = path_clamp(starts[q], 0, F), hi = path_clamp(starts[q + 1], 0, F);
+    if (lo >= hi) return;
+    int i = path_clamp(idx_out[hi - 1], 0, P - 1);
+    for (int t = hi - 1; t >= lo; --t) {
+        const int y = i / wm, x = i - y * wm;
+        float px, py, pz;
+        stab_dir(tabx[x], taby[y], px, py, pz);
+        idx_out[t] = i;
+        dir_out[(size_t)t * 3] = px;
+        dir_out[(size_t)t * 3 + 1] = py;
+        dir_out[(size_t)t * 3 + 2] = pz;
+        i = path_clamp((int)back[(size_t)t * P + i], 0, P - 1);
     }
-    dir_out[(size_t)f * 3] = ox;
-    dir_out[(size_t)f * 3 + 1] = oy;
-    dir_out[(size_t)f * 3 + 2] = oz;
-    idx_out[f] = bi;
-    val_out[f] = best;
+}
+
+// K16c.  grid F, 256 threads: K12d's step about dir(idx[f]); an index outside the map looks ahead
+__global__ __launch_bounds__(256) void view_refine_kernel(const float* __restrict__ maps, const int* __restrict__ idx,
+                                                          const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                          float* __restrict__ dir_out, int hm, int wm, float kappa) {
+    __shared__ double red_c[4][3];
+    const int P = hm * wm, f = blockIdx.x, bi = idx[f];
+    if (bi < 0 || bi >= P) {
+        if (threadIdx.x == 0) {
+            dir_out[(size_t)f * 3] = 1.f;
+            dir_out[(size_t)f * 3 + 1] = 0.f;
+            dir_out[(size_t)f * 3 + 2] = 0.f;
+        }
+        return;
+    }
+    mean_shift_step(maps + (size_t)f * P, tabx, taby, hm, wm, kappa, bi, red_c, dir_out + (size_t)f * 3);
 }
 
 // ------------------------------------------------------------------ host side
@@ -234,6 +401,41 @@ int map_args(int F, int hm, int wm, double sigma_rad, const void* work, size_t w
     if ((long long)hm * wm > kMaxMapPx || F > 65535) return CP360_ERR_UNSUPPORTED;
     *kappa = (float)(1.0 / (sigma_rad * sigma_rad));
     return check_work(work, work_bytes, tab_bytes(hm, wm));
+}
+
+// K16: the shapes of a table / a path; F = 1 stands in where there are no frames
+int path_args(int F, int hm, int wm) {
+    if (bad_image(F, hm, wm)) return CP360_ERR_BAD_SHAPE;
+    return (long long)hm * wm > kMaxMapPx || F > 65535 ? CP360_ERR_UNSUPPORTED : CP360_OK;
+}
+
+size_t path_table_ints(int hm, int wm) { return (size_t)hm * hm * (wm / 2 + 1) + (size_t)hm * hm; }
+size_t path_back_bytes(int F, int hm, int wm) { return align16((size_t)F * hm * wm * sizeof(uint16_t)); }
+
+// the angle between the pixel centres of rows ri and rj, d columns apart, in radians: atan2(|p x q|, p . q) in double
+double path_angle(int hm, int wm, int ri, int rj, int d) {
+    const double pi_ = kPi * 0.5 * (1.0 - (2.0 * (double)ri + 1.0) / (double)hm);
+    const double pj_ = kPi * 0.5 * (1.0 - (2.0 * (double)rj + 1.0) / (double)hm);
+    const double dt = 2.0 * kPi * (double)d / (double)wm;
+    const double px = cos(pi_), py = sin(pi_);                          // p at theta 0: pz = 0
+    const double qx = cos(pj_) * cos(dt), qy = sin(pj_), qz = cos(pj_) * sin(dt);
+    const double cx = py * qz, cy = -px * qz, cz = px * qy - py * qx;
+    return atan2(sqrt(cx * cx + cy * cy + cz * cz), px * qx + py * qy);
+}
+
+// K16a's 2 P ints of LDS pass the 64 KB a kernel gets unasked: raise the limit once per device, as cubepad.hip does
+int path_big_lds() {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return CP360_ERR_HIP;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(done.load(std::memory_order_acquire) & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(path_dp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                2 * kMaxMapPx * (int)sizeof(int)) != hipSuccess)
+            return CP360_ERR_HIP;
+        done.fetch_or(bit, std::memory_order_release);
+    }
+    return CP360_OK;
 }
 
 }  // namespace
@@ -299,6 +501,83 @@ extern "C" int cp360_view_peak(const float* smooth, const float* maps, int F, in
     st = launch_tables(work, hm, wm, s, &t);
     if (st != CP360_OK) return st;
     hipLaunchKernelGGL(view_peak_kernel, dim3(F), dim3(256), 0, s, smooth, maps, t.x, t.y, dir_out, idx_out, val_out, hm, wm, kappa);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// ------------------------------------------------------------------ K16: the camera path
+extern "C" size_t cp360_path_table_bytes(int hm, int wm) {
+    return path_args(1, hm, wm) != CP360_OK ? 0 : path_table_ints(hm, wm) * sizeof(int32_t);
+}
+
+extern "C" int cp360_path_table_host(int hm, int wm, double turn_cost, double step_rad, int32_t* out) {
+    if (!out) return CP360_ERR_NULL;
+    if (bad_image(1, hm, wm) || !(turn_cost >= 0.0 && turn_cost <= 4096.0) || !(step_rad > 0.0 && step_rad <= kPi))
+        return CP360_ERR_BAD_SHAPE;
+    const int st = path_args(1, hm, wm);
+    if (st != CP360_OK) return st;
+    const int half = wm / 2 + 1;
+    int32_t* span = out + (size_t)hm * hm * half;
+    for (int ri = 0; ri < hm; ++ri) {
+        for (int rj = ri; rj < hm; ++rj) {                              // the mirror image is a copy: symmetric to the bit
+            int32_t* c = out + ((size_t)ri * hm + rj) * half;
+            int D = -1;
+            for (int d = 0; d < half; ++d) {
+                const double a = path_angle(hm, wm, ri, rj, d);
+                const bool ok = D == d - 1 && a <= step_rad;            // one interval: nothing behind the first forbidden one
+                c[d] = ok ? (int32_t)rint(turn_cost * (a * (180.0 / kPi))) : -1;
+                if (ok) D = d;
+            }
+            span[ri * hm + rj] = span[rj * hm + ri] = D;
+            int32_t* m = out + ((size_t)rj * hm + ri) * half;
+            for (int d = 0; d < half && m != c; ++d) m[d] = c[d];
+        }
+    }
+    return CP360_OK;
+}
+
+extern "C" size_t cp360_path_work_bytes(int F, int hm, int wm) {
+    return path_args(F, hm, wm) != CP360_OK ? 0 : tab_bytes(hm, wm) + path_back_bytes(F, hm, wm);
+}
+
+extern "C" int cp360_view_path(const float* smooth, const float* gain, int F, int hm, int wm, const int32_t* table_dev,
+                               const int32_t* starts_dev, int S, int32_t* idx_out, float* dir_out, int32_t* score_out, void* work,
+                               size_t work_bytes, void* stream) {
+    if (!smooth || !gain || !table_dev || !starts_dev || !idx_out || !dir_out || !score_out || !work) return CP360_ERR_NULL;
+    if (bad_image(F, hm, wm) || S < 1 || S > F) return CP360_ERR_BAD_SHAPE;
+    int st = path_args(F, hm, wm);
+    if (st != CP360_OK) return st;
+    st = check_work(work, work_bytes, cp360_path_work_bytes(F, hm, wm));
+    if (st != CP360_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = launch_tables(work, hm, wm, s, &t);
+    if (st != CP360_OK) return st;
+    st = path_big_lds();
+    if (st != CP360_OK) return st;
+    const int P = hm * wm;
+    const int threads = P >= kPathThreads ? kPathThreads : (P + 63) / 64 * 64;
+    uint16_t* back = (uint16_t*)((char*)work + tab_bytes(hm, wm));
+    hipLaunchKernelGGL(path_dp_kernel, dim3(S), dim3(threads), 2 * (size_t)P * sizeof(int), s, smooth, gain, (const int*)table_dev,
+                       (const int*)starts_dev, back, (int*)idx_out, (int*)score_out, F, hm, wm);
+    CP360_CHECK_HIP();
+    hipLaunchKernelGGL(path_trace_kernel, dim3((S + 63) / 64), dim3(64), 0, s, (const uint16_t*)back, (const int*)starts_dev, t.x, t.y,
+                       (int*)idx_out, dir_out, S, F, hm, wm);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_view_refine(const float* maps, const int32_t* idx, int F, int hm, int wm, double sigma_rad, float* dir_out,
+                                 void* work, size_t work_bytes, void* stream) {
+    if (!maps || !idx || !dir_out || !work) return CP360_ERR_NULL;
+    float kappa = 0.f;
+    int st = map_args(F, hm, wm, sigma_rad, work, work_bytes, &kappa);
+    if (st != CP360_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = launch_tables(work, hm, wm, s, &t);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_refine_kernel, dim3(F), dim3(256), 0, s, maps, (const int*)idx, t.x, t.y, dir_out, hm, wm, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
 }

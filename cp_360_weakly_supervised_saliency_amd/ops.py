@@ -1571,6 +1571,89 @@ def sphere_peak(maps, sigma_deg=15.0, smooth=None, work=None):
     return dirs, idx, val
 
 
+# ----------------------------------------------------------------------------- K16: the camera path (csrc/viewport.hip)
+_PATH_TABLES = {}
+
+
+def _path_params(hm, wm, turn_cost, step_deg):
+    hm, wm, turn_cost, step_deg = int(hm), int(wm), float(turn_cost), float(step_deg)
+    if hm < 1 or wm < 1 or hm * wm > 16384:
+        raise ValueError("a path needs a map of 1 .. 16384 pixels, got %d x %d" % (hm, wm))
+    if not 0.0 <= turn_cost <= 4096.0 or not 0.0 < step_deg <= 180.0:
+        raise ValueError("turn_cost must be in [0, 4096] and step_deg in (0, 180], got %r, %r" % (turn_cost, step_deg))
+    if step_deg < 180.0 / hm:
+        raise ValueError("step_deg %g is below the map's row pitch of %g degrees: no move is ever allowed" % (step_deg, 180.0 / hm))
+    return hm, wm, turn_cost, step_deg
+
+
+def path_table_host(hm, wm, turn_cost, step_deg):
+    """cp360_path_table_host: the turn costs of an hm x wm map as one int32 numpy array, cost [hm, hm, wm // 2 + 1] by (row of i,
+    row of j, folded column difference) = rint(turn_cost * angle in degrees), -1 where the angle exceeds step_deg, and behind it
+    span [hm, hm], the largest allowed column difference (``path_table_split`` gives the two views).  Host only: needs no GPU."""
+    hm, wm, turn_cost, step_deg = _path_params(hm, wm, turn_cost, step_deg)
+    out = np.empty(lib().cp360_path_table_bytes(hm, wm) // 4, np.int32)
+    check(lib().cp360_path_table_host(hm, wm, turn_cost, math.radians(step_deg), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def path_table_split(table, hm, wm):
+    """A table of ``path_table_host`` -> (cost [hm, hm, wm // 2 + 1], span [hm, hm]), views of it."""
+    n = hm * hm * (wm // 2 + 1)
+    return table[:n].reshape(hm, hm, wm // 2 + 1), table[n:].reshape(hm, hm)
+
+
+def path_table(hm, wm, turn_cost, step_deg, device):
+    """The table on `device`, uploaded once per (hm, wm, turn_cost, step_deg, device)."""
+    key = _path_params(hm, wm, turn_cost, step_deg) + (torch.device(device),)
+    if key not in _PATH_TABLES:
+        _PATH_TABLES[key] = torch.from_numpy(path_table_host(*key[:4])).to(key[4])
+    return _PATH_TABLES[key]
+
+
+def sphere_path(smooth, gain, turn_cost=16.0, step_deg=15.0, starts=None, work=None):
+    """cp360_view_path: the path over the pixels of smooth f32 [F, hm, wm] that collects the most votes q = rint(clamp(smooth *
+    gain[t], 0, 4096)) (gain f32 [F]) minus turn_cost per degree turned, turning at most step_deg a frame -> (idx i32 [F], dirs
+    f32 [F, 3] = the pixel centres, score i32 [S]).  ``starts`` i32 [S + 1] on the device (ascending, from 0 to F) cuts the video
+    into S independent sequences; None: one.  Exact integers: bit-identical between runs."""
+    require_gpu(smooth, gain, starts, work)
+    if smooth.dim() != 3 or smooth.numel() == 0:
+        raise ValueError("smooth must be a non-empty float32 [F, hm, wm], got %s" % (tuple(smooth.shape),))
+    _check_buf('smooth', smooth, torch.float32)
+    F, hm, wm = (int(s) for s in smooth.shape)
+    hm, wm, turn_cost, step_deg = _path_params(hm, wm, turn_cost, step_deg)
+    if tuple(gain.shape) != (F,) or gain.device != smooth.device:
+        raise ValueError("gain must be float32 [%d] on the maps' device" % F)
+    _check_buf('gain', gain, torch.float32)
+    if starts is None:
+        starts = torch.tensor([0, F], dtype=torch.int32, device=smooth.device)
+    elif starts.dim() != 1 or not 2 <= starts.numel() <= F + 1 or starts.device != smooth.device:
+        raise ValueError("starts must be int32 [S + 1] with 1 <= S <= %d on the maps' device" % F)
+    _check_buf('starts', starts, torch.int32)
+    S = starts.numel() - 1
+    table = path_table(hm, wm, turn_cost, step_deg, smooth.device)
+    work = _work(lib().cp360_path_work_bytes, "sphere_path", F, hm, wm, smooth.device, work, " (F <= 65535, hm wm <= 16384)")
+    idx = torch.empty((F,), dtype=torch.int32, device=smooth.device)
+    dirs = torch.empty((F, 3), dtype=torch.float32, device=smooth.device)
+    score = torch.empty((S,), dtype=torch.int32, device=smooth.device)
+    check(lib().cp360_view_path(ptr(smooth), ptr(gain), F, hm, wm, ptr(table), ptr(starts), S, ptr(idx), ptr(dirs), ptr(score),
+                                ptr(work), work.numel() * 8, stream()))
+    return idx, dirs, score
+
+
+def sphere_refine(maps, idx, sigma_deg=15.0, work=None):
+    """cp360_view_refine: ``sphere_peak``'s mean-shift step on the raw maps f32 [F, hm, wm] about the pixels idx i32 [F] -> dirs
+    f32 [F, 3]; with ``sphere_peak``'s idx, its dirs bit for bit.  idx < 0: (1, 0, 0)."""
+    require_gpu(maps, idx, work)
+    F, hm, wm, sigma = _view_maps(maps, sigma_deg)
+    if tuple(idx.shape) != (F,) or idx.device != maps.device:
+        raise ValueError("idx must be int32 [%d] on the maps' device" % F)
+    _check_buf('idx', idx, torch.int32)
+    work = _stab_work(0, hm, wm, maps.device, work)
+    dirs = torch.empty((F, 3), dtype=torch.float32, device=maps.device)
+    check(lib().cp360_view_refine(ptr(maps), ptr(idx), F, hm, wm, sigma, ptr(dirs), ptr(work), work.numel() * 8, stream()))
+    return dirs
+
+
 # ----------------------------------------------------------------------------- K13: shot detection (csrc/shots.hip)
 _SHOT_WEIGHTS = {}
 

@@ -5,14 +5,16 @@ has this purpose and does not compile; the definition is the package's own (DESI
 Per frame the saliency map is smoothed on the sphere and its peak refined by one mean-shift step (``ops.sphere_peak``); the peaks
 become a smooth camera path on the host (``smooth_path``: a zero-phase exponential filter along great circles; ``look_at``: the
 camera with a level horizon), and the views are rendered at the frames' own resolution (``ops.viewport_render``);
-``ops.viewport_outline`` draws the view's frame on the panorama.  A camera is a rotation R, camera-to-world, with the columns
+``ops.viewport_outline`` draws the view's frame on the panorama.  ``planner='viterbi'`` replaces the per-frame peaks by the path
+that collects the most saliency under a turn limit and a turn cost (K16: ``ops.sphere_path``, then ``ops.sphere_refine``): it
+chooses which of several targets to follow, where the peaks hop between them.  A camera is a rotation R, camera-to-world, with the columns
 (forward, up, right): R = I looks at the panorama's centre.  Roll, translation and anti-aliased views are out of scope.
 """
 import numpy as np
 import torch
 
 from .. import ops
-from ._device import TabWork, on_device
+from ._device import TabWork, host_tensor, on_device
 from .shots import check_cuts, segments
 
 _Y = np.array([0.0, 1.0, 0.0])
@@ -96,9 +98,14 @@ def cameras(path, cuts=None):
 
 
 class ViewportPilot:
-    """``ViewportPilot((h, w), hfov_deg)``: views of h x w pixels that follow the saliency maps' peak.  Holds the workspaces."""
+    """``ViewportPilot((h, w), hfov_deg)``: views of h x w pixels that follow the saliency maps' peak.  Holds the workspaces.
 
-    def __init__(self, hw=(720, 1280), hfov_deg=90.0, sigma_deg=15.0, alpha=0.85, max_step_deg=None, device='cuda'):
+    ``planner``: 'peak', every frame's own peak, or 'viterbi', the best path of K16 under ``turn_cost`` (votes per degree turned;
+    a frame's peak votes 4096) and ``plan_step_deg`` (the most the path may turn between two frames).  16 per degree and 15
+    degrees are conventions, chosen on the synthetic videos of tests/campath_restate.py and not tuned on data."""
+
+    def __init__(self, hw=(720, 1280), hfov_deg=90.0, sigma_deg=15.0, alpha=0.85, max_step_deg=None, device='cuda', planner='peak',
+                 turn_cost=16.0, plan_step_deg=15.0):
         self.hw = (int(hw[0]), int(hw[1]))
         if min(self.hw) < 1 or not 0.0 < float(hfov_deg) < 180.0 or not float(sigma_deg) > 0.0:
             raise ValueError("hw must be positive, 0 < hfov_deg < 180 and sigma_deg > 0, got %r, %r, %r" % (hw, hfov_deg, sigma_deg))
@@ -106,19 +113,48 @@ class ViewportPilot:
             raise ValueError("alpha must be in [0, 1) and max_step_deg positive, got %r, %r" % (alpha, max_step_deg))
         self.hfov_deg, self.sigma_deg, self.alpha = float(hfov_deg), float(sigma_deg), float(alpha)
         self.max_step_deg = None if max_step_deg is None else float(max_step_deg)
+        if planner not in ('peak', 'viterbi'):
+            raise ValueError("planner must be 'peak' or 'viterbi', got %r" % (planner,))
+        if not 0.0 <= float(turn_cost) <= 4096.0 or not 0.0 < float(plan_step_deg) <= 180.0:
+            raise ValueError("turn_cost must be in [0, 4096] and plan_step_deg in (0, 180], got %r, %r" % (turn_cost, plan_step_deg))
+        self.planner, self.turn_cost, self.plan_step_deg = planner, float(turn_cost), float(plan_step_deg)
         self.device = torch.device(device)
         self._tab_work = TabWork()
+        self._path_work = None
 
     def peaks(self, maps):
         """maps f32 [F, hm, wm] -> the direction of every map's peak, f32 [F, 3] on the device."""
         maps = on_device(maps, self.device, torch.float32)
         return ops.sphere_peak(maps, self.sigma_deg, work=self._tab_work(maps))[0]
 
+    def plan(self, maps, cuts=None):
+        """maps f32 [F, hm, wm] -> the directions of the planned path, f32 [F, 3] on the device: the maps smoothed, every frame's
+        votes scaled so that its peak votes 4096, the best path over the map's pixels (``ops.sphere_path``; every shot of ``cuts``
+        has its own) and one mean-shift step about each of its pixels (``ops.sphere_refine``).  No host synchronisation."""
+        maps = host_tensor(maps)
+        if maps.dim() != 3 or maps.numel() == 0:
+            raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+        F, hm = int(maps.shape[0]), int(maps.shape[1])
+        if self.plan_step_deg < 180.0 / hm:
+            raise ValueError("plan_step_deg %g is below the row pitch of a map of %d rows, %g degrees: no move is ever allowed"
+                             % (self.plan_step_deg, hm, 180.0 / hm))
+        edges = [0] + check_cuts(cuts, F) + [F]
+        maps = on_device(maps, self.device, torch.float32)
+        starts = torch.tensor(edges, dtype=torch.int32).to(self.device)
+        work = self._tab_work(maps)
+        sm = ops.sphere_smooth(maps, self.sigma_deg, work=work)
+        val = ops.sphere_peak(maps, self.sigma_deg, smooth=sm, work=work)[2]
+        self._path_work = ops._work(ops.lib().cp360_path_work_bytes, "sphere_path", F, hm, int(maps.shape[2]), maps.device,
+                                    self._path_work, " (F <= 65535, hm wm <= 16384)")
+        idx = ops.sphere_path(sm, 4096.0 / val, self.turn_cost, self.plan_step_deg, starts, work=self._path_work)[0]
+        return ops.sphere_refine(maps, idx, self.sigma_deg, work=work)
+
     def path(self, maps, cuts=None):
-        """maps f32 [F, hm, wm] -> the cameras R f32 [F, 3, 3] on the device: the peaks, copied to the host (3 F floats, the one
-        synchronisation of a video), ``smooth_path`` and ``look_at`` with every frame's right chained, copied back.  With
-        ``cuts`` (``utils.shots``) the path of every shot is its own: the concatenation of the shots' paths."""
-        dirs = self.peaks(maps).cpu().numpy()
+        """maps f32 [F, hm, wm] -> the cameras R f32 [F, 3, 3] on the device: the peaks (the planned path with the planner
+        'viterbi'), copied to the host (3 F floats, the one synchronisation of a video), ``smooth_path`` and ``look_at`` with every
+        frame's right chained, copied back.  With ``cuts`` (``utils.shots``) the path of every shot is its own: the concatenation
+        of the shots' paths."""
+        dirs = (self.plan(maps, cuts) if self.planner == 'viterbi' else self.peaks(maps)).cpu().numpy()
         R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg, cuts), cuts)
         return torch.from_numpy(R.astype(np.float32)).to(self.device)
 

@@ -557,6 +557,39 @@ int cp360_view_smooth(const float* maps, int F, int hm, int wm, double sigma_rad
 int cp360_view_peak(const float* smooth, const float* maps, int F, int hm, int wm, double sigma_rad, float* dir_out, int* idx_out,
                     float* val_out, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K16: the camera path by dynamic programming
+ * Which target to follow over time: the path over the map's pixels that collects the most saliency while the camera turns at
+ * most step degrees a frame and pays turn_cost per degree (the dynamic programme of Pano2Vid / AutoCam and Deep 360 Pilot).  The
+ * definition is the package's own and exact in integers, DESIGN.md "K16", restated in tests/campath_restate.py.  A state is a pixel
+ * of the hm x wm map, P = hm wm <= 16384, p_j its centre's direction.
+ *
+ *   table_host  out int32 (HOST memory, cp360_path_table_bytes(hm, wm) bytes): cost [hm][hm][wm / 2 + 1] by (row of i, row of j,
+ *               column difference folded to 0 .. wm / 2) = rint(turn_cost * the angle of p_i and p_j in degrees) where the angle
+ *               (atan2(|p x q|, p . q), double) is at most step_rad, else -1; behind it span [hm][hm], the largest allowed column
+ *               difference of the row pair, -1 for none.  Symmetric in the rows.  0 <= turn_cost <= 4096, 0 < step_rad <= pi.
+ *   path        smooth f32 [F, hm, wm], gain f32 [F], table_dev = the table in DEVICE memory, starts_dev int32 [S + 1] in device
+ *               memory: ascending, starts[0] = 0, starts[S] = F, sequence s = frames starts[s] .. starts[s + 1] - 1 (values are
+ *               clamped into 0 .. F; an empty sequence writes nothing).  Vote q[t][j] = (int)rintf(min(max(smooth[t][j] gain[t], 0),
+ *               4096)), one f32 product, 0 where it is not finite.  Per sequence [lo, hi): acc[lo] = q[lo], acc[t][j] = q[t][j] +
+ *               max_i (acc[t-1][i] - cost(i, j)) over the allowed i, back[t][j] = the lowest maximising i; idx[hi-1] = the lowest
+ *               argmax of acc[hi-1], idx[t-1] = back[t][idx[t]].  -> idx_out int32 [F], dir_out f32 [F, 3] = the pixel centres'
+ *               directions, score_out int32 [S] = acc[hi-1][idx[hi-1]] (< 2^28).  Integers: bit-identical between runs, and a
+ *               sequence's result does not depend on the others.  One workgroup per sequence, then one thread per sequence.
+ *   refine      K12's mean-shift step on the raw maps about p* = dir(idx[t]) for GIVEN indices (int32 [F], device): with peak's idx
+ *               it is peak's dir bit for bit; an index outside 0 .. P - 1 gives (1, 0, 0).
+ * work: 16-byte aligned device memory; path: cp360_path_work_bytes(F, hm, wm) bytes (K11's tables, then the back-pointers u16
+ * [F][P]); refine: as K12's.  The _bytes functions return 0 for bad or unsupported sizes.  NULL: CP360_ERR_NULL; F, hm, wm < 1,
+ * S < 1, S > F or a parameter out of range: CP360_ERR_BAD_SHAPE; P > 16384 or F > 65535: CP360_ERR_UNSUPPORTED.  Asynchronous on
+ * the stream, no atomics, no host synchronisation. */
+size_t cp360_path_table_bytes(int hm, int wm);
+int cp360_path_table_host(int hm, int wm, double turn_cost, double step_rad, int32_t* out);
+size_t cp360_path_work_bytes(int F, int hm, int wm);
+int cp360_view_path(const float* smooth, const float* gain, int F, int hm, int wm, const int32_t* table_dev,
+                    const int32_t* starts_dev, int S, int32_t* idx_out, float* dir_out, int32_t* score_out, void* work,
+                    size_t work_bytes, void* stream);
+int cp360_view_refine(const float* maps, const int32_t* idx, int F, int hm, int wm, double sigma_rad, float* dir_out, void* work,
+                      size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K13: shot detection
  * Where the hard cuts of an equirectangular video are: K10 - K12 assume one continuous take.  The signature of a frame is the
  * colour histogram of the whole sphere, every pixel weighted by the solid angle of its row: a camera rotation leaves it nearly

@@ -11,8 +11,12 @@ current stream, the median after warm-up, the shader clock the chip holds under 
   outline   64 u8 panoramas of 1024 x 2048, in place (bytes = the border pixels written) and out of place (read + written)
   smooth    64 maps of 14 x 28 and of 32 x 64: all pairs, P^2 terms per map; bytes = maps read + written
   peak      the same maps; bytes = smoothed + raw maps read
+  path      K16, ops.sphere_path on the same maps (smoothed, every frame's gain 4096 / its peak): one sequence of F frames (one
+            workgroup on one CU, F dependent steps) and 64 sequences of F frames each; bytes = maps read + back-pointers written
+  refine    K16c, ops.sphere_refine about the path's pixels; bytes = raw maps read
   follow    ViewportPilot.follow end to end: smooth, peak, the copy of the peaks to the host with its synchronisation, the path
             on the host, the copy back, render
+  .path     ViewportPilot.path alone with both planners: 'peak' is the yardstick of 'viterbi' in the same run
 
   python tools/viewport_bench.py [--frames 64] [--src 1024,2048] [--view 720,1280] [--hfov 90] [--reps 20] [--warmup 5]
 Prints a table and one JSON line."""
@@ -116,7 +120,8 @@ def main():
     del flat, flat_out
 
     pilot = vp.ViewportPilot((h, w), args.hfov)
-    follow = {}
+    planner = vp.ViewportPilot((h, w), args.hfov, planner='viterbi')
+    follow, paths = {}, {}
     for hm, wm in ((14, 28), (32, 64)):
         maps = torch.from_numpy(hashrng.uniform(32, (F, hm, wm), 0.0, 0.1)).cuda()
         for f in range(F):
@@ -128,8 +133,22 @@ def main():
         sm = ops.sphere_smooth(maps, 15.0, work=mwork)
         ms, fastest = time_ms(lambda: ops.sphere_peak(maps, 15.0, smooth=sm, work=mwork), args.reps, args.warmup)
         rows.append(row('peak %dx%d' % (hm, wm), ms, fastest, F * hm * wm, 8.0 * F * hm * wm, 2))
+        val = ops.sphere_peak(maps, 15.0, smooth=sm, work=mwork)[2]
+        for S in (1, 64):
+            sm_s, gain_s, maps_s = sm.repeat(S, 1, 1), (4096.0 / val).repeat(S), maps.repeat(S, 1, 1)
+            starts = torch.arange(0, S * F + 1, F, dtype=torch.int32, device='cuda')
+            pwork = ops._work(ops.lib().cp360_path_work_bytes, 'sphere_path', S * F, hm, wm, maps.device, None)
+            ms, fastest = time_ms(lambda: ops.sphere_path(sm_s, gain_s, starts=starts, work=pwork), args.reps, args.warmup)
+            rows.append(row('path %dx%d, %d x %d frames' % (hm, wm, S, F), ms, fastest, S * F * hm * wm, 6.0 * S * F * hm * wm, 3))
+            idx = ops.sphere_path(sm_s, gain_s, starts=starts, work=pwork)[0]
+            ms, fastest = time_ms(lambda: ops.sphere_refine(maps_s, idx, 15.0, work=mwork), args.reps, args.warmup)
+            rows.append(row('refine %dx%d, %d x %d frames' % (hm, wm, S, F), ms, fastest, S * F * hm * wm, 4.0 * S * F * hm * wm, 2))
+            del sm_s, gain_s, maps_s, pwork
         ms, _ = time_ms(lambda: pilot.follow(frames, maps), args.reps, args.warmup)
         follow['%dx%d' % (hm, wm)] = {'ms_per_call': ms, 'ms_per_frame': ms / F}
+        ms_peak, _ = time_ms(lambda: pilot.path(maps), args.reps, args.warmup)
+        ms_plan, _ = time_ms(lambda: planner.path(maps), args.reps, args.warmup)
+        paths['%dx%d' % (hm, wm)] = {'peak_ms_per_call': ms_peak, 'viterbi_ms_per_call': ms_plan}
 
     print('%d frames; held shader clock under a bare MFMA loop %.3f GHz; median of %d after %d warm-up calls (HIP events)'
           % (F, clock, args.reps, args.warmup))
@@ -141,9 +160,11 @@ def main():
           'the panorama per view' % (render_ns / rotate_ns, ms2, ms3, ms2 / ms3, 100.0 * footprint / (F * H * W)))
     for k, v in follow.items():
         print('follow, maps %s: %.3f ms / call, %.3f ms / frame' % (k, v['ms_per_call'], v['ms_per_frame']))
+    for k, v in paths.items():
+        print(".path, maps %s: planner 'peak' %.3f ms / call, 'viterbi' %.3f ms / call" % (k, v['peak_ms_per_call'], v['viterbi_ms_per_call']))
     print(json.dumps({'tool': 'viewport_bench', 'frames': F, 'src': [H, W], 'view': [h, w], 'hfov_deg': args.hfov,
                       'held_clock_ghz': clock, 'rows': rows, 'render_over_rotate': render_ns / rotate_ns,
-                      'render_over_rotate_again': ms2 / ms3, 'footprint_fraction': footprint / (F * H * W), 'follow': follow}))
+                      'render_over_rotate_again': ms2 / ms3, 'footprint_fraction': footprint / (F * H * W), 'follow': follow, 'path': paths}))
 
 
 if __name__ == '__main__':
