@@ -35,17 +35,18 @@ PUBLIC_SYMBOLS = [
     'cp360_cubepad_nhwc', 'cp360_nchw_to_nhwc', 'cp360_nhwc_to_nchw', 'cp360_equi2cube', 'cp360_cube2equi',
     'cp360_conv_packed_bytes', 'cp360_conv_partial_bytes', 'cp360_conv_suggest_splits', 'cp360_conv_pack_weights',
     'cp360_conv_pack_weights2', 'cp360_conv_forward', 'cp360_conv_forward2', 'cp360_conv_finish',
-    'cp360_cubepad_maxpool3s2', 'cp360_lstm_gates', 'cp360_lstm_gates_next', 'cp360_window_minmax',
+    'cp360_cubepad_maxpool3s2', 'cp360_lstm_gates', 'cp360_lstm_gates_next', 'cp360_lstm_gates_next_groups', 'cp360_window_minmax',
     'cp360_window_normalize', 'cp360_resize_ksize', 'cp360_resize_coeffs_host', 'cp360_resize_lanczos_u8',
     'cp360_resize_linear_f32', 'cp360_metric_work_bytes', 'cp360_metric_auc_prepare', 'cp360_metric_auc_judd',
     'cp360_metric_auc_borji', 'cp360_metric_cc_sim', 'cp360_resize_ksize2', 'cp360_resize_coeffs_host2',
     'cp360_overlay_colorize', 'cp360_overlay_blend_u8', 'cp360_fold_bn', 'cp360_create', 'cp360_destroy',
     'cp360_resnet_load', 'cp360_resnet_workspace_bytes', 'cp360_resnet_forward', 'cp360_clstm_load', 'cp360_clstm_workspace_bytes',
     'cp360_clstm_step', 'cp360_conv_finish_add', 'cp360_window_normalize_frames',
-    'cp360_clstm_window_workspace_bytes', 'cp360_clstm_window', 'cp360_clock_probe', 'cp360_conv_prefer_clip',
+    'cp360_clstm_window_workspace_bytes', 'cp360_clstm_window', 'cp360_clstm_window_multi_workspace_bytes',
+    'cp360_clstm_window_multi', 'cp360_clock_probe', 'cp360_conv_prefer_clip',
     'cp360_conv_plan_describe', 'cp360_resnet_plan_describe', 'cp360_resize_plan_describe', 'cp360_wino_packed_bytes', 'cp360_wino_v_bytes',
     'cp360_wino_m_bytes', 'cp360_wino_preferred', 'cp360_wino_pack_weights', 'cp360_wino_input', 'cp360_wino_gemm',
-    'cp360_wino_output', 'cp360_wino_output_gates', 'cp360_wino_forward', 'cp360_wino_output_input', 'cp360_clstm_wino_state', 'cp360_clstm_load_wino',
+    'cp360_wino_output', 'cp360_wino_output_gates', 'cp360_wino_output_gates_groups', 'cp360_wino_forward', 'cp360_wino_output_input', 'cp360_clstm_wino_state', 'cp360_clstm_load_wino',
     # K5t: ConvLSTM training
     'cp360_train_gates', 'cp360_train_gates_backward', 'cp360_train_dgrad_packed_bytes', 'cp360_train_dgrad_pack',
     'cp360_train_dgrad', 'cp360_train_cubepad_inverse_host', 'cp360_train_cubepad_adjoint', 'cp360_train_wgrad',
@@ -147,6 +148,7 @@ def lib():
     L.cp360_cubepad_maxpool3s2.argtypes = [vp, vp, i, i, i, i, vp]
     L.cp360_lstm_gates.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp, i, i, i, vp]
     L.cp360_lstm_gates_next.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp, i, i, i, vp, vp, i, i, sz, vp]
+    L.cp360_lstm_gates_next_groups.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp, i, i, i, vp, i, i, vp, i, i, sz, vp]
     L.cp360_window_minmax.argtypes = [vp, vp, vp, i, sz, sz, vp]
     L.cp360_window_normalize.argtypes = [vp, vp, vp, i, i, i, vp, i, i, i, i, i, sz, vp]
     L.cp360_resize_ksize.argtypes = [i, i]
@@ -214,6 +216,10 @@ def lib():
     L.cp360_clstm_window_workspace_bytes.restype = sz
     L.cp360_clstm_window_workspace_bytes.argtypes = [vp, i, i, i]
     L.cp360_clstm_window.argtypes = [vp, vp, sz, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.cp360_clstm_window_multi_workspace_bytes.restype = sz
+    L.cp360_clstm_window_multi_workspace_bytes.argtypes = [vp, i, i, i, i]
+    # cams / h_out / h_all: host arrays of device pointers (ctypes c_void_p * n_groups)
+    L.cp360_clstm_window_multi.argtypes = [vp, vp, sz, i, i, i, i, vp, vp, vp, vp, sz, vp]
     L.cp360_clock_probe.argtypes = [vp, i, i, vp]
     L.cp360_conv_prefer_clip.argtypes = [pd]
     L.cp360_conv_plan_describe.argtypes = [pd, C.c_char_p, sz]
@@ -230,6 +236,7 @@ def lib():
     L.cp360_wino_output.argtypes = [pw, vp, vp, vp, vp]
     L.cp360_wino_output_input.argtypes = [pw, vp, vp, vp, vp]
     L.cp360_wino_output_gates.argtypes = [pw, vp, vp, vp, vp, vp, i, i, vp, vp, vp, i, sz, vp]
+    L.cp360_wino_output_gates_groups.argtypes = [pw, vp, vp, vp, vp, vp, i, i, vp, vp, i, i, vp, i, sz, vp]
     L.cp360_wino_forward.argtypes = [pw, vp, vp, vp, vp, vp, vp, vp]
     L.cp360_wino_gemm_raw.argtypes = [i, vp, vp, vp, i, i, i, i, i, vp]
     L.cp360_clstm_wino_state.argtypes = [vp, i, i]

@@ -104,6 +104,33 @@ static inline bool big_image(int N, int h, int w) {
 static inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// ---------------------------------------------------------------------------------
+// x_next of the gate kernels (conv_igemm.hip, wino.hip): the clips of a cell update may sit in several separately allocated
+// buffers of `clips` clips each (cp360_clstm_window_multi).  Passed by value; one group covers every clip of a plain step.
+// ---------------------------------------------------------------------------------
+struct ClipGroups {
+    const float* base[CP360_MAX_CLIP_GROUPS];
+    int clips;                                     // clips per group (> 0)
+};
+// Frame of clip b: a select chain over the kernel arguments (a lane-indexed array would be copied to scratch memory)
+__device__ __forceinline__ const float* clip_frame(const ClipGroups& g, int b, size_t clip_stride) {
+    const int grp = b / g.clips;
+    const float* p = g.base[0];
+#pragma unroll
+    for (int k = 1; k < CP360_MAX_CLIP_GROUPS; ++k) p = grp == k ? g.base[k] : p;
+    return p + (size_t)(b - grp * g.clips) * clip_stride;
+}
+// Host side: the checked form of (x_groups, n_groups, group_clips) for n_clips clips in all; false = refuse the call
+static inline bool clip_groups(const float* const* x_groups, int n_groups, int group_clips, int n_clips, ClipGroups* g) {
+    if (!x_groups || n_groups < 1 || n_groups > CP360_MAX_CLIP_GROUPS || group_clips < 1 || (long long)n_groups * group_clips < n_clips) return false;
+    for (int k = 0; k < CP360_MAX_CLIP_GROUPS; ++k) {
+        g->base[k] = k < n_groups ? x_groups[k] : nullptr;
+        if (k < n_groups && !x_groups[k]) return false;
+    }
+    g->clips = group_clips;
+    return true;
+}
+
 // Traversal order of the launch being issued by this host thread (cp360_set_launch_order, include/cp360.h): 0 = work
 // items in ascending order, 1 = descending; in the alternating mode every call flips it.  Results never depend on it.
 // Defined in cubepad.hip; called once per launch by the kernels that honour it.

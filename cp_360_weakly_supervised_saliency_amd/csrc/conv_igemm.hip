@@ -1166,7 +1166,7 @@ __global__ __launch_bounds__(256) void lstm_gates_kernel(const float* __restrict
                                                          const float* __restrict__ c_prev, float* __restrict__ c_next,
                                                          T* __restrict__ h_out, int ld_h, int h_coff,
                                                          float* __restrict__ h_f32, int M, int Hc, int slab_rows,
-                                                         const float* __restrict__ x_next,
+                                                         const bool x_next, const ClipGroups xg,
                                                          const float* __restrict__ minmax, int x_coff, int P,
                                                          size_t clip_stride) {
     const int q = Hc >> 2, G = 4 * Hc;
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(256) void lstm_gates_kernel(const float* __restrict
         if (x_next) {   // the NEXT step's input frame, window-normalised (test_temporal.py:77), into the x half of the same pixel
             const int b = m / P, pix = m - b * P;
             const float mn = minmax[2 * b], den = minmax[2 * b + 1] - mn;
-            const float4 v = *reinterpret_cast<const float4*>(x_next + (size_t)b * clip_stride + (size_t)pix * Hc + j);
+            const float4 v = *reinterpret_cast<const float4*>(clip_frame(xg, b, clip_stride) + (size_t)pix * Hc + j);
             const float xn[4] = {(v.x - mn) / den, (v.y - mn) / den, (v.z - mn) / den, (v.w - mn) / den};
             store4(h_out + (size_t)m * ld_h + x_coff + j, xn);
         }
@@ -1792,7 +1792,19 @@ extern "C" int cp360_lstm_gates_next(const float* gates_partial, int splits, con
                                      float* c_next, void* h_out, int h_dtype, int ld_h, int h_coff, float* h_f32, int M,
                                      int Hc, int slab_rows, const float* x_next, const float* minmax, int x_coff,
                                      int P, size_t clip_stride, void* stream) {
+    return cp360_lstm_gates_next_groups(gates_partial, splits, bias, c_prev, c_next, h_out, h_dtype, ld_h, h_coff, h_f32, M, Hc,
+                                        slab_rows, x_next ? &x_next : nullptr, 1, P > 0 ? M / P : 0, minmax, x_coff, P,
+                                        clip_stride, stream);
+}
+
+extern "C" int cp360_lstm_gates_next_groups(const float* gates_partial, int splits, const float* bias, const float* c_prev,
+                                            float* c_next, void* h_out, int h_dtype, int ld_h, int h_coff, float* h_f32, int M,
+                                            int Hc, int slab_rows, const float* const* x_groups, int n_groups, int group_clips,
+                                            const float* minmax, int x_coff, int P, size_t clip_stride, void* stream) {
     if (!gates_partial || !bias || !c_prev || !c_next || !h_out) return CP360_ERR_NULL;
+    const bool x_next = x_groups != nullptr;
+    ClipGroups xg{};
+    if (x_next && (P <= 0 || !clip_groups(x_groups, n_groups, group_clips, M / P, &xg))) return CP360_ERR_BAD_SHAPE;
     if (x_next && (!minmax || P <= 0 || M % P != 0 || x_coff % 4 != 0 || clip_stride % 4 != 0 || x_coff + Hc > ld_h ||
                    (x_coff < h_coff + Hc && h_coff < x_coff + Hc)))
         return CP360_ERR_BAD_SHAPE;
@@ -1807,7 +1819,7 @@ extern "C" int cp360_lstm_gates_next(const float* gates_partial, int splits, con
     with_elem(h_dtype, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((lstm_gates_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, gates_partial, splits, bias,
-                           c_prev, c_next, (T*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, minmax, x_coff, P,
+                           c_prev, c_next, (T*)h_out, ld_h, h_coff, h_f32, M, Hc, slab_rows, x_next, xg, minmax, x_coff, P,
                            clip_stride);
     });
     CP360_CHECK_HIP();

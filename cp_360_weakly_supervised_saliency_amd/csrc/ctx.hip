@@ -911,7 +911,9 @@ struct CellIo {
     void* xh;
     const float* c_prev;
     float *c_next, *h_f32;
-    const float *x_next, *minmax;
+    const float* const* x_groups;                  // NULL, or frame t+1 of the first clip of every group (host array)
+    int n_groups, group_clips;
+    const float* minmax;
     size_t clip_stride;
 };
 
@@ -941,8 +943,8 @@ int run_clstm(const ClstmPlan& P, const CClstm& Cl, const CellIo& c, unsigned ch
         }
         if (rc) return rc;
         if ((rc = cp360_wino_gemm(&P.dg, v, Cl.ug, m, st))) return rc;
-        return cp360_wino_output_gates(&P.dg, m, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.cin + Cl.ch, Cl.cin, c.h_f32, c.x_next,
-                                       c.minmax, 0, c.clip_stride, st);
+        return cp360_wino_output_gates_groups(&P.dg, m, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.cin + Cl.ch, Cl.cin, c.h_f32,
+                                              c.x_groups, c.n_groups, c.group_clips, c.minmax, 0, c.clip_stride, st);
     }
     Bufs at;
     at.p[SLOT_INPUT] = c.xh;
@@ -953,9 +955,9 @@ int run_clstm(const ClstmPlan& P, const CClstm& Cl, const CellIo& c, unsigned ch
         if ((rc = run_step(s, P, at, st))) return rc;
     // clstm.py:68-80: gates, cell / hidden update; the new hidden goes into the h half of xh; with x_next the next
     // frame's window normalisation (test_temporal.py:77) is written into the x half in the same pass
-    return cp360_lstm_gates_next((const float*)at[SLOT_PARTIAL], P.splits, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.dtype,
-                                 Cl.cin + Cl.ch, Cl.cin, c.h_f32, P.M, Cl.ch, P.slab_rows, c.x_next, c.minmax, 0,
-                                 6 * P.face * P.face, c.clip_stride, st);
+    return cp360_lstm_gates_next_groups((const float*)at[SLOT_PARTIAL], P.splits, Cl.gbias, c.c_prev, c.c_next, c.xh, Cl.dtype,
+                                        Cl.cin + Cl.ch, Cl.cin, c.h_f32, P.M, Cl.ch, P.slab_rows, c.x_groups, c.n_groups,
+                                        c.group_clips, c.minmax, 0, 6 * P.face * P.face, c.clip_stride, st);
 }
 }  // namespace
 
@@ -978,7 +980,7 @@ extern "C" int cp360_clstm_step(cp360_ctx* ctx, void* xh, const float* c_prev, f
     if (!xh || !c_prev || !c_next || !workspace) return CP360_ERR_NULL;
     if (((size_t)workspace & 255) != 0) return CP360_ERR_ALIGN;
     if (workspace_bytes < plan.ws.total()) return CP360_ERR_BAD_SHAPE;
-    const CellIo cell{xh, c_prev, c_next, h_f32, x_next, minmax, clip_stride};
+    const CellIo cell{xh, c_prev, c_next, h_f32, x_next ? &x_next : nullptr, 1, n_clips, minmax, clip_stride};
     return run_clstm(plan, ctx->cl, cell, (unsigned char*)workspace, (hipStream_t)stream);
 }
 
@@ -1033,5 +1035,87 @@ extern "C" int cp360_clstm_window(cp360_ctx* ctx, const float* cam, size_t clip_
     }
     if (h_all && hipMemcpyAsync(h_out, h_all + (size_t)(T - 1) * M * H, M * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return CP360_ERR_HIP;
+    return CP360_OK;
+}
+
+// ---------------------------------------------------------------- the windows of several batches in one run
+// The cell updates run ONCE at n_groups * n_clips clips: a Winograd GEMM launch then has n_groups tile blocks per (position,
+// channel tile) and reads that pair's filters from HBM once for all of them (csrc/wino.hip) instead of once per batch.
+namespace {
+struct MultiWs {
+    size_t xh = 0, cell = 0, h = 0, scratch = 0, step = 0;
+    size_t total() const { return xh + 2 * cell + h + scratch + step; }
+};
+
+int multi_plan(cp360_ctx* ctx, int n_groups, int n_clips, int T, int face, ClstmPlan* plan, MultiWs* ws) {
+    CClstm& Cl = ctx->cl;
+    if (!Cl.loaded) return CP360_ERR_NULL;
+    if (n_groups <= 0 || n_groups > CP360_MAX_CLIP_GROUPS || n_clips <= 0 || T <= 0 || face <= 0 || Cl.cin != Cl.ch) return CP360_ERR_BAD_SHAPE;
+    if ((long long)n_groups * n_clips > 65535) return CP360_ERR_BAD_SHAPE;
+    const int rc = plan_clstm(Cl, n_groups * n_clips, face, plan);
+    if (rc) return rc;
+    const size_t M = (size_t)plan->M;
+    ws->xh = align_up(M * (Cl.cin + Cl.ch) * es_of(Cl.dtype));
+    ws->cell = ws->h = align_up(M * Cl.ch * sizeof(float));
+    ws->scratch = align_up((size_t)n_groups * n_clips * 512 * sizeof(float));
+    ws->step = plan->ws.total();
+    return CP360_OK;
+}
+}  // namespace
+
+extern "C" size_t cp360_clstm_window_multi_workspace_bytes(cp360_ctx* ctx, int n_groups, int n_clips, int T, int face) {
+    if (!ctx) return 0;
+    ClstmPlan plan;
+    MultiWs ws;
+    return multi_plan(ctx, n_groups, n_clips, T, face, &plan, &ws) ? 0 : ws.total();
+}
+
+extern "C" int cp360_clstm_window_multi(cp360_ctx* ctx, const float* const* cams, size_t clip_stride, int n_groups, int n_clips,
+                                        int T, int face, float* const* h_out, float* const* h_all, float* minmax, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (!ctx || !cams || !h_out || !minmax || !workspace) return CP360_ERR_NULL;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return CP360_ERR_HIP;
+    CClstm& Cl = ctx->cl;
+    ClstmPlan plan;
+    MultiWs mw;
+    int rc = multi_plan(ctx, n_groups, n_clips, T, face, &plan, &mw);
+    if (rc) return rc;
+    for (int g = 0; g < n_groups; ++g)
+        if (!cams[g] || !h_out[g] || (h_all && !h_all[g])) return CP360_ERR_NULL;
+    if (((size_t)workspace & 255) != 0) return CP360_ERR_ALIGN;
+    if (workspace_bytes < mw.total()) return CP360_ERR_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = 6 * face * face, C = Cl.cin, H = Cl.ch;
+    const size_t Mg = (size_t)n_clips * P;                                 // pixels of one group
+    const size_t per_clip = (size_t)T * P * C, stride = clip_stride ? clip_stride : per_clip;
+    unsigned char* w = (unsigned char*)workspace;
+    unsigned char* xh = w;
+    float* c[2] = {(float*)(w + mw.xh), (float*)(w + mw.xh + mw.cell)};
+    float* hj = (float*)(w + mw.xh + 2 * mw.cell);                         // the hidden state of all groups after a step
+    float* scratch = (float*)(w + mw.xh + 2 * mw.cell + mw.h);
+    unsigned char* step_ws = w + mw.xh + 2 * mw.cell + mw.h + mw.scratch;
+    // per group what cp360_clstm_window does up front, on that group's rows of the joint buffers
+    for (int g = 0; g < n_groups; ++g) {
+        float* mm = minmax + (size_t)g * n_clips * 2;
+        unsigned char* xg = xh + (size_t)g * Mg * (C + H) * es_of(Cl.dtype);
+        if ((rc = cp360_window_minmax(cams[g], mm, scratch + (size_t)g * n_clips * 512, n_clips, per_clip, stride, st))) return rc;
+        if ((rc = cp360_window_normalize(cams[g], mm, xg, Cl.dtype, C + H, C, c[0] + (size_t)g * Mg * H, n_clips, T, 0, P, C, stride, st))) return rc;
+        if ((rc = cp360_window_normalize(cams[g], mm, xg, Cl.dtype, C + H, 0, nullptr, n_clips, T, 0, P, C, stride, st))) return rc;
+    }
+    const float* xn[CP360_MAX_CLIP_GROUPS];
+    for (int t = 0; t < T; ++t) {
+        const bool keep = h_all || t == T - 1;
+        for (int g = 0; g < n_groups; ++g) xn[g] = cams[g] + (size_t)(t + 1) * P * C;   // frame t+1's normalisation rides on the gates
+        const CellIo cell{xh, c[t & 1], c[(t + 1) & 1], keep ? hj : nullptr, t + 1 < T ? xn : nullptr, n_groups, n_clips, minmax, stride};
+        if ((rc = run_clstm(plan, Cl, cell, step_ws, st))) return rc;
+        for (int g = 0; keep && g < n_groups; ++g) {
+            const float* src = hj + (size_t)g * Mg * H;
+            if (h_all && hipMemcpyAsync(h_all[g] + (size_t)t * Mg * H, src, Mg * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+                return CP360_ERR_HIP;
+            if (t == T - 1 && hipMemcpyAsync(h_out[g], src, Mg * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+                return CP360_ERR_HIP;
+        }
+    }
     return CP360_OK;
 }

@@ -520,7 +520,7 @@ __global__ __launch_bounds__(256, 6) void wino_gates_kernel(const float* __restr
                                                          const float* __restrict__ c_prev, float* __restrict__ c_next,
                                                          T* __restrict__ h_out, int ld_h, int h_coff, float* __restrict__ h_f32,
                                                          int tiles, int w, int th_, int Hc, int ldm, int m_pad,
-                                                         const float* __restrict__ x_next, const float* __restrict__ minmax,
+                                                         const bool x_next, const ClipGroups xg, const float* __restrict__ minmax,
                                                          int x_coff, size_t clip_stride) {
     __shared__ f32x4 ex[4][4][64];                                 // [gate][pixel][item]: lanes of a wave touch consecutive 16-byte slots
     const int th = TH ? TH : th_;
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(256, 6) void wino_gates_kernel(const float* __restr
     if (x_next) {
         const int b = (int)(mpx / P), pix = (int)(mpx - (size_t)b * P);
         const float mn = minmax[2 * b], den = minmax[2 * b + 1] - mn;
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x_next + (size_t)b * clip_stride + (size_t)pix * Hc + j);
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(clip_frame(xg, b, clip_stride) + (size_t)pix * Hc + j);
         const float xn[4] = {(xv[0] - mn) / den, (xv[1] - mn) / den, (xv[2] - mn) / den, (xv[3] - mn) / den};
         store4(h_out + mpx * ld_h + x_coff + j, xn);
     }
@@ -733,10 +733,21 @@ extern "C" int cp360_wino_output_input(const cp360_wino_desc* d, const float* m,
 extern "C" int cp360_wino_output_gates(const cp360_wino_desc* d, const float* m, const float* bias, const float* c_prev, float* c_next,
                                        void* h_out, int ld_h, int h_coff, float* h_f32, const float* x_next, const float* minmax,
                                        int x_coff, size_t clip_stride, void* stream) {
+    return cp360_wino_output_gates_groups(d, m, bias, c_prev, c_next, h_out, ld_h, h_coff, h_f32, x_next ? &x_next : nullptr, 1,
+                                          d ? d->n_img / 6 : 0, minmax, x_coff, clip_stride, stream);
+}
+
+extern "C" int cp360_wino_output_gates_groups(const cp360_wino_desc* d, const float* m, const float* bias, const float* c_prev,
+                                              float* c_next, void* h_out, int ld_h, int h_coff, float* h_f32,
+                                              const float* const* x_groups, int n_groups, int group_clips, const float* minmax,
+                                              int x_coff, size_t clip_stride, void* stream) {
     WinoGeom g;
     int rc = wino_check(d, &g);
     if (rc) return rc;
     if (!m || !bias || !c_prev || !c_next || !h_out) return CP360_ERR_NULL;
+    const bool x_next = x_groups != nullptr;
+    ClipGroups xg{};
+    if (x_next && !clip_groups(x_groups, n_groups, group_clips, d->n_img / 6, &xg)) return CP360_ERR_BAD_SHAPE;
     if (d->c_out % 16 != 0) return CP360_ERR_ALIGN;
     const int Hc = d->c_out / 4;
     if (ld_h % 4 != 0 || h_coff % 4 != 0 || h_coff + Hc > ld_h) return CP360_ERR_BAD_SHAPE;
@@ -748,7 +759,7 @@ extern "C" int cp360_wino_output_gates(const cp360_wino_desc* d, const float* m,
     hipStream_t st = (hipStream_t)stream;
 #define CP360_WG(TT, THV)                                                                                                           \
     hipLaunchKernelGGL((wino_gates_kernel<TT, THV>), dim3((unsigned)blocks), dim3(256), 0, st, m, bias, c_prev, c_next, (TT*)h_out, ld_h, \
-                       h_coff, h_f32, g.tiles, d->face, g.th, Hc, g.ldm, g.m_pad, x_next, minmax, x_coff, clip_stride)
+                       h_coff, h_f32, g.tiles, d->face, g.th, Hc, g.ldm, g.m_pad, x_next, xg, minmax, x_coff, clip_stride)
     if (d->dtype == CP360_F16) { if (g.th == 4) CP360_WG(f16_raw, 4); else if (g.th == 8) CP360_WG(f16_raw, 8); else CP360_WG(f16_raw, 0); }
     else { if (g.th == 4) CP360_WG(bf16_raw, 4); else if (g.th == 8) CP360_WG(bf16_raw, 8); else CP360_WG(bf16_raw, 0); }
 #undef CP360_WG

@@ -21,6 +21,7 @@ from . import _lib, ops
 from .model.resnet_cubic import resnet50
 from .model.clstm import ConvLSTMCell
 from .static_model.class_activation_model import cam_device
+from .temporal_model.paired import PairRunner
 from .temporal_model.test_temporal import ClipRunner
 from .utils.cube_to_equi import Cube2Equi
 from .utils.equi_to_cube import Equi2Cube
@@ -90,6 +91,7 @@ class SaliencyEngine:
         self.e2c = Equi2Cube(self.cube_dim, (self.H, self.W), device=self.device, cv_fixed_point=cv_fixed_point)
         self.c2e = Cube2Equi(self.w, align_corners=align_corners, device=self.device)
         self.runner = ClipRunner(self.cell, self.c2e, self.B, self.T, self.w)
+        self.pair = PairRunner(self.runner)                # stream(): two batches' windows in one temporal call
         self.cam = torch.empty((self.B, self.T, 6 * self.w * self.w, input_size), dtype=torch.float32,
                                device=self.device)
         self._mm_host = None                               # pinned copy of the runner's [B, 2] window min / max
@@ -123,7 +125,13 @@ class SaliencyEngine:
         workgroups get its tails and launch gaps: +2-3 % throughput, tools/overlap_probe.py).  Results are the same bits as
         ``__call__`` gives batch by batch (same kernels, same order inside each stage; the two CAM buffers alternate).  Each
         yielded tensor is overwritten two batches later - consume or clone it.  The fp16 range guard polls as in ``__call__``
-        (a switch to bf16 takes effect for the batches whose static stage has not been queued yet)."""
+        (a switch to bf16 takes effect for the batches whose static stage has not been queued yet).
+
+        Where the ConvLSTM is the Winograd plan at B and at 2B clips (``PairRunner.can_pair``: 16-bit, e.g. 4 clips of 7x7
+        faces) the stream runs in PAIRS instead, see ``_stream_paired``: the same bits, map k one batch later."""
+        if self.pair.can_pair():
+            yield from self._stream_paired(batches)
+            return
         if self._cam2 is None:
             self._cam2 = torch.empty_like(self.cam)
             self._side = torch.cuda.Stream(device=self.device)
@@ -172,19 +180,72 @@ class SaliencyEngine:
             if out2[i & 1] is None:
                 out2[i & 1] = torch.empty_like(sal)
             out2[i & 1].copy_(sal)                         # (the runner's map buffer is reused by the next window)
-        if self._guard_on():
-            if not self._first_checked:
-                self._first_checked = True
-                if self.nonfinite():
-                    raise FloatingPointError("fp16 static stage overflowed on the first batch of the stream: build the engine with "
-                                             "static_precision='bf16' (or run one batch through __call__ first, which repairs it)")
-            else:
-                self._queue_flag()
-        self._batch += 1
+        self._stream_guard()
         done = torch.cuda.Event()
         done.record(main)
         temporal_done[i & 1] = done
         return out2[i & 1]
+
+    def _stream_guard(self, minmax=None):
+        """The fp16 range guard behind one batch of a stream (``minmax``: its [B, 2] rows of a paired temporal call)."""
+        if self._guard_on():
+            if not self._first_checked:
+                self._first_checked = True
+                if self.nonfinite(minmax):
+                    raise FloatingPointError("fp16 static stage overflowed on the first batch of the stream: build the engine with "
+                                             "static_precision='bf16' (or run one batch through __call__ first, which repairs it)")
+            else:
+                self._queue_flag(minmax)
+        self._batch += 1
+
+    def _stream_paired(self, batches):
+        """``stream`` where two batches' ConvLSTM windows may share one temporal call: the static stages of batches k and k+1,
+        then ONE run of the T cell updates at 2B clips (PairRunner.run -> cp360_clstm_window_multi), in which every
+        Winograd GEMM launch streams its filters from HBM once for both batches; the two maps are yielded in order, so map k
+        arrives one batch later than from the unpaired stream.  A last odd batch runs alone.  Every GEMM row, transform and
+        gate is the arithmetic of the unpaired call: the same bits as ``__call__``.
+
+        Everything is queued on the caller's stream, stage after stage: with the filters shared a GEMM launch is no longer
+        waiting on HBM, and static-stage workgroups beside it then cost more than they fill (4 clips x 16 frames at
+        1024 x 2048: 11.75 ms per batch in order, 11.88 with the next pair's static stages on a second stream, 12.01 unpaired;
+        docs/rounds/r07_pairing.md).  A yielded tensor is overwritten four batches later."""
+        if self._cam2 is None:
+            self._cam2 = torch.empty_like(self.cam)
+        cams = (self.cam, self._cam2)
+        main = torch.cuda.current_stream(self.device)
+        outs = [None] * 4
+
+        def keep(i, sal):
+            if outs[i & 3] is None:
+                outs[i & 3] = torch.empty_like(sal)
+            outs[i & 3].copy_(sal)                         # (the runner's map buffers are reused by the next window)
+            return outs[i & 3]
+        n = 0
+        for i, frames in enumerate(batches):
+            B, T = frames.shape[:2]
+            if (B, T) != (self.B, self.T):
+                raise ValueError("engine built for %dx%d clips x frames" % (self.B, self.T))
+            if self._guard_on() and self._poll():
+                import warnings
+                warnings.warn("fp16 static stage overflowed on batch(es) %s (their maps are NaN): switching the static stage "
+                              "to bf16" % self.overflow_batches)
+                main.synchronize()
+                self._fallback_to_bf16()
+            n = i + 1
+            with torch.no_grad():
+                self.static_stage(frames.reshape((B * T,) + tuple(frames.shape[2:])), cam=cams[i & 1])
+                if not i & 1:
+                    continue
+                sals = self.pair.run(cams[0], cams[1], return_all_steps=self.return_all_steps)
+                maps = [keep(i - 1, sals[0]), keep(i, sals[1])]
+            for mm in self.pair.minmax.view(2, self.B, 2):
+                self._stream_guard(mm)
+            yield from maps
+        if n & 1:                                          # the last batch has no partner
+            with torch.no_grad():
+                last = keep(n - 1, self.temporal_stage(cams[0]))
+            self._stream_guard()
+            yield last
 
     # ---- hipGraph replay (launch-bound small configurations: one frame / one clip)
     def capture(self, frames):
@@ -216,13 +277,13 @@ class SaliencyEngine:
             if st is not None:
                 st.close()
 
-    def nonfinite(self):
+    def nonfinite(self, minmax=None):
         """True when the last batch's CAM scores held an inf / NaN: the window min / max pairs of that batch (poisoned
         with NaN by the reduction kernel, csrc/misc.hip) read back - 8 bytes per clip and a sync.  With an fp16 static
-        stage this is how activations beyond 65504 show."""
+        stage this is how activations beyond 65504 show.  (``minmax``: a batch's [B, 2] rows of a paired temporal call.)"""
         if self._mm_host is None:
             self._mm_host = torch.empty(tuple(self.runner.minmax.shape), dtype=torch.float32).pin_memory()
-        self._mm_host.copy_(self.runner.minmax, non_blocking=True)
+        self._mm_host.copy_(self.runner.minmax if minmax is None else minmax, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return not bool(torch.isfinite(self._mm_host).all())
 
@@ -237,11 +298,12 @@ class SaliencyEngine:
     def _guard_on(self):
         return self._guard and self.static_precision == 'fp16'
 
-    def _queue_flag(self):
+    def _queue_flag(self, minmax=None):
         """Copy this batch's window min / max pairs to pinned memory behind the batch (8 bytes per clip, no wait)."""
+        minmax = self.runner.minmax if minmax is None else minmax
         host = self._free_hosts.pop() if self._free_hosts else \
             torch.empty(tuple(self.runner.minmax.shape), dtype=torch.float32).pin_memory()
-        host.copy_(self.runner.minmax, non_blocking=True)
+        host.copy_(minmax, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._pending.append((self._batch, ev, host))

@@ -294,3 +294,41 @@ class ClstmStage(_Stage):
         ws = self.ctx.workspace(('window', B, T, w), nbytes)
         check(lib().cp360_clstm_window(self.ctx.h, ptr(cam), int(clip_stride), B, T, w, ptr(xh), ptr(cells[0]), ptr(cells[1]),
                                        ptr(h_out), ptr(h_all), ptr(minmax), ptr(scratch), ptr(ws), ws.numel(), stream()))
+
+    def can_pair(self, B, w, groups=2):
+        """True when the windows of ``groups`` batches of B clips may run as ONE cp360_clstm_window_multi call and give the bits
+        of one cp360_clstm_window call per batch: the cell update is the Winograd plan at B clips AND at groups * B clips
+        (every GEMM row is computed independently of the others and there is no split-K; on the direct kernels the tile and
+        split choice depends on the clip count).  Packs the Winograd filters when a shape asks for them."""
+        self._load(w)
+        state = lib().cp360_clstm_wino_state
+        if state(self.ctx.h, int(B), int(w)) == 0 or state(self.ctx.h, int(groups * B), int(w)) == 0:
+            return False                                   # (before any packing: a shape that stays direct needs no filters)
+        self._load_wino(B, w)
+        return state(self.ctx.h, int(B), int(w)) == 1 and state(self.ctx.h, int(groups * B), int(w)) == 1
+
+    def window_multi(self, cams, B, T, w, h_outs, minmax, clip_stride=0, h_alls=None):
+        """cp360_clstm_window_multi: the windows of len(cams) batches of B clips each in one run of the T cell updates.
+        cams / h_outs / h_alls: one tensor per batch, each as ``window``'s cam / h_out / h_all; minmax f32 [len(cams) * B, 2]."""
+        self._load(w)
+        G = len(cams)
+        self._load_wino(G * B, w)
+        c = self.cell
+        if len(h_outs) != G or (h_alls is not None and len(h_alls) != G):
+            raise ValueError("one h_out (and h_all) per cam buffer")
+        require_gpu(minmax, *cams, *h_outs, *(h_alls or ()))
+        P, Cc, Hh = 6 * w * w, c.input_size, c.hidden_size
+        stride = int(clip_stride) or T * P * Cc
+        for name, ts, n in (('cam', cams, (B - 1) * stride + T * P * Cc), ('h_out', h_outs, 6 * B * w * w * Hh),
+                            ('h_all', h_alls or (), T * 6 * B * w * w * Hh), ('minmax', (minmax,), 2 * G * B)):
+            for t in ts:
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+                    raise ValueError("%s must be a contiguous f32 tensor of at least %d elements" % (name, n))
+        nbytes = lib().cp360_clstm_window_multi_workspace_bytes(self.ctx.h, G, B, T, w)
+        if nbytes == 0:
+            raise ValueError("unsupported window geometry (needs input_size == hidden_size and at most 4 batches)")
+        ws = self.ctx.workspace(('window_multi', G, B, T, w), nbytes)
+        arr = lambda ts: (C.c_void_p * G)(*[t.data_ptr() for t in ts])
+        check(lib().cp360_clstm_window_multi(self.ctx.h, arr(cams), int(clip_stride), G, B, T, w, arr(h_outs),
+                                             arr(h_alls) if h_alls is not None else None, ptr(minmax), ptr(ws), ws.numel(),
+                                             stream()))

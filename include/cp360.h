@@ -286,6 +286,15 @@ int cp360_lstm_gates_next(const float* gates_partial, int splits, const float* b
                           int ld_h, int h_coff, float* h_f32, int M, int Hc, int slab_rows,
                           const float* x_next, const float* minmax, int x_coff, int P, size_t clip_stride,
                           void* stream);
+/* The same when the clips sit in n_groups separately allocated buffers of group_clips clips each (cp360_clstm_window_multi):
+ * clip b's frame is at x_groups[b / group_clips] + (b % group_clips) * clip_stride; x_groups is a HOST array of
+ * 1 .. CP360_MAX_CLIP_GROUPS device pointers, minmax [M/P, 2] covers all clips.  One group = cp360_lstm_gates_next. */
+#define CP360_MAX_CLIP_GROUPS 4
+int cp360_lstm_gates_next_groups(const float* gates_partial, int splits, const float* bias,
+                                 const float* c_prev, float* c_next, void* h_out, int h_dtype,
+                                 int ld_h, int h_coff, float* h_f32, int M, int Hc, int slab_rows,
+                                 const float* const* x_groups, int n_groups, int group_clips, const float* minmax,
+                                 int x_coff, int P, size_t clip_stride, void* stream);
 
 /* ------------------------------------------------------------------ K5t: ConvLSTM training
  * The backward pass of one cell update (model/clstm.py:54-80) and of the saliency map (to_equi_nn + channel max), for
@@ -372,6 +381,10 @@ int cp360_wino_output(const cp360_wino_desc* d, const float* m, const float* bia
 int cp360_wino_output_gates(const cp360_wino_desc* d, const float* m, const float* bias, const float* c_prev, float* c_next,
                             void* h_out, int ld_h, int h_coff, float* h_f32, const float* x_next, const float* minmax,
                             int x_coff, size_t clip_stride, void* stream);
+/* x_next in n_groups buffers of group_clips clips each: as cp360_lstm_gates_next_groups. */
+int cp360_wino_output_gates_groups(const cp360_wino_desc* d, const float* m, const float* bias, const float* c_prev, float* c_next,
+                                   void* h_out, int ld_h, int h_coff, float* h_f32, const float* const* x_groups, int n_groups,
+                                   int group_clips, const float* minmax, int x_coff, size_t clip_stride, void* stream);
 /* cp360_wino_output of THIS convolution fused with cp360_wino_input of the NEXT one (same faces, next c_in = this c_out, dense
  * pixels): v_next = what cp360_wino_input would make of this convolution's output, bit for bit, in one launch and without the
  * activation tensor.  Faces up to 9 x 9 (a cube's 32-channel image in LDS); larger: CP360_ERR_UNSUPPORTED, run the two calls. */
@@ -779,6 +792,20 @@ size_t cp360_clstm_window_workspace_bytes(cp360_ctx* ctx, int n_clips, int T, in
 int cp360_clstm_window(cp360_ctx* ctx, const float* cam, size_t clip_stride, int n_clips, int T, int face, void* xh,
                        float* cell0, float* cell1, float* h_out, float* h_all, float* minmax, float* mm_scratch,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The windows of n_groups independent batches of n_clips clips each in ONE run of the T cell updates, at n_groups * n_clips
+ * clips: the batches' CAM buffers stay where they are (cams: a HOST array of n_groups device pointers, each as
+ * cp360_clstm_window's cam with the same clip_stride), the fused [x | h] buffer and the cell state for all clips are built in
+ * the workspace.  With the Winograd plan at both clip counts every row of every GEMM is computed as in n_groups
+ * cp360_clstm_window calls (rows are independent, no split-K): the same bits, and each launch streams the filters once for all
+ * groups.  (On the direct kernels the split counts depend on the clip count: right, not bit-equal.)
+ *   h_out     HOST array of n_groups device pointers, each f32 [6 n_clips, face, face, H]
+ *   h_all     NULL, or a HOST array of n_groups device pointers, each f32 [T, 6 n_clips, face, face, H]
+ *   minmax    f32 [n_groups * n_clips, 2] (out): group g's rows start at row g * n_clips
+ * 1 <= n_groups <= CP360_MAX_CLIP_GROUPS.  workspace: cp360_clstm_window_multi_workspace_bytes (256-byte aligned). */
+size_t cp360_clstm_window_multi_workspace_bytes(cp360_ctx* ctx, int n_groups, int n_clips, int T, int face);
+int cp360_clstm_window_multi(cp360_ctx* ctx, const float* const* cams, size_t clip_stride, int n_groups, int n_clips, int T,
+                             int face, float* const* h_out, float* const* h_all, float* minmax, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* The launch plan cp360_resnet_forward would follow for n_img faces of cube_dim^2, one line per layer: which fused kernel or
  * generic path runs (the fused Bottleneck kernels are specialised to 16-bit types and the face sizes of cube 224 / 512; any
