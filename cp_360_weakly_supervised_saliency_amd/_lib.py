@@ -72,6 +72,8 @@ PUBLIC_SYMBOLS = [
     'cp360_fix_work_bytes', 'cp360_fix_counts', 'cp360_fix_density', 'cp360_fix_sauc',
     # K16: the camera path by dynamic programming
     'cp360_path_table_bytes', 'cp360_path_table_host', 'cp360_path_work_bytes', 'cp360_view_path', 'cp360_view_refine',
+    # K17: ground truth from head tracking
+    'cp360_head_footprints', 'cp360_head_agreement',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -303,6 +305,8 @@ def lib():
     L.cp360_path_work_bytes.argtypes = [i, i, i]
     L.cp360_view_path.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, sz, vp]
     L.cp360_view_refine.argtypes = [vp, vp, i, i, i, dbl, vp, vp, sz, vp]
+    L.cp360_head_footprints.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, sz, vp]
+    L.cp360_head_agreement.argtypes = [vp, dbl, dbl, vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)        # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

@@ -74,8 +74,6 @@ FixLayout fix_layout(int F, int h, int w) {
 
 __device__ __forceinline__ bool fix_finite(double v) { return fabs(v) < INFINITY; }
 
-__device__ __forceinline__ int fix_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // the pixel of (lon, lat); false for a point that contributes nothing
 __device__ __forceinline__ bool fix_bin(double lon, double lat, int h, int w, int& x, int& y) {
     if (!fix_finite(lon) || !fix_finite(lat)) return false;
@@ -87,12 +85,6 @@ __device__ __forceinline__ bool fix_bin(double lon, double lat, int h, int w, in
     const double yf = floor(v);
     y = yf < 0.0 ? 0 : (yf > (double)(h - 1) ? h - 1 : (int)yf);
     return true;
-}
-
-// the points of frame f, inside 0 .. N whatever the offsets hold
-__device__ __forceinline__ void fix_range(const int* __restrict__ offsets, int f, int N, int& k0, int& k1) {
-    k0 = fix_clamp(offsets[f], 0, N);
-    k1 = fix_clamp(offsets[f + 1], k0, N);
 }
 
 // ------------------------------------------------------------------ K15a: counts

@@ -1,8 +1,9 @@
-// The sphere geometry of an equirectangular image, shared by stabilize.hip (K11), viewport.hip (K12), sphere_eval.hip (K14) and
-// fixations.hip (K15): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables of the pixel centres
-// and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry; tests/stabilize_restate.py restates it);
-// and what their kernels and entry points repeat: the von Mises-Fisher term, the ordered sum of a 256-thread workgroup, how a
-// caller's workspace is opened and the dispatch on the pixel type (DESIGN.md "What the sphere kernels share").
+// The sphere geometry of an equirectangular image, shared by stabilize.hip (K11), viewport.hip (K12), sphere_eval.hip (K14),
+// fixations.hip (K15) and headtrack.hip (K17): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
+// of the pixel centres and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry;
+// tests/stabilize_restate.py restates it); and what their kernels and entry points repeat: the von Mises-Fisher term, whether a
+// direction lies in a camera's view, the items of a frame in CSR form, the ordered sum of a 256-thread workgroup, how a caller's
+// workspace is opened and the dispatch on the pixel type (DESIGN.md "What the sphere kernels share").
 //
 //     theta = (2 (x + 1/2) / W - 1) pi        phi = (1 - 2 (y + 1/2) / H) pi / 2        dir = (cos phi cos theta, sin phi, cos phi sin theta)
 //     pix(q): theta = atan2(q_z, q_x), phi = asin(clamp(q_y, -1, 1)), x = (theta / pi + 1) W / 2 - 1/2, y = (1 - phi / (pi / 2)) H / 2 - 1/2
@@ -106,6 +107,39 @@ __global__ __launch_bounds__(256) void stab_tables_kernel(float2* __restrict__ t
 __device__ __forceinline__ float vmf(float kappa, float px, float py, float pz, float qx, float qy, float qz) {
     const float dot = px * qx + py * qy + pz * qz;
     return expf(kappa * (dot - 1.f));
+}
+
+// ------------------------------------------------------------------ the view of a camera on the panorama (K17; K12b's decision)
+// A camera is K12's: camera-to-world, columns (forward, up, right).  view_rot loads one for view_inside: a camera with a
+// non-finite entry comes back all NaN, so that every comparison below fails - its view is empty.
+__device__ __forceinline__ Rot view_rot(const float* R) {
+    Rot r = load_rot(R);
+    const float s = fabsf(r.r00) + fabsf(r.r01) + fabsf(r.r02) + fabsf(r.r10) + fabsf(r.r11) + fabsf(r.r12) + fabsf(r.r20) +
+                    fabsf(r.r21) + fabsf(r.r22);
+    if (!isfinite(s)) r.r00 = r.r01 = r.r02 = r.r10 = r.r11 = r.r12 = r.r20 = r.r21 = r.r22 = NAN;
+    return r;
+}
+
+__device__ __forceinline__ bool view_rot_finite(const Rot& r) { return r.r00 == r.r00; }   // of view_rot's result
+
+// whether the direction p lies in the view of the camera R (from view_rot) with the tangents tx = tan(hfov / 2), ty = tx h / w:
+// d = R^T p = (d_f, d_u, d_r), u = d_r / d_f, v = d_u / d_f, inside <=> d_f > 0, |u| <= tx, |v| <= ty - view_outline_kernel's
+// terms in its order
+__device__ __forceinline__ bool view_inside(const Rot& R, float tx, float ty, float px, float py, float pz) {
+    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
+    const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
+    const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
+    const float au = fabsf(dr / df), av = fabsf(du / df);
+    return df > 0.f && au <= tx && av <= ty;
+}
+
+// ------------------------------------------------------------------ items in CSR form (K15's points, K17's cameras)
+__device__ __forceinline__ int fix_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the items of frame f, inside 0 .. N whatever the offsets hold
+__device__ __forceinline__ void fix_range(const int* __restrict__ offsets, int f, int N, int& k0, int& k1) {
+    k0 = fix_clamp(offsets[f], 0, N);
+    k1 = fix_clamp(offsets[f + 1], k0, N);
 }
 
 // ------------------------------------------------------------------ the ordered sum of a 256-thread workgroup

@@ -1845,3 +1845,68 @@ def shuffled_auc(S, pos, neg, work=None):
     check(lib().cp360_fix_sauc(ptr(S), ptr(pos), ptr(neg), int(neg.shape[0]), F, h, w, ptr(auc), ptr(c_tot), ptr(a_neg), ptr(work),
                                work.numel() * 8, stream()))
     return auc, c_tot, a_neg
+
+
+# ----------------------------------------------------------------------------- K17: head-tracking ground truth (csrc/headtrack.hip)
+def _head_view(view_hw, hfov_deg):
+    """A view (h_v, w_v) of hfov_deg degrees -> (hfov in radians, the aspect h_v / w_v) as the library takes it."""
+    hv, wv = (float(v) for v in view_hw)
+    hfov_deg = float(hfov_deg)
+    if not (hv > 0.0 and wv > 0.0 and math.isfinite(hv / wv) and hv / wv > 0.0 and 0.0 < hfov_deg < 180.0):
+        raise ValueError("a view needs h_v, w_v > 0 and 0 < hfov_deg < 180, got %r, %r" % (view_hw, hfov_deg))
+    return math.radians(hfov_deg), hv / wv
+
+
+def _head_cameras(R, offsets, hw):
+    """The checks the two head ops share -> (N, F, h, w)."""
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3):
+        raise ValueError("R must be float32 [N, 3, 3], got %s" % (tuple(R.shape),))
+    _check_buf('R', R, torch.float32)
+    if offsets.dim() != 1 or offsets.shape[0] < 2 or offsets.device != R.device:
+        raise ValueError("offsets must be int32 [F + 1] with F >= 1 on R's device, got %s" % (tuple(offsets.shape),))
+    _check_buf('offsets', offsets, torch.int32)
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError("the grid must be at least 1 x 1, got %d x %d" % (h, w))
+    return int(R.shape[0]), int(offsets.shape[0]) - 1, h, w
+
+
+def head_work(h, w, device, work=None):
+    """The workspace of the two head ops, the grid's tables: `work` when it is large enough, else a new one."""
+    return _work(lib().cp360_fix_work_bytes, "head tracking", 0, h, w, device, work, " (h w <= 2^21)")
+
+
+def head_footprints(R, offsets, hw, view_hw, hfov_deg, work=None):
+    """cp360_head_footprints: the viewers' cameras R f32 [N, 3, 3] (camera-to-world, columns forward / up / right), offsets int32
+    [F + 1] (CSR: frame f owns the cameras offsets[f] .. offsets[f + 1] - 1), each with the view (view_hw, hfov_deg) ->
+    (counts int32 [F, h, w] = the number of the frame's cameras that have the grid pixel in view, n_views int32 [F] = the number
+    of its finite cameras), both on the device, without a synchronisation.  A non-finite camera sees nothing."""
+    require_gpu(R, offsets, work)
+    N, F, h, w = _head_cameras(R, offsets, hw)
+    hfov, aspect = _head_view(view_hw, hfov_deg)
+    work = head_work(h, w, R.device, work)
+    counts = torch.empty((F, h, w), dtype=torch.int32, device=R.device)
+    n_views = torch.empty((F,), dtype=torch.int32, device=R.device)
+    check(lib().cp360_head_footprints(ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(counts), ptr(n_views), ptr(work),
+                                      work.numel() * 8, stream()))
+    return counts, n_views
+
+
+def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
+    """cp360_head_agreement: the camera Rc f32 [F, 3, 3] with cam_view = ((h_c, w_c), hfov_deg) against every viewer of its frame
+    (R, offsets as in ``head_footprints``, view = ((h_v, w_v), hfov_deg)); weights int32 [h] (``sphere_eval_weights``) -> (inter
+    int64 [N], uni int64 [N]): the weighted pixels inside both windows and inside either, on the device, without a
+    synchronisation."""
+    require_gpu(Rc, R, offsets, weights, work)
+    N, F, h, w = _head_cameras(R, offsets, hw)
+    _stab_rotations(Rc, F)
+    if Rc.device != R.device or tuple(weights.shape) != (h,) or weights.device != R.device:
+        raise ValueError("Rc [%d, 3, 3] and weights int32 [%d] must be on R's device" % (F, h))
+    _check_buf('weights', weights, torch.int32)
+    (cam_hfov, cam_aspect), (hfov, aspect) = _head_view(*cam_view), _head_view(*view)
+    work = head_work(h, w, R.device, work)
+    inter = torch.empty((N,), dtype=torch.int64, device=R.device)
+    uni = torch.empty((N,), dtype=torch.int64, device=R.device)
+    check(lib().cp360_head_agreement(ptr(Rc), cam_hfov, cam_aspect, ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
+                                     ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
+    return inter, uni

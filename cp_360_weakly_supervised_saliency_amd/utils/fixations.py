@@ -28,42 +28,59 @@ def _unit(lon, lat):
     return np.stack([cl * np.cos(lon), np.sin(lat), cl * np.sin(lon)], axis=-1)
 
 
+def _frame_times(fps, n_frames, max_gap):
+    """The checks of the scan-path functions -> (the frames' times (f + 0.5) / fps float64 [n_frames], max_gap)."""
+    fps, n_frames, max_gap = float(fps), int(n_frames), float(max_gap)
+    if not fps > 0.0 or n_frames < 1 or not max_gap >= 0.0:
+        raise ValueError("fps > 0, n_frames >= 1 and max_gap >= 0 are needed, got %r, %r, %r" % (fps, n_frames, max_gap))
+    return (np.arange(n_frames, dtype=np.float64) + 0.5) / fps, max_gap
+
+
+def _track_directions(v, t, lon, lat, tf, max_gap):
+    """Viewer v's direction at the times tf: (p float64 [F, 3], ok bool [F], i0, i1 int [F], s float64 [F]) - the unit direction
+    by spherical linear interpolation between the samples i0 and i1 at the fraction s, and whether the viewer gives one to the
+    frame; None for an empty track.  ``scanpaths_to_points`` and ``headtrack.head_cameras`` both take their directions from here."""
+    t, lon, lat = (np.asarray(a, np.float64).reshape(-1) for a in (t, lon, lat))
+    if not (t.shape == lon.shape == lat.shape):
+        raise ValueError("viewer %d: t, lon and lat must be as long, got %d, %d, %d" % (v, t.size, lon.size, lat.size))
+    if t.size == 0:
+        return None
+    if np.any(np.diff(t) < 0.0) or not np.all(np.isfinite(t)):
+        raise ValueError("viewer %d: t must be finite and ascending" % v)
+    i1 = np.searchsorted(t, tf, side='left')                           # the first sample at or after the frame's time
+    inside = (tf >= t[0]) & (tf <= t[-1])
+    i1 = np.clip(i1, 0, t.size - 1)
+    i0 = np.where(t[i1] == tf, i1, np.maximum(i1 - 1, 0))              # on a sample: that sample alone
+    dt = t[i1] - t[i0]
+    ok = inside & (dt <= max_gap)
+    a, b = _unit(lon[i0], lat[i0]), _unit(lon[i1], lat[i1])
+    with np.errstate(all='ignore'):
+        s = np.where(dt > 0.0, (tf - t[i0]) / np.where(dt > 0.0, dt, 1.0), 0.0)
+        omega = np.arctan2(np.linalg.norm(np.cross(a, b), axis=-1), np.sum(a * b, axis=-1))
+        so = np.sin(omega)
+        small = so < 1e-12                                             # the same direction (or opposite ones: no great circle)
+        wa = np.where(small, 1.0 - s, np.sin((1.0 - s) * omega) / np.where(small, 1.0, so))
+        wb = np.where(small, s, np.sin(s * omega) / np.where(small, 1.0, so))
+        p = wa[:, None] * a + wb[:, None] * b
+        p = p / np.linalg.norm(p, axis=-1, keepdims=True)
+    ok &= np.all(np.isfinite(p), axis=-1)
+    return p, ok, i0, i1, s
+
+
 def scanpaths_to_points(tracks, fps, n_frames, max_gap=0.5):
     """tracks: one ``(t, lon, lat)`` per viewer, t in seconds ascending, angles in radians -> (lonlat float64 [N, 2], offsets
     int32 [n_frames + 1]), frame by frame, viewers in their order.  Frame f takes each viewer's direction at (f + 0.5) / fps by
     spherical linear interpolation between the two bracketing samples; a viewer gives no point to a frame outside the track's
     span, between samples more than max_gap seconds apart, or between samples that are not finite."""
-    fps, n_frames, max_gap = float(fps), int(n_frames), float(max_gap)
-    if not fps > 0.0 or n_frames < 1 or not max_gap >= 0.0:
-        raise ValueError("fps > 0, n_frames >= 1 and max_gap >= 0 are needed, got %r, %r, %r" % (fps, n_frames, max_gap))
-    tf = (np.arange(n_frames, dtype=np.float64) + 0.5) / fps
+    tf, max_gap = _frame_times(fps, n_frames, max_gap)
+    n_frames = tf.size
     lon_out = np.full((len(tracks), n_frames), np.nan)
     lat_out = np.full((len(tracks), n_frames), np.nan)
     for v, (t, lon, lat) in enumerate(tracks):
-        t, lon, lat = (np.asarray(a, np.float64).reshape(-1) for a in (t, lon, lat))
-        if not (t.shape == lon.shape == lat.shape):
-            raise ValueError("viewer %d: t, lon and lat must be as long, got %d, %d, %d" % (v, t.size, lon.size, lat.size))
-        if t.size == 0:
+        found = _track_directions(v, t, lon, lat, tf, max_gap)
+        if found is None:
             continue
-        if np.any(np.diff(t) < 0.0) or not np.all(np.isfinite(t)):
-            raise ValueError("viewer %d: t must be finite and ascending" % v)
-        i1 = np.searchsorted(t, tf, side='left')                       # the first sample at or after the frame's time
-        inside = (tf >= t[0]) & (tf <= t[-1])
-        i1 = np.clip(i1, 0, t.size - 1)
-        i0 = np.where(t[i1] == tf, i1, np.maximum(i1 - 1, 0))          # on a sample: that sample alone
-        dt = t[i1] - t[i0]
-        ok = inside & (dt <= max_gap)
-        a, b = _unit(lon[i0], lat[i0]), _unit(lon[i1], lat[i1])
-        with np.errstate(all='ignore'):
-            s = np.where(dt > 0.0, (tf - t[i0]) / np.where(dt > 0.0, dt, 1.0), 0.0)
-            omega = np.arctan2(np.linalg.norm(np.cross(a, b), axis=-1), np.sum(a * b, axis=-1))
-            so = np.sin(omega)
-            small = so < 1e-12                                         # the same direction (or opposite ones: no great circle)
-            wa = np.where(small, 1.0 - s, np.sin((1.0 - s) * omega) / np.where(small, 1.0, so))
-            wb = np.where(small, s, np.sin(s * omega) / np.where(small, 1.0, so))
-            p = wa[:, None] * a + wb[:, None] * b
-            p = p / np.linalg.norm(p, axis=-1, keepdims=True)
-        ok &= np.all(np.isfinite(p), axis=-1)
+        p, ok = found[:2]
         lon_out[v, ok] = np.arctan2(p[ok, 2], p[ok, 0])
         lat_out[v, ok] = np.arcsin(np.clip(p[ok, 1], -1.0, 1.0))
     keep = np.isfinite(lon_out).T                                      # [F, V]: frame by frame, viewers in order

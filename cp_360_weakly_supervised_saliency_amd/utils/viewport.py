@@ -168,6 +168,14 @@ class ViewportPilot:
         frames, R = on_device(frames, self.device), on_device(R, self.device, torch.float32)
         return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=self._tab_work(frames))
 
+    def agreement(self, R_cam, R, offsets, head=None):
+        """The cameras R_cam [F, 3, 3] (``path``) with this pilot's view against the viewers' head cameras R [N, 3, 3], offsets
+        [F + 1] (``headtrack.head_cameras``) -> ``headtrack.HeadAgreement``: how much of what the people had in view is in the
+        pilot's frame.  ``head``: the ``headtrack.HeadMaps`` that holds the grid and the viewers' window (default: its defaults)."""
+        from .headtrack import HeadMaps                                 # headtrack imports look_at from here
+        head = head or HeadMaps(device=self.device)
+        return head.agreement(R_cam, self.hw, self.hfov_deg, R, offsets)
+
     def follow(self, frames, maps, cuts=None):
         """frames u8 [F, H, W, 3], maps f32 [F, hm, wm] (one per frame, e.g. ``SaliencyEngine(.., return_all_steps=True)``'s
         output) -> (views u8 [F, h, w, 3], R f32 [F, 3, 3]) on the device; the frames keep their own resolution.  ``cuts``: as

@@ -683,6 +683,34 @@ int cp360_fix_density(const double* lonlat, const int32_t* offsets, long long N,
 int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t* neg, int Fn, int F, int h, int w, double* auc,
                    long long* c_tot, long long* a_neg, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K17: ground truth from head tracking
+ * A headset logs the head's orientation: what a viewer saw is the headset's window, the view of a camera in K12's convention
+ * (R f32 [3, 3] camera-to-world, columns forward / up / right).  A video's viewers are N cameras in CSR form: R f32 [N, 3, 3] (may
+ * be NULL when N = 0), offsets int32 [F + 1] ascending from 0 to N as for K15 (DEVICE memory; whatever it holds, every access
+ * stays inside R).  A view is (hfov_rad, aspect = h_v / w_v): tx = tan(hfov_rad / 2), ty = tx aspect in double, each rounded to
+ * f32 once.  The direction p = dir(x, y) of a grid pixel is inside the view of R <=> d_f > 0, |d_r / d_f| <= tx and |d_u / d_f| <= ty
+ * with (d_f, d_u, d_r) = R^T p in f32, term by term as cp360_view_outline decides it (the pixels its frame encloses); a camera with
+ * a non-finite entry has an empty view.  The specification is the package's own, DESIGN.md "K17", restated in
+ * tests/headtrack_restate.py.
+ *
+ *   footprints  counts int32 [F, h, w] = the number of frame f's cameras whose view holds the pixel, n_views int32 [F] = the number
+ *               of its finite cameras: counts / n_views is the share of the viewers who had the pixel in view.
+ *   agreement   Rc f32 [F, 3, 3], the camera that is judged, one per frame, with its own view (cam_hfov_rad, cam_aspect); weights
+ *               int32 [h] as for cp360_seval_scores (DEVICE memory, clamped to 0 .. 1024) -> inter, uni int64 [N]: for viewer k of
+ *               frame f, inter[k] = sum of a_y over the pixels inside both views, uni[k] = over the pixels inside either;
+ *               inter / uni is the intersection over union of the two windows on the sphere.  A non-finite viewer: inter = 0, uni
+ *               = the area of Rc[f]'s view; a non-finite Rc[f] is an empty view.
+ * Both decide with the one function, so inter, uni and counts agree pixel for pixel.  Exact integers, no atomics: a frame's
+ * counts and a pair's sums are bit-identical between runs and whatever F, N and their place in the batch.
+ * work: 16-byte aligned device memory of cp360_fix_work_bytes(0, h, w) bytes (K11's tables, which every call rebuilds); too small:
+ * CP360_ERR_BAD_SHAPE.  F, h or w < 1, N < 0, hfov_rad outside (0, pi), aspect <= 0 or a tangent that is not finite in f32:
+ * CP360_ERR_BAD_SHAPE; F > 65535, h w > 2^21 or N >= 2^31: CP360_ERR_UNSUPPORTED.  N = 0 is valid.  Asynchronous on the stream. */
+int cp360_head_footprints(const float* R, const int32_t* offsets, long long N, int F, int h, int w, double hfov_rad, double aspect,
+                          int32_t* counts, int32_t* n_views, void* work, size_t work_bytes, void* stream);
+int cp360_head_agreement(const float* Rc, double cam_hfov_rad, double cam_aspect, const float* R, const int32_t* offsets,
+                         long long N, int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
+                         long long* uni, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with

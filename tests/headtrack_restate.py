@@ -1,0 +1,184 @@
+"""Numpy restatement of the head-tracking ground truth (K17, csrc/headtrack.hip and utils/headtrack.py; the specification is
+DESIGN.md "K17").  A viewer is a camera of the viewport pilot (tests/viewport_restate.py): R [3, 3], camera-to-world, columns
+(forward, up, right); a view is ((h_v, w_v), hfov_deg) with tx = tan(hfov / 2), ty = tx h_v / w_v.
+
+    inside      d = R^T dir(x, y) = (d_f, d_u, d_r), u = d_r / d_f, v = d_u / d_f: d_f > 0, |u| <= tx, |v| <= ty - the pixels that
+                ``viewport_restate.outline``'s frame encloses, from its own u, v, d_f and thresholds; a non-finite R sees nothing
+    footprints  counts[f, y, x] = the number of frame f's cameras with the pixel inside, n_views[f] = its finite cameras
+    agreement   inter[k] = sum a_y [in_cam(f_k) and in_view(k)], uni[k] = sum a_y [in_cam(f_k) or in_view(k)], a_y the integer row
+                weights of K13 (``ops.shot_weights_host``) or 1024
+
+``dtype=np.float32`` evaluates every term in float32, operation by operation as the kernels do.  ``classify`` says which (camera,
+pixel) pairs float32 cannot decide: |u| or |v| within 8 d32 of its threshold, d32 as in tests/test_viewport_gpu.py::outline_case,
+the largest float32-to-float64 difference of u, v and the thresholds where d_f > 0.1.  Nothing here imports the code under test
+but the hash generator and the host table of the row weights.
+"""
+import functools
+
+import numpy as np
+
+from cp_360_weakly_supervised_saliency_amd import ops
+from cp_360_weakly_supervised_saliency_amd.utils import hashrng
+from tests import viewport_restate as vr
+
+
+def tangents(view, dtype=np.float64):
+    """(tx, ty) as the library rounds them: tan(hfov / 2) and tan(hfov / 2) (h_v / w_v) in float64, each rounded once to dtype."""
+    (hv, wv), hfov_deg = view
+    t = np.tan(0.5 * np.deg2rad(float(hfov_deg)))
+    return dtype(t), dtype(t * (float(hv) / float(wv)))
+
+
+def inside(R, h, w, view, dtype=np.float64):
+    """One camera on the h x w grid -> (mask bool [h, w], u, v, d_f [h, w] in dtype, (tx, ty) in dtype)."""
+    hw, hfov_deg = view
+    _, u, v, df, _ = vr.outline(R, h, w, hw, hfov_deg, 1, dtype)
+    tx, ty = tangents(view, dtype)                                     # outline's own, but for the last bit of t h / w in float64
+    with np.errstate(invalid='ignore'):
+        mask = (df > 0) & (np.abs(u) <= tx) & (np.abs(v) <= ty)
+    if not np.all(np.isfinite(np.asarray(R, np.float64))):
+        mask = np.zeros((h, w), bool)
+    return mask, u, v, df, (tx, ty)
+
+
+def masks(R, h, w, view, dtype=np.float64):
+    """R [N, 3, 3] -> bool [N, h, w]."""
+    return np.stack([inside(r, h, w, view, dtype)[0] for r in R]) if len(R) else np.zeros((0, h, w), bool)
+
+
+def frame_of(offsets, N):
+    """The frame of every camera: offsets[f] <= k < offsets[f + 1]."""
+    return np.searchsorted(np.asarray(offsets)[1:], np.arange(N), side='right')
+
+
+def footprints(R, offsets, h, w, view, dtype=np.float64):
+    """-> (counts int64 [F, h, w], n_views int64 [F])."""
+    offsets = np.asarray(offsets)
+    F = len(offsets) - 1
+    m = masks(R, h, w, view, dtype)
+    counts, n_views = np.zeros((F, h, w), np.int64), np.zeros(F, np.int64)
+    for f in range(F):
+        k0, k1 = int(offsets[f]), int(offsets[f + 1])
+        counts[f] = m[k0:k1].sum(axis=0)
+        n_views[f] = sum(bool(np.all(np.isfinite(np.asarray(r, np.float64)))) for r in R[k0:k1])
+    return counts, n_views
+
+
+def row_weights(h, mode):
+    return ops.shot_weights_host(h)[0].astype(np.int64) if mode == 'solid_angle' else np.full(h, 1024, np.int64)
+
+
+def agreement(Rc, cam_view, R, offsets, h, w, view, weights, dtype=np.float64):
+    """-> (inter int64 [N], uni int64 [N]); weights: int [h]."""
+    a = np.asarray(weights, np.int64)[:, None]
+    mc, mv = masks(Rc, h, w, cam_view, dtype), masks(R, h, w, view, dtype)
+    fr = frame_of(offsets, len(R))
+    inter = np.array([int((a * (mc[fr[k]] & mv[k])).sum()) for k in range(len(R))], np.int64)
+    uni = np.array([int((a * (mc[fr[k]] | mv[k])).sum()) for k in range(len(R))], np.int64)
+    return inter, uni
+
+
+def classify(R, h, w, view):
+    """R [N, 3, 3] (as the device holds them: float32 values) -> (inside bool [N, h, w] in float64, undecided bool [N, h, w])."""
+    ins, und = np.zeros((len(R), h, w), bool), np.zeros((len(R), h, w), bool)
+    for n, r in enumerate(R):
+        r = np.asarray(r, np.float32).astype(np.float64)
+        if not np.all(np.isfinite(r)):
+            continue
+        m64, u64, v64, f64, thr64 = inside(r, h, w, view)
+        _, u32, v32, _, thr32 = inside(r, h, w, view, np.float32)
+        front = f64 > 0.1
+        d32 = max(float(np.max(np.abs(u32 - u64)[front])), float(np.max(np.abs(v32 - v64)[front])),
+                  max(abs(float(a) - float(b)) for a, b in zip(thr32, thr64)))
+        with np.errstate(invalid='ignore'):
+            und[n] = (np.abs(np.abs(u64) - thr64[0]) <= 8 * d32) | (np.abs(np.abs(v64) - thr64[1]) <= 8 * d32)
+        ins[n] = m64
+    return ins, und
+
+
+# ----------------------------------------------------------------------------- test inputs shared by the CPU and GPU tests
+VIEW_A, VIEW_B = ((9, 16), 100.0), ((10, 10), 110.0)
+CHUNK = 64                                                             # kHeadChunk of csrc/headtrack.hip
+
+
+def random_cameras(seed, n):
+    """n rotations from hashed unit quaternions, rounded to float32: float32 [n, 3, 3]."""
+    q = hashrng.normal(seed, (n, 4), dtype=np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    a, b, c, d = q.T
+    R = np.stack([np.stack([a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c)], -1),
+                  np.stack([2 * (b * c + a * d), a * a - b * b + c * c - d * d, 2 * (c * d - a * b)], -1),
+                  np.stack([2 * (b * d - a * c), 2 * (c * d + a * b), a * a - b * b - c * c + d * d], -1)], 1)
+    return R.astype(np.float32)
+
+
+def rolled_pole_camera(sign, roll):
+    """The camera that looks at a pole (sign +1: north) with the right (0, 0, 1), rolled by `roll` radians: float64 [3, 3]."""
+    f, right = np.array([0.0, float(sign), 0.0]), np.array([0.0, 0.0, 1.0])
+    up = np.cross(right, f)
+    return np.stack([f, np.cos(roll) * up + np.sin(roll) * right, np.cos(roll) * right - np.sin(roll) * up], 1)
+
+
+def _offsets(per_frame):
+    return np.concatenate([[0], np.cumsum(per_frame)]).astype(np.int32)
+
+
+# name -> (grid, viewers per frame, the viewers' view, the camera's view, weights, seed)
+CASES = {
+    'one_frame_5x9': ((5, 9), [CHUNK + 6], VIEW_B, VIEW_A, 'solid_angle', 171),
+    'chunks_12x24': ((12, 24), [0, 1, CHUNK, CHUNK + 1, 2], VIEW_A, VIEW_B, 'solid_angle', 172),
+    'gaps_30x60': ((30, 60), [20, 0, 30, 20, 0], VIEW_A, VIEW_B, 'solid_angle', 173),
+    'uniform_12x24': ((12, 24), [3, 0, 5], VIEW_B, VIEW_B, 'uniform', 174),
+    'narrow_5x9': ((5, 9), [3, 3], ((1, 1), 10.0), VIEW_A, 'solid_angle', 175),
+    'wide_5x9': ((5, 9), [3, 3], ((3, 4), 170.0), ((1, 1), 10.0), 'uniform', 176),
+    'empty_5x9': ((5, 9), [0, 0, 0], VIEW_A, VIEW_B, 'solid_angle', 177),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """-> dict: grid (h, w), R float32 [N, 3, 3], offsets int32 [F + 1], Rc float32 [F, 3, 3], view, cam_view, mode, weights, and
+    the float64 classification of the viewers (ins, und) and of the cameras (cins, cund).  'gaps_30x60' holds a NaN camera, an
+    inf camera and two rolled pole cameras among its viewers, and an inf camera for its fourth frame."""
+    (h, w), per_frame, view, cam_view, mode, seed = CASES[name]
+    offsets = _offsets(per_frame)
+    N, F = int(offsets[-1]), len(per_frame)
+    R, Rc = random_cameras(seed, N), random_cameras(seed + 1000, F)
+    if name == 'gaps_30x60':
+        R[3, 1, 1] = np.nan
+        R[25, 0, 2] = np.inf
+        R[7] = rolled_pole_camera(1, 0.7).astype(np.float32)
+        R[55] = rolled_pole_camera(-1, -2.1).astype(np.float32)
+        Rc[3, 2, 0] = -np.inf
+    ins, und = classify(R, h, w, view)
+    cins, cund = classify(Rc, h, w, cam_view)
+    return dict(name=name, grid=(h, w), R=R, offsets=offsets, Rc=Rc, view=view, cam_view=cam_view, mode=mode,
+                weights=row_weights(h, mode), ins=ins, und=und, cins=cins, cund=cund)
+
+
+def count_bounds(c):
+    """-> (lo, hi) int64 [F, h, w]: the counts float32 may give, lo the cameras that are inside and decided."""
+    F = len(c['offsets']) - 1
+    lo, hi = (np.zeros((F,) + c['grid'], np.int64) for _ in range(2))
+    for f in range(F):
+        k0, k1 = int(c['offsets'][f]), int(c['offsets'][f + 1])
+        lo[f] = (c['ins'][k0:k1] & ~c['und'][k0:k1]).sum(axis=0)
+        hi[f] = lo[f] + c['und'][k0:k1].sum(axis=0)
+    return lo, hi
+
+
+def agreement_bounds(c):
+    """-> (inter_lo, inter_hi, uni_lo, uni_hi) int64 [N]: the weighted sums with every undecided pixel of either window counted
+    as outside it, and as inside it."""
+    a = c['weights'][:, None]
+    fr = frame_of(c['offsets'], len(c['R']))
+    out = np.zeros((4, len(c['R'])), np.int64)
+    for k in range(len(c['R'])):
+        f = fr[k]
+        cam_lo, view_lo = c['cins'][f] & ~c['cund'][f], c['ins'][k] & ~c['und'][k]
+        cam_hi, view_hi = cam_lo | c['cund'][f], view_lo | c['und'][k]
+        out[0, k] = (a * (cam_lo & view_lo)).sum()
+        out[1, k] = (a * (cam_hi & view_hi)).sum()
+        out[2, k] = (a * (cam_lo | view_lo)).sum()
+        out[3, k] = (a * (cam_hi | view_hi)).sum()
+    return out
