@@ -74,6 +74,8 @@ PUBLIC_SYMBOLS = [
     'cp360_path_table_bytes', 'cp360_path_table_host', 'cp360_path_work_bytes', 'cp360_view_path', 'cp360_view_refine',
     # K17: ground truth from head tracking
     'cp360_head_footprints', 'cp360_head_agreement',
+    # K18: the supervised loss
+    'cp360_sup_loss_work_bytes', 'cp360_sup_loss_forward', 'cp360_sup_loss_backward',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -307,6 +309,10 @@ def lib():
     L.cp360_view_refine.argtypes = [vp, vp, i, i, i, dbl, vp, vp, sz, vp]
     L.cp360_head_footprints.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, sz, vp]
     L.cp360_head_agreement.argtypes = [vp, dbl, dbl, vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, vp, sz, vp]
+    L.cp360_sup_loss_work_bytes.restype = sz
+    L.cp360_sup_loss_work_bytes.argtypes = [i, i, i, i, i]
+    L.cp360_sup_loss_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, vp, vp, sz, vp]
+    L.cp360_sup_loss_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)        # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

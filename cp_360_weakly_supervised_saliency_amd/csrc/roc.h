@@ -3,6 +3,7 @@
 // K15 with pos_i = [i in M], neg_i = [i not in M] a_i, and the tests hold the two entries to the same bits (DESIGN.md "K14 and
 // K15: one ROC").  Shared here: the launch shapes, the limits and their check, and the fixed-tree workgroup reduction and the
 // wave compaction of the two prepare kernels.  The rank kernels stay apart, for a measured reason (same place).
+// suploss.hip (K18, K14's KL, CC and NSS as a loss) takes the limits and the reduction from here too: its sums are K14a's.
 // Everything here has internal linkage: each file that includes it compiles its own copy.
 #pragma once
 #include "sphere.h"

@@ -1910,3 +1910,67 @@ def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
     check(lib().cp360_head_agreement(ptr(Rc), cam_hfov, cam_aspect, ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
                                      ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
     return inter, uni
+
+
+# ----------------------------------------------------------------------------- K18: the supervised loss (csrc/suploss.hip)
+SUP_LOSS_STATS = 16                                                    # CP360_SUP_LOSS_STATS
+
+
+def sup_loss_work(N, mhw, hw, device, work=None):
+    """The workspace of one cp360_sup_loss_forward / _backward call: `work` when it is large enough, else a new one."""
+    mh, mw = (int(v) for v in mhw)
+    return _work(lambda n, h, w: lib().cp360_sup_loss_work_bytes(n, mh, mw, h, w), "sup_loss", N, hw[0], hw[1], device, work,
+                 " from maps of %d x %d (N <= 65535, h w <= 2^21, mh mw <= 2^21)" % (mh, mw))
+
+
+def _sup_loss_args(maps, G, fix, weights, kl_eps):
+    """The checks the two passes share -> (N, mh, mw, h, w, kl_eps)."""
+    N, mh, mw = _eval_maps('maps', maps)
+    if _eval_maps('G', G)[0] != N or G.device != maps.device:
+        raise ValueError("G must be float32 [%d, h, w] on the maps' device, got %s" % (N, tuple(G.shape)))
+    h, w = int(G.shape[1]), int(G.shape[2])
+    if tuple(weights.shape) != (h,) or weights.device != maps.device:
+        raise ValueError("weights must be int32 [%d] on the maps' device" % h)
+    _check_buf('weights', weights, torch.int32)
+    if fix is not None:
+        if fix.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("fix must be uint8 or bool, got %s" % fix.dtype)
+        if tuple(fix.shape) != (N, h, w) or fix.device != maps.device:
+            raise ValueError("fix must be [%d, %d, %d] on the maps' device, got %s" % (N, h, w, tuple(fix.shape)))
+        _check_buf('fix', fix, fix.dtype)
+    kl_eps = float(kl_eps)
+    if not (kl_eps > 0.0 and kl_eps < float('inf')):
+        raise ValueError("kl_eps must be finite and > 0, got %r" % (kl_eps,))
+    return N, mh, mw, h, w, kl_eps
+
+
+def sup_loss_forward(maps, G, weights, fix=None, kl_eps=2.0 ** -52, work=None):
+    """cp360_sup_loss_forward: maps f32 [N, mh, mw], G f32 [N, h, w], weights int32 [h] (``sphere_eval_weights``), fix u8 / bool
+    [N, h, w] or None (K14's derived mask) -> (terms f64 [N, 3] = (kl, cc, nss), valid u8 [N, 3], stats f64 [N, 16]) on the
+    device, without a synchronisation: K14's numbers of ``sphere_eval_resample(maps, (h, w))``, and what the backward pass needs."""
+    require_gpu(maps, G, weights, fix, work)
+    N, mh, mw, h, w, kl_eps = _sup_loss_args(maps, G, fix, weights, kl_eps)
+    work = sup_loss_work(N, (mh, mw), (h, w), maps.device, work)
+    terms = torch.empty((N, 3), dtype=torch.float64, device=maps.device)
+    valid = torch.empty((N, 3), dtype=torch.uint8, device=maps.device)
+    stats = torch.empty((N, SUP_LOSS_STATS), dtype=torch.float64, device=maps.device)
+    check(lib().cp360_sup_loss_forward(ptr(maps), ptr(G), ptr(fix), ptr(weights), N, mh, mw, h, w, kl_eps, ptr(terms), ptr(valid),
+                                       ptr(stats), ptr(work), work.numel() * 8, stream()))
+    return terms, valid, stats
+
+
+def sup_loss_backward(maps, G, weights, stats, valid, gterms, fix=None, kl_eps=2.0 ** -52, work=None):
+    """cp360_sup_loss_backward: the inputs of ``sup_loss_forward``, its stats f64 [N, 16] and valid u8 [N, 3], and gterms f64
+    [N, 3] -> dmaps f32 [N, mh, mw] = sum_t gterms[n, t] valid[n, t] dterm_t/dmaps[n]; an invalid term contributes +0."""
+    require_gpu(maps, G, weights, stats, valid, gterms, fix, work)
+    N, mh, mw, h, w, kl_eps = _sup_loss_args(maps, G, fix, weights, kl_eps)
+    for name, t, dtype, cols in (('stats', stats, torch.float64, SUP_LOSS_STATS), ('valid', valid, torch.uint8, 3),
+                                 ('gterms', gterms, torch.float64, 3)):
+        if tuple(t.shape) != (N, cols) or t.device != maps.device:
+            raise ValueError("%s must be %s [%d, %d] on the maps' device, got %s" % (name, dtype, N, cols, tuple(t.shape)))
+        _check_buf(name, t, dtype)
+    work = sup_loss_work(N, (mh, mw), (h, w), maps.device, work)
+    dmaps = torch.empty_like(maps)
+    check(lib().cp360_sup_loss_backward(ptr(maps), ptr(G), ptr(fix), ptr(weights), ptr(stats), ptr(valid), ptr(gterms), N, mh, mw,
+                                        h, w, kl_eps, ptr(dmaps), ptr(work), work.numel() * 8, stream()))
+    return dmaps

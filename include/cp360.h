@@ -711,6 +711,37 @@ int cp360_head_agreement(const float* Rc, double cam_hfov_rad, double cam_aspect
                          long long N, int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
                          long long* uni, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K18: the supervised loss - K14's KL, CC and NSS with a gradient
+ * N maps f32 [N, mh, mw] (a training window's maps, flattened over clips and steps) against ground truth G f32 [N, h, w] on the
+ * loss grid; fix u8 [N, h, w] (non-zero = fixated) or NULL = K14's derived mask; weights int32 [h] as for cp360_seval_scores
+ * (DEVICE memory, clamped to 0 .. 1024); kl_eps finite and > 0 (K14's is 2^-52).  The specification is the package's own,
+ * DESIGN.md "K18", restated in tests/suploss_restate.py.
+ *
+ *   forward   S = cp360_seval_resample(maps) on the h x w grid (mh > h is valid: no anti-aliasing), then K14's sums in K14's
+ *             order -> terms f64 [N, 3] = (kl, cc, nss), valid u8 [N, 3], stats f64 [N, CP360_SUP_LOSS_STATS] = (mu_S, mu_G, Vs,
+ *             Vg, min S, min G, Z, Z_G, K1, K2, mm, n_fix, A, the mask's threshold, cc, nss).  A term K14 defines as NaN (a
+ *             non-finite value in the map's S or G, no variance, no mass above the minimum, n_fix = 0 or h w) is K14's NaN with
+ *             valid = 0; valid is also 0 where the term or a scalar of its gradient is not finite.  A map's numbers do not depend
+ *             on N or on its place in the batch.
+ *   backward  stats and valid from forward, gterms f64 [N, 3] -> dmaps f32 [N, mh, mw] = sum_t gterms[n, t] valid[n, t]
+ *             dterm_t/dmaps[n]: the gradient with respect to S (the header of csrc/suploss.hip) through the adjoint of the
+ *             resampler, tap weights formed in double from the sampler's f32 fractions, f64 sums in a fixed order rounded to f32
+ *             once.  An invalid term, or one whose gterms entry is 0, contributes exactly +0.  Bit-reproducible; a map alone gives
+ *             the bits it gives inside a batch.  dmaps must not share memory with the inputs.
+ * work: 16-byte aligned device memory of cp360_sup_loss_work_bytes(N, mh, mw, h, w) bytes (12 bytes per grid pixel: S in f32 and dS
+ * in f64; both entry points rebuild what they read); 0 = bad or unsupported sizes.  Status, decided before any HIP call: NULL:
+ * CP360_ERR_NULL; N, mh, mw, h or w < 1, or kl_eps not finite or <= 0: CP360_ERR_BAD_SHAPE; N > 65535, h w > 2^21, mh mw > 2^21 or
+ * mh > 65535: CP360_ERR_UNSUPPORTED; a misaligned pointer: CP360_ERR_ALIGN; a workspace that is too small: CP360_ERR_BAD_SHAPE.
+ * Asynchronous on the stream, no host synchronisation, no atomics. */
+#define CP360_SUP_LOSS_STATS 16
+size_t cp360_sup_loss_work_bytes(int N, int mh, int mw, int h, int w);
+int cp360_sup_loss_forward(const float* maps, const float* G, const uint8_t* fix, const int32_t* weights, int N, int mh, int mw,
+                           int h, int w, double kl_eps, double* terms, uint8_t* valid, double* stats, void* work, size_t work_bytes,
+                           void* stream);
+int cp360_sup_loss_backward(const float* maps, const float* G, const uint8_t* fix, const int32_t* weights, const double* stats,
+                            const uint8_t* valid, const double* gterms, int N, int mh, int mw, int h, int w, double kl_eps,
+                            float* dmaps, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K8: saliency metrics
  * utils/eval_saliency.py on the device: AUC_Judd (:90-146), AUC_Borji (:14-87), CorrCoeff (:149-176),
  * similarity (:179-190).  Every reference metric first resizes both maps with
