@@ -76,6 +76,8 @@ PUBLIC_SYMBOLS = [
     'cp360_head_footprints', 'cp360_head_agreement',
     # K18: the supervised loss
     'cp360_sup_loss_work_bytes', 'cp360_sup_loss_forward', 'cp360_sup_loss_backward',
+    # K19: the human ceiling and the prior baselines, per fixation point
+    'cp360_fix_point_work_bytes', 'cp360_fix_point_scores',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -300,6 +302,9 @@ def lib():
     L.cp360_fix_counts.argtypes = [vp, vp, C.c_longlong, i, i, i, vp, vp, vp]
     L.cp360_fix_density.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, vp, vp, sz, vp]
     L.cp360_fix_sauc.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]
+    L.cp360_fix_point_work_bytes.restype = sz
+    L.cp360_fix_point_work_bytes.argtypes = [i, i, i]
+    L.cp360_fix_point_scores.argtypes = [vp, i, vp, vp, C.c_longlong, i, i, i, dbl, vp, vp, vp, sz, vp]
     L.cp360_path_table_bytes.restype = sz
     L.cp360_path_table_bytes.argtypes = [i, i]
     L.cp360_path_table_host.argtypes = [i, i, dbl, dbl, vp]

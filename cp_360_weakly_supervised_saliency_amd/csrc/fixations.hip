@@ -32,6 +32,22 @@
 //         of positives per frame, not P: the workgroups that the positives leave over split the pixel loop (T is linear in A)
 //         as far as kSplit allows, the rest exit at once.
 //   K15e  sAUC finish: the quotient
+//
+// K19: the human ceiling and the prior baselines, one score pair per fixation point (DESIGN.md "K19"; tests/ceiling_restate.py).
+// Point k of frame f lies in pixel i_k (the binning above) and is scored against a map l_k f64 [P]:
+//   leave-one-out  l_k[j] = max(T_f[j] - (double)e_k(j), 0): T_f[j] = sum_k (double)e_k(j) over the frame's finite points in
+//                  ascending k, e_k(j) K15b's f32 term.  The subtraction stands for the sum over the other viewers: a video
+//                  costs N P terms, not N n P.
+//   map            l_k[j] = (double)S[f or 0][j]
+//   scores         mu = sum_a l_k / A, sigma = sqrt(sum_a (l_k - mu)^2 / A), nss = (l_k[i_k] - mu) / sigma;  A_k = sum of a_j over
+//                  j != i_k with l_k[j] >= l_k[i_k], A_neg = A - a_{i_k}, auc = (double)(2 A_neg - A_k) / (2.0 (double)A_neg): K14's
+//                  AUC-Judd with the one fixated pixel i_k.  NaN for both: a point with a non-finite coordinate, a point that no
+//                  frame owns, a non-finite value in the frame's S.
+//   K19a  totals: K15b's kernel with an f64 sum, T to the workspace
+//   K19b  scores: a wave per point, four points per workgroup (K17b's shape); l_k[i_k] first (every lane the same), pass 1 strides
+//         over the pixels for sum_a l and, in int32 per lane, A and A_k, pass 2 for the centred sum; each pass recomputes e_k(j)
+//         from the tables: two expf per (point, pixel) pair.  wave_sum_down in its fixed order, no LDS, no barrier, no atomics: a
+//         point's two numbers do not depend on F, N or the point's place in the batch.
 #pragma clang fp contract(off)
 #include "roc.h"
 
@@ -42,6 +58,8 @@ namespace {
 constexpr int kFixTile = 256;                // K15b: points staged at a time
 constexpr int kMaxPos = 1023;
 constexpr int kMaxNeg = 1 << 20;
+constexpr int kPointWaves = 4;               // K19b: points (waves) per workgroup
+constexpr int kMaxWeight = 1024;             // K19b: the row weights, as K14 clamps them
 // K15d: a workgroup that shares a tile's pixel loop repeats the tile's list loop (n entries), so it takes a share only while the
 // share is at least kSplit n pixels.  Measured on one MI355X, cp360_fix_sauc alone at the bench shape (256 frames of 120 x 240,
 // n = 25 .. 32, 29 pixel tiles; three runs each): kSplit 4 (113 chunks) 0.162 / 0.164 / 0.162 ms, 16 (60 chunks) 0.138 / 0.138 /
@@ -87,6 +105,16 @@ __device__ __forceinline__ bool fix_bin(double lon, double lat, int h, int w, in
     return true;
 }
 
+// q = dir(lon, lat) in double, rounded to f32, and 1 for a finite point; zeros for one that is dropped
+__device__ __forceinline__ float4 fix_dir(double lon, double lat) {
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (fix_finite(lon) && fix_finite(lat)) {
+        const double cl = cos(lat);
+        q = make_float4((float)(cl * cos(lon)), (float)sin(lat), (float)(cl * sin(lon)), 1.f);
+    }
+    return q;
+}
+
 // ------------------------------------------------------------------ K15a: counts
 // grid F, 256 threads; counts cleared before
 __global__ __launch_bounds__(256) void fix_counts_kernel(const double* __restrict__ lonlat, const int* __restrict__ offsets, int N,
@@ -110,11 +138,12 @@ __global__ __launch_bounds__(256) void fix_counts_kernel(const double* __restric
     if (tid == 0) n_points[f] = waves4_sum(red, 1);
 }
 
-// ------------------------------------------------------------------ K15b: density
-// grid (ceil(P / 256), F), 256 threads
+// ------------------------------------------------------------------ K15b: density (T = float), K19a: totals (T = double)
+// grid (ceil(P / 256), F), 256 threads; the terms are f32 for both, T is the type of the sum and of out
+template <typename T>
 __global__ __launch_bounds__(256) void fix_density_kernel(const double* __restrict__ lonlat, const int* __restrict__ offsets, int N,
                                                           const float2* __restrict__ tabx, const float2* __restrict__ taby,
-                                                          float* __restrict__ out, int h, int w, float kappa) {
+                                                          T* __restrict__ out, int h, int w, float kappa) {
     __shared__ float4 tile_q[kFixTile];                                // q_k, and 1 for a finite point, 0 for one that is dropped
     const int P = h * w, tid = threadIdx.x, f = blockIdx.y;
     const int i = blockIdx.x * 256 + tid;
@@ -125,28 +154,110 @@ __global__ __launch_bounds__(256) void fix_density_kernel(const double* __restri
         const int y = i / w, x = i - y * w;
         stab_dir(tabx[x], taby[y], px, py, pz);
     }
-    float acc = 0.f;
+    T acc = (T)0.f;
     for (long long t0 = k0; t0 < k1; t0 += kFixTile) {                 // k0, k1 are the workgroup's: the barriers are uniform
         const long long k = t0 + tid;
-        if (k < k1) {
-            const double lon = lonlat[2 * k], lat = lonlat[2 * k + 1];
-            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (fix_finite(lon) && fix_finite(lat)) {
-                const double cl = cos(lat);
-                q = make_float4((float)(cl * cos(lon)), (float)sin(lat), (float)(cl * sin(lon)), 1.f);
-            }
-            tile_q[tid] = q;
-        }
+        if (k < k1) tile_q[tid] = fix_dir(lonlat[2 * k], lonlat[2 * k + 1]);
         __syncthreads();
         const int n = k1 - t0 < kFixTile ? (int)(k1 - t0) : kFixTile;
         for (int k = 0; k < n; ++k) {
             const float4 q = tile_q[k];
             const float e = vmf(kappa, px, py, pz, q.x, q.y, q.z);
-            acc += q.w != 0.f ? e : 0.f;                               // acc >= +0: adding +0 changes no bit
+            acc += (T)(q.w != 0.f ? e : 0.f);                          // acc >= +0: adding +0 changes no bit
         }
         __syncthreads();
     }
     if (i < P) out[(size_t)f * P + i] = acc;                           // a frame without points: zeros
+}
+
+// ------------------------------------------------------------------ K19b: the scores of every point
+// the scored map of a point at pixel j, whose column and row entries of the tables are ctheta and cphi
+template <bool kLoo>
+__device__ __forceinline__ double point_map(const double* __restrict__ Tf, const float* __restrict__ Sf, int j, const float2 ctheta,
+                                            const float2 cphi, float kappa, const float4 q) {
+    if (!kLoo) return (double)Sf[j];
+    float px, py, pz;
+    stab_dir(ctheta, cphi, px, py, pz);
+    const double e = (double)vmf(kappa, px, py, pz, q.x, q.y, q.z);    // K19a's term, bit for bit
+    return fmax(Tf[j] - e, 0.0);
+}
+
+// grid ceil(N / 4), 256 threads; kLoo: T f64 [F, P] from K19a, else S f32 with s_stride = P or 0 floats between the frames
+template <bool kLoo>
+__global__ __launch_bounds__(64 * kPointWaves) void fix_point_scores_kernel(const float* __restrict__ S, size_t s_stride,
+                                                                            const double* __restrict__ T, const double* __restrict__ lonlat,
+                                                                            const int* __restrict__ offsets, int N, int F,
+                                                                            const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                                            const int* __restrict__ weights, double* __restrict__ scores,
+                                                                            int h, int w, float kappa) {
+    const int lane = threadIdx.x & 63;
+    const long long k = (long long)blockIdx.x * kPointWaves + (threadIdx.x >> 6);
+    if (k >= N) return;                                                // the whole wave; the kernel has no barrier
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const int f = fix_frame(offsets, F, (int)k);
+    int k0, k1, xi = 0, yi = 0;
+    fix_range(offsets, f, N, k0, k1);
+    const double lon = lonlat[2 * k], lat = lonlat[2 * k + 1];
+    if (k < k0 || k >= k1 || !fix_bin(lon, lat, h, w, xi, yi)) {       // no frame owns the point, or it is dropped
+        if (lane == 0) {
+            scores[2 * k] = nan;
+            scores[2 * k + 1] = nan;
+        }
+        return;
+    }
+    const int P = h * w, ik = yi * w + xi;
+    const float4 q = fix_dir(lon, lat);
+    const double* Tf = kLoo ? T + (size_t)f * P : nullptr;
+    const float* Sf = kLoo ? nullptr : S + (size_t)f * s_stride;
+    const double li = point_map<kLoo>(Tf, Sf, ik, tabx[xi], taby[yi], kappa, q);      // every lane the same
+    const int ai = fix_clamp(weights[yi], 0, kMaxWeight);
+    const int dx = 64 % w, dy = 64 / w;
+    // pass 1: sum_a l, A, A_k and whether every value is finite; at most 2^15 pixels of weight 1024 a lane
+    double s1 = 0.0;
+    int at = 0, ak = 0, bad = 0;
+    int x = lane % w, y = lane / w;
+    for (int j = lane; j < P; j += 64) {
+        const int a = fix_clamp(weights[y], 0, kMaxWeight);
+        const double l = point_map<kLoo>(Tf, Sf, j, tabx[x], taby[y], kappa, q);
+        s1 += (double)a * l;
+        at += a;
+        ak += j != ik && l >= li ? a : 0;
+        bad += !(fabs(l) < INFINITY);
+        x += dx;
+        y += dy;
+        if (x >= w) {
+            x -= w;
+            ++y;
+        }
+    }
+    const double sum1 = __shfl(wave_sum_down(s1), 0, 64);
+    const long long A = __shfl(wave_sum_down((long long)at), 0, 64);
+    const long long Ak = wave_sum_down((long long)ak);
+    const int nbad = wave_sum_down(bad);
+    const double mu = sum1 / (double)A;
+    // pass 2: the centred sum
+    double s2 = 0.0;
+    x = lane % w;
+    y = lane / w;
+    for (int j = lane; j < P; j += 64) {
+        const double a = (double)fix_clamp(weights[y], 0, kMaxWeight);
+        const double d = point_map<kLoo>(Tf, Sf, j, tabx[x], taby[y], kappa, q) - mu;
+        s2 += a * (d * d);
+        x += dx;
+        y += dy;
+        if (x >= w) {
+            x -= w;
+            ++y;
+        }
+    }
+    s2 = wave_sum_down(s2);
+    if (lane == 0) {
+        const double sigma = sqrt(s2 / (double)A);
+        const long long a_neg = A - ai;
+        const bool ok = nbad == 0;
+        scores[2 * k] = ok ? (double)(2 * a_neg - Ak) / (2.0 * (double)a_neg) : nan;   // A_neg = 0: 0 / 0
+        scores[2 * k + 1] = ok ? (li - mu) / sigma : nan;
+    }
 }
 
 // ------------------------------------------------------------------ K15c: sums and the compacted positives
@@ -337,7 +448,7 @@ extern "C" int cp360_fix_density(const double* lonlat, const int32_t* offsets, l
     st = open_tabs(work, work_bytes, tab_bytes(h, w), h, w, s, &t);
     if (st != CP360_OK) return st;
     const float kappa = (float)(1.0 / (sigma_rad * sigma_rad));
-    hipLaunchKernelGGL(fix_density_kernel, dim3((h * w + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N, t.x,
+    hipLaunchKernelGGL(fix_density_kernel<float>, dim3((h * w + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N, t.x,
                        t.y, out, h, w, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
@@ -368,6 +479,46 @@ extern "C" int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t*
                        (const int*)neg, neg_stride, hdr, (const float*)cs, (const unsigned*)cp, P);
     CP360_CHECK_HIP();
     hipLaunchKernelGGL(fix_sauc_finish_kernel, dim3((F + 255) / 256), dim3(256), 0, s, (const SaucHdr*)hdr, auc, F);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" size_t cp360_fix_point_work_bytes(int F, int h, int w) {
+    if (roc_args(F, h, w) != CP360_OK) return 0;
+    return tab_bytes(h, w) + align16((size_t)F * (size_t)h * (size_t)w * sizeof(double));
+}
+
+extern "C" int cp360_fix_point_scores(const float* S, int Fs, const double* lonlat, const int32_t* offsets, long long N, int F, int h,
+                                      int w, double sigma_rad, const int32_t* weights, double* scores, void* work, size_t work_bytes,
+                                      void* stream) {
+    if (!offsets || !weights || !work || ((!lonlat || !scores) && N > 0)) return CP360_ERR_NULL;
+    if (bad_image(F, h, w) || N < 0) return CP360_ERR_BAD_SHAPE;
+    if (S ? (Fs != 1 && Fs != F) : (!(sigma_rad > 0.0) || !isfinite(sigma_rad))) return CP360_ERR_BAD_SHAPE;
+    if (roc_args(F, h, w) != CP360_OK || N >= (1LL << 31)) return CP360_ERR_UNSUPPORTED;
+    if ((((uintptr_t)lonlat | (uintptr_t)scores) & 7) != 0 || (((uintptr_t)offsets | (uintptr_t)weights | (uintptr_t)S) & 3) != 0)
+        return CP360_ERR_ALIGN;
+    const size_t tabs = tab_bytes(h, w);
+    int st = check_work(work, work_bytes, tabs + align16((size_t)F * (size_t)h * (size_t)w * sizeof(double)));
+    if (st != CP360_OK || N == 0) return st;                           // no points: nothing to launch
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = launch_tables(work, h, w, s, &t);
+    if (st != CP360_OK) return st;
+    const int P = h * w;
+    const dim3 grid((unsigned)((N + kPointWaves - 1) / kPointWaves)), block(64 * kPointWaves);
+    if (S) {
+        hipLaunchKernelGGL(fix_point_scores_kernel<false>, grid, block, 0, s, S, Fs == 1 ? (size_t)0 : (size_t)P, (const double*)nullptr,
+                           lonlat, (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, scores, h, w, 0.f);
+        CP360_CHECK_HIP();
+        return CP360_OK;
+    }
+    double* T = (double*)((char*)work + tabs);
+    const float kappa = (float)(1.0 / (sigma_rad * sigma_rad));
+    hipLaunchKernelGGL(fix_density_kernel<double>, dim3((P + 255) / 256, F), dim3(256), 0, s, lonlat, (const int*)offsets, (int)N, t.x,
+                       t.y, T, h, w, kappa);
+    CP360_CHECK_HIP();
+    hipLaunchKernelGGL(fix_point_scores_kernel<true>, grid, block, 0, s, (const float*)nullptr, (size_t)0, (const double*)T, lonlat,
+                       (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, scores, h, w, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
 }

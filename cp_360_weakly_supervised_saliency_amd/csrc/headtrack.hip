@@ -69,18 +69,7 @@ __global__ __launch_bounds__(256) void head_footprints_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------ K17b: agreement
-// the frame of pair k: offsets[f] <= k < offsets[f + 1] (empty frames repeat an offset); inside 0 .. F - 1 whatever the offsets hold
-__device__ __forceinline__ int head_frame(const int* __restrict__ offsets, int F, int k) {
-    int lo = 0, hi = F - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid + 1] > k) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// grid ceil(N / 4), 256 threads
+// grid ceil(N / 4), 256 threads; the frame of pair k is sphere.h's fix_frame
 __global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_kernel(const float* __restrict__ Rc, const float* __restrict__ R,
                                                                          const int* __restrict__ offsets, int N, int F,
                                                                          const float2* __restrict__ tabx, const float2* __restrict__ taby,
@@ -90,7 +79,7 @@ __global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_kernel(const f
     const int lane = threadIdx.x & 63;
     const long long k = (long long)blockIdx.x * kHeadPairs + (threadIdx.x >> 6);
     if (k >= N) return;                                                // the whole wave; the kernel has no barrier
-    const Rot cam = view_rot(Rc + (size_t)head_frame(offsets, F, (int)k) * 9);
+    const Rot cam = view_rot(Rc + (size_t)fix_frame(offsets, F, (int)k) * 9);
     const Rot view = view_rot(R + k * 9);
     const int P = h * w;
     int x = lane % w, y = lane / w;

@@ -142,6 +142,18 @@ __device__ __forceinline__ void fix_range(const int* __restrict__ offsets, int f
     k1 = fix_clamp(offsets[f + 1], k0, N);
 }
 
+// the frame of item k (K17b's pairs, K19b's points): offsets[f] <= k < offsets[f + 1] (empty frames repeat an offset); inside
+// 0 .. F - 1 whatever the offsets hold
+__device__ __forceinline__ int fix_frame(const int* __restrict__ offsets, int F, int k) {
+    int lo = 0, hi = F - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid + 1] > k) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 // ------------------------------------------------------------------ the ordered sum of a 256-thread workgroup
 // One fixed tree, whose bits the callers see: a wave's 64 values by __shfl_down with offsets 32, 16, .. 1 (lane 0 ends with the
 // sum), then lane 0 of each of the four waves leaves it in LDS and the slots add up as ((r0 + r1) + r2) + r3.

@@ -1847,6 +1847,43 @@ def shuffled_auc(S, pos, neg, work=None):
     return auc, c_tot, a_neg
 
 
+# ----------------------------------------------------------------------------- K19: the ceiling and the baselines, per point (csrc/fixations.hip)
+def fixation_point_work(F, h, w, device, work=None):
+    """The workspace of one cp360_fix_point_scores call over F frames (the tables and 8 F h w bytes): `work` when it is large
+    enough, else a new one."""
+    return _work(lib().cp360_fix_point_work_bytes, "fixation point scores", F, h, w, device, work, " (F <= 65535, h w <= 2^21)")
+
+
+def fixation_point_scores(lonlat, offsets, hw, weights, sigma_rad=None, maps=None, work=None):
+    """cp360_fix_point_scores: the points of ``fixation_counts`` (the points of one frame are taken as different viewers'), weights
+    int32 [h] (``sphere_eval_weights``) -> f64 [N, 2] = (auc, nss) of every point on the device, without a synchronisation.
+    Exactly one of sigma_rad and maps is given.  sigma_rad: leave-one-out - point k is scored against the density of the other
+    points of its frame (``fixation_density``'s terms, the frame's f64 total minus the point's own term).  maps f32 [1 or F, h, w]:
+    every point of frame f is scored against maps[f] (or maps[0]).  The AUC is ``sphere_eval``'s AUC-Judd with the point's pixel as
+    the one fixation.  A point's numbers do not depend on F, N or its place in the batch; a non-finite point gets NaN."""
+    if (sigma_rad is None) == (maps is None):
+        raise ValueError("exactly one of sigma_rad (leave-one-out) and maps must be given")
+    require_gpu(lonlat, offsets, weights, maps, work)
+    N, F, h, w = _fix_points(lonlat, offsets, hw)
+    if tuple(weights.shape) != (h,) or weights.device != lonlat.device:
+        raise ValueError("weights must be int32 [%d] on lonlat's device" % h)
+    _check_buf('weights', weights, torch.int32)
+    if maps is None:
+        sigma_rad, Fs = float(sigma_rad), 0
+        if not (sigma_rad > 0.0 and math.isfinite(sigma_rad)):
+            raise ValueError("sigma_rad must be finite and positive, got %r" % (sigma_rad,))
+    else:
+        if maps.dim() != 3 or tuple(maps.shape) not in ((1, h, w), (F, h, w)) or maps.device != lonlat.device:
+            raise ValueError("maps must be float32 [1 or %d, %d, %d] on lonlat's device, got %s" % (F, h, w, tuple(maps.shape)))
+        _check_buf('maps', maps, torch.float32)
+        sigma_rad, Fs = 0.0, int(maps.shape[0])
+    work = fixation_point_work(F, h, w, lonlat.device, work)
+    scores = torch.empty((N, 2), dtype=torch.float64, device=lonlat.device)
+    check(lib().cp360_fix_point_scores(ptr(maps), Fs, ptr(lonlat), ptr(offsets), N, F, h, w, sigma_rad, ptr(weights), ptr(scores),
+                                       ptr(work), work.numel() * 8, stream()))
+    return scores
+
+
 # ----------------------------------------------------------------------------- K17: head-tracking ground truth (csrc/headtrack.hip)
 def _head_view(view_hw, hfov_deg):
     """A view (h_v, w_v) of hfov_deg degrees -> (hfov in radians, the aspect h_v / w_v) as the library takes it."""

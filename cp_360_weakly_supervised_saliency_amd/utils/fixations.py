@@ -9,10 +9,15 @@ definitions are the package's own (DESIGN.md "K15") and tests/fix
     save_gt(gt_dir, vid_name, gt)                                             # <gt_dir>/<vid_name>.mp4/{:05}.npy
     counts, _ = fm.counts(lonlat, offsets)
     auc, c_tot, a_neg = fm.shuffled_auc(sal, counts)                          # negatives: the other frames' fixations
+    top = fm.ceiling(lonlat, offsets)                                         # K19: the other viewers predict the one left out
+    mine = fm.score_points(sal, lonlat, offsets)                              # the same scores of a model's maps: .video_auc, ..
+    rows = fm.baselines(lonlat, offsets, sal)                                 # 'ceiling', 'prior', 'model', 'normalised'
 
-Longitude is theta and latitude phi of the package's sphere geometry (north up, radians).  ``sigma_deg = 5`` is a convention: it
+The ceiling and the point scores (K19) take the points of one frame as different viewers', which is what ``scanpaths_to_points``
+gives: at most one point per viewer and frame.  Longitude is theta and latitude phi of the package's sphere geometry (north up, radians).  ``sigma_deg = 5`` is a convention: it
 has not been tuned on a dataset.  No CPU fallback for the maps and the score; the scan-path interpolation is host numpy.
 """
+import collections
 import os
 
 import numpy as np
@@ -21,6 +26,10 @@ import torch
 from .. import ops
 from . import npy_io
 from ._device import host_tensor, on_device
+
+
+POINT_CHUNK = 256                                                      # K19: frames per call, 59 MB of workspace on 120 x 240
+PointScores = collections.namedtuple('PointScores', 'auc nss frame_auc frame_nss video_auc video_nss')
 
 
 def _unit(lon, lat):
@@ -162,6 +171,102 @@ class FixationMaps:
                 raise ValueError("negatives must be integers [%d, %d], got %s %s" % (h, w, negatives.dtype, tuple(negatives.shape)))
             neg = negatives.to(self.device, torch.int32).reshape(1, h, w).contiguous()
         return ops.shuffled_auc(S, pos, neg.contiguous(), work=self._workspace(F, S.device))
+
+    # ------------------------------------------------------------------------- K19: the ceiling and the baselines
+    def _score(self, lonlat, offsets, weights, sal):
+        """The point scores of a video, POINT_CHUNK frames a call -> PointScores.  sal None: leave-one-out."""
+        h, w = self.grid_hw
+        off = (offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else np.asarray(offsets)).astype(np.int64).reshape(-1)
+        if not torch.is_tensor(lonlat):
+            lonlat = torch.from_numpy(np.array(lonlat, dtype=np.float64).reshape(-1, 2))       # a copy: the caller's may be read-only
+        N, F = int(lonlat.shape[0]), off.size - 1
+        if lonlat.dim() != 2 or lonlat.shape[1] != 2 or F < 1 or np.any(np.diff(off) < 0) or off[0] < 0 or off[-1] > N:
+            raise ValueError("lonlat must be [N, 2] and offsets [F + 1] with F >= 1, ascending within 0 .. N")
+        if weights not in ('solid_angle', 'uniform'):
+            raise ValueError("weights must be 'solid_angle' or 'uniform', got %r" % (weights,))
+        if sal is not None:
+            sal = host_tensor(sal, np.float32)
+            if not sal.dtype.is_floating_point or not (sal.dim() == 2 or (sal.dim() == 3 and sal.shape[0] == F)) or sal.numel() == 0:
+                raise ValueError("sal must be floating-point [%d, h, w] or one [h, w] map, got %s %s" % (F, sal.dtype, tuple(sal.shape)))
+        lonlat = on_device(lonlat, self.device, torch.float64)
+        dev = lonlat.device
+        a = ops.sphere_eval_weights(h, weights, dev)
+        one = None
+        if sal is not None and sal.dim() == 2:
+            one = ops.sphere_eval_resample(sal.detach()[None].to(dev, torch.float32).contiguous(), self.grid_hw)
+        scores = torch.full((N, 2), float('nan'), dtype=torch.float64, device=dev)
+        for c0 in range(0, F, POINT_CHUNK):
+            c1 = min(F, c0 + POINT_CHUNK)
+            k0, k1 = int(off[c0]), int(off[c1])
+            if k1 == k0:
+                continue
+            offs = torch.from_numpy((off[c0:c1 + 1] - k0).astype(np.int32)).to(dev)
+            self._work = ops.fixation_point_work(c1 - c0, h, w, dev, self._work)
+            if sal is None:
+                part = ops.fixation_point_scores(lonlat[k0:k1], offs, self.grid_hw, a, sigma_rad=np.deg2rad(self.sigma_deg), work=self._work)
+            else:
+                maps = one if one is not None else ops.sphere_eval_resample(
+                    sal[c0:c1].detach().to(dev, torch.float32).contiguous(), self.grid_hw)
+                part = ops.fixation_point_scores(lonlat[k0:k1], offs, self.grid_hw, a, maps=maps, work=self._work)
+            scores[k0:k1] = part
+        # the means: a frame's points are consecutive, one segment each, added in their order
+        lengths = torch.from_numpy(np.diff(off)).to(dev)
+        owned = scores[int(off[0]):int(off[-1])]
+        out = []
+        for c in range(2):
+            v = owned[:, c].contiguous()
+            ok = ~torch.isnan(v)
+            tot = torch.segment_reduce(torch.where(ok, v, torch.zeros_like(v)), 'sum', lengths=lengths, unsafe=True)
+            cnt = torch.segment_reduce(ok.to(torch.float64), 'sum', lengths=lengths, unsafe=True)
+            out.append((tot / cnt, tot.sum() / cnt.sum()))                 # 0 / 0: NaN for a frame, or a video, without a number
+        return PointScores(scores[:, 0], scores[:, 1], out[0][0], out[1][0], out[0][1], out[1][1])
+
+    def ceiling(self, lonlat, offsets, weights='solid_angle'):
+        """The human ceiling (inter-observer consistency): every point scored against the density of the other points of its
+        frame, blurred with sigma_deg - how well the other viewers predict the one left out.  The points of one frame are taken
+        as different viewers', which is what ``scanpaths_to_points`` gives: at most one point per viewer and frame.  -> PointScores
+        on the device: auc, nss f64 [N]; frame_auc, frame_nss f64 [F], the mean over the frame's points that have a number (NaN
+        for a frame with none: a viewer alone has an AUC of 1/2 and no NSS); video_auc, video_nss, the mean over all points that
+        have one.  weights: 'solid_angle' or 'uniform', as ``SphereEval``.  The video goes through in chunks of POINT_CHUNK
+        frames, which bounds the workspace; a point's bits do not depend on the chunking."""
+        return self._score(lonlat, offsets, weights, None)
+
+    def score_points(self, sal, lonlat, offsets, weights='solid_angle'):
+        """The same scores of maps: sal [F, ., .] (numpy or tensor, any size: resampled to the grid as ``SphereEval`` does) or
+        one [., .] map for every frame; every point of frame f is scored against sal[f] -> PointScores, in the units of
+        ``ceiling``."""
+        if sal is None:
+            raise ValueError("sal must be [F, h, w] or one [h, w] map")
+        return self._score(lonlat, offsets, weights, sal)
+
+    def prior(self, lonlat, offsets, exclude_own=True):
+        """The prior baseline, a map that has never seen the frame: float32 [F, h, w], for frame f the mean of the other frames'
+        raw densities, (sum_g D_g - D_f) / (F - 1), summed in float64; exclude_own=False: the [h, w] mean of all frames."""
+        D = self.density(lonlat, offsets, None)
+        F = int(D.shape[0])
+        tot = D.sum(dim=0, dtype=torch.float64)
+        if not exclude_own:
+            return (tot / F).to(torch.float32)
+        if F < 2:
+            raise ValueError("the prior of the other frames needs F >= 2 (or exclude_own=False)")
+        out = torch.empty_like(D)
+        for c0 in range(0, F, POINT_CHUNK):
+            out[c0:c0 + POINT_CHUNK] = ((tot[None] - D[c0:c0 + POINT_CHUNK]).clamp_(min=0.0) / (F - 1)).to(torch.float32)
+        return out
+
+    def baselines(self, lonlat, offsets, sal=None):
+        """The reference lines of a report -> {'ceiling': (video_auc, video_nss), 'prior': ..} and, when sal is given, 'model' and
+        'normalised' = (model - prior) / (ceiling - prior) per score: 0 at the prior, 1 at the ceiling.  'prior' is
+        ``score_points(prior(lonlat, offsets), ..)``, the other frames' densities; 0-dim float64 tensors on the device."""
+        rows = {}
+        for name, r in (('ceiling', self.ceiling(lonlat, offsets)),
+                        ('prior', self.score_points(self.prior(lonlat, offsets), lonlat, offsets))):
+            rows[name] = (r.video_auc, r.video_nss)
+        if sal is not None:
+            r = self.score_points(sal, lonlat, offsets)
+            rows['model'] = (r.video_auc, r.video_nss)
+            rows['normalised'] = tuple((m - p) / (c - p) for m, p, c in zip(rows['model'], rows['prior'], rows['ceiling']))
+        return rows
 
 
 def save_gt(gt_dir, vid_name, maps, first_frame_no=0):

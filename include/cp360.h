@@ -683,6 +683,35 @@ int cp360_fix_density(const double* lonlat, const int32_t* offsets, long long N,
 int cp360_fix_sauc(const float* S, const int32_t* pos, const int32_t* neg, int Fn, int F, int h, int w, double* auc,
                    long long* c_tot, long long* a_neg, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K19: the human ceiling and the prior baselines, per point
+ * One score pair per fixation point of K15's CSR points (lonlat, offsets as above; the points of one frame are taken as different
+ * viewers'): scores f64 [N, 2] = (auc, nss) of point k against a map l_k f64 [h w], weights int32 [h] as for cp360_seval_scores
+ * (DEVICE memory, clamped to 0 .. 1024), A = the sum of the weights a_j over all pixels, i_k = the pixel of point k by the binning
+ * of counts.  The specification is the package's own, DESIGN.md "K19", restated in tests/ceiling_restate.py.
+ *
+ *   leave-one-out  S = NULL (Fs is ignored): e_k(j) = density's f32 term expf(kappa (p_j . q_k - 1)) with its kappa =
+ *                  (float)(1 / sigma_rad^2), its rounding of q_k and its order in the dot product; T_f[j] = sum_k (double)e_k(j)
+ *                  over the frame's finite points in ascending k; l_k[j] = max(T_f[j] - (double)e_k(j), 0) - the sum over the other
+ *                  viewers, at N h w terms a video and not N n h w.  sigma_rad finite and > 0, else CP360_ERR_BAD_SHAPE.
+ *   map            S f32 [Fs, h, w], Fs = 1 (one map for every frame) or F: l_k[j] = (double)S[f or 0][j] for every point of
+ *                  frame f; sigma_rad is ignored.
+ *   scores         mu = sum_a l_k / A, sigma = sqrt(sum_a (l_k - mu)^2 / A), nss = (l_k[i_k] - mu) / sigma.  A_k = the sum of a_j
+ *                  over j != i_k with l_k[j] >= l_k[i_k] (int64), A_neg = A - a_{i_k}, auc = (double)(2 A_neg - A_k) / (2.0
+ *                  (double)A_neg), rounded once: cp360_seval_scores' AUC-Judd with the one fixated pixel i_k, bit for bit in map
+ *                  mode.  A point with a non-finite coordinate, or one outside every frame's (clamped) range: NaN, NaN.  A frame
+ *                  with one finite point in leave-one-out mode has l = 0 everywhere: auc = 1/2 exactly, nss = NaN.  A_neg = 0: auc
+ *                  = NaN.  A non-finite value in a frame's S: NaN, NaN for that frame's points alone.  A constant S: auc = 1/2.
+ * A point's two numbers are bit-identical between runs and whatever F, N and the point's place in the batch: a wave per point,
+ * sums in one fixed order, no atomics.
+ * work: 16-byte aligned device memory of cp360_fix_point_work_bytes(F, h, w) bytes (K11's tables, which every call rebuilds, and
+ * 8 F h w bytes for T; 0 = bad or unsupported sizes); too small: CP360_ERR_BAD_SHAPE.  In this order, before any launch: a NULL
+ * pointer (S may be NULL; lonlat and scores when N = 0): CP360_ERR_NULL; F, h or w < 1, N < 0, Fs not 1 or F (map), sigma_rad
+ * (leave-one-out): CP360_ERR_BAD_SHAPE; F > 65535, h w > 2^21 or N >= 2^31: CP360_ERR_UNSUPPORTED; alignment (lonlat, scores 8
+ * bytes, the others 4, work 16): CP360_ERR_ALIGN; the workspace.  N = 0 is valid.  Asynchronous on the stream. */
+size_t cp360_fix_point_work_bytes(int F, int h, int w);
+int cp360_fix_point_scores(const float* S, int Fs, const double* lonlat, const int32_t* offsets, long long N, int F, int h, int w,
+                           double sigma_rad, const int32_t* weights, double* scores, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K17: ground truth from head tracking
  * A headset logs the head's orientation: what a viewer saw is the headset's window, the view of a camera in K12's convention
  * (R f32 [3, 3] camera-to-world, columns forward / up / right).  A video's viewers are N cameras in CSR form: R f32 [N, 3, 3] (may
