@@ -43,7 +43,9 @@ PUBLIC_SYMBOLS = [
     'cp360_resnet_load', 'cp360_resnet_workspace_bytes', 'cp360_resnet_forward', 'cp360_clstm_load', 'cp360_clstm_workspace_bytes',
     'cp360_clstm_step', 'cp360_conv_finish_add', 'cp360_window_normalize_frames',
     'cp360_clstm_window_workspace_bytes', 'cp360_clstm_window', 'cp360_clstm_window_multi_workspace_bytes',
-    'cp360_clstm_window_multi', 'cp360_clock_probe', 'cp360_conv_prefer_clip',
+    'cp360_clstm_window_multi', 'cp360_clock_probe', 'cp360_conv_prefer_clip', 'cp360_conv_plan_tile',
+    'cp360_resnet_can_pair_static', 'cp360_resnet_forward_multi_workspace_bytes', 'cp360_resnet_forward_multi',
+    'cp360_resnet_plan_describe_multi',
     'cp360_conv_plan_describe', 'cp360_resnet_plan_describe', 'cp360_resize_plan_describe', 'cp360_wino_packed_bytes', 'cp360_wino_v_bytes',
     'cp360_wino_m_bytes', 'cp360_wino_preferred', 'cp360_wino_pack_weights', 'cp360_wino_input', 'cp360_wino_gemm',
     'cp360_wino_output', 'cp360_wino_output_gates', 'cp360_wino_output_gates_groups', 'cp360_wino_forward', 'cp360_wino_output_input', 'cp360_clstm_wino_state', 'cp360_clstm_load_wino',
@@ -230,6 +232,13 @@ def lib():
     L.cp360_conv_prefer_clip.argtypes = [pd]
     L.cp360_conv_plan_describe.argtypes = [pd, C.c_char_p, sz]
     L.cp360_resnet_plan_describe.argtypes = [vp, i, i, C.c_char_p, sz]
+    L.cp360_conv_plan_tile.argtypes = [pd]
+    L.cp360_resnet_can_pair_static.argtypes = [vp, i, i, i]
+    L.cp360_resnet_forward_multi_workspace_bytes.restype = sz
+    L.cp360_resnet_forward_multi_workspace_bytes.argtypes = [vp, i, i, i]
+    # faces_p3 / cam_out: host arrays of device pointers (ctypes c_void_p * n_groups)
+    L.cp360_resnet_forward_multi.argtypes = [vp, vp, i, i, i, vp, vp, sz, vp]
+    L.cp360_resnet_plan_describe_multi.argtypes = [vp, i, i, i, C.c_char_p, sz]
     L.cp360_resize_plan_describe.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, C.c_char_p, sz]
     pw = C.POINTER(WinoDesc)
     for fn in ('cp360_wino_packed_bytes', 'cp360_wino_v_bytes', 'cp360_wino_m_bytes'):

@@ -1594,6 +1594,26 @@ extern "C" int cp360_conv_suggest_splits(const cp360_conv_desc* d) {
     return L.splits;
 }
 
+// The cp360_conv_desc.tile_px value that names the kernel this descriptor launches on (0 where the kernel follows from the
+// descriptor without the image count: clip-resident, fewer than 256 output channels).  A caller that runs the SAME
+// convolution on more images and wants the K loop of this launch (cp360_resnet_forward_multi's joint back half) writes it
+// into the larger descriptor: the cost model would otherwise choose again, by rounds of the chip.
+extern "C" int cp360_conv_plan_tile(const cp360_conv_desc* d) {
+    if (!d || check_desc(d)) return 0;
+    ConvLaunch L;
+    if (resolve_launch(d, true, &L)) return 0;
+    switch (L.kernel) {
+    case K_SMALL:   return 6464;
+    case K_T128:    return d->c_out >= 256 ? 64 : 0;
+    case K_DMA:     return 128;
+    case K_RING2:   return 129;
+    case K_RING160: return 160;
+    case K_RING256: return 256;
+    case K_RING304: return 304;
+    default:        return 0;
+    }
+}
+
 // For a caller that holds BOTH weight layouts of a CubePad(1) + 3x3 convolution on small faces (layer4's conv2): should this
 // launch take the clip-resident kernel (1) or the tap-major path (0)?  The clip-resident tile is 256 channels x a whole cube:
 // with few cubes and few channels (one frame, 512 channels: 2 tiles) it cannot fill the chip even with split-K, and the

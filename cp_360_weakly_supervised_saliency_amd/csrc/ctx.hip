@@ -404,6 +404,7 @@ enum Slot {
     SLOT_ACT0, SLOT_ACT1, SLOT_ACT2, SLOT_ACT3,  // activation quarters of the workspace (at most x, mid, out and the next mid live)
     SLOT_INPUT, SLOT_CAM,                        // the caller's input (the stage's faces, the cell's [x | h]) and CAM buffer
     SLOT_PARTIAL, SLOT_BORDER,                   // split-K partial slabs; the fused stem + max-pool kernel's border scratch
+    SLOT_HAND,                                   // the hand-over buffer between the per-group front and the joint back (JointPlan)
     SLOT_COUNT
 };
 
@@ -574,6 +575,10 @@ struct StagePlan : Plan {
         note(line);
     }
     size_t n_ordered = 0;                        // steps [0, n_ordered) run under launch order 2, the CAM after the restore
+    // The cut of cp360_resnet_forward_multi (0: this plan has none): steps [0, cut) are the front, run per group; the running
+    // activation there (layer3.0's output, in slot cut_x, cut_bytes of it) is handed over; steps [cut, end) are the back
+    size_t cut = 0, cut_bytes = 0, text_cut = 0;
+    int cut_x = SLOT_NONE;
     int feat = SLOT_NONE;                        // where layer4's output ends up, and its size
     size_t feat_bytes = 0;
     ResnetWs ws;
@@ -699,6 +704,15 @@ int plan_resnet(const CResnet& R, int n_img, int cd, StagePlan* P) {
         P->note(L == 1 ? "layer2.1-3: conv1 + ONE fused tail launch per Bottleneck (K3e; at 28x28 faces the next block's conv1 rides on the tail)"
                        : "layer3.1-5: conv1 + ONE fused tail launch per Bottleneck (K3e, C = 256)");
         const bool chain = L == 1 && face == 28;          // the next block's conv1 rides on the tail kernel
+        if (L == 2 && cd == 224) {
+            // the 14x14 and 7x7 layers of several batches may run as ONE pass from here (layer3.1's conv1): measured at 64 against
+            // 128 frames, the layer3 tails cost 0.96 and layer4's 7x7 launches 0.70 - 0.76 of twice the single pass (148 tiles of
+            // 256 pixels per batch fill the chip badly); the 56x56 / 28x28 launches are 5 - 10 rounds of the chip either way
+            P->cut = P->steps.size();
+            P->cut_x = x;
+            P->cut_bytes = (size_t)n_img * face * face * Lr[0].c3.c_out * es;
+            P->text_cut = P->text.size();
+        }
         for (size_t b = 1; b < Lr.size(); ++b) {
             const CBlock& B = Lr[b];
             P->at(L + 1, (int)b);
@@ -755,6 +769,170 @@ int run_plan(const StagePlan& P, const void* faces_p3, float* cam_out, void* fea
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- the static stages of several batches, back half as one pass
+// The front (stem .. layer3.0) runs per group at n_img faces; each group's layer3.0 output goes straight into its rows of a
+// hand-over buffer; the back (layer3.1 .. layer4, CAM) runs ONCE at n_groups * n_img faces.  The back's steps are the steps
+// of the plan at n_img faces with the image count replaced: split-K count, K ranges, finish order and epilogue are the
+// descriptor's, the kernel is pinned through tile_px - every output row is summed exactly as in the plan at n_img faces.
+namespace {
+struct JointPlan {
+    StagePlan one;                               // the plan of one group; its steps [0, cut) are the front
+    Plan back;
+    size_t back_ordered = 0;                     // back steps [0, back_ordered) run under launch order 2
+    size_t partial = 0, hand = 0;                // hand: the hand-over buffer of all groups
+    int n_groups = 0;
+    size_t total() const { return 4 * one.ws.act + partial + one.ws.border + hand; }
+};
+
+// CP360_OK: the joint plan; CP360_ERR_UNSUPPORTED: this geometry / type has no cut (run cp360_resnet_forward per group)
+int plan_joint(const CResnet& R, int n_groups, int n_img, int cd, JointPlan* J) {
+    if (n_groups <= 0 || n_groups > CP360_MAX_CLIP_GROUPS) return CP360_ERR_BAD_SHAPE;
+    const int rc = plan_resnet(R, n_img, cd, &J->one);
+    if (rc) return rc;
+    J->n_groups = n_groups;
+    const StagePlan& S = J->one;
+    J->partial = S.ws.partial;
+    if (n_groups == 1) return CP360_OK;                   // the plain plan
+    // the producer of the handed-over activation must be the front's last step, and the back must fit the front's slots
+    if (S.cut == 0 || S.cut >= S.n_ordered || S.steps[S.cut - 1].out != S.cut_x) return CP360_ERR_UNSUPPORTED;
+    if ((size_t)n_groups * S.cut_bytes > S.ws.act) return CP360_ERR_UNSUPPORTED;
+    if ((long long)n_groups * n_img > 0x7fffffff / (14 * 14 * 1024)) return CP360_ERR_BAD_SHAPE;   // the kernels' 32-bit offsets
+    Plan& B = J->back;
+    B.dtype = S.dtype;
+    B.n_img = n_groups * n_img;
+    bool handed = true;                                   // until a back step reuses slot cut_x, reads of it mean the hand-over buffer
+    for (size_t i = S.cut; i < S.steps.size(); ++i) {
+        Step s = S.steps[i];
+        if (handed) {
+            if (s.in == S.cut_x) s.in = SLOT_HAND;
+            if (s.in2 == S.cut_x) s.in2 = SLOT_HAND;
+            if (s.res == S.cut_x) s.res = SLOT_HAND;
+            if (s.out == S.cut_x || s.out2 == S.cut_x) handed = false;
+        }
+        const int tile = s.kind == STEP_CONV ? cp360_conv_plan_tile(&s.d) : 0;
+        if (s.kind == STEP_CONV || s.kind == STEP_F32_FINISH) {
+            s.d.n_img = B.n_img;
+            if (tile == 160 || tile == 256 || tile == 304) {
+                // the three pixel tiles of conv_igemm_ring_kernel share one K loop (ring_body: the same steps in the same order for
+                // every output element), so among them the cost model may choose again for the joint pixel count; any other
+                // kernel stays the one of the plan at n_img faces
+                const int joint = cp360_conv_plan_tile(&s.d);
+                s.d.tile_px = (joint == 160 || joint == 256 || joint == 304) ? joint : tile;
+            } else {
+                s.d.tile_px = tile;
+            }
+            if (s.kind == STEP_CONV && cp360_conv_packed_bytes(&s.d) == 0) return CP360_ERR_UNSUPPORTED;   // (a bound of the kernels at this count)
+            if (s.sums == SLOT_PARTIAL || (s.kind == STEP_F32_FINISH && s.in == SLOT_PARTIAL))
+                B.partial_need = std::max(B.partial_need, (size_t)s.d.splits * B.n_img * s.d.h_out * s.d.w_out * s.d.c_out * sizeof(float));
+        }
+        B.steps.push_back(s);
+    }
+    J->back_ordered = S.n_ordered - S.cut;
+    J->partial = std::max(S.ws.partial, align_up(B.partial_need));
+    J->hand = align_up((size_t)n_groups * S.cut_bytes);
+    return CP360_OK;
+}
+
+int run_joint(const JointPlan& J, const void* const* faces_p3, float* cam_out, unsigned char* ws, hipStream_t st) {
+    const StagePlan& S = J.one;
+    Bufs at;
+    for (int i = 0; i < 4; ++i) at.p[SLOT_ACT0 + i] = ws + i * S.ws.act;
+    at.p[SLOT_CAM] = cam_out;
+    at.p[SLOT_PARTIAL] = ws + 4 * S.ws.act;
+    at.p[SLOT_BORDER] = ws + 4 * S.ws.act + J.partial;
+    unsigned char* hand = ws + 4 * S.ws.act + J.partial + S.ws.border;
+    LaunchOrder order(2);
+    for (int g = 0; g < J.n_groups; ++g) {
+        cp360_set_launch_order(2);                        // every front starts the alternation where the plain pass does;
+        at.p[SLOT_INPUT] = const_cast<void*>(faces_p3[g]);            // the back goes on from the last front's phase at the cut
+        at.p[SLOT_HAND] = hand + (size_t)g * S.cut_bytes;
+        for (size_t i = 0; i < S.cut; ++i) {
+            Step s = S.steps[i];
+            if (i == S.cut - 1) s.out = SLOT_HAND;
+            const int rc = run_step(s, S, at, st);
+            if (rc) return rc;
+        }
+    }
+    at.p[SLOT_INPUT] = nullptr;
+    at.p[SLOT_HAND] = hand;
+    for (size_t i = 0; i < J.back.steps.size(); ++i) {
+        if (i == J.back_ordered) order.restore();
+        const int rc = run_step(J.back.steps[i], J.back, at, st);
+        if (rc) return rc;
+    }
+    return CP360_OK;
+}
+
+}  // namespace
+
+// 1: cp360_resnet_forward_multi runs the back half of n_groups batches of n_img faces as one pass (16-bit types, cube 224,
+// 2 .. CP360_MAX_CLIP_GROUPS groups); 0: it does not (f32, other cube sizes, one group, nothing loaded): one
+// cp360_resnet_forward per batch is the way there.
+extern "C" int cp360_resnet_can_pair_static(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim) {
+    if (!ctx || n_groups < 2) return 0;
+    JointPlan J;
+    return plan_joint(ctx->rn, n_groups, n_img, cube_dim, &J) == CP360_OK ? 1 : 0;
+}
+
+extern "C" size_t cp360_resnet_forward_multi_workspace_bytes(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim) {
+    if (!ctx) return 0;
+    JointPlan J;
+    return plan_joint(ctx->rn, n_groups, n_img, cube_dim, &J) ? 0 : J.total();
+}
+
+extern "C" int cp360_resnet_forward_multi(cp360_ctx* ctx, const void* const* faces_p3, int n_groups, int n_img, int cube_dim,
+                                          float* const* cam_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ctx || !faces_p3 || !cam_out) return CP360_ERR_NULL;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return CP360_ERR_HIP;
+    JointPlan J;
+    const int rc = plan_joint(ctx->rn, n_groups, n_img, cube_dim, &J);
+    if (rc) return rc;
+    if (!workspace) return CP360_ERR_NULL;
+    const size_t per_group = (size_t)n_img * (cube_dim / 32) * (cube_dim / 32) * ctx->rn.num_classes;
+    for (int g = 0; g < n_groups; ++g) {
+        if (!faces_p3[g] || !cam_out[g]) return CP360_ERR_NULL;
+        if (cam_out[g] != cam_out[0] + (size_t)g * per_group) return CP360_ERR_BAD_SHAPE;   // ONE CAM launch writes all groups
+    }
+    if (((size_t)workspace & 255) != 0) return CP360_ERR_ALIGN;
+    if (workspace_bytes < J.total()) return CP360_ERR_BAD_SHAPE;
+    if (n_groups == 1) return run_plan(J.one, faces_p3[0], cam_out[0], nullptr, (unsigned char*)workspace, (hipStream_t)stream);
+    return run_joint(J, faces_p3, cam_out[0], (unsigned char*)workspace, (hipStream_t)stream);
+}
+
+extern "C" int cp360_resnet_plan_describe_multi(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim, char* buf, size_t cap) {
+    if (!ctx || !buf || cap == 0) return CP360_ERR_NULL;
+    JointPlan J;
+    J.one.describe = true;
+    const int rc = plan_joint(ctx->rn, n_groups, n_img, cube_dim, &J);
+    if (rc) return rc;
+    std::string text;
+    if (n_groups == 1) {
+        text = J.one.text;
+    } else {
+        char line[320];
+        const std::string& t = J.one.text;
+        const size_t head = t.find('\n') + 1;
+        snprintf(line, sizeof(line), "static stages of %d groups, back half as one pass; per group: %s", n_groups, t.substr(0, head).c_str());
+        text = line;
+        snprintf(line, sizeof(line), "FRONT: %zu launch steps, once per group at %d faces (stem .. layer3.0)\n", J.one.cut, n_img);
+        text += line;
+        text += t.substr(head, J.one.text_cut - head);
+        snprintf(line, sizeof(line), "CUT: in front of layer3.1's conv1; layer3.0's output [%d, 14, 14, 1024] of every group is written into its "
+                 "rows of the hand-over buffer (%zu bytes)\n", n_img, J.hand);
+        text += line;
+        snprintf(line, sizeof(line), "BACK: %zu launch steps, ONCE at %d x %d = %d faces; kernel, split-K count and K ranges of every launch "
+                 "are those of the plan at %d faces listed here (workgroups: x %d)\n", J.back.steps.size(), n_groups, n_img, n_groups * n_img,
+                 n_img, n_groups);
+        text += line;
+        text += t.substr(J.one.text_cut);
+    }
+    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+    memcpy(buf, text.data(), n);
+    buf[n] = 0;
+    return (int)n;
+}
 
 extern "C" int cp360_resnet_plan_describe(cp360_ctx* ctx, int n_img, int cube_dim, char* buf, size_t cap) {
     if (!ctx || !buf || cap == 0) return CP360_ERR_NULL;

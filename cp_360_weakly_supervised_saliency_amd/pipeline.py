@@ -17,7 +17,7 @@ ConvLSTM work seq_len times and is available through ``ClipRunner`` directly).
 """
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, stage_ctx
 from .model.resnet_cubic import resnet50
 from .model.clstm import ConvLSTMCell
 from .static_model.class_activation_model import cam_device
@@ -107,16 +107,33 @@ class SaliencyEngine:
         cam_flat = cam.view(self.B * self.T, 6 * self.w * self.w, -1)
         for lo in range(0, F, self.frame_chunk):
             hi = min(F, lo + self.frame_chunk)
-            chunk = frames[lo:hi]
-            if self.resize is not None:
-                chunk = self.resize(chunk)
-            # K1 writes the CubePad(3)-padded faces directly (one pass instead of project + pad)
-            x4 = self.e2c.to_cube_batch(chunk, out_dtype=self.dtype, layout='nhwc4p3')
+            x4 = self._cube_faces(frames[lo:hi])
             cam_device(x4, self.resnet, out=cam_flat[lo:hi], padded=True, want_feat=False)     # CAM conv writes the clip buffer directly
         return cam
 
+    def _cube_faces(self, chunk):
+        """K0 + K1: frames [F, H, W, 3] -> the CubePad(3)-padded faces [6F, cd+6, cd+6, 4] the stem reads."""
+        if self.resize is not None:
+            chunk = self.resize(chunk)
+        # K1 writes the CubePad(3)-padded faces directly (one pass instead of project + pad)
+        return self.e2c.to_cube_batch(chunk, out_dtype=self.dtype, layout='nhwc4p3')
+
     def temporal_stage(self, cam=None):
         return self.runner.run(self.cam if cam is None else cam, return_all_steps=self.return_all_steps)
+
+    def _resnet_stage(self):
+        stage = self.resnet.__dict__.get('_stage')
+        if stage is None:
+            stage = self.resnet.__dict__['_stage'] = stage_ctx.ResnetStage(self.resnet)
+        return stage
+
+    def can_pair_static(self):
+        """True when ``stream`` runs the 14x14 and 7x7 layers of two batches' static stages as ONE pass
+        (ResnetStage.forward_multi: 16-bit static stage, cube 224, the whole batch in one frame chunk, the stage contexts in
+        use and no captured graph, whose launches hold the buffers of the plain call)."""
+        if not stage_ctx.USE_CTX or self.frame_chunk < self.B * self.T or getattr(self, '_graph', None) is not None:
+            return False
+        return self._resnet_stage().can_pair_static(6 * self.B * self.T, self.cube_dim)
 
     def stream(self, batches):
         """Software-pipelined form for a STREAM of batches (serving): a generator that takes an iterable of frame batches
@@ -208,12 +225,24 @@ class SaliencyEngine:
         Everything is queued on the caller's stream, stage after stage: with the filters shared a GEMM launch is no longer
         waiting on HBM, and static-stage workgroups beside it then cost more than they fill (4 clips x 16 frames at
         1024 x 2048: 11.75 ms per batch in order, 11.88 with the next pair's static stages on a second stream, 12.01 unpaired;
-        docs/rounds/r07_pairing.md).  A yielded tensor is overwritten four batches later."""
+        docs/rounds/r07_pairing.md).  A yielded tensor is overwritten four batches later.
+
+        Where ``can_pair_static`` holds (16-bit static stage at cube 224) the pair's static stages are ONE call as well
+        (ResnetStage.forward_multi -> cp360_resnet_forward_multi): K1 per batch as the batches arrive, stem .. layer3.0 per
+        batch, layer3.1 .. layer4 and the CAM once for both - the same bits again (docs/rounds/r08_static_back_pair.md).  The
+        first batch's frames are kept until its partner arrives (read again only if the fp16 range guard switches the static
+        stage to bf16 in between); an odd last batch takes the plain static call."""
+        pair_static = self.can_pair_static()
+        if pair_static and getattr(self, '_cam_pair', None) is None:
+            # the joint CAM launch writes both batches' scores: the two CAM buffers are the halves of one tensor
+            self._cam_pair = torch.empty((2,) + tuple(self.cam.shape), dtype=torch.float32, device=self.device)
+            self.cam, self._cam2 = self._cam_pair[0], self._cam_pair[1]
         if self._cam2 is None:
             self._cam2 = torch.empty_like(self.cam)
         cams = (self.cam, self._cam2)
         main = torch.cuda.current_stream(self.device)
         outs = [None] * 4
+        held = None                                        # pair_static: (frames, faces) of a pair's first batch
 
         def keep(i, sal):
             if outs[i & 3] is None:
@@ -231,11 +260,29 @@ class SaliencyEngine:
                               "to bf16" % self.overflow_batches)
                 main.synchronize()
                 self._fallback_to_bf16()
+                pair_static = pair_static and self.can_pair_static()
+                if held is not None:                       # the pair's first batch: its faces are fp16, projected again in bf16
+                    with torch.no_grad():
+                        if pair_static:
+                            held = (held[0], self._cube_faces(held[0]))
+                        else:
+                            self.static_stage(held[0], cam=cams[0])
+                            held = None
             n = i + 1
+            flat = frames.reshape((B * T,) + tuple(frames.shape[2:]))
             with torch.no_grad():
-                self.static_stage(frames.reshape((B * T,) + tuple(frames.shape[2:])), cam=cams[i & 1])
-                if not i & 1:
-                    continue
+                if pair_static:
+                    # K1 per batch, then ONE static call for the pair: the front per batch, layer3.1 .. CAM once for both
+                    if not i & 1:
+                        held = (flat, self._cube_faces(flat))
+                        continue
+                    faces, held = [held[1], self._cube_faces(flat)], None
+                    self._resnet_stage().forward_multi(faces, self._cam_pair)
+                    del faces
+                else:
+                    self.static_stage(flat, cam=cams[i & 1])
+                    if not i & 1:
+                        continue
                 sals = self.pair.run(cams[0], cams[1], return_all_steps=self.return_all_steps)
                 maps = [keep(i - 1, sals[0]), keep(i, sals[1])]
             for mm in self.pair.minmax.view(2, self.B, 2):
@@ -243,6 +290,10 @@ class SaliencyEngine:
             yield from maps
         if n & 1:                                          # the last batch has no partner
             with torch.no_grad():
+                if held is not None:                       # its faces are projected; the plain static call on them
+                    cam_device(held[1], self.resnet, out=cams[0].view(self.B * self.T, 6 * self.w * self.w, -1), padded=True,
+                               want_feat=False)
+                    held = None
                 last = keep(n - 1, self.temporal_stage(cams[0]))
             self._stream_guard()
             yield last

@@ -210,6 +210,50 @@ class ResnetStage(_Stage):
                                          stream()))
         return cam_out.view(-1)[:need].view(n_img, hw, hw, nc), feat
 
+    def can_pair_static(self, n_img, cube_dim, groups=2):
+        """True when ``forward_multi`` runs the 14x14 and 7x7 layers of ``groups`` batches of n_img faces as ONE pass with the
+        bits of one ``forward`` per batch (cp360_resnet_can_pair_static: 16-bit types at cube 224); False (f32, other cube
+        sizes): call ``forward`` per batch."""
+        self._load()
+        return bool(lib().cp360_resnet_can_pair_static(self.ctx.h, int(groups), int(n_img), int(cube_dim)))
+
+    def describe_multi(self, groups, n_img, cube_dim):
+        """cp360_resnet_plan_describe_multi: the plan of ``forward_multi`` as text - the front, the cut and the back."""
+        self._load()
+        buf = C.create_string_buffer(1 << 15)
+        n = lib().cp360_resnet_plan_describe_multi(self.ctx.h, int(groups), int(n_img), int(cube_dim), buf, len(buf))
+        check(n if n < 0 else 0)
+        return buf.value.decode()
+
+    def forward_multi(self, faces, cam_out):
+        """cp360_resnet_forward_multi: faces = one [6N, cd+6, cd+6, 4] tensor per batch (as ``forward``'s), cam_out = ONE
+        contiguous f32 tensor of at least len(faces) * 6N * h * w * classes elements: batch g's scores are its rows
+        [g * 6N, (g + 1) * 6N).  Returns them as [len(faces), 6N, h, w, classes]."""
+        self._load()
+        m = self.model
+        dt = precision_dtype(m.precision)
+        G = len(faces)
+        require_gpu(cam_out, *faces)
+        for f in faces:
+            if f.dtype != dt or not f.is_contiguous() or f.dim() != 4 or f.shape[3] != 4 or f.shape[1] != f.shape[2] \
+                    or f.shape != faces[0].shape:
+                raise ValueError("every faces_p3 must be a contiguous %s [6N, cd+6, cd+6, 4] tensor of one shape" % dt)
+        n_img, cd = faces[0].shape[0], faces[0].shape[1] - 6
+        hw, nc = cd // 32, int(m.fc.weight.shape[0])
+        per = n_img * hw * hw * nc
+        if cam_out.dtype != torch.float32 or not cam_out.is_contiguous() or cam_out.numel() < G * per:
+            raise ValueError("cam_out must be a contiguous f32 tensor of at least %d elements" % (G * per))
+        nbytes = lib().cp360_resnet_forward_multi_workspace_bytes(self.ctx.h, G, n_img, cd)
+        if nbytes == 0:
+            raise ValueError("unsupported joint static-stage geometry: %d x %d faces of %d^2 (see can_pair_static)" % (G, n_img, cd))
+        # (the workspace of the plain forward at this shape is a prefix of this one: they share the allocation)
+        ws = self.ctx.workspace(('resnet', n_img, cd), nbytes)
+        arr = lambda ps: (C.c_void_p * G)(*ps)
+        check(lib().cp360_resnet_forward_multi(self.ctx.h, arr([f.data_ptr() for f in faces]), G, n_img, cd,
+                                               arr([cam_out.data_ptr() + 4 * g * per for g in range(G)]), ptr(ws), ws.numel(),
+                                               stream()))
+        return cam_out.view(-1)[:G * per].view(G, n_img, hw, hw, nc)
+
 
 class ClstmStage(_Stage):
     """``ConvLSTMCell`` (model/clstm.py) behind cp360_clstm_step, for one face size."""

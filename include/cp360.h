@@ -228,6 +228,11 @@ int cp360_conv_plan_describe(const cp360_conv_desc* d, char* buf, size_t cap);
  * output channels, e.g. layer4's conv2 of ONE frame in f32, give the clip kernel 2 tiles for 256 CUs).  d->clip_resident
  * and d->splits are ignored. */
 int cp360_conv_prefer_clip(const cp360_conv_desc* d);
+/* The tile_px value that names the kernel the planner launches this descriptor on (0: the kernel follows from the
+ * descriptor without the image count - clip-resident, fewer than 256 output channels - or the descriptor is refused).
+ * Written into a descriptor of the same convolution on MORE images it keeps that launch on the same kernel, where the
+ * cost model would choose again by rounds of the chip (the joint back half of cp360_resnet_forward_multi). */
+int cp360_conv_plan_tile(const cp360_conv_desc* d);
 /* Bytes of split-K workspace (0 when splits == 1). */
 size_t cp360_conv_partial_bytes(const cp360_conv_desc* d);
 /* Pack OIHW f32 weights [c_out, c_in_w, kh_w, kw_w] times scale[c_out] (BatchNorm
@@ -900,6 +905,26 @@ int cp360_clstm_window_multi(cp360_ctx* ctx, const float* const* cams, size_t cl
  * other geometry - and f32 - takes the per-convolution path, whose tile / split-K choice per launch is listed).  Returns the
  * length written (truncated to cap - 1) or a negative status.  Costs no GPU work. */
 int cp360_resnet_plan_describe(cp360_ctx* ctx, int n_img, int cube_dim, char* buf, size_t cap);
+
+/* The static stages of n_groups in-flight batches of n_img faces each, the 14x14 and 7x7 layers as ONE pass (16-bit types,
+ * cube 224).  FRONT: stem .. layer3.0 runs per group at n_img faces, as in cp360_resnet_forward; each group's layer3.0
+ * output is written into its rows of a hand-over buffer in the workspace.  BACK: layer3.1 .. layer4 and the CAM run once at
+ * n_groups * n_img faces - the 7x7 launches of layer4, 0.6 - 0.9 of a round of the chip per batch of 384 faces, fill it at
+ * 768, and the layer3 tails lose their half-empty last round.  Every back launch keeps the kernel family, the split-K count, the K ranges, the finish order and the
+ * epilogue of the plan at n_img faces (GEMM rows are independent, CubePad stays inside a cube): each group's CAM is
+ * cp360_resnet_forward's bit for bit.
+ *   faces_p3  HOST array of n_groups device pointers, each as cp360_resnet_forward's faces_p3
+ *   cam_out   HOST array of n_groups device pointers with cam_out[g] == cam_out[0] + g * n_img * (cd/32)^2 * num_classes:
+ *             the CAM launch writes all groups at once (anything else: CP360_ERR_BAD_SHAPE, before any launch)
+ * n_groups == 1 is cp360_resnet_forward (any type, any cube size).  n_groups >= 2 where cp360_resnet_can_pair_static
+ * answers 0 (f32, other cube sizes): CP360_ERR_UNSUPPORTED - call cp360_resnet_forward per batch there.
+ * workspace: cp360_resnet_forward_multi_workspace_bytes (256-byte aligned).  cp360_resnet_plan_describe_multi: the plan as
+ * text, naming the front, the cut and the back. */
+int cp360_resnet_can_pair_static(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim);
+size_t cp360_resnet_forward_multi_workspace_bytes(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim);
+int cp360_resnet_forward_multi(cp360_ctx* ctx, const void* const* faces_p3, int n_groups, int n_img, int cube_dim,
+                               float* const* cam_out, void* workspace, size_t workspace_bytes, void* stream);
+int cp360_resnet_plan_describe_multi(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim, char* buf, size_t cap);
 
 /* Diagnostic only (bench.py `held_clock_ghz`): a bare bf16 MFMA loop on pseudo-random operands, n_workgroups x 4 waves, each
  * wave stamped once around `iters` x 16 MFMAs.  stamps: device u64 [n_workgroups * 4][2] = {d s_memtime (shader cycles),
