@@ -1,10 +1,11 @@
 // K12: the viewport pilot - a saliency map turned into a camera: the perspective (gnomonic) view of an equirectangular frame
 // under a camera rotation (K12a), the view's frame drawn on the panorama (K12b), the saliency map smoothed on the sphere (K12c)
 // and its peak with one mean-shift step (K12d); and the camera path that collects the most saliency under a turn limit and a turn
-// cost, by dynamic programming over the map's pixels (K16a - K16c).  The reference's utils/fov_visual.py (box_proh, fov_module,
-// draw_cube_fov_box) has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12" and "K16";
-// tests/viewport_restate.py restates K12 in float64, tests/campath_restate.py K16 in integers.  Geometry, tables and the
-// bilinear sample are sphere.h's.
+// cost, by dynamic programming over the map's pixels (K16a - K16c); and several cameras at once: the caps about earlier cameras
+// taken out of a map (K20a) and several views on one canvas (K20b).  The reference's utils/fov_visual.py (box_proh, fov_module,
+// draw_cube_fov_box) has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12", "K16" and
+// "K20"; tests/viewport_restate.py restates K12 in float64, tests/campath_restate.py K16 in integers, tests/director_restate.py
+// K20.  Geometry, tables and the bilinear sample are sphere.h's.
 //
 // Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
 // centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
@@ -18,6 +19,10 @@
 //         acc[t][j] = q[t][j] + max_i (acc[t-1][i] - cost(i, j)) over the allowed i, back[t][j] = that i (lowest on ties)
 //   K16b  idx[hi-1] = argmax acc[hi-1] (lowest on ties), idx[t-1] = back[t][idx[t]], dir = dir(idx), score = acc[hi-1][idx[hi-1]]
 //   K16c  K12d's mean-shift step about p* = dir(idx[t]) for given indices
+//   K20a  out[t][j] = +0 where ((p_x d_x + p_y d_y) + p_z d_z) >= (float)cos(radius) for any finite direction d of frame t, else
+//         the input's bits
+//   K20b  canvas pixel (x0_k + i, y0_k + j) of tile k = K12a's view pixel (i, j) of the view (h_k, w_k, hfov_k) under R[n][k];
+//         fill outside every tile and in the tile of a non-finite camera
 // Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d / K16c are f64 in a fixed order;
 // K16a / K16b are integers.  No atomics, no host synchronisation, results independent of the batch size.
 #pragma clang fp contract(off)
@@ -47,6 +52,20 @@ __device__ __forceinline__ void peak_take(V ov, int oi, V& best, int& bi) {
 }
 
 // ------------------------------------------------------------------ K12a: the view
+// K12a's pixel, which K20b repeats per tile: view pixel (i, j) of the view (h, w, tx, ty) under R, sampled from the H x W frame
+// `img` into the C channels at o
+template <typename T, int C>
+__device__ __forceinline__ void view_pixel(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty,
+                                           int i, int j, T* __restrict__ o) {
+    const float u = ((float)(2 * i + 1) / (float)w - 1.f) * tx;
+    const float v = (1.f - (float)(2 * j + 1) / (float)h) * ty;
+    const float r = 1.f / sqrtf((1.f + v * v) + u * u);
+    float qx, qy, qz, sx, sy;
+    stab_rotate(R, r, v * r, u * r, qx, qy, qz);
+    stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
+    sphere_sample<T, C>(img, H, W, sx, sy, o);
+}
+
 // grid (ceil(w / 256), h, N): one thread per view pixel, all C channels
 template <typename T, int C>
 __global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ src, const float* __restrict__ Rs, T* __restrict__ dst,
@@ -54,13 +73,89 @@ __global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ 
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (i >= w) return;
     const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    const float u = ((float)(2 * i + 1) / (float)w - 1.f) * tx;
-    const float v = (1.f - (float)(2 * j + 1) / (float)h) * ty;
-    const float r = 1.f / sqrtf((1.f + v * v) + u * u);
-    float qx, qy, qz, sx, sy;
-    stab_rotate(R, r, v * r, u * r, qx, qy, qz);
-    stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
-    sphere_sample<T, C>(src + (size_t)blockIdx.z * H * W * C, H, W, sx, sy, dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
+    view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
+}
+
+// ------------------------------------------------------------------ K20b: several views on one canvas
+// The tiles of a canvas, by value: rectangle k = (x0, y0, w, h) shows the view (h, w, tx, ty) of camera k.  The host has checked
+// that the K <= 8 rectangles are not empty, lie on the canvas and do not overlap.  fill: what a pixel in no tile takes.
+constexpr int kMaxTiles = 8;
+
+template <typename T>
+struct ViewTiles {
+    int x0[kMaxTiles], y0[kMaxTiles], w[kMaxTiles], h[kMaxTiles];
+    float tx[kMaxTiles], ty[kMaxTiles];
+    T fill[4];
+    int K;
+};
+
+// grid (ceil(wc / 256), hc, N): one thread per canvas pixel.  The scan over the tiles is unrolled: every index into the table is
+// a constant, the table stays in the kernel's arguments and the chosen tile in registers.  A pixel in no tile, or in the tile of
+// a camera with a non-finite entry, takes fill.
+template <typename T, int C>
+__global__ __launch_bounds__(256) void view_render_multi_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
+                                                                T* __restrict__ dst, int H, int W, int hc, int wc,
+                                                                const ViewTiles<T> tiles) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= wc) return;
+    int sel = -1, i = 0, j = 0, w = 1, h = 1;
+    float tx = 0.f, ty = 0.f;
+#pragma unroll
+    for (int k = 0; k < kMaxTiles; ++k) {
+        const int di = x - tiles.x0[k], dj = y - tiles.y0[k];
+        if (k < tiles.K && di >= 0 && di < tiles.w[k] && dj >= 0 && dj < tiles.h[k]) {
+            sel = k;
+            i = di;
+            j = dj;
+            w = tiles.w[k];
+            h = tiles.h[k];
+            tx = tiles.tx[k];
+            ty = tiles.ty[k];
+        }
+    }
+    T* o = dst + (((size_t)blockIdx.z * hc + y) * wc + x) * C;
+    if (sel >= 0) {
+        const Rot R = load_rot(Rs + ((size_t)blockIdx.z * tiles.K + sel) * 9);
+        if (rot_finite(R)) {
+            view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, o);
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = tiles.fill[c];
+}
+
+// ------------------------------------------------------------------ K20a: the caps of earlier cameras taken out of a map
+// grid (ceil(P / 256), F): one thread per pixel.  dirs f32 [F][Kx][3]; the pixel is +0 where ((p_x d_x + p_y d_y) + p_z d_z) >= c
+// for any k, else the input's bits.  A direction with a non-finite component excludes nothing (an infinite dot would pass the
+// comparison, so it is tested).  The loop over the directions is unrolled to its bound of 7: registers only.  Element-wise: out
+// may be maps.
+constexpr int kMaxCaps = 7;
+
+__device__ __forceinline__ bool in_any_cap(const float* __restrict__ d, int Kx, float px, float py, float pz, float c) {
+    bool hit = false;
+#pragma unroll
+    for (int k = 0; k < kMaxCaps; ++k) {
+        if (k < Kx) {
+            const float dx = d[3 * k], dy = d[3 * k + 1], dz = d[3 * k + 2];
+            const float dot = (px * dx + py * dy) + pz * dz;
+            hit = hit || (isfinite(fabsf(dx) + fabsf(dy) + fabsf(dz)) && dot >= c);
+        }
+    }
+    return hit;
+}
+
+__global__ __launch_bounds__(256) void view_exclude_kernel(const float* maps, const float* __restrict__ dirs,
+                                                           const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                           float* out, int hm, int wm, int Kx, float c) {
+    const int P = hm * wm, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= P) return;
+    const int y = j / wm, x = j - y * wm;
+    float px, py, pz;
+    stab_dir(tabx[x], taby[y], px, py, pz);
+    const size_t o = (size_t)blockIdx.y * P + j;
+    if (in_any_cap(dirs + (size_t)blockIdx.y * Kx * 3, Kx, px, py, pz, c)) out[o] = 0.f;
+    else if (out != maps) out[o] = maps[o];
 }
 
 // ------------------------------------------------------------------ K12b: the view's frame on the panorama
@@ -395,6 +490,39 @@ int launch_render(const void* frames, const float* R, void* out, int N, int H, i
     return CP360_OK;
 }
 
+template <typename T, int C>
+int launch_render_multi(const void* frames, const float* R, void* out, int N, int H, int W, int hc, int wc, int K,
+                        const int32_t* rects, const float* tx, const float* ty, const void* fill, hipStream_t s) {
+    ViewTiles<T> t = {};
+    t.K = K;
+    for (int k = 0; k < K; ++k) {
+        t.x0[k] = rects[4 * k];
+        t.y0[k] = rects[4 * k + 1];
+        t.w[k] = rects[4 * k + 2];
+        t.h[k] = rects[4 * k + 3];
+        t.tx[k] = tx[k];
+        t.ty[k] = ty[k];
+    }
+    for (int c = 0; c < C; ++c) t.fill[c] = ((const T*)fill)[c];
+    hipLaunchKernelGGL((view_render_multi_kernel<T, C>), dim3((wc + 255) / 256, hc, N), dim3(256), 0, s, (const T*)frames, R,
+                       (T*)out, H, W, hc, wc, t);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// K20b: whether the K rectangles (x0, y0, w, h) are not empty, lie on the hc x wc canvas and share no pixel
+bool bad_tiles(const int32_t* rects, int K, int hc, int wc) {
+    for (int k = 0; k < K; ++k) {
+        const long long x0 = rects[4 * k], y0 = rects[4 * k + 1], w = rects[4 * k + 2], h = rects[4 * k + 3];
+        if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || x0 + w > wc || y0 + h > hc) return true;
+        for (int m = 0; m < k; ++m) {
+            const long long mx = rects[4 * m], my = rects[4 * m + 1], mw = rects[4 * m + 2], mh = rects[4 * m + 3];
+            if (x0 < mx + mw && mx < x0 + w && y0 < my + mh && my < y0 + h) return true;
+        }
+    }
+    return false;
+}
+
 // the checks smooth and peak share; *kappa = 1 / sigma^2 rounded once
 int map_args(int F, int hm, int wm, double sigma_rad, const void* work, size_t work_bytes, float* kappa) {
     if (bad_image(F, hm, wm) || bad_sigma(sigma_rad)) return CP360_ERR_BAD_SHAPE;
@@ -580,4 +708,44 @@ extern "C" int cp360_view_refine(const float* maps, const int32_t* idx, int F, i
     hipLaunchKernelGGL(view_refine_kernel, dim3(F), dim3(256), 0, s, maps, (const int*)idx, t.x, t.y, dir_out, hm, wm, kappa);
     CP360_CHECK_HIP();
     return CP360_OK;
+}
+
+// ------------------------------------------------------------------ K20: several cameras at once
+extern "C" int cp360_view_exclude(const float* maps, const float* dirs, int F, int hm, int wm, int Kx, double radius_rad, float* out,
+                                  void* work, size_t work_bytes, void* stream) {
+    if (!maps || !dirs || !out || !work) return CP360_ERR_NULL;
+    if (bad_image(F, hm, wm) || Kx < 1 || Kx > kMaxCaps || !(radius_rad > 0.0 && radius_rad <= kPi)) return CP360_ERR_BAD_SHAPE;
+    int st = path_args(F, hm, wm);
+    if (st != CP360_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = open_tabs(work, work_bytes, tab_bytes(hm, wm), hm, wm, s, &t);
+    if (st != CP360_OK) return st;
+    const float c = (float)cos(radius_rad);
+    hipLaunchKernelGGL(view_exclude_kernel, dim3((hm * wm + 255) / 256, F), dim3(256), 0, s, maps, dirs, t.x, t.y, out, hm, wm, Kx, c);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_view_render_multi(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K,
+                                       const int32_t* tiles, const double* hfov_rad, const void* fill, void* out, int hc, int wc,
+                                       void* stream) {
+    if (!frames || !R || !tiles || !hfov_rad || !fill || !out) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || bad_image(N, hc, wc) || C < 1 || K < 1 || K > kMaxTiles) return CP360_ERR_BAD_SHAPE;
+    for (int k = 0; k < K; ++k)
+        if (bad_hfov(hfov_rad[k])) return CP360_ERR_BAD_SHAPE;
+    if (bad_tiles(tiles, K, hc, wc)) return CP360_ERR_BAD_SHAPE;
+    if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
+    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, hc, wc)) return CP360_ERR_UNSUPPORTED;
+    if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
+    float tx[kMaxTiles], ty[kMaxTiles];
+    for (int k = 0; k < K; ++k) {                                       // cp360_view_render's, per tile
+        const double t = tan(0.5 * hfov_rad[k]);
+        tx[k] = (float)t;
+        ty[k] = (float)(t * (double)tiles[4 * k + 3] / (double)tiles[4 * k + 2]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_pixels(dtype, C, [&](auto px, auto c) {
+        return launch_render_multi<decltype(px), decltype(c)::value>(frames, R, out, N, H, W, hc, wc, K, tiles, tx, ty, fill, s);
+    });
 }

@@ -1654,6 +1654,79 @@ def sphere_refine(maps, idx, sigma_deg=15.0, work=None):
     return dirs
 
 
+# ----------------------------------------------------------------------------- K20: several cameras at once (csrc/viewport.hip)
+def sphere_exclude(maps, dirs, radius_deg, out=None, work=None):
+    """cp360_view_exclude: maps f32 [F, hm, wm] with the caps of radius_deg degrees about the directions dirs f32 [F, Kx, 3]
+    (1 <= Kx <= 7) set to +0: a pixel goes where the f32 dot of its centre with any direction of its frame is at least
+    cos(radius_deg); every other pixel keeps its bits.  A direction with a non-finite component excludes nothing.  out may be
+    maps."""
+    if maps.dim() != 3 or maps.numel() == 0:
+        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+    if dirs.dim() != 3 or dirs.shape[0] != maps.shape[0] or not 1 <= dirs.shape[1] <= 7 or dirs.shape[2] != 3:
+        raise ValueError("dirs must be float32 [%d, Kx, 3] with 1 <= Kx <= 7, got %s" % (maps.shape[0], tuple(dirs.shape)))
+    if not 0.0 < float(radius_deg) <= 180.0:
+        raise ValueError("radius_deg must be in (0, 180], got %r" % (radius_deg,))
+    require_gpu(maps, dirs, out, work)
+    _check_buf('maps', maps, torch.float32)
+    F, hm, wm = (int(s) for s in maps.shape)
+    if hm * wm > 16384:
+        raise ValueError("maps of more than 16384 pixels are not supported, got %d x %d" % (hm, wm))
+    if dirs.device != maps.device:
+        raise ValueError("dirs must be on the maps' device")
+    _check_buf('dirs', dirs, torch.float32)
+    out = _out_for(out, maps.shape, torch.float32, maps.device, maps, same_ok=True)
+    work = _stab_work(0, hm, wm, maps.device, work)
+    check(lib().cp360_view_exclude(ptr(maps), ptr(dirs), F, hm, wm, int(dirs.shape[1]), math.radians(float(radius_deg)), ptr(out),
+                                   ptr(work), work.numel() * 8, stream()))
+    return out
+
+
+def check_tiles(tiles, canvas_hw):
+    """The tiles of a canvas: K rectangles (x0, y0, w, h), 1 <= K <= 8, none empty, all on the canvas of canvas_hw = (hc, wc),
+    no two sharing a pixel -> ([(x0, y0, w, h)] as ints, (hc, wc)); ValueError otherwise."""
+    hc, wc = (int(v) for v in canvas_hw)
+    tiles = [tuple(int(v) for v in t) for t in tiles]
+    if hc < 1 or wc < 1 or not 1 <= len(tiles) <= 8 or any(len(t) != 4 for t in tiles):
+        raise ValueError("a canvas needs hc, wc >= 1 and 1 .. 8 tiles (x0, y0, w, h), got %r, %r" % (canvas_hw, tiles))
+    for k, (x0, y0, w, h) in enumerate(tiles):
+        if w < 1 or h < 1:
+            raise ValueError("tile %d is empty: %r" % (k, tiles[k]))
+        if x0 < 0 or y0 < 0 or x0 + w > wc or y0 + h > hc:
+            raise ValueError("tile %d %r leaves the canvas of %d x %d" % (k, tiles[k], hc, wc))
+        for m, (mx, my, mw, mh) in enumerate(tiles[:k]):
+            if x0 < mx + mw and mx < x0 + w and y0 < my + mh and my < y0 + h:
+                raise ValueError("tiles %d and %d overlap: %r, %r" % (m, k, tiles[m], tiles[k]))
+    return tiles, (hc, wc)
+
+
+def viewport_render_multi(frames, R, tiles, hfov_deg, canvas_hw, fill=None, out=None):
+    """cp360_view_render_multi: K views of every frame on one canvas in one launch.  frames as ``viewport_render``'s, R f32
+    [N, K, 3, 3], tiles K rectangles (x0, y0, w, h) on the canvas of canvas_hw = (hc, wc), hfov_deg a scalar or one value per
+    tile -> [N, hc, wc, C] of the frames' type.  Tile k is ``viewport_render(frames, R[:, k], (h, w), hfov_deg[k])`` bit for bit;
+    a pixel in no tile, and the tile of a camera with a non-finite entry, take fill (C values, default 0)."""
+    tiles, (hc, wc) = check_tiles(tiles, canvas_hw)
+    require_gpu(frames, R, out)
+    N, H, W, C_ = _frames_nhwc(frames, u8_only=False)
+    K = len(tiles)
+    if R.dim() != 4 or tuple(R.shape) != (N, K, 3, 3):
+        raise ValueError("R must be [%d, %d, 3, 3], got %s" % (N, K, tuple(R.shape)))
+    _check_buf('R', R, torch.float32)
+    hfov = [float(hfov_deg)] * K if np.ndim(hfov_deg) == 0 else [float(v) for v in hfov_deg]
+    if len(hfov) != K or not all(0.0 < v < 180.0 for v in hfov):
+        raise ValueError("hfov_deg must be one value or one per tile, each in (0, 180), got %r" % (hfov_deg,))
+    u8 = frames.dtype == torch.uint8
+    fill = [0] * C_ if fill is None else list(fill)
+    if len(fill) != C_ or (u8 and any(int(v) != v or not 0 <= v <= 255 for v in fill)):
+        raise ValueError("fill must be %d values of the frames' type, got %r" % (C_, fill))
+    out = _out_for(out, (N, hc, wc, C_), frames.dtype, frames.device, frames)
+    rects = (C.c_int32 * (4 * K))(*[v for t in tiles for v in t])
+    fovs = (C.c_double * K)(*[math.radians(v) for v in hfov])
+    colour = (C.c_ubyte * C_)(*[int(v) for v in fill]) if u8 else (C.c_float * C_)(*[float(v) for v in fill])
+    check(lib().cp360_view_render_multi(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, K, C.cast(rects, C.c_void_p),
+                                        C.cast(fovs, C.c_void_p), C.cast(colour, C.c_void_p), ptr(out), hc, wc, stream()))
+    return out
+
+
 # ----------------------------------------------------------------------------- K13: shot detection (csrc/shots.hip)
 _SHOT_WEIGHTS = {}
 

@@ -7,8 +7,12 @@ become a smooth camera path on the host (``smooth_path``: a zero-phase exponenti
 camera with a level horizon), and the views are rendered at the frames' own resolution (``ops.viewport_render``);
 ``ops.viewport_outline`` draws the view's frame on the panorama.  ``planner='viterbi'`` replaces the per-frame peaks by the path
 that collects the most saliency under a turn limit and a turn cost (K16: ``ops.sphere_path``, then ``ops.sphere_refine``): it
-chooses which of several targets to follow, where the peaks hop between them.  A camera is a rotation R, camera-to-world, with the columns
-(forward, up, right): R = I looks at the panorama's centre.  Roll, translation and anti-aliased views are out of scope.
+chooses which of several targets to follow, where the peaks hop between them.  Several cameras at once (K20, DESIGN.md "K20"):
+``plan_multi`` plans them one after the other, each on the maps with a cap about the cameras before it taken out
+(``ops.sphere_exclude``), ``paths`` turns the plans into cameras, drops those that found nothing and orders them, and
+``render_multi`` shows their views side by side on one canvas (``ops.viewport_render_multi``).  A camera is a rotation R,
+camera-to-world, with the columns (forward, up, right): R = I looks at the panorama's centre.  Roll, translation and anti-aliased
+views are out of scope.
 """
 import numpy as np
 import torch
@@ -97,6 +101,81 @@ def cameras(path, cuts=None):
     return np.stack(out)
 
 
+def split_layout(n, hw, gutter=8, direction='row'):
+    """n tiles of hw = (h, w) pixels side by side ('row') or stacked ('column') with ``gutter`` pixels between them ->
+    (tiles [(x0, y0, w, h)] * n, canvas_hw): what ``ViewportPilot.render_multi`` takes."""
+    n, h, w, gutter = int(n), int(hw[0]), int(hw[1]), int(gutter)
+    if not 1 <= n <= 8 or h < 1 or w < 1 or gutter < 0 or direction not in ('row', 'column'):
+        raise ValueError("a layout needs 1 <= n <= 8, h, w >= 1, gutter >= 0 and direction 'row' or 'column', got %r, %r, %r, %r"
+                         % (n, hw, gutter, direction))
+    if direction == 'row':
+        return [(k * (w + gutter), 0, w, h) for k in range(n)], (h, n * w + (n - 1) * gutter)
+    return [(0, k * (h + gutter), w, h) for k in range(n)], (n * h + (n - 1) * gutter, w)
+
+
+def _longitude_deg(v):
+    return np.rad2deg(np.arctan2(v[2], v[0]))
+
+
+def longitude_order(means):
+    """means float64 [m, 3], the unit mean directions of a shot's active cameras -> their order from left to right on the
+    panorama: by wrap(lon(m_k) - lon(c)) into (-180, 180] with c the normalised sum of the means and lon = atan2(z, x), ties by
+    index.  Where c has no longitude (hypot(c_x, c_z) < 1e-9) the given order stays."""
+    means = np.asarray(means, np.float64)
+    c = means.sum(axis=0)
+    if np.hypot(c[0], c[2]) < 1e-9:
+        return list(range(len(means)))
+    keys = [180.0 - ((180.0 - (_longitude_deg(m) - _longitude_deg(c))) % 360.0) for m in means]
+    return sorted(range(len(means)), key=lambda k: (keys[k], k))
+
+
+def multi_cameras(dirs, score, cuts=None, alpha=0.85, max_step_deg=None, min_share=0.0, arrange='score'):
+    """The host half of ``ViewportPilot.paths``, float64: dirs [n, F, 3], the planned directions of n cameras, and score [n, S],
+    their votes per shot -> (R [F, n, 3, 3], share [n, S]).  Every camera's path is ``smooth_path`` and ``cameras`` with
+    ``cuts``; share[k][s] = score[k][s] / score[0][s] (0 where score[0][s] is 0).  Camera k >= 1 is dropped in the shots where
+    its share is below min_share: its R is NaN there.  arrange 'score' keeps the cameras in their order; 'longitude' puts every
+    shot's active cameras in ``longitude_order`` of the normalised means of their filtered paths over the shot, the dropped ones
+    behind them - R and share are then both by position."""
+    dirs, score = np.asarray(dirs, np.float64), np.asarray(score, np.float64)
+    if dirs.ndim != 3 or dirs.shape[2] != 3 or not 1 <= dirs.shape[0] <= 8 or dirs.shape[1] < 1:
+        raise ValueError("dirs must be [n, F, 3] with 1 <= n <= 8, got %s" % (dirs.shape,))
+    if not 0.0 <= float(min_share) <= 1.0:
+        raise ValueError("min_share must be in [0, 1], got %r" % (min_share,))
+    if arrange not in ('score', 'longitude'):
+        raise ValueError("arrange must be 'score' or 'longitude', got %r" % (arrange,))
+    n, F = dirs.shape[:2]
+    shots = segments(cuts, F)
+    if score.shape != (n, len(shots)):
+        raise ValueError("score must be [%d, %d], one value per camera and shot, got %s" % (n, len(shots), score.shape))
+    paths = np.stack([smooth_path(dirs[k], alpha, max_step_deg, cuts) for k in range(n)])
+    cams = np.stack([cameras(paths[k], cuts) for k in range(n)])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        share = np.where(score[0] == 0, 0.0, score / score[0])
+    R, placed = np.full((F, n, 3, 3), np.nan), np.zeros_like(share)
+    for s, (lo, hi) in enumerate(shots):
+        active = [k for k in range(n) if k == 0 or share[k][s] >= float(min_share)]
+        order = list(range(n))
+        if arrange == 'longitude':
+            means = [_unit(paths[k, lo:hi].mean(axis=0)) for k in active]
+            order = [active[j] for j in longitude_order(means)] + [k for k in range(n) if k not in active]
+        for slot, k in enumerate(order):
+            placed[slot][s] = share[k][s]
+            if k in active:
+                R[lo:hi, slot] = cams[k, lo:hi]
+    return R, placed
+
+
+class MultiAgreement:
+    """What ``ViewportPilot.agreement_multi`` returns, on the device: ``best_iou`` float64 [N], the largest finite ``iou`` of the
+    viewer over the cameras that are finite in its frame (NaN without any), ``best_cam`` int64 [N], that camera (the lowest on
+    ties, -1 without any); ``frame_iou``, ``centre_angle_deg`` (of the best camera) and ``finite`` as ``HeadAgreement``'s, so
+    that ``HeadMaps.means`` takes it; ``cameras``, the n ``HeadAgreement``s."""
+
+    def __init__(self, best_iou, best_cam, frame_iou, centre_angle_deg, finite, cameras):
+        self.best_iou, self.best_cam, self.frame_iou = best_iou, best_cam, frame_iou
+        self.centre_angle_deg, self.finite, self.cameras = centre_angle_deg, finite, cameras
+
+
 class ViewportPilot:
     """``ViewportPilot((h, w), hfov_deg)``: views of h x w pixels that follow the saliency maps' peak.  Holds the workspaces.
 
@@ -131,6 +210,20 @@ class ViewportPilot:
         """maps f32 [F, hm, wm] -> the directions of the planned path, f32 [F, 3] on the device: the maps smoothed, every frame's
         votes scaled so that its peak votes 4096, the best path over the map's pixels (``ops.sphere_path``; every shot of ``cuts``
         has its own) and one mean-shift step about each of its pixels (``ops.sphere_refine``).  No host synchronisation."""
+        return self.plan_multi(maps, 1, cuts)[0][0]
+
+    def plan_multi(self, maps, n, cuts=None, exclude_deg=None):
+        """maps f32 [F, hm, wm] -> (dirs f32 [n, F, 3], score i32 [n, S]) on the device: the planned paths of n <= 8 cameras and
+        the votes each collected in each of the S shots of ``cuts``.  Camera 0 is ``plan``'s.  Camera k >= 1 plans on the
+        smoothed maps, and refines on the raw ones, with the caps of ``exclude_deg`` degrees about the refined directions of
+        the cameras 0 .. k - 1 set to zero (``ops.sphere_exclude``): greedy, one target after the other.  Every camera votes
+        with camera 0's gain, so the scores compare; camera k does not depend on n.  ``exclude_deg`` defaults to hfov_deg / 2:
+        two targets closer than half a view fit in one view - a convention, not tuned on data.  Always the dynamic programme,
+        whatever ``planner`` is.  No host synchronisation."""
+        n = int(n)
+        exclude_deg = 0.5 * self.hfov_deg if exclude_deg is None else float(exclude_deg)
+        if not 1 <= n <= 8 or not 0.0 < exclude_deg <= 180.0:
+            raise ValueError("n must be 1 .. 8 and exclude_deg in (0, 180], got %r, %r" % (n, exclude_deg))
         maps = host_tensor(maps)
         if maps.dim() != 3 or maps.numel() == 0:
             raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
@@ -144,10 +237,22 @@ class ViewportPilot:
         work = self._tab_work(maps)
         sm = ops.sphere_smooth(maps, self.sigma_deg, work=work)
         val = ops.sphere_peak(maps, self.sigma_deg, smooth=sm, work=work)[2]
+        gain = 4096.0 / val
         self._path_work = ops._work(ops.lib().cp360_path_work_bytes, "sphere_path", F, hm, int(maps.shape[2]), maps.device,
                                     self._path_work, " (F <= 65535, hm wm <= 16384)")
-        idx = ops.sphere_path(sm, 4096.0 / val, self.turn_cost, self.plan_step_deg, starts, work=self._path_work)[0]
-        return ops.sphere_refine(maps, idx, self.sigma_deg, work=work)
+        dirs = torch.empty((n, F, 3), dtype=torch.float32, device=maps.device)
+        score = torch.empty((n, len(edges) - 1), dtype=torch.int32, device=maps.device)
+        sm_k, raw_k = sm, maps
+        for k in range(n):
+            if k == 1:
+                sm_k, raw_k = torch.empty_like(sm), torch.empty_like(maps)
+            if k >= 1:
+                before = dirs[:k].permute(1, 0, 2).contiguous()
+                ops.sphere_exclude(sm, before, exclude_deg, out=sm_k, work=work)
+                ops.sphere_exclude(maps, before, exclude_deg, out=raw_k, work=work)
+            idx, _, score[k] = ops.sphere_path(sm_k, gain, self.turn_cost, self.plan_step_deg, starts, work=self._path_work)
+            dirs[k] = ops.sphere_refine(raw_k, idx, self.sigma_deg, work=work)
+        return dirs, score
 
     def path(self, maps, cuts=None):
         """maps f32 [F, hm, wm] -> the cameras R f32 [F, 3, 3] on the device: the peaks (the planned path with the planner
@@ -185,3 +290,86 @@ class ViewportPilot:
             raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
         R = self.path(maps, cuts)
         return self.render(frames, R), R
+
+    # ------------------------------------------------------------------------- several cameras at once (K20)
+    def paths(self, maps, n, cuts=None, exclude_deg=None, min_share=0.0, arrange='score'):
+        """maps f32 [F, hm, wm] -> (R f32 [F, n, 3, 3] on the device, share float64 [n, S] on the host): ``plan_multi``, one
+        copy to the host (the directions and the scores together, the one synchronisation of a video) and ``multi_cameras``:
+        a camera whose share of camera 0's votes in a shot is below ``min_share`` is dropped there (its R is NaN, its tile
+        empty); ``arrange='longitude'`` orders every shot's cameras as the panorama reads, left to right."""
+        if not 0.0 <= float(min_share) <= 1.0:
+            raise ValueError("min_share must be in [0, 1], got %r" % (min_share,))
+        if arrange not in ('score', 'longitude'):
+            raise ValueError("arrange must be 'score' or 'longitude', got %r" % (arrange,))
+        dirs, score = self.plan_multi(maps, n, cuts, exclude_deg)
+        n, F = int(dirs.shape[0]), int(dirs.shape[1])
+        both = torch.cat([dirs.reshape(-1).view(torch.int32), score.reshape(-1)]).cpu().numpy()
+        R, share = multi_cameras(both[:n * F * 3].view(np.float32).reshape(n, F, 3), both[n * F * 3:].reshape(n, -1), cuts,
+                                 self.alpha, self.max_step_deg, min_share, arrange)
+        return torch.from_numpy(R.astype(np.float32)).to(self.device), share
+
+    def render_multi(self, frames, R, tiles=None, canvas_hw=None, fill=None, out=None):
+        """frames under the cameras R [N, K, 3, 3] -> the canvas [N, hc, wc, C] on the device: camera k's view in tile k
+        (``ops.viewport_render_multi``), ``fill`` elsewhere and in the tile of a dropped camera.  The default layout is
+        ``split_layout(K, self.hw)``; tiles of other sizes show the same field of view."""
+        R = on_device(R, self.device, torch.float32)
+        if R.dim() != 4:
+            raise ValueError("R must be [N, K, 3, 3], got %s" % (tuple(R.shape),))
+        if tiles is None:
+            tiles, canvas_hw = split_layout(int(R.shape[1]), self.hw)
+        elif canvas_hw is None:
+            raise ValueError("tiles need their canvas_hw")
+        return ops.viewport_render_multi(on_device(frames, self.device), R, tiles, self.hfov_deg, canvas_hw, fill=fill, out=out)
+
+    def follow_multi(self, frames, maps, n, cuts=None, exclude_deg=None, min_share=0.0, arrange='score', tiles=None,
+                     canvas_hw=None, fill=None):
+        """``follow`` with n cameras: (canvas [F, hc, wc, C], R f32 [F, n, 3, 3]) on the device - ``paths``, then
+        ``render_multi``."""
+        frames = on_device(frames, self.device)
+        if frames.dim() != 4 or len(maps) != frames.shape[0]:
+            raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
+        R = self.paths(maps, n, cuts, exclude_deg, min_share, arrange)[0]
+        return self.render_multi(frames, R, tiles, canvas_hw, fill), R
+
+    def outline_multi(self, frames, R, colours=((0, 255, 0), (255, 0, 255), (0, 255, 255), (255, 255, 0), (255, 128, 0),
+                                                (0, 128, 255), (255, 0, 0), (255, 255, 255)), border_px=3, out=None):
+        """frames u8 [N, H, W, 3] -> the panoramas with the frame of every camera of R [N, K, 3, 3] drawn in its colour, on the
+        device: K calls of ``ops.viewport_outline``, all but the first in place.  A dropped camera draws nothing."""
+        frames, R = on_device(frames, self.device), on_device(R, self.device, torch.float32)
+        if R.dim() != 4 or not 1 <= R.shape[1] <= len(colours):
+            raise ValueError("R must be [N, K, 3, 3] with one colour per camera, got %s and %d colours" % (tuple(R.shape), len(colours)))
+        work = self._tab_work(frames)
+        for k in range(int(R.shape[1])):
+            out = ops.viewport_outline(frames if k == 0 else out, R[:, k].contiguous(), self.hw, self.hfov_deg, border_px,
+                                       colours[k], out=out, work=work)
+        return out
+
+    def agreement_multi(self, R_cam, R, offsets, head=None):
+        """The cameras R_cam [F, n, 3, 3] (``paths``) against the viewers' head cameras, as ``agreement`` -> ``MultiAgreement``:
+        every viewer is scored against the camera that shows most of what they had in view, so viewers who split between two
+        targets no longer count half against the pilot.  ``HeadMaps.agreement`` once per camera, the best of n with torch."""
+        from .headtrack import HeadMaps
+        head = head or HeadMaps(device=self.device)
+        R_cam = on_device(R_cam, self.device, torch.float32)
+        if R_cam.dim() != 4 or tuple(R_cam.shape[2:]) != (3, 3) or R_cam.shape[1] < 1:
+            raise ValueError("R_cam must be [F, n, 3, 3], got %s" % (tuple(R_cam.shape),))
+        F, n = int(R_cam.shape[0]), int(R_cam.shape[1])
+        per = [head.agreement(R_cam[:, k].contiguous(), self.hw, self.hfov_deg, R, offsets) for k in range(n)]
+        offsets = on_device(offsets, self.device, torch.int32)
+        N, dev = int(per[0].iou.shape[0]), per[0].iou.device
+        frame = torch.bucketize(torch.arange(N, device=dev, dtype=torch.int32), offsets[1:], right=True).clamp(max=F - 1)
+        iou = torch.stack([p.iou for p in per])                                             # [n, N]
+        usable = torch.isfinite(R_cam).all(dim=3).all(dim=2).t()[:, frame] & torch.isfinite(iou)
+        masked = torch.where(usable, iou, torch.full_like(iou, -1.0))
+        top = masked.max(dim=0).values
+        first = (masked == top[None, :]).to(torch.int64).argmax(dim=0)                      # the lowest camera on ties
+        none = ~usable.any(dim=0)
+        best_cam = torch.where(none, torch.full_like(first, -1), first)
+        best_iou = torch.where(none, torch.full_like(top, float('nan')), top)
+        finite = per[0].finite
+        zero = torch.zeros(F, dtype=torch.float64, device=dev)
+        total = zero.index_add(0, frame, torch.where(finite, best_iou, torch.zeros_like(best_iou)))
+        frame_iou = total / zero.index_add(0, frame, finite.to(torch.float64))
+        angles = torch.stack([p.centre_angle_deg for p in per])
+        angle = torch.where(none, torch.full_like(top, float('nan')), angles.gather(0, first[None, :])[0])
+        return MultiAgreement(best_iou, best_cam, frame_iou, angle, finite, per)

@@ -608,6 +608,30 @@ int cp360_view_path(const float* smooth, const float* gain, int F, int hm, int w
 int cp360_view_refine(const float* maps, const int32_t* idx, int F, int hm, int wm, double sigma_rad, float* dir_out, void* work,
                       size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K20: several cameras at once
+ * Two people talking are two targets: camera k >= 1 plans K16's path on the maps with the caps about the cameras before it taken
+ * out (exclude), and the views of all cameras are rendered side by side on one canvas (render_multi).  The definition is the
+ * package's own, DESIGN.md "K20", restated in tests/director_restate.py.
+ *
+ *   exclude       maps f32 [F, hm, wm], dirs f32 [F, Kx, 3] (device), 1 <= Kx <= 7, c = (float)cos(radius_rad), 0 < radius_rad
+ *                 <= pi: out[t][j] = +0 where ((p_x d_x + p_y d_y) + p_z d_z) >= c in f32 for any direction d of frame t, p the
+ *                 pixel centre's direction from K11's tables; else the input's bits, a NaN included.  A direction with a
+ *                 non-finite component excludes nothing.  Element-wise: out may be maps.  work: as cp360_view_smooth's.
+ *   render_multi  frames as cp360_view_render's, R f32 [N, K, 3, 3], 1 <= K <= 8 -> out [N, hc, wc, C] of the frames' type.
+ *                 tiles int32 [K][4] = (x0, y0, w, h) and hfov_rad double [K] in HOST memory: canvas pixel (x0 + i, y0 + j) is
+ *                 pixel (i, j) of cp360_view_render's view of h x w pixels and hfov_rad[k] under R[n][k], bit for bit.  A pixel in
+ *                 no tile, or in the tile of a camera with a non-finite entry, takes fill: C values of the frames' type in HOST
+ *                 memory, read during the call.  One launch; not in place.
+ * In this order, before any launch: a NULL pointer: CP360_ERR_NULL; a size < 1, Kx outside 1 .. 7, K outside 1 .. 8, a radius or a
+ * field of view out of range, a tile that is empty, leaves the canvas or overlaps another: CP360_ERR_BAD_SHAPE; a dtype that is
+ * neither CP360_F32 nor CP360_U8: CP360_ERR_BAD_DTYPE; hm wm > 16384, F > 65535, C > 4, u8 with C != 3, an image beyond
+ * cp360_view_render's limits or frames == out: CP360_ERR_UNSUPPORTED; a misaligned workspace: CP360_ERR_ALIGN; one that is too
+ * small: CP360_ERR_BAD_SHAPE.  Asynchronous on the stream, no atomics, no host synchronisation, independent of F / N. */
+int cp360_view_exclude(const float* maps, const float* dirs, int F, int hm, int wm, int Kx, double radius_rad, float* out, void* work,
+                       size_t work_bytes, void* stream);
+int cp360_view_render_multi(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K, const int32_t* tiles,
+                            const double* hfov_rad, const void* fill, void* out, int hc, int wc, void* stream);
+
 /* ------------------------------------------------------------------ K13: shot detection
  * Where the hard cuts of an equirectangular video are: K10 - K12 assume one continuous take.  The signature of a frame is the
  * colour histogram of the whole sphere, every pixel weighted by the solid angle of its row: a camera rotation leaves it nearly
