@@ -82,6 +82,8 @@ PUBLIC_SYMBOLS = [
     'cp360_fix_point_work_bytes', 'cp360_fix_point_scores',
     # K20: several cameras at once
     'cp360_view_exclude', 'cp360_view_render_multi',
+    # K21: anti-aliased views
+    'cp360_view_render_aa', 'cp360_view_render_multi_aa',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -325,6 +327,8 @@ def lib():
     L.cp360_view_refine.argtypes = [vp, vp, i, i, i, dbl, vp, vp, sz, vp]
     L.cp360_view_exclude.argtypes = [vp, vp, i, i, i, i, dbl, vp, vp, sz, vp]
     L.cp360_view_render_multi.argtypes = [i, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, i, vp]
+    L.cp360_view_render_aa.argtypes = [i, vp, vp, i, i, i, i, dbl, i, vp, i, i, vp]
+    L.cp360_view_render_multi_aa.argtypes = [i, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, i, i, vp]
     L.cp360_head_footprints.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, sz, vp]
     L.cp360_head_agreement.argtypes = [vp, dbl, dbl, vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, vp, sz, vp]
     L.cp360_sup_loss_work_bytes.restype = sz

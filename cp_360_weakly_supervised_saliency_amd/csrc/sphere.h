@@ -65,8 +65,9 @@ __device__ __forceinline__ void store_px(uint8_t* p, float v) { *p = (uint8_t)fm
 
 // The C channels of the H x W image `img` at the real position (sx, sy), bilinear: four taps, columns wrap modulo W, rows
 // clamp to 0 .. H - 1, top + ty (bot - top).  A non-finite position (a non-finite R) samples inside the frame.
+// sphere_sample_f32 leaves the C values in f32, not rounded for u8 images (K21 adds them up); sphere_sample stores them.
 template <typename T, int C>
-__device__ __forceinline__ void sphere_sample(const T* img, int H, int W, float sx, float sy, T* o) {
+__device__ __forceinline__ void sphere_sample_f32(const T* img, int H, int W, float sx, float sy, float* v) {
     if (!(fabsf(sx) <= (float)W)) sx = 0.f;                            // a non-finite R: stay inside the frame
     sy = fminf(fmaxf(sy, 0.f), (float)(H - 1));                        // fmaxf(NaN, 0) = 0
     const float x0f = floorf(sx), y0f = floorf(sy);
@@ -85,8 +86,16 @@ __device__ __forceinline__ void sphere_sample(const T* img, int H, int W, float 
         const float v00 = to_f32(p00[c]), v01 = to_f32(p01[c]), v10 = to_f32(p10[c]), v11 = to_f32(p11[c]);
         const float top = v00 + tx * (v01 - v00);
         const float bot = v10 + tx * (v11 - v10);
-        store_px(o + c, top + ty * (bot - top));
+        v[c] = top + ty * (bot - top);
     }
+}
+
+template <typename T, int C>
+__device__ __forceinline__ void sphere_sample(const T* img, int H, int W, float sx, float sy, T* o) {
+    float v[C];
+    sphere_sample_f32<T, C>(img, H, W, sx, sy, v);
+#pragma unroll
+    for (int c = 0; c < C; ++c) store_px(o + c, v[c]);
 }
 
 // ------------------------------------------------------------------ tables

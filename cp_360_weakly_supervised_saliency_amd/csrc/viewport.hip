@@ -2,10 +2,11 @@
 // under a camera rotation (K12a), the view's frame drawn on the panorama (K12b), the saliency map smoothed on the sphere (K12c)
 // and its peak with one mean-shift step (K12d); and the camera path that collects the most saliency under a turn limit and a turn
 // cost, by dynamic programming over the map's pixels (K16a - K16c); and several cameras at once: the caps about earlier cameras
-// taken out of a map (K20a) and several views on one canvas (K20b).  The reference's utils/fov_visual.py (box_proh, fov_module,
-// draw_cube_fov_box) has this purpose and does not compile; the specification is the package's own, DESIGN.md "K12", "K16" and
-// "K20"; tests/viewport_restate.py restates K12 in float64, tests/campath_restate.py K16 in integers, tests/director_restate.py
-// K20.  Geometry, tables and the bilinear sample are sphere.h's.
+// taken out of a map (K20a) and several views on one canvas (K20b); and the view anti-aliased by supersampling (K21).  The
+// reference's utils/fov_visual.py (box_proh, fov_module, draw_cube_fov_box) has this purpose and does not compile; the
+// specification is the package's own, DESIGN.md "K12", "K16", "K20" and "K21"; tests/viewport_restate.py restates K12 in float64,
+// tests/campath_restate.py K16 in integers, tests/director_restate.py K20, tests/viewport_aa_restate.py K21.  Geometry, tables
+// and the bilinear sample are sphere.h's.
 //
 // Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
 // centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
@@ -23,6 +24,9 @@
 //         the input's bits
 //   K20b  canvas pixel (x0_k + i, y0_k + j) of tile k = K12a's view pixel (i, j) of the view (h_k, w_k, hfov_k) under R[n][k];
 //         fill outside every tile and in the tile of a non-finite camera
+//   K21   view pixel (i, j) with the factor n = 1 .. 4: s = the n n unrounded f32 samples (n i + a, n j + b) of K12a's view
+//         (n h, n w, tx, ty) under R, added in f32 with b outer and a inner from the first sample; out = s / (float)(n n), stored
+//         as K12a stores (u8: rintf, clamp).  n = 1 is K12a.  K20b's tiles have a factor each
 // Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d / K16c are f64 in a fixed order;
 // K16a / K16b are integers.  No atomics, no host synchronisation, results independent of the batch size.
 #pragma clang fp contract(off)
@@ -52,18 +56,59 @@ __device__ __forceinline__ void peak_take(V ov, int oi, V& best, int& bi) {
 }
 
 // ------------------------------------------------------------------ K12a: the view
+// K12a's position: where view pixel (i, j) of the view (h, w, tx, ty) under R lies on the H x W panorama
+__device__ __forceinline__ void view_pos(const Rot& R, int H, int W, int h, int w, float tx, float ty, int i, int j, float& sx,
+                                         float& sy) {
+    const float u = ((float)(2 * i + 1) / (float)w - 1.f) * tx;
+    const float v = (1.f - (float)(2 * j + 1) / (float)h) * ty;
+    const float r = 1.f / sqrtf((1.f + v * v) + u * u);
+    float qx, qy, qz;
+    stab_rotate(R, r, v * r, u * r, qx, qy, qz);
+    stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
+}
+
 // K12a's pixel, which K20b repeats per tile: view pixel (i, j) of the view (h, w, tx, ty) under R, sampled from the H x W frame
 // `img` into the C channels at o
 template <typename T, int C>
 __device__ __forceinline__ void view_pixel(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty,
                                            int i, int j, T* __restrict__ o) {
-    const float u = ((float)(2 * i + 1) / (float)w - 1.f) * tx;
-    const float v = (1.f - (float)(2 * j + 1) / (float)h) * ty;
-    const float r = 1.f / sqrtf((1.f + v * v) + u * u);
-    float qx, qy, qz, sx, sy;
-    stab_rotate(R, r, v * r, u * r, qx, qy, qz);
-    stab_pix(qx, qy, qz, 0.5f * (float)W, 0.5f * (float)H, sx, sy);
+    float sx, sy;
+    view_pos(R, H, W, h, w, tx, ty, i, j, sx, sy);
     sphere_sample<T, C>(img, H, W, sx, sy, o);
+}
+
+// K21's pixel: the NS x NS box mean of the unrounded samples (NS i + a, NS j + b) of the fine view (NS h, NS w, tx, ty) - K12a's
+// positions with the fine view's indices and sizes -, added in f32 with b outer and a inner from the first sample, divided by
+// (float)(NS NS) and stored as K12a stores.  C accumulators; both loops unrolled.
+template <typename T, int C, int NS>
+__device__ __forceinline__ void view_pixel_aa(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty,
+                                              int i, int j, T* __restrict__ o) {
+    float acc[C];
+#pragma unroll
+    for (int b = 0; b < NS; ++b) {
+#pragma unroll
+        for (int a = 0; a < NS; ++a) {
+            float sx, sy, s[C];
+            view_pos(R, H, W, NS * h, NS * w, tx, ty, NS * i + a, NS * j + b, sx, sy);
+            sphere_sample_f32<T, C>(img, H, W, sx, sy, s);
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = a + b == 0 ? s[c] : acc[c] + s[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) store_px(o + c, acc[c] / (float)(NS * NS));
+}
+
+// view_pixel_aa for a factor known at run time (K20b's tiles); 1 is K12a's pixel itself
+template <typename T, int C>
+__device__ __forceinline__ void view_pixel_ss(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty,
+                                              int i, int j, int ss, T* __restrict__ o) {
+    switch (ss) {
+        case 2: view_pixel_aa<T, C, 2>(img, R, H, W, h, w, tx, ty, i, j, o); break;
+        case 3: view_pixel_aa<T, C, 3>(img, R, H, W, h, w, tx, ty, i, j, o); break;
+        case 4: view_pixel_aa<T, C, 4>(img, R, H, W, h, w, tx, ty, i, j, o); break;
+        default: view_pixel<T, C>(img, R, H, W, h, w, tx, ty, i, j, o); break;
+    }
 }
 
 // grid (ceil(w / 256), h, N): one thread per view pixel, all C channels
@@ -76,29 +121,44 @@ __global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ 
     view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
 }
 
+// K21: the anti-aliased view, NS = 2, 3, 4.  K12a's grid and thread mapping: one thread per view pixel, its NS NS samples one after
+// the other in registers
+template <typename T, int C, int NS>
+__global__ __launch_bounds__(256) void view_render_aa_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
+                                                             T* __restrict__ dst, int H, int W, int h, int w, float tx, float ty) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= w) return;
+    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
+    view_pixel_aa<T, C, NS>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j,
+                            dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
+}
+
 // ------------------------------------------------------------------ K20b: several views on one canvas
-// The tiles of a canvas, by value: rectangle k = (x0, y0, w, h) shows the view (h, w, tx, ty) of camera k.  The host has checked
-// that the K <= 8 rectangles are not empty, lie on the canvas and do not overlap.  fill: what a pixel in no tile takes.
+// The tiles of a canvas, by value: rectangle k = (x0, y0, w, h) shows the view (h, w, tx, ty) of camera k, supersampled ss times
+// (K21; 1 = K12a's pixel).  The host has checked that the K <= 8 rectangles are not empty, lie on the canvas and do not overlap
+// and that every ss is 1 .. 4.  fill: what a pixel in no tile takes.
 constexpr int kMaxTiles = 8;
 
 template <typename T>
 struct ViewTiles {
     int x0[kMaxTiles], y0[kMaxTiles], w[kMaxTiles], h[kMaxTiles];
     float tx[kMaxTiles], ty[kMaxTiles];
+    int ss[kMaxTiles];
     T fill[4];
     int K;
 };
 
 // grid (ceil(wc / 256), hc, N): one thread per canvas pixel.  The scan over the tiles is unrolled: every index into the table is
 // a constant, the table stays in the kernel's arguments and the chosen tile in registers.  A pixel in no tile, or in the tile of
-// a camera with a non-finite entry, takes fill.
-template <typename T, int C>
+// a camera with a non-finite entry, takes fill.  AA = false never reads ss: K20b's kernel as it was, which a canvas whose tiles
+// all have the factor 1 takes.
+template <typename T, int C, bool AA>
 __global__ __launch_bounds__(256) void view_render_multi_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
                                                                 T* __restrict__ dst, int H, int W, int hc, int wc,
                                                                 const ViewTiles<T> tiles) {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= wc) return;
-    int sel = -1, i = 0, j = 0, w = 1, h = 1;
+    int sel = -1, i = 0, j = 0, w = 1, h = 1, ss = 1;
     float tx = 0.f, ty = 0.f;
 #pragma unroll
     for (int k = 0; k < kMaxTiles; ++k) {
@@ -111,13 +171,15 @@ __global__ __launch_bounds__(256) void view_render_multi_kernel(const T* __restr
             h = tiles.h[k];
             tx = tiles.tx[k];
             ty = tiles.ty[k];
+            if (AA) ss = tiles.ss[k];
         }
     }
     T* o = dst + (((size_t)blockIdx.z * hc + y) * wc + x) * C;
     if (sel >= 0) {
         const Rot R = load_rot(Rs + ((size_t)blockIdx.z * tiles.K + sel) * 9);
         if (rot_finite(R)) {
-            view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, o);
+            if (AA) view_pixel_ss<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, ss, o);
+            else view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, o);
             return;
         }
     }
@@ -490,9 +552,20 @@ int launch_render(const void* frames, const float* R, void* out, int N, int H, i
     return CP360_OK;
 }
 
+template <typename T, int C, int NS>
+int launch_render_aa(const void* frames, const float* R, void* out, int N, int H, int W, int h, int w, float tx, float ty,
+                     hipStream_t s) {
+    hipLaunchKernelGGL((view_render_aa_kernel<T, C, NS>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R, (T*)out,
+                       H, W, h, w, tx, ty);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// ss = the K factors of K21, or nullptr for K20b as it was (every factor 1)
 template <typename T, int C>
 int launch_render_multi(const void* frames, const float* R, void* out, int N, int H, int W, int hc, int wc, int K,
-                        const int32_t* rects, const float* tx, const float* ty, const void* fill, hipStream_t s) {
+                        const int32_t* rects, const float* tx, const float* ty, const int32_t* ss, const void* fill,
+                        hipStream_t s) {
     ViewTiles<T> t = {};
     t.K = K;
     for (int k = 0; k < K; ++k) {
@@ -502,10 +575,14 @@ int launch_render_multi(const void* frames, const float* R, void* out, int N, in
         t.h[k] = rects[4 * k + 3];
         t.tx[k] = tx[k];
         t.ty[k] = ty[k];
+        t.ss[k] = ss ? ss[k] : 1;
     }
     for (int c = 0; c < C; ++c) t.fill[c] = ((const T*)fill)[c];
-    hipLaunchKernelGGL((view_render_multi_kernel<T, C>), dim3((wc + 255) / 256, hc, N), dim3(256), 0, s, (const T*)frames, R,
-                       (T*)out, H, W, hc, wc, t);
+    const dim3 grid((wc + 255) / 256, hc, N);
+    if (ss) hipLaunchKernelGGL((view_render_multi_kernel<T, C, true>), grid, dim3(256), 0, s, (const T*)frames, R, (T*)out, H, W, hc,
+                               wc, t);
+    else hipLaunchKernelGGL((view_render_multi_kernel<T, C, false>), grid, dim3(256), 0, s, (const T*)frames, R, (T*)out, H, W, hc,
+                            wc, t);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -569,19 +646,39 @@ int path_big_lds() {
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
-extern "C" int cp360_view_render(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad,
-                                 void* out, int h, int w, void* stream) {
+// K12a and K21 behind one list of checks: ss = 1 is K12a's kernel.  The fine view (ss h, ss w) must be a view K12a would take, so
+// that the identity with it holds wherever the call is accepted (h, w are within big_image's range before they are multiplied)
+static int view_render_ss(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad, int ss,
+                          void* out, int h, int w, void* stream) {
     if (!frames || !R || !out) return CP360_ERR_NULL;
-    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1 || bad_hfov(hfov_rad)) return CP360_ERR_BAD_SHAPE;
+    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1 || bad_hfov(hfov_rad) || ss < 1 || ss > 4) return CP360_ERR_BAD_SHAPE;
     if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
-    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w)) return CP360_ERR_UNSUPPORTED;
+    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || big_image(N, ss * h, ss * w))
+        return CP360_ERR_UNSUPPORTED;
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
     const double t = tan(0.5 * hfov_rad);
     const float tx = (float)t, ty = (float)(t * (double)h / (double)w);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
-        return launch_render<decltype(px), decltype(c)::value>(frames, R, out, N, H, W, h, w, tx, ty, s);
+        using T = decltype(px);
+        constexpr int Cn = decltype(c)::value;
+        switch (ss) {
+            case 2: return launch_render_aa<T, Cn, 2>(frames, R, out, N, H, W, h, w, tx, ty, s);
+            case 3: return launch_render_aa<T, Cn, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
+            case 4: return launch_render_aa<T, Cn, 4>(frames, R, out, N, H, W, h, w, tx, ty, s);
+            default: return launch_render<T, Cn>(frames, R, out, N, H, W, h, w, tx, ty, s);
+        }
     });
+}
+
+extern "C" int cp360_view_render(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad,
+                                 void* out, int h, int w, void* stream) {
+    return view_render_ss(dtype, frames, R, N, H, W, C, hfov_rad, 1, out, h, w, stream);
+}
+
+extern "C" int cp360_view_render_aa(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad,
+                                    int ss, void* out, int h, int w, void* stream) {
+    return view_render_ss(dtype, frames, R, N, H, W, C, hfov_rad, ss, out, h, w, stream);
 }
 
 extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, int H, int W, double hfov_rad, int h, int w,
@@ -727,16 +824,24 @@ extern "C" int cp360_view_exclude(const float* maps, const float* dirs, int F, i
     return CP360_OK;
 }
 
-extern "C" int cp360_view_render_multi(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K,
-                                       const int32_t* tiles, const double* hfov_rad, const void* fill, void* out, int hc, int wc,
-                                       void* stream) {
-    if (!frames || !R || !tiles || !hfov_rad || !fill || !out) return CP360_ERR_NULL;
+// K20b and K21 behind one list of checks: ss = nullptr is K20b (every factor 1), and so is a list of ones.  A tile lies on the
+// canvas, so its (h, w) are within big_image's range before they are multiplied.
+static int view_render_multi_ss(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K,
+                                const int32_t* tiles, const double* hfov_rad, const int32_t* ss, const void* fill, void* out, int hc,
+                                int wc, void* stream) {
     if (bad_image(N, H, W) || bad_image(N, hc, wc) || C < 1 || K < 1 || K > kMaxTiles) return CP360_ERR_BAD_SHAPE;
     for (int k = 0; k < K; ++k)
         if (bad_hfov(hfov_rad[k])) return CP360_ERR_BAD_SHAPE;
     if (bad_tiles(tiles, K, hc, wc)) return CP360_ERR_BAD_SHAPE;
+    bool ones = true;
+    for (int k = 0; ss && k < K; ++k) {
+        if (ss[k] < 1 || ss[k] > 4) return CP360_ERR_BAD_SHAPE;
+        ones = ones && ss[k] == 1;
+    }
     if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
     if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, hc, wc)) return CP360_ERR_UNSUPPORTED;
+    for (int k = 0; ss && k < K; ++k)
+        if (big_image(N, ss[k] * tiles[4 * k + 3], ss[k] * tiles[4 * k + 2])) return CP360_ERR_UNSUPPORTED;
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
     float tx[kMaxTiles], ty[kMaxTiles];
     for (int k = 0; k < K; ++k) {                                       // cp360_view_render's, per tile
@@ -746,6 +851,21 @@ extern "C" int cp360_view_render_multi(int dtype, const void* frames, const floa
     }
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
-        return launch_render_multi<decltype(px), decltype(c)::value>(frames, R, out, N, H, W, hc, wc, K, tiles, tx, ty, fill, s);
+        return launch_render_multi<decltype(px), decltype(c)::value>(frames, R, out, N, H, W, hc, wc, K, tiles, tx, ty,
+                                                                     ones ? nullptr : ss, fill, s);
     });
+}
+
+extern "C" int cp360_view_render_multi(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K,
+                                       const int32_t* tiles, const double* hfov_rad, const void* fill, void* out, int hc, int wc,
+                                       void* stream) {
+    if (!frames || !R || !tiles || !hfov_rad || !fill || !out) return CP360_ERR_NULL;
+    return view_render_multi_ss(dtype, frames, R, N, H, W, C, K, tiles, hfov_rad, nullptr, fill, out, hc, wc, stream);
+}
+
+extern "C" int cp360_view_render_multi_aa(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K,
+                                          const int32_t* tiles, const double* hfov_rad, const int32_t* ss, const void* fill,
+                                          void* out, int hc, int wc, void* stream) {
+    if (!frames || !R || !tiles || !hfov_rad || !ss || !fill || !out) return CP360_ERR_NULL;
+    return view_render_multi_ss(dtype, frames, R, N, H, W, C, K, tiles, hfov_rad, ss, fill, out, hc, wc, stream);
 }

@@ -1497,16 +1497,33 @@ def _view_geometry(hw, hfov_deg):
     return h, w, math.radians(float(hfov_deg))
 
 
-def viewport_render(frames, R, hw, hfov_deg, out=None):
+def _supersample(supersample, K=None):
+    """K21's factor(s): one int 1 .. 4 - or, for the K tiles of a canvas, one per tile - as a list of ints; ValueError otherwise."""
+    many = K is not None and np.ndim(supersample) != 0
+    ss = list(supersample) if many else [supersample] * (K or 1)
+    if len(ss) != (K or 1) or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= v <= 4 for v in ss):
+        raise ValueError("supersample must be an int 1 .. 4%s, got %r" % (" or one per tile" if K is not None else "", supersample))
+    return [int(v) for v in ss]
+
+
+def viewport_render(frames, R, hw, hfov_deg, out=None, supersample=1):
     """cp360_view_render: the perspective view of hw = (h, w) pixels and hfov_deg degrees of every frame under its camera R[n]
     (f32 [N, 3, 3], camera-to-world, columns forward / up / right; I looks at the panorama's centre): frames u8 [N, H, W, 3] or
-    f32 [N, H, W, C], C <= 4 -> [N, h, w, C] of the frames' type.  Bilinear, columns wrap, rows clamp, no anti-aliasing."""
+    f32 [N, H, W, C], C <= 4 -> [N, h, w, C] of the frames' type.  Bilinear, columns wrap, rows clamp.  ``supersample`` = n in
+    2 .. 4 (cp360_view_render_aa, K21): every pixel is the mean of the n x n unrounded samples of the view (n h, n w), added in
+    f32 row by row - anti-aliased for up to n source pixels per view pixel (``utils.viewport.supersample_for``); 1: no
+    anti-aliasing, today's call."""
+    ss = _supersample(supersample)[0]
     require_gpu(frames, R, out)
     N, H, W, C = _frames_nhwc(frames, u8_only=False)
     _stab_rotations(R, N)
     h, w, hfov = _view_geometry(hw, hfov_deg)
     out = _out_for(out, (N, h, w, C), frames.dtype, frames.device, frames)
-    check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
+    if ss == 1:
+        check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
+    else:
+        check(lib().cp360_view_render_aa(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ss, ptr(out), h, w,
+                                         stream()))
     return out
 
 
@@ -1699,12 +1716,15 @@ def check_tiles(tiles, canvas_hw):
     return tiles, (hc, wc)
 
 
-def viewport_render_multi(frames, R, tiles, hfov_deg, canvas_hw, fill=None, out=None):
+def viewport_render_multi(frames, R, tiles, hfov_deg, canvas_hw, fill=None, out=None, supersample=1):
     """cp360_view_render_multi: K views of every frame on one canvas in one launch.  frames as ``viewport_render``'s, R f32
     [N, K, 3, 3], tiles K rectangles (x0, y0, w, h) on the canvas of canvas_hw = (hc, wc), hfov_deg a scalar or one value per
     tile -> [N, hc, wc, C] of the frames' type.  Tile k is ``viewport_render(frames, R[:, k], (h, w), hfov_deg[k])`` bit for bit;
-    a pixel in no tile, and the tile of a camera with a non-finite entry, take fill (C values, default 0)."""
+    a pixel in no tile, and the tile of a camera with a non-finite entry, take fill (C values, default 0).  ``supersample``: one
+    factor 1 .. 4 or one per tile (cp360_view_render_multi_aa, K21): tile k is ``viewport_render(.., supersample=s_k)`` bit for
+    bit; all 1: today's call."""
     tiles, (hc, wc) = check_tiles(tiles, canvas_hw)
+    ss = _supersample(supersample, len(tiles))
     require_gpu(frames, R, out)
     N, H, W, C_ = _frames_nhwc(frames, u8_only=False)
     K = len(tiles)
@@ -1722,8 +1742,14 @@ def viewport_render_multi(frames, R, tiles, hfov_deg, canvas_hw, fill=None, out=
     rects = (C.c_int32 * (4 * K))(*[v for t in tiles for v in t])
     fovs = (C.c_double * K)(*[math.radians(v) for v in hfov])
     colour = (C.c_ubyte * C_)(*[int(v) for v in fill]) if u8 else (C.c_float * C_)(*[float(v) for v in fill])
-    check(lib().cp360_view_render_multi(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, K, C.cast(rects, C.c_void_p),
-                                        C.cast(fovs, C.c_void_p), C.cast(colour, C.c_void_p), ptr(out), hc, wc, stream()))
+    if all(v == 1 for v in ss):
+        check(lib().cp360_view_render_multi(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, K, C.cast(rects, C.c_void_p),
+                                            C.cast(fovs, C.c_void_p), C.cast(colour, C.c_void_p), ptr(out), hc, wc, stream()))
+    else:
+        factors = (C.c_int32 * K)(*ss)
+        check(lib().cp360_view_render_multi_aa(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, K,
+                                               C.cast(rects, C.c_void_p), C.cast(fovs, C.c_void_p), C.cast(factors, C.c_void_p),
+                                               C.cast(colour, C.c_void_p), ptr(out), hc, wc, stream()))
     return out
 
 

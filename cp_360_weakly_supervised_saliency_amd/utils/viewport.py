@@ -11,8 +11,9 @@ chooses which of several targets to follow, where the peaks hop between them.  S
 ``plan_multi`` plans them one after the other, each on the maps with a cap about the cameras before it taken out
 (``ops.sphere_exclude``), ``paths`` turns the plans into cameras, drops those that found nothing and orders them, and
 ``render_multi`` shows their views side by side on one canvas (``ops.viewport_render_multi``).  A camera is a rotation R,
-camera-to-world, with the columns (forward, up, right): R = I looks at the panorama's centre.  Roll, translation and anti-aliased
-views are out of scope.
+camera-to-world, with the columns (forward, up, right): R = I looks at the panorama's centre.  A view coarser than its source is
+anti-aliased by supersampling (K21, DESIGN.md "K21"): ``supersample_for`` is the factor a view needs, ``ViewportPilot(..,
+antialias=True)`` uses it.  Roll and translation are out of scope.
 """
 import numpy as np
 import torch
@@ -113,6 +114,17 @@ def split_layout(n, hw, gutter=8, direction='row'):
     return [(0, k * (h + gutter), w, h) for k in range(n)], (n * h + (n - 1) * gutter, w)
 
 
+def supersample_for(HW, hw, hfov_deg, limit=4):
+    """The supersampling factor (K21, ``ops.viewport_render(.., supersample=)``) that a view of hw = (h, w) pixels and hfov_deg
+    degrees of H x W frames needs: rho = tan(hfov / 2) max(W, 2 H) / (pi w) is the number of source pixels per view pixel at the
+    view's centre (the edges of a gnomonic view are finer), and the factor is min(limit, max(1, ceil(rho - 1e-9))).  float64."""
+    (H, W), (h, w), limit = (int(v) for v in HW), (int(v) for v in hw), int(limit)
+    if min(H, W, h, w) < 1 or not 0.0 < float(hfov_deg) < 180.0 or not 1 <= limit <= 4:
+        raise ValueError("sizes must be positive, 0 < hfov_deg < 180 and 1 <= limit <= 4, got %r, %r, %r, %r" % (HW, hw, hfov_deg, limit))
+    rho = np.tan(0.5 * np.deg2rad(float(hfov_deg))) * max(W, 2 * H) / (np.pi * w)
+    return int(min(limit, max(1, int(np.ceil(rho - 1e-9)))))
+
+
 def _longitude_deg(v):
     return np.rad2deg(np.arctan2(v[2], v[0]))
 
@@ -181,10 +193,17 @@ class ViewportPilot:
 
     ``planner``: 'peak', every frame's own peak, or 'viterbi', the best path of K16 under ``turn_cost`` (votes per degree turned;
     a frame's peak votes 4096) and ``plan_step_deg`` (the most the path may turn between two frames).  16 per degree and 15
-    degrees are conventions, chosen on the synthetic videos of tests/campath_restate.py and not tuned on data."""
+    degrees are conventions, chosen on the synthetic videos of tests/campath_restate.py and not tuned on data.
+
+    ``antialias`` (K21): False renders with one bilinear sample per view pixel; True supersamples every view by
+    ``supersample_for`` of the frames it is given - in ``render_multi`` per tile; an int 1 .. 4 is that factor.  ``render``,
+    ``follow``, ``render_multi`` and ``follow_multi`` honour it."""
 
     def __init__(self, hw=(720, 1280), hfov_deg=90.0, sigma_deg=15.0, alpha=0.85, max_step_deg=None, device='cuda', planner='peak',
-                 turn_cost=16.0, plan_step_deg=15.0):
+                 turn_cost=16.0, plan_step_deg=15.0, antialias=False):
+        if not isinstance(antialias, bool) and not (isinstance(antialias, (int, np.integer)) and 1 <= antialias <= 4):
+            raise ValueError("antialias must be False, True or an int 1 .. 4, got %r" % (antialias,))
+        self.antialias = antialias if isinstance(antialias, bool) else int(antialias)
         self.hw = (int(hw[0]), int(hw[1]))
         if min(self.hw) < 1 or not 0.0 < float(hfov_deg) < 180.0 or not float(sigma_deg) > 0.0:
             raise ValueError("hw must be positive, 0 < hfov_deg < 180 and sigma_deg > 0, got %r, %r, %r" % (hw, hfov_deg, sigma_deg))
@@ -263,10 +282,21 @@ class ViewportPilot:
         R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg, cuts), cuts)
         return torch.from_numpy(R.astype(np.float32)).to(self.device)
 
+    def _factor(self, frames, hw):
+        """``antialias`` as the factor of a view of hw pixels of these frames."""
+        if self.antialias is False:
+            return 1
+        if self.antialias is True:
+            if frames.dim() != 4:
+                raise ValueError("frames must be [N, H, W, C], got %s" % (tuple(frames.shape),))
+            return supersample_for(frames.shape[1:3], hw, self.hfov_deg)
+        return self.antialias
+
     def render(self, frames, R, out=None):
         """frames u8 [N, H, W, 3] or f32 [N, H, W, C] under the cameras R [N, 3, 3] -> the views [N, h, w, C] on the device."""
         R = on_device(R, self.device, torch.float32)
-        return ops.viewport_render(on_device(frames, self.device), R, self.hw, self.hfov_deg, out=out)
+        frames = on_device(frames, self.device)
+        return ops.viewport_render(frames, R, self.hw, self.hfov_deg, out=out, supersample=self._factor(frames, self.hw))
 
     def outline(self, frames, R, border_px=3, rgb=(0, 255, 0), out=None):
         """frames u8 [N, H, W, 3] -> the panoramas with every view's frame drawn in rgb, on the device."""
@@ -319,7 +349,10 @@ class ViewportPilot:
             tiles, canvas_hw = split_layout(int(R.shape[1]), self.hw)
         elif canvas_hw is None:
             raise ValueError("tiles need their canvas_hw")
-        return ops.viewport_render_multi(on_device(frames, self.device), R, tiles, self.hfov_deg, canvas_hw, fill=fill, out=out)
+        frames = on_device(frames, self.device)
+        tiles = ops.check_tiles(tiles, canvas_hw)[0]
+        factors = [self._factor(frames, (h, w)) for _, _, w, h in tiles]
+        return ops.viewport_render_multi(frames, R, tiles, self.hfov_deg, canvas_hw, fill=fill, out=out, supersample=factors)
 
     def follow_multi(self, frames, maps, n, cuts=None, exclude_deg=None, min_share=0.0, arrange='score', tiles=None,
                      canvas_hw=None, fill=None):

@@ -632,6 +632,27 @@ int cp360_view_exclude(const float* maps, const float* dirs, int F, int hm, int 
 int cp360_view_render_multi(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K, const int32_t* tiles,
                             const double* hfov_rad, const void* fill, void* out, int hc, int wc, void* stream);
 
+/* ------------------------------------------------------------------ K21: anti-aliased views by supersampling
+ * A view coarser than its source aliases: rho = tan(hfov / 2) max(W, 2 H) / (pi w) source pixels per view pixel at the view's
+ * centre passes 1 for 2048 x 4096 frames in 1280 columns.  The definition is the package's own, DESIGN.md "K21", restated in
+ * float64 in tests/viewport_aa_restate.py.  For a factor ss = 1 .. 4:
+ *
+ *   render_aa        out[n](i, j) = the mean of the ss x ss samples (ss i + a, ss j + b), a, b = 0 .. ss - 1, of cp360_view_render's
+ *                    view of ss h x ss w pixels and the same hfov_rad under R[n], each sample in f32 and NOT rounded for u8
+ *                    frames: added in f32 with b outer and a inner, starting from the first sample, divided by (float)(ss ss), then
+ *                    stored as render stores (u8: rintf, clamp).  So out is an ordered f32 sum of cp360_view_render's own output
+ *                    for f32 frames of the fine view, bit for bit, and ss = 1 is cp360_view_render itself.  A box filter over the
+ *                    pixel in the view plane; no pyramid, no workspace, one launch.  Arguments otherwise as cp360_view_render's.
+ *   render_multi_aa  cp360_view_render_multi with a factor per tile, ss int32 [K] in HOST memory: tile k is render_aa's view with
+ *                    ss[k], bit for bit; a list of ones is cp360_view_render_multi itself.
+ * The status codes are their counterparts', in the same order; in addition ss == NULL: CP360_ERR_NULL; a factor outside 1 .. 4:
+ * CP360_ERR_BAD_SHAPE (last of its group); a fine view ss h x ss w beyond cp360_view_render's limits: CP360_ERR_UNSUPPORTED
+ * (before frames == out).  Asynchronous on the stream, no atomics, no host synchronisation, independent of N. */
+int cp360_view_render_aa(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad, int ss,
+                         void* out, int h, int w, void* stream);
+int cp360_view_render_multi_aa(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K, const int32_t* tiles,
+                               const double* hfov_rad, const int32_t* ss, const void* fill, void* out, int hc, int wc, void* stream);
+
 /* ------------------------------------------------------------------ K13: shot detection
  * Where the hard cuts of an equirectangular video are: K10 - K12 assume one continuous take.  The signature of a frame is the
  * colour histogram of the whole sphere, every pixel weighted by the solid angle of its row: a camera rotation leaves it nearly
