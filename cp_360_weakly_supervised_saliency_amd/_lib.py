@@ -84,6 +84,8 @@ PUBLIC_SYMBOLS = [
     'cp360_view_exclude', 'cp360_view_render_multi',
     # K21: anti-aliased views
     'cp360_view_render_aa', 'cp360_view_render_multi_aa',
+    # K22: zoom, a field of view per frame
+    'cp360_view_lens_host', 'cp360_view_render_zoom', 'cp360_view_outline_zoom', 'cp360_view_spread', 'cp360_head_agreement_zoom',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -331,6 +333,11 @@ def lib():
     L.cp360_view_render_multi_aa.argtypes = [i, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, i, i, vp]
     L.cp360_head_footprints.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, sz, vp]
     L.cp360_head_agreement.argtypes = [vp, dbl, dbl, vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, vp, sz, vp]
+    L.cp360_view_lens_host.argtypes = [vp, i, i, i, dbl, vp]
+    L.cp360_view_render_zoom.argtypes = [i, vp, vp, vp, vp, i, i, i, i, vp, i, i, vp]
+    L.cp360_view_outline_zoom.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.cp360_view_spread.argtypes = [vp, vp, i, i, i, dbl, dbl, vp, vp, sz, vp]
+    L.cp360_head_agreement_zoom.argtypes = [vp, vp, vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, vp, vp, sz, vp]
     L.cp360_sup_loss_work_bytes.restype = sz
     L.cp360_sup_loss_work_bytes.argtypes = [i, i, i, i, i]
     L.cp360_sup_loss_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, vp, vp, sz, vp]

@@ -19,6 +19,7 @@
 //   K17b  agreement: a wave per pair, four pairs per workgroup; the wave finds its frame by a search in offsets, strides over the
 //         pixels with int32 partial sums (at most 2^15 pixels of weight 1024 a lane) and adds them up in 64 bits by
 //         wave_sum_down; no LDS, no barrier
+//   K22c  K17b with the camera's tangents per frame, from K22's lens table (DESIGN.md "K22")
 #pragma clang fp contract(off)
 #include "roc.h"
 
@@ -104,6 +105,46 @@ __global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_kernel(const f
     }
 }
 
+// K22c: K17b with a lens per frame for the camera: head_agreement_kernel with (ctx, cty) = the first two values of
+// cam_lens[frame of pair k] (K22's lens (tx, ty, b, 0), one 16-byte load, uniform over the wave); the viewers' window stays the
+// call's.  A tangent that is not finite fails every comparison of view_inside: that camera's view is empty.
+__global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_zoom_kernel(const float* __restrict__ Rc, const float4* __restrict__ cam_lens,
+                                                                              const float* __restrict__ R, const int* __restrict__ offsets,
+                                                                              int N, int F, const float2* __restrict__ tabx,
+                                                                              const float2* __restrict__ taby, const int* __restrict__ weights,
+                                                                              long long* __restrict__ inter, long long* __restrict__ uni, int h,
+                                                                              int w, float tx, float ty) {
+    const int lane = threadIdx.x & 63;
+    const long long k = (long long)blockIdx.x * kHeadPairs + (threadIdx.x >> 6);
+    if (k >= N) return;                                                // the whole wave; the kernel has no barrier
+    const int f = fix_frame(offsets, F, (int)k);
+    const float4 L = cam_lens[f];
+    const float ctx = L.x, cty = L.y;
+    const Rot cam = view_rot(Rc + (size_t)f * 9);
+    const Rot view = view_rot(R + k * 9);
+    const int P = h * w;
+    int x = lane % w, y = lane / w;
+    int si = 0, su = 0;
+    for (int i = lane; i < P; i += 64) {
+        float px, py, pz;
+        stab_dir(tabx[x], taby[y], px, py, pz);
+        const bool c = view_inside(cam, ctx, cty, px, py, pz), v = view_inside(view, tx, ty, px, py, pz);
+        const int a = fix_clamp(weights[y], 0, kMaxWeight);
+        si += c && v ? a : 0;
+        su += c || v ? a : 0;
+        x += 64;
+        while (x >= w) {
+            x -= w;
+            ++y;
+        }
+    }
+    const long long ti = wave_sum_down((long long)si), tu = wave_sum_down((long long)su);
+    if (lane == 0) {
+        inter[k] = ti;
+        uni[k] = tu;
+    }
+}
+
 // ------------------------------------------------------------------ host side
 // the two tangents of a view, rounded once; false for a view that is refused
 bool head_tangents(double hfov_rad, double aspect, float* tx, float* ty) {
@@ -163,6 +204,30 @@ extern "C" int cp360_head_agreement(const float* Rc, double cam_hfov_rad, double
     if (st != CP360_OK) return st;
     hipLaunchKernelGGL(head_agreement_kernel, dim3((unsigned)((N + kHeadPairs - 1) / kHeadPairs)), dim3(64 * kHeadPairs), 0, s, Rc, R,
                        (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, inter, uni, h, w, ctx, cty, tx, ty);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// K22c: cp360_head_agreement's checks in its order, the cameras' lenses in place of their view
+extern "C" int cp360_head_agreement_zoom(const float* Rc, const float* cam_lens, const float* R, const int32_t* offsets, long long N,
+                                         int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
+                                         long long* uni, void* work, size_t work_bytes, void* stream) {
+    if (!Rc || !cam_lens || !weights || !work || ((!inter || !uni) && N > 0)) return CP360_ERR_NULL;
+    int st = head_cameras(R, offsets, N, F, h, w);
+    if (st != CP360_OK) return st;
+    float tx, ty;
+    if (!head_tangents(hfov_rad, aspect, &tx, &ty)) return CP360_ERR_BAD_SHAPE;
+    if ((((uintptr_t)Rc | (uintptr_t)weights) & 3) != 0 || !aligned16(cam_lens) || (((uintptr_t)inter | (uintptr_t)uni) & 7) != 0)
+        return CP360_ERR_ALIGN;
+    st = check_work(work, work_bytes, tab_bytes(h, w));
+    if (st != CP360_OK || N == 0) return st;                           // no pairs: nothing to launch
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = launch_tables(work, h, w, s, &t);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(head_agreement_zoom_kernel, dim3((unsigned)((N + kHeadPairs - 1) / kHeadPairs)), dim3(64 * kHeadPairs), 0, s, Rc,
+                       (const float4*)cam_lens, R, (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, inter, uni, h, w, tx,
+                       ty);
     CP360_CHECK_HIP();
     return CP360_OK;
 }

@@ -2,11 +2,12 @@
 // under a camera rotation (K12a), the view's frame drawn on the panorama (K12b), the saliency map smoothed on the sphere (K12c)
 // and its peak with one mean-shift step (K12d); and the camera path that collects the most saliency under a turn limit and a turn
 // cost, by dynamic programming over the map's pixels (K16a - K16c); and several cameras at once: the caps about earlier cameras
-// taken out of a map (K20a) and several views on one canvas (K20b); and the view anti-aliased by supersampling (K21).  The
+// taken out of a map (K20a) and several views on one canvas (K20b); and the view anti-aliased by supersampling (K21); and zoom:
+// the view and its frame with a lens per frame (K22a, K22b) and how wide the target is (K22d).  The
 // reference's utils/fov_visual.py (box_proh, fov_module, draw_cube_fov_box) has this purpose and does not compile; the
-// specification is the package's own, DESIGN.md "K12", "K16", "K20" and "K21"; tests/viewport_restate.py restates K12 in float64,
-// tests/campath_restate.py K16 in integers, tests/director_restate.py K20, tests/viewport_aa_restate.py K21.  Geometry, tables
-// and the bilinear sample are sphere.h's.
+// specification is the package's own, DESIGN.md "K12", "K16", "K20", "K21" and "K22"; tests/viewport_restate.py restates K12 in
+// float64, tests/campath_restate.py K16 in integers, tests/director_restate.py K20, tests/viewport_aa_restate.py K21,
+// tests/zoom_restate.py K22.  Geometry, tables and the bilinear sample are sphere.h's.
 //
 // Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
 // centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
@@ -27,8 +28,12 @@
 //   K21   view pixel (i, j) with the factor n = 1 .. 4: s = the n n unrounded f32 samples (n i + a, n j + b) of K12a's view
 //         (n h, n w, tx, ty) under R, added in f32 with b outer and a inner from the first sample; out = s / (float)(n n), stored
 //         as K12a stores (u8: rintf, clamp).  n = 1 is K12a.  K20b's tiles have a factor each
-// Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d / K16c are f64 in a fixed order;
-// K16a / K16b are integers.  No atomics, no host synchronisation, results independent of the batch size.
+//   K22   lens f32 [N, 4] = (tx, ty, b, 0) per frame: K22a is K12a / K21 and K22b is K12b with frame n's lens (and factor), bit for
+//         bit.  K22d: in_j = ((p_x d_x + p_y d_y) + p_z d_z) >= (float)cos(window), top = max of the finite s_j in the cap,
+//         m_j = a_j fmaxf(s_j - (float)level top, 0), g_j = (((p_x - d_x)^2 + (p_y - d_y)^2) + (p_z - d_z)^2) / 2,
+//         q = sum m_j g_j / sum m_j
+// Every per-pixel term is f32 with plain operators and contraction off; the sums of K12c / K12d / K16c / K22d are f64 in a fixed
+// order; K16a / K16b are integers.  No atomics, no host synchronisation, results independent of the batch size.
 #pragma clang fp contract(off)
 
 #include "sphere.h"
@@ -131,6 +136,24 @@ __global__ __launch_bounds__(256) void view_render_aa_kernel(const T* __restrict
     const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
     view_pixel_aa<T, C, NS>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j,
                             dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
+}
+
+// K22a: K12a / K21 with a lens per frame.  K12a's grid and thread mapping; frame blockIdx.z takes (tx, ty) from its lens (tx, ty, b,
+// 0) in one 16-byte load, the same address for the whole workgroup, and with AA its factor from ss[blockIdx.z]: uniform over the
+// workgroup, so view_pixel_ss's switch does not diverge; a factor outside 2 .. 4 is 1 there.  AA = false never reads ss and calls
+// view_pixel.  A tangent that is not finite or not positive decides no address: it ends in the sampler's guard, as a non-finite R.
+template <typename T, int C, bool AA>
+__global__ __launch_bounds__(256) void view_render_zoom_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
+                                                               const float4* __restrict__ lens, const int* __restrict__ ss,
+                                                               T* __restrict__ dst, int H, int W, int h, int w) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= w) return;
+    const float4 L = lens[blockIdx.z];
+    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
+    const T* img = src + (size_t)blockIdx.z * H * W * C;
+    T* o = dst + (((size_t)blockIdx.z * h + j) * w + i) * C;
+    if (AA) view_pixel_ss<T, C>(img, R, H, W, h, w, L.x, L.y, i, j, ss[blockIdx.z], o);
+    else view_pixel<T, C>(img, R, H, W, h, w, L.x, L.y, i, j, o);
 }
 
 // ------------------------------------------------------------------ K20b: several views on one canvas
@@ -239,6 +262,38 @@ __global__ __launch_bounds__(256) void view_outline_kernel(const uint8_t* src, c
     const bool inner = au <= tx - b && av <= ty - b;
     const size_t o = (((size_t)blockIdx.z * H + y) * W + x) * 3;
     if (inside && !inner && rot_finite(R)) {
+        dst[o] = (uint8_t)cr;
+        dst[o + 1] = (uint8_t)cg;
+        dst[o + 2] = (uint8_t)cb;
+    } else if (dst != src) {
+        const uint8_t v0 = src[o], v1 = src[o + 1], v2 = src[o + 2];
+        dst[o] = v0;
+        dst[o + 1] = v1;
+        dst[o + 2] = v2;
+    }
+}
+
+// K22b: K12b with a lens per frame: view_outline_kernel's decision with (tx, ty, b) of frame blockIdx.z, its terms in its order.
+// A frame whose b is not greater than 0 (a NaN too) draws nothing.  Element-wise, so dst may be src.
+__global__ __launch_bounds__(256) void view_outline_zoom_kernel(const uint8_t* src, const float* __restrict__ Rs,
+                                                                const float4* __restrict__ lens, const float2* __restrict__ tabx,
+                                                                const float2* __restrict__ taby, uint8_t* dst, int H, int W, int cr,
+                                                                int cg, int cb) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const float4 L = lens[blockIdx.z];
+    const float tx = L.x, ty = L.y, b = L.z;
+    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
+    float px, py, pz;
+    stab_dir(tabx[x], taby[y], px, py, pz);
+    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
+    const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
+    const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
+    const float au = fabsf(dr / df), av = fabsf(du / df);
+    const bool inside = df > 0.f && au <= tx && av <= ty;
+    const bool inner = au <= tx - b && av <= ty - b;
+    const size_t o = (((size_t)blockIdx.z * H + y) * W + x) * 3;
+    if (inside && !inner && b > 0.f && rot_finite(R)) {
         dst[o] = (uint8_t)cr;
         dst[o + 1] = (uint8_t)cg;
         dst[o + 2] = (uint8_t)cb;
@@ -391,6 +446,86 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------ K22d: how wide the target is
+// The larger of two candidates of the cap's peak; have = 0 is no candidate.  A maximum: the order of the visit is free.
+__device__ __forceinline__ void spread_take(float ov, int oh, float& top, int& have) {
+    if (oh && (!have || ov > top)) {
+        top = ov;
+        have = 1;
+    }
+}
+
+// grid F, 256 threads: thread t takes pixels t, t + 256, .. in order, twice.  d = dirs[f]; a pixel is in the cap where
+// ((p_x d_x + p_y d_y) + p_z d_z) >= cw.  Pass 1: top = the largest finite s_j in the cap, through the shuffle tree and the four
+// waves.  Pass 2: m_j = a_j fmaxf(s_j - lv top, 0) for the finite s_j in the cap, g_j = ((p_x - d_x)^2 + (p_y - d_y)^2 + (p_z -
+// d_z)^2) / 2 = 1 - cos of the angle without the cancellation; M = sum m_j and Q = sum m_j g_j in f64 by sphere.h's ordered sum;
+// q = (float)(Q / M).  NaN for a non-finite d, a cap without a finite pixel, top <= 0 or an M that is not positive and finite.
+// Every exit before a barrier is the whole workgroup's: d, have and top are uniform.
+__global__ __launch_bounds__(256) void view_spread_kernel(const float* __restrict__ maps, const float* __restrict__ dirs,
+                                                          const float2* __restrict__ tabx, const float2* __restrict__ taby,
+                                                          float* __restrict__ q_out, int hm, int wm, float cw, float lv) {
+    __shared__ float red_t[4];
+    __shared__ int red_h[4];
+    __shared__ double red_s[4][2];
+    const int P = hm * wm, tid = threadIdx.x, f = blockIdx.x;
+    const float* s = maps + (size_t)f * P;
+    const float dx = dirs[(size_t)f * 3], dy = dirs[(size_t)f * 3 + 1], dz = dirs[(size_t)f * 3 + 2];
+    if (!isfinite(fabsf(dx) + fabsf(dy) + fabsf(dz))) {                 // an infinite dot would pass the comparison
+        if (tid == 0) q_out[f] = nanf("");
+        return;
+    }
+    float top = 0.f;
+    int have = 0;
+    for (int j = tid; j < P; j += 256) {
+        const int y = j / wm, x = j - y * wm;
+        float px, py, pz;
+        stab_dir(tabx[x], taby[y], px, py, pz);
+        const float dot = (px * dx + py * dy) + pz * dz;
+        const float sj = s[j];
+        spread_take(sj, dot >= cw && isfinite(sj), top, have);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) spread_take(__shfl_down(top, off, 64), __shfl_down(have, off, 64), top, have);
+    if ((tid & 63) == 0) {
+        red_t[tid >> 6] = top;
+        red_h[tid >> 6] = have;
+    }
+    __syncthreads();
+    top = red_t[0];
+    have = red_h[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) spread_take(red_t[k], red_h[k], top, have);
+    if (!have || !(top > 0.f)) {
+        if (tid == 0) q_out[f] = nanf("");
+        return;
+    }
+    const float floor_ = lv * top;
+    double M = 0.0, Q = 0.0;
+    for (int j = tid; j < P; j += 256) {
+        const int y = j / wm, x = j - y * wm;
+        const float2 csp = taby[y];
+        float px, py, pz;
+        stab_dir(tabx[x], csp, px, py, pz);
+        const float dot = (px * dx + py * dy) + pz * dz;
+        const float sj = s[j];
+        const float m = dot >= cw && isfinite(sj) ? csp.x * fmaxf(sj - floor_, 0.f) : 0.f;
+        const float ex = px - dx, ey = py - dy, ez = pz - dz;
+        const float g = 0.5f * ((ex * ex + ey * ey) + ez * ez);
+        M += (double)m;
+        Q += (double)(m * g);
+    }
+    M = wave_sum_down(M);
+    Q = wave_sum_down(Q);
+    if ((tid & 63) == 0) {
+        red_s[tid >> 6][0] = M;
+        red_s[tid >> 6][1] = Q;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double Ms = waves4_sum(&red_s[0][0], 2), Qs = waves4_sum(&red_s[0][1], 2);
+    q_out[f] = Ms > 0.0 && isfinite(Ms) ? (float)(Qs / Ms) : nanf("");
+}
+
 // ------------------------------------------------------------------ K16: the camera path by dynamic programming
 // The table (cp360_path_table_host): cost int32 [hm][hm][wm / 2 + 1] by (row of i, row of j, column difference folded to
 // 0 .. wm / 2), -1 = forbidden; behind it span int32 [hm][hm], the largest allowed column difference of the row pair, -1 = none.
@@ -541,6 +676,17 @@ __global__ __launch_bounds__(256) void view_refine_kernel(const float* __restric
 const double kPi = 3.14159265358979323846;
 
 bool bad_hfov(double hfov) { return !(hfov > 0.0 && hfov < kPi); }
+
+// The lens of a view (h, w) of hfov radians with a border of border_px view pixels, each value rounded to f32 once: what every
+// entry point hands its kernel, and a row of cp360_view_lens_host's table (K22)
+struct ViewLens {
+    float tx, ty, b;
+};
+
+ViewLens view_lens(double hfov_rad, int h, int w, double border_px) {
+    const double t = tan(0.5 * hfov_rad);
+    return {(float)t, (float)(t * (double)h / (double)w), border_px == 0.0 ? 0.f : (float)(border_px * 2.0 * t / (double)w)};
+}
 bool bad_sigma(double sigma) { return !(sigma > 0.0) || !isfinite(sigma); }
 
 template <typename T, int C>
@@ -557,6 +703,19 @@ int launch_render_aa(const void* frames, const float* R, void* out, int N, int H
                      hipStream_t s) {
     hipLaunchKernelGGL((view_render_aa_kernel<T, C, NS>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R, (T*)out,
                        H, W, h, w, tx, ty);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+// K22a: ss = the N factors on the device, or nullptr for one sample per pixel in every frame
+template <typename T, int C>
+int launch_render_zoom(const void* frames, const float* R, const float* lens, const int32_t* ss, void* out, int N, int H, int W,
+                       int h, int w, hipStream_t s) {
+    const dim3 grid((w + 255) / 256, h, N);
+    if (ss) hipLaunchKernelGGL((view_render_zoom_kernel<T, C, true>), grid, dim3(256), 0, s, (const T*)frames, R, (const float4*)lens,
+                               (const int*)ss, (T*)out, H, W, h, w);
+    else hipLaunchKernelGGL((view_render_zoom_kernel<T, C, false>), grid, dim3(256), 0, s, (const T*)frames, R, (const float4*)lens,
+                            (const int*)nullptr, (T*)out, H, W, h, w);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -656,8 +815,8 @@ static int view_render_ss(int dtype, const void* frames, const float* R, int N, 
     if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || big_image(N, ss * h, ss * w))
         return CP360_ERR_UNSUPPORTED;
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
-    const double t = tan(0.5 * hfov_rad);
-    const float tx = (float)t, ty = (float)(t * (double)h / (double)w);
+    const ViewLens lens = view_lens(hfov_rad, h, w, 0.0);
+    const float tx = lens.tx, ty = lens.ty;
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
         using T = decltype(px);
@@ -691,10 +850,9 @@ extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, 
     SphereTabs tabs;
     const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
     if (st != CP360_OK) return st;
-    const double t = tan(0.5 * hfov_rad);
-    const float tx = (float)t, ty = (float)(t * (double)h / (double)w), b = (float)(border_px * 2.0 * t / (double)w);
-    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, tabs.x, tabs.y, out, H, W, tx,
-                       ty, b, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
+    const ViewLens lens = view_lens(hfov_rad, h, w, border_px);
+    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, tabs.x, tabs.y, out, H, W,
+                       lens.tx, lens.ty, lens.b, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -845,9 +1003,9 @@ static int view_render_multi_ss(int dtype, const void* frames, const float* R, i
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
     float tx[kMaxTiles], ty[kMaxTiles];
     for (int k = 0; k < K; ++k) {                                       // cp360_view_render's, per tile
-        const double t = tan(0.5 * hfov_rad[k]);
-        tx[k] = (float)t;
-        ty[k] = (float)(t * (double)tiles[4 * k + 3] / (double)tiles[4 * k + 2]);
+        const ViewLens lens = view_lens(hfov_rad[k], tiles[4 * k + 3], tiles[4 * k + 2], 0.0);
+        tx[k] = lens.tx;
+        ty[k] = lens.ty;
     }
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
@@ -868,4 +1026,69 @@ extern "C" int cp360_view_render_multi_aa(int dtype, const void* frames, const f
                                           void* out, int hc, int wc, void* stream) {
     if (!frames || !R || !tiles || !hfov_rad || !ss || !fill || !out) return CP360_ERR_NULL;
     return view_render_multi_ss(dtype, frames, R, N, H, W, C, K, tiles, hfov_rad, ss, fill, out, hc, wc, stream);
+}
+
+// ------------------------------------------------------------------ K22: zoom, a lens per frame
+extern "C" int cp360_view_lens_host(const double* hfov_rad, int N, int h, int w, double border_px, float* lens) {
+    if (!hfov_rad || !lens) return CP360_ERR_NULL;
+    if (bad_image(N, h, w) || !(border_px >= 0.0) || !isfinite(border_px)) return CP360_ERR_BAD_SHAPE;
+    for (int n = 0; n < N; ++n)
+        if (bad_hfov(hfov_rad[n])) return CP360_ERR_BAD_SHAPE;
+    for (int n = 0; n < N; ++n) {
+        const ViewLens l = view_lens(hfov_rad[n], h, w, border_px);
+        lens[4 * n] = l.tx;
+        lens[4 * n + 1] = l.ty;
+        lens[4 * n + 2] = l.b;
+        lens[4 * n + 3] = 0.f;
+    }
+    return CP360_OK;
+}
+
+// view_render_ss's checks in its order, the lens in place of the field of view; then the alignment
+extern "C" int cp360_view_render_zoom(int dtype, const void* frames, const float* R, const float* lens, const int32_t* ss, int N,
+                                      int H, int W, int C, void* out, int h, int w, void* stream) {
+    if (!frames || !R || !lens || !out) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1) return CP360_ERR_BAD_SHAPE;
+    if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
+    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || (ss && big_image(N, 4 * h, 4 * w)))
+        return CP360_ERR_UNSUPPORTED;
+    if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
+    if (!aligned16(lens) || ((uintptr_t)ss & 3) != 0) return CP360_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_pixels(dtype, C, [&](auto px, auto c) {
+        return launch_render_zoom<decltype(px), decltype(c)::value>(frames, R, lens, ss, out, N, H, W, h, w, s);
+    });
+}
+
+extern "C" int cp360_view_outline_zoom(const uint8_t* frames, const float* R, const float* lens, int N, int H, int W,
+                                       const uint8_t* rgb, uint8_t* out, void* work, size_t work_bytes, void* stream) {
+    if (!frames || !R || !lens || !rgb || !out || !work) return CP360_ERR_NULL;
+    if (bad_image(N, H, W)) return CP360_ERR_BAD_SHAPE;
+    if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (!aligned16(lens)) return CP360_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs tabs;
+    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_outline_zoom_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, (const float4*)lens, tabs.x,
+                       tabs.y, out, H, W, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+extern "C" int cp360_view_spread(const float* maps, const float* dirs, int F, int hm, int wm, double window_rad, double level,
+                                 float* q, void* work, size_t work_bytes, void* stream) {
+    if (!maps || !dirs || !q || !work) return CP360_ERR_NULL;
+    if (bad_image(F, hm, wm) || !(window_rad > 0.0 && window_rad <= kPi) || !(level > 0.0 && level < 1.0))
+        return CP360_ERR_BAD_SHAPE;
+    int st = path_args(F, hm, wm);
+    if (st != CP360_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = open_tabs(work, work_bytes, tab_bytes(hm, wm), hm, wm, s, &t);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_spread_kernel, dim3(F), dim3(256), 0, s, maps, dirs, t.x, t.y, q, hm, wm, (float)cos(window_rad),
+                       (float)level);
+    CP360_CHECK_HIP();
+    return CP360_OK;
 }

@@ -1753,6 +1753,107 @@ def viewport_render_multi(frames, R, tiles, hfov_deg, canvas_hw, fill=None, out=
     return out
 
 
+# ----------------------------------------------------------------------------- K22: zoom, a lens per frame (csrc/viewport.hip)
+def viewport_lens_host(hfov_deg, hw, border_px=0.0, n=None):
+    """cp360_view_lens_host: the lenses of views of hw = (h, w) pixels as a float32 numpy [N, 4] = (tx, ty, b, 0) per frame, tx =
+    tan(hfov / 2), ty = tx h / w, b = border_px 2 tx / w, each formed in double and rounded once - the values ``viewport_render``
+    and ``viewport_outline`` hand their kernels.  hfov_deg: N values in degrees, or a scalar repeated ``n`` times (default 1).
+    Host only: needs no GPU."""
+    h, w = (int(v) for v in hw)
+    fov = np.asarray(hfov_deg, np.float64)
+    if fov.ndim == 0:
+        fov = np.full(1 if n is None else int(n), float(fov))
+    if fov.ndim != 1 or fov.size < 1 or (n is not None and fov.size != int(n)):
+        raise ValueError("hfov_deg must be a scalar or %s values, got shape %s" % ('N' if n is None else int(n), fov.shape))
+    if h < 1 or w < 1 or not all(0.0 < v < 180.0 for v in fov) or not (float(border_px) >= 0.0 and math.isfinite(float(border_px))):
+        raise ValueError("a lens needs h, w >= 1, 0 < hfov_deg < 180 and a finite border_px >= 0, got %r, %r, %r"
+                         % (hw, hfov_deg, border_px))
+    rad = (C.c_double * fov.size)(*[math.radians(float(v)) for v in fov])
+    out = np.empty((fov.size, 4), np.float32)
+    check(lib().cp360_view_lens_host(C.cast(rad, C.c_void_p), int(fov.size), h, w, float(border_px), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def viewport_lens(hfov_deg, hw, border_px=0.0, device='cuda', n=None):
+    """``viewport_lens_host`` on `device`: f32 [N, 4], what the ``_zoom`` ops take."""
+    return torch.from_numpy(viewport_lens_host(hfov_deg, hw, border_px, n)).to(device)
+
+
+def _lens(lens, N, device, name='lens'):
+    if lens.dim() != 2 or tuple(lens.shape) != (N, 4) or lens.device != device:
+        raise ValueError("%s must be float32 [%d, 4] on the frames' device (viewport_lens), got %s" % (name, N, tuple(lens.shape)))
+    _check_buf(name, lens, torch.float32)
+    if lens.data_ptr() % 16:
+        raise ValueError("%s must be 16-byte aligned" % name)
+
+
+def viewport_render_zoom(frames, R, hw, lens, out=None, supersample=None):
+    """cp360_view_render_zoom: ``viewport_render`` with a lens per frame (``viewport_lens``, f32 [N, 4]) in one launch: frame n is
+    ``viewport_render(frames[n:n + 1], R[n:n + 1], hw, hfov_n, supersample=ss_n)`` bit for bit.  ``supersample``: None (one
+    sample per pixel), or int32 [N] on the device, a factor per frame; a value outside 2 .. 4 renders as 1."""
+    if supersample is not None and not torch.is_tensor(supersample):
+        raise ValueError("supersample must be None or an int32 tensor [N] on the frames' device, got %r" % (supersample,))
+    require_gpu(frames, R, lens, out, supersample)
+    N, H, W, C_ = _frames_nhwc(frames, u8_only=False)
+    _stab_rotations(R, N)
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError("a view needs h, w >= 1, got %r" % (hw,))
+    _lens(lens, N, frames.device)
+    if supersample is not None:
+        if tuple(supersample.shape) != (N,) or supersample.device != frames.device:
+            raise ValueError("supersample must be None or int32 [%d] on the frames' device" % N)
+        _check_buf('supersample', supersample, torch.int32)
+    out = _out_for(out, (N, h, w, C_), frames.dtype, frames.device, frames)
+    check(lib().cp360_view_render_zoom(dtype_code(frames.dtype), ptr(frames), ptr(R), ptr(lens), ptr(supersample), N, H, W, C_,
+                                       ptr(out), h, w, stream()))
+    return out
+
+
+def viewport_outline_zoom(frames, R, lens, rgb=(0, 255, 0), out=None, work=None):
+    """cp360_view_outline_zoom: ``viewport_outline`` with a lens per frame (``viewport_lens(hfov_deg, hw, border_px)``): frame n is
+    ``viewport_outline`` with that frame's field of view and border, bit for bit; a frame whose b is not above 0 draws nothing.
+    out may be frames."""
+    require_gpu(frames, R, lens, out)
+    N, H, W, _ = _frames_nhwc(frames, u8_only=True)
+    _stab_rotations(R, N)
+    _lens(lens, N, frames.device)
+    rgb = tuple(int(v) for v in rgb)
+    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise ValueError("rgb must be three values of 0 .. 255, got %r" % (rgb,))
+    out = _out_for(out, (N, H, W, 3), torch.uint8, frames.device, frames, same_ok=True)
+    work = _stab_work(0, H, W, frames.device, work)
+    colour = (C.c_ubyte * 3)(*rgb)
+    check(lib().cp360_view_outline_zoom(ptr(frames), ptr(R), ptr(lens), N, H, W, C.cast(colour, C.c_void_p), ptr(out), ptr(work),
+                                        work.numel() * 8, stream()))
+    return out
+
+
+def sphere_spread(maps, dirs, window_deg=45.0, level=0.5, work=None):
+    """cp360_view_spread: how wide the target about dirs f32 [F, 3] (``sphere_peak``'s or ``sphere_refine``'s) is on maps f32
+    [F, hm, wm] -> q f32 [F]: the mean of 1 - cos(angle to dirs[f]), weighted by solid angle times the map's excess over ``level``
+    times its peak, both inside the cap of window_deg degrees about dirs[f].  For a Gaussian blob of width sigma_b that is narrow
+    against the cap q = ``utils.viewport.spread_constant(level)`` sigma_b^2.  NaN for a non-finite direction, a cap without a
+    finite pixel or a peak that is not positive."""
+    require_gpu(maps, dirs, work)
+    if maps.dim() != 3 or maps.numel() == 0:
+        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+    _check_buf('maps', maps, torch.float32)
+    F, hm, wm = (int(s) for s in maps.shape)
+    if hm * wm > 16384:
+        raise ValueError("maps of more than 16384 pixels are not supported, got %d x %d" % (hm, wm))
+    if tuple(dirs.shape) != (F, 3) or dirs.device != maps.device:
+        raise ValueError("dirs must be float32 [%d, 3] on the maps' device, got %s" % (F, tuple(dirs.shape)))
+    _check_buf('dirs', dirs, torch.float32)
+    if not 0.0 < float(window_deg) <= 180.0 or not 0.0 < float(level) < 1.0:
+        raise ValueError("window_deg must be in (0, 180] and level in (0, 1), got %r, %r" % (window_deg, level))
+    work = _stab_work(0, hm, wm, maps.device, work)
+    q = torch.empty((F,), dtype=torch.float32, device=maps.device)
+    check(lib().cp360_view_spread(ptr(maps), ptr(dirs), F, hm, wm, math.radians(float(window_deg)), float(level), ptr(q), ptr(work),
+                                  work.numel() * 8, stream()))
+    return q
+
+
 # ----------------------------------------------------------------------------- K13: shot detection (csrc/shots.hip)
 _SHOT_WEIGHTS = {}
 
@@ -2045,6 +2146,25 @@ def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
     uni = torch.empty((N,), dtype=torch.int64, device=R.device)
     check(lib().cp360_head_agreement(ptr(Rc), cam_hfov, cam_aspect, ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
                                      ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
+    return inter, uni
+
+
+def head_agreement_zoom(Rc, cam_lens, R, offsets, hw, view, weights, work=None):
+    """cp360_head_agreement_zoom (K22c): ``head_agreement`` with a lens per frame for the camera, cam_lens f32 [F, 4]
+    (``viewport_lens`` of the camera's view and its field of view per frame); the viewers' window stays ``view``."""
+    require_gpu(Rc, cam_lens, R, offsets, weights, work)
+    N, F, h, w = _head_cameras(R, offsets, hw)
+    _stab_rotations(Rc, F)
+    if Rc.device != R.device or tuple(weights.shape) != (h,) or weights.device != R.device:
+        raise ValueError("Rc [%d, 3, 3] and weights int32 [%d] must be on R's device" % (F, h))
+    _check_buf('weights', weights, torch.int32)
+    _lens(cam_lens, F, R.device, 'cam_lens')
+    hfov, aspect = _head_view(*view)
+    work = head_work(h, w, R.device, work)
+    inter = torch.empty((N,), dtype=torch.int64, device=R.device)
+    uni = torch.empty((N,), dtype=torch.int64, device=R.device)
+    check(lib().cp360_head_agreement_zoom(ptr(Rc), ptr(cam_lens), ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
+                                          ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
     return inter, uni
 
 

@@ -117,12 +117,18 @@ class HeadMaps:
 
     def agreement(self, R_cam, cam_hw, cam_hfov_deg, R, offsets, weights='solid_angle'):
         """The camera R_cam [F, 3, 3] (``ViewportPilot.path``) with views of cam_hw and cam_hfov_deg against every viewer of its
-        frame -> ``HeadAgreement``.  weights: 'solid_angle' (areas on the sphere) or 'uniform' (pixels of the grid times 1024)."""
+        frame -> ``HeadAgreement``.  weights: 'solid_angle' (areas on the sphere) or 'uniform' (pixels of the grid times 1024).
+        cam_hfov_deg may be F values, a field of view per frame of R_cam (K22c, ``ops.head_agreement_zoom``)."""
         R, offsets = self._cameras(R, offsets)
         R_cam = on_device(R_cam, R.device, torch.float32)
         a = ops.sphere_eval_weights(self.grid_hw[0], weights, R.device)
-        inter, union = ops.head_agreement(R_cam, (cam_hw, cam_hfov_deg), R, offsets, self.grid_hw, (self.view_hw, self.hfov_deg), a,
-                                          work=self._workspace(R.device))
+        if np.ndim(cam_hfov_deg) == 0:
+            inter, union = ops.head_agreement(R_cam, (cam_hw, cam_hfov_deg), R, offsets, self.grid_hw, (self.view_hw, self.hfov_deg),
+                                              a, work=self._workspace(R.device))
+        else:                                                           # K22c: a field of view per frame of R_cam
+            lens = ops.viewport_lens(cam_hfov_deg, cam_hw, device=R.device, n=len(R_cam))
+            inter, union = ops.head_agreement_zoom(R_cam, lens, R, offsets, self.grid_hw, (self.view_hw, self.hfov_deg), a,
+                                                   work=self._workspace(R.device))
         N, F = int(R.shape[0]), int(offsets.shape[0]) - 1
         iou = inter.to(torch.float64) / union.to(torch.float64)                             # 0 / 0 = NaN
         frame = torch.bucketize(torch.arange(N, device=R.device, dtype=torch.int32), offsets[1:], right=True).clamp(max=F - 1)

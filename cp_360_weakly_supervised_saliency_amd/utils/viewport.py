@@ -13,7 +13,9 @@ chooses which of several targets to follow, where the peaks hop between them.  S
 ``render_multi`` shows their views side by side on one canvas (``ops.viewport_render_multi``).  A camera is a rotation R,
 camera-to-world, with the columns (forward, up, right): R = I looks at the panorama's centre.  A view coarser than its source is
 anti-aliased by supersampling (K21, DESIGN.md "K21"): ``supersample_for`` is the factor a view needs, ``ViewportPilot(..,
-antialias=True)`` uses it.  Roll and translation are out of scope.
+antialias=True)`` uses it.  Zoom (K22, DESIGN.md "K22"): ``ops.sphere_spread`` measures how wide the target is,
+``zoom_from_spread`` and ``smooth_zoom`` turn that into a field of view per frame, ``ViewportPilot(.., zoom=True).follow_zoom``
+renders every frame through its own lens in one launch (``ops.viewport_render_zoom``).  Roll and translation are out of scope.
 """
 import numpy as np
 import torch
@@ -125,6 +127,63 @@ def supersample_for(HW, hw, hfov_deg, limit=4):
     return int(min(limit, max(1, int(np.ceil(rho - 1e-9)))))
 
 
+# ----------------------------------------------------------------------------- zoom (K22)
+def spread_constant(level=0.5):
+    """c(level) of ``ops.sphere_spread``: for a Gaussian blob exp(-theta^2 / (2 sigma_b^2)) that is narrow against the cap, q = c
+    sigma_b^2 - the mean of theta^2 / 2 over the disc where the blob stands above ``level`` of its peak, weighted by its excess.
+    With L = -ln(level): c = (1 - (1 + L) level - level L^2 / 2) / (1 - level - level L); c(0.5) = 0.21713."""
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must be in (0, 1), got %r" % (level,))
+    L = -np.log(level)
+    return float((1.0 - (1.0 + L) * level - 0.5 * level * L * L) / (1.0 - level - level * L))
+
+
+def zoom_from_spread(q, hw, level=0.5, sigmas=2.5, range_deg=(40.0, 110.0), default_deg=90.0):
+    """q [F] (``ops.sphere_spread``) -> the field of view of every frame, float64 [F] in degrees: sigma_b = sqrt(q / c(level)) is
+    the target's width, the shorter side of the view of hw = (h, w) pixels spans +- sigmas sigma_b (at most 89 degrees), so tx =
+    tan(min(sigmas sigma_b, radians(89))) max(1, w / h) and hfov = 2 atan(tx), clamped to ``range_deg``.  A NaN q (no target)
+    gives ``default_deg``.  2.5 widths and 40 .. 110 degrees are conventions, not tuned on data."""
+    q = np.atleast_1d(np.asarray(q, np.float64))
+    h, w = int(hw[0]), int(hw[1])
+    lo, hi = float(range_deg[0]), float(range_deg[1])
+    if q.ndim != 1 or h < 1 or w < 1 or not float(sigmas) > 0.0 or not 0.0 < lo <= hi < 180.0 or not 0.0 < float(default_deg) < 180.0:
+        raise ValueError("q must be [F], hw positive, sigmas > 0, 0 < range_deg[0] <= range_deg[1] < 180 and 0 < default_deg < 180, "
+                         "got %s, %r, %r, %r, %r" % (q.shape, hw, sigmas, range_deg, default_deg))
+    with np.errstate(invalid='ignore'):
+        sigma_b = np.sqrt(q / spread_constant(level))
+        tx = np.tan(np.minimum(float(sigmas) * sigma_b, np.deg2rad(89.0))) * max(1.0, w / h)
+        hfov = np.clip(np.rad2deg(2.0 * np.arctan(tx)), lo, hi)
+    return np.where(np.isnan(q), float(default_deg), hfov)
+
+
+def _scalar_pass(x, alpha):
+    out = np.empty_like(x)
+    out[0] = x[0]
+    for t in range(1, x.shape[0]):
+        out[t] = out[t - 1] + (1.0 - alpha) * (x[t] - out[t - 1])
+    return out
+
+
+def smooth_zoom(hfov_deg, alpha=0.9, cuts=None):
+    """hfov_deg [F] in degrees -> float64 [F]: ``smooth_path``'s zero-phase exponential filter on z = log(tan(hfov / 2)) - zoom
+    multiplies, so the filter works in that log domain -, shot by shot (``cuts``).  A pass is m_0 = z_0, m_t = m_t-1 + (1 - alpha)
+    (z_t - m_t-1); the result is the mean of forward-then-backward and backward-then-forward, which a scalar can afford and a
+    great circle cannot: the filter is then exactly symmetric under time reversal, edges included."""
+    x = np.asarray(hfov_deg, np.float64)
+    if x.ndim != 1 or x.shape[0] < 1 or not np.all((x > 0.0) & (x < 180.0)):
+        raise ValueError("hfov_deg must be [F] with every value in (0, 180), got %s" % (x.shape,))
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError("alpha must be in [0, 1), got %r" % (alpha,))
+    shots = segments(cuts, x.shape[0])
+    if len(shots) > 1:
+        return np.concatenate([smooth_zoom(x[lo:hi], alpha) for lo, hi in shots])
+    z, alpha = np.log(np.tan(0.5 * np.deg2rad(x))), float(alpha)
+    fb = _scalar_pass(_scalar_pass(z, alpha)[::-1], alpha)[::-1]
+    bf = _scalar_pass(_scalar_pass(z[::-1], alpha)[::-1], alpha)
+    return np.rad2deg(2.0 * np.arctan(np.exp(0.5 * (fb + bf))))
+
+
 def _longitude_deg(v):
     return np.rad2deg(np.arctan2(v[2], v[0]))
 
@@ -197,10 +256,17 @@ class ViewportPilot:
 
     ``antialias`` (K21): False renders with one bilinear sample per view pixel; True supersamples every view by
     ``supersample_for`` of the frames it is given - in ``render_multi`` per tile; an int 1 .. 4 is that factor.  ``render``,
-    ``follow``, ``render_multi`` and ``follow_multi`` honour it."""
+    ``follow``, ``render_multi`` and ``follow_multi`` honour it.
+
+    ``zoom`` (K22): True lets ``track`` and ``follow_zoom`` choose a field of view per frame from how wide the target is
+    (``ops.sphere_spread`` inside ``zoom_window_deg`` degrees of the path's direction, above ``zoom_level`` of the peak there;
+    ``zoom_from_spread`` with ``zoom_sigmas`` and ``zoom_range_deg``; ``smooth_zoom`` with ``zoom_alpha``).  2.5 widths, 40 .. 110
+    degrees, 45 degrees, 0.5 and 0.9 are conventions, not tuned on data.  ``render``, ``outline`` and ``agreement`` take the
+    fields of view as ``hfov_deg=``; a canvas (``render_multi``) keeps one field of view per call."""
 
     def __init__(self, hw=(720, 1280), hfov_deg=90.0, sigma_deg=15.0, alpha=0.85, max_step_deg=None, device='cuda', planner='peak',
-                 turn_cost=16.0, plan_step_deg=15.0, antialias=False):
+                 turn_cost=16.0, plan_step_deg=15.0, antialias=False, zoom=False, zoom_sigmas=2.5, zoom_range_deg=(40.0, 110.0),
+                 zoom_window_deg=45.0, zoom_level=0.5, zoom_alpha=0.9):
         if not isinstance(antialias, bool) and not (isinstance(antialias, (int, np.integer)) and 1 <= antialias <= 4):
             raise ValueError("antialias must be False, True or an int 1 .. 4, got %r" % (antialias,))
         self.antialias = antialias if isinstance(antialias, bool) else int(antialias)
@@ -216,6 +282,14 @@ class ViewportPilot:
         if not 0.0 <= float(turn_cost) <= 4096.0 or not 0.0 < float(plan_step_deg) <= 180.0:
             raise ValueError("turn_cost must be in [0, 4096] and plan_step_deg in (0, 180], got %r, %r" % (turn_cost, plan_step_deg))
         self.planner, self.turn_cost, self.plan_step_deg = planner, float(turn_cost), float(plan_step_deg)
+        self.zoom, self.zoom_sigmas, self.zoom_window_deg = bool(zoom), float(zoom_sigmas), float(zoom_window_deg)
+        self.zoom_range_deg = (float(zoom_range_deg[0]), float(zoom_range_deg[1]))
+        self.zoom_level, self.zoom_alpha = float(zoom_level), float(zoom_alpha)
+        if not self.zoom_sigmas > 0.0 or not 0.0 < self.zoom_range_deg[0] <= self.zoom_range_deg[1] < 180.0 \
+                or not 0.0 < self.zoom_window_deg <= 180.0 or not 0.0 < self.zoom_level < 1.0 or not 0.0 <= self.zoom_alpha < 1.0:
+            raise ValueError("zoom needs zoom_sigmas > 0, 0 < zoom_range_deg[0] <= zoom_range_deg[1] < 180, zoom_window_deg in "
+                             "(0, 180], zoom_level in (0, 1) and zoom_alpha in [0, 1), got %r, %r, %r, %r, %r"
+                             % (zoom_sigmas, zoom_range_deg, zoom_window_deg, zoom_level, zoom_alpha))
         self.device = torch.device(device)
         self._tab_work = TabWork()
         self._path_work = None
@@ -282,6 +356,26 @@ class ViewportPilot:
         R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg, cuts), cuts)
         return torch.from_numpy(R.astype(np.float32)).to(self.device)
 
+    def track(self, maps, cuts=None):
+        """maps f32 [F, hm, wm] -> (R f32 [F, 3, 3] on the device, hfov_deg float64 [F] on the host): ``path``'s cameras and a
+        field of view per frame.  The peaks (or the plan) exactly as ``path`` takes them, ``ops.sphere_spread`` about them on
+        the device, ONE copy to the host of the 4 F floats (directions and spreads together: still the one synchronisation of a
+        video), then ``smooth_path``, ``cameras``, ``zoom_from_spread`` and ``smooth_zoom``, all with ``cuts``.  With
+        ``zoom=False`` R is ``path``'s bit for bit and hfov_deg is the pilot's constant."""
+        maps = on_device(maps, self.device, torch.float32)
+        dirs = self.plan(maps, cuts) if self.planner == 'viterbi' else self.peaks(maps)
+        F = int(dirs.shape[0])
+        if self.zoom:
+            q = ops.sphere_spread(maps, dirs, self.zoom_window_deg, self.zoom_level, work=self._tab_work(maps))
+            both = torch.cat([dirs.reshape(-1), q]).cpu().numpy()
+            dirs, q = both[:3 * F].reshape(F, 3), both[3 * F:]
+            hfov = smooth_zoom(zoom_from_spread(q, self.hw, self.zoom_level, self.zoom_sigmas, self.zoom_range_deg, self.hfov_deg),
+                               self.zoom_alpha, cuts)
+        else:
+            dirs, hfov = dirs.cpu().numpy(), np.full(F, self.hfov_deg)
+        R = cameras(smooth_path(dirs, self.alpha, self.max_step_deg, cuts), cuts)
+        return torch.from_numpy(R.astype(np.float32)).to(self.device), hfov
+
     def _factor(self, frames, hw):
         """``antialias`` as the factor of a view of hw pixels of these frames."""
         if self.antialias is False:
@@ -292,24 +386,54 @@ class ViewportPilot:
             return supersample_for(frames.shape[1:3], hw, self.hfov_deg)
         return self.antialias
 
-    def render(self, frames, R, out=None):
-        """frames u8 [N, H, W, 3] or f32 [N, H, W, C] under the cameras R [N, 3, 3] -> the views [N, h, w, C] on the device."""
+    @staticmethod
+    def _fovs(hfov_deg, N):
+        """``hfov_deg=`` of render / outline / agreement: N fields of view in degrees, float64 on the host."""
+        fov = np.asarray(hfov_deg.cpu() if torch.is_tensor(hfov_deg) else hfov_deg, np.float64)
+        if fov.shape != (N,) or not np.all((fov > 0.0) & (fov < 180.0)):
+            raise ValueError("hfov_deg must be None or %d values in (0, 180), got %r" % (N, hfov_deg))
+        return fov
+
+    def render(self, frames, R, out=None, hfov_deg=None):
+        """frames u8 [N, H, W, 3] or f32 [N, H, W, C] under the cameras R [N, 3, 3] -> the views [N, h, w, C] on the device.
+        ``hfov_deg``: N fields of view, one per frame (``track``), rendered in one launch (``ops.viewport_render_zoom``); with
+        ``antialias=True`` every frame has its own ``supersample_for``.  None: the pilot's own, today's call."""
         R = on_device(R, self.device, torch.float32)
         frames = on_device(frames, self.device)
-        return ops.viewport_render(frames, R, self.hw, self.hfov_deg, out=out, supersample=self._factor(frames, self.hw))
+        if hfov_deg is None:
+            return ops.viewport_render(frames, R, self.hw, self.hfov_deg, out=out, supersample=self._factor(frames, self.hw))
+        fov = self._fovs(hfov_deg, int(frames.shape[0]))
+        if self.antialias is True:
+            if frames.dim() != 4:
+                raise ValueError("frames must be [N, H, W, C], got %s" % (tuple(frames.shape),))
+            factors = [supersample_for(frames.shape[1:3], self.hw, v) for v in fov]
+        else:
+            factors = [self._factor(frames, self.hw)] * len(fov)
+        ss = None if all(v == 1 for v in factors) else torch.tensor(factors, dtype=torch.int32).to(self.device)
+        return ops.viewport_render_zoom(frames, R, self.hw, ops.viewport_lens(fov, self.hw, device=self.device), out=out,
+                                        supersample=ss)
 
-    def outline(self, frames, R, border_px=3, rgb=(0, 255, 0), out=None):
-        """frames u8 [N, H, W, 3] -> the panoramas with every view's frame drawn in rgb, on the device."""
+    def outline(self, frames, R, border_px=3, rgb=(0, 255, 0), out=None, hfov_deg=None):
+        """frames u8 [N, H, W, 3] -> the panoramas with every view's frame drawn in rgb, on the device.  ``hfov_deg``: as in
+        ``render`` (``ops.viewport_outline_zoom``)."""
         frames, R = on_device(frames, self.device), on_device(R, self.device, torch.float32)
-        return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=self._tab_work(frames))
+        if hfov_deg is None:
+            return ops.viewport_outline(frames, R, self.hw, self.hfov_deg, border_px, rgb, out=out, work=self._tab_work(frames))
+        if not float(border_px) > 0.0:
+            raise ValueError("border_px must be positive, got %r" % (border_px,))
+        lens = ops.viewport_lens(self._fovs(hfov_deg, int(frames.shape[0])), self.hw, border_px, device=self.device)
+        return ops.viewport_outline_zoom(frames, R, lens, rgb, out=out, work=self._tab_work(frames))
 
-    def agreement(self, R_cam, R, offsets, head=None):
+    def agreement(self, R_cam, R, offsets, head=None, hfov_deg=None):
         """The cameras R_cam [F, 3, 3] (``path``) with this pilot's view against the viewers' head cameras R [N, 3, 3], offsets
         [F + 1] (``headtrack.head_cameras``) -> ``headtrack.HeadAgreement``: how much of what the people had in view is in the
-        pilot's frame.  ``head``: the ``headtrack.HeadMaps`` that holds the grid and the viewers' window (default: its defaults)."""
+        pilot's frame.  ``head``: the ``headtrack.HeadMaps`` that holds the grid and the viewers' window (default: its defaults).
+        ``hfov_deg``: F fields of view, one per frame of R_cam (``track``; ``ops.head_agreement_zoom``)."""
         from .headtrack import HeadMaps                                 # headtrack imports look_at from here
         head = head or HeadMaps(device=self.device)
-        return head.agreement(R_cam, self.hw, self.hfov_deg, R, offsets)
+        if hfov_deg is None:
+            return head.agreement(R_cam, self.hw, self.hfov_deg, R, offsets)
+        return head.agreement(R_cam, self.hw, self._fovs(hfov_deg, len(R_cam)), R, offsets)
 
     def follow(self, frames, maps, cuts=None):
         """frames u8 [F, H, W, 3], maps f32 [F, hm, wm] (one per frame, e.g. ``SaliencyEngine(.., return_all_steps=True)``'s
@@ -320,6 +444,15 @@ class ViewportPilot:
             raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
         R = self.path(maps, cuts)
         return self.render(frames, R), R
+
+    def follow_zoom(self, frames, maps, cuts=None):
+        """``follow`` with a field of view per frame: (views [F, h, w, C], R f32 [F, 3, 3] on the device, hfov_deg float64 [F] on
+        the host) - ``track``, then ``render`` with its fields of view."""
+        frames = on_device(frames, self.device)
+        if frames.dim() != 4 or len(maps) != frames.shape[0]:
+            raise ValueError("one map per frame: got %d frames and %d maps" % (frames.shape[0], len(maps)))
+        R, hfov = self.track(maps, cuts)
+        return self.render(frames, R, hfov_deg=hfov), R, hfov
 
     # ------------------------------------------------------------------------- several cameras at once (K20)
     def paths(self, maps, n, cuts=None, exclude_deg=None, min_share=0.0, arrange='score'):

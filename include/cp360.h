@@ -653,6 +653,42 @@ int cp360_view_render_aa(int dtype, const void* frames, const float* R, int N, i
 int cp360_view_render_multi_aa(int dtype, const void* frames, const float* R, int N, int H, int W, int C, int K, const int32_t* tiles,
                                const double* hfov_rad, const int32_t* ss, const void* fill, void* out, int hc, int wc, void* stream);
 
+/* ------------------------------------------------------------------ K22: zoom, a field of view per frame
+ * One lens per frame instead of one per call, and a measure of how wide the target is, from which the host chooses the lens.  The
+ * definition is the package's own, DESIGN.md "K22", restated in float64 in tests/zoom_restate.py.  Every launch has an earlier call
+ * as its bit-exact oracle.
+ *
+ *   lens          lens f32 [N, 4] = (tx, ty, b, 0) per frame, 16-byte aligned, on the device for the three launches below.
+ *                 lens_host fills it in HOST memory without a GPU call, with the arithmetic of cp360_view_render and
+ *                 cp360_view_outline: t = tan(hfov / 2) in double, tx = (float)t, ty = (float)(t h / w), b = (float)(border_px 2 t /
+ *                 w), 0.f for border_px == 0.
+ *   render_zoom   frame n of out = cp360_view_render's (ss == NULL) or cp360_view_render_aa's (ss int32 [N] on the DEVICE, 4-byte
+ *                 aligned; a value outside 2 .. 4 renders as the factor 1) frame under the lens (tx, ty) of frame n, bit for bit.
+ *                 No value of a lens decides an address: a tangent that is not finite or not positive ends in the sampler's guard.
+ *   outline_zoom  frame n of out = cp360_view_outline's frame with (tx, ty, b) of frame n, bit for bit; a frame whose b is not
+ *                 greater than 0 draws nothing.  out may be frames.
+ *   spread        maps f32 [F, hm, wm], dirs f32 [F, 3] (cp360_view_peak's or cp360_view_refine's) -> q f32 [F]: with d = dirs[f], the
+ *                 cap in_j = ((p_x d_x + p_y d_y) + p_z d_z) >= (float)cos(window_rad), top = the largest finite s_j in the cap, m_j
+ *                 = a_j fmaxf(s_j - (float)level top, 0) for the finite s_j in the cap (else 0), g_j = ((p_x - d_x)^2 + (p_y - d_y)^2
+ *                 + (p_z - d_z)^2) / 2: q[f] = (float)(sum m_j g_j / sum m_j), the two sums in f64 in K12d's order - the mean of 1 -
+ *                 cos(angle) over the part of the target above level times its peak.  NaN for a non-finite d, a cap without a finite
+ *                 pixel, top <= 0 or a sum of m that is not positive and finite.  One workgroup per frame; workspace: the tables.
+ * cp360_head_agreement_zoom (below, K17) is cp360_head_agreement with the camera's tangents from cam_lens[f].
+ * Status codes, in this order and before any launch.  lens_host: NULL: CP360_ERR_NULL; N, h, w < 1, border_px negative or not
+ * finite, a field of view outside (0, pi): CP360_ERR_BAD_SHAPE.  render_zoom: cp360_view_render's (lens NULL: CP360_ERR_NULL; ss
+ * given and a view 4 h x 4 w beyond the limits: CP360_ERR_UNSUPPORTED), then lens not 16-byte or ss not 4-byte aligned:
+ * CP360_ERR_ALIGN.  outline_zoom: NULL; N, H, W < 1: CP360_ERR_BAD_SHAPE; an image beyond the limits: CP360_ERR_UNSUPPORTED; lens or
+ * workspace misaligned: CP360_ERR_ALIGN; workspace too small: CP360_ERR_BAD_SHAPE.  spread: NULL; F, hm, wm < 1, window_rad outside
+ * (0, pi], level outside (0, 1): CP360_ERR_BAD_SHAPE; hm wm > 16384 or F > 65535: CP360_ERR_UNSUPPORTED; the workspace as above.
+ * Asynchronous on the stream, no atomics, no host synchronisation, independent of N / F. */
+int cp360_view_lens_host(const double* hfov_rad, int N, int h, int w, double border_px, float* lens);
+int cp360_view_render_zoom(int dtype, const void* frames, const float* R, const float* lens, const int32_t* ss, int N, int H, int W,
+                           int C, void* out, int h, int w, void* stream);
+int cp360_view_outline_zoom(const uint8_t* frames, const float* R, const float* lens, int N, int H, int W, const uint8_t* rgb,
+                            uint8_t* out, void* work, size_t work_bytes, void* stream);
+int cp360_view_spread(const float* maps, const float* dirs, int F, int hm, int wm, double window_rad, double level, float* q,
+                      void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------ K13: shot detection
  * Where the hard cuts of an equirectangular video are: K10 - K12 assume one continuous take.  The signature of a frame is the
  * colour histogram of the whole sphere, every pixel weighted by the solid angle of its row: a camera rotation leaves it nearly
@@ -789,6 +825,14 @@ int cp360_head_footprints(const float* R, const int32_t* offsets, long long N, i
 int cp360_head_agreement(const float* Rc, double cam_hfov_rad, double cam_aspect, const float* R, const int32_t* offsets,
                          long long N, int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
                          long long* uni, void* work, size_t work_bytes, void* stream);
+/* K22c: agreement with a lens per frame for the camera that is judged: cam_lens f32 [F, 4] = K22's (tx, ty, b, 0) per frame (DEVICE
+ * memory, 16-byte aligned; cp360_view_lens_host's table), of which (tx, ty) of frame f take the place of the tangents of
+ * (cam_hfov_rad, cam_aspect); everything else, the viewers' window and the status codes are agreement's (cam_lens NULL:
+ * CP360_ERR_NULL, misaligned: CP360_ERR_ALIGN).  The lens rounds ty as (float)(t h / w), agreement as (float)(t aspect): the same
+ * value where h / w is exact in double and the product rounds alike, as for a power of two. */
+int cp360_head_agreement_zoom(const float* Rc, const float* cam_lens, const float* R, const int32_t* offsets, long long N, int F,
+                              int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
+                              long long* uni, void* work, size_t work_bytes, void* stream);
 
 /* ------------------------------------------------------------------ K18: the supervised loss - K14's KL, CC and NSS with a gradient
  * N maps f32 [N, mh, mw] (a training window's maps, flattened over clips and steps) against ground truth G f32 [N, h, w] on the

@@ -1,0 +1,318 @@
+"""K22 without a GPU: the five exports and their status codes, the lens table against K12's own arithmetic, the spread's
+definition (tests/zoom_restate.py) on synthetic targets, and the host chain of utils/viewport.py (spread_constant,
+zoom_from_spread, smooth_zoom, ViewportPilot.track) against its restatement."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import _lib, ops
+from cp_360_weakly_supervised_saliency_amd.utils import viewport as vp
+from tests import viewport_restate as vr
+from tests import zoom_restate as zr
+
+NULL, BAD_SHAPE, BAD_DTYPE, ALIGN, UNSUPPORTED = -5, -1, -4, -6, -8
+EXPORTS = ['cp360_view_lens_host', 'cp360_view_render_zoom', 'cp360_view_outline_zoom', 'cp360_view_spread',
+           'cp360_head_agreement_zoom']
+
+
+# ----------------------------------------------------------------------------- exports and statuses
+def test_the_five_exports_are_bound_at_version_306():
+    L = _lib.lib()
+    assert L.cp360_version() == 306 == _lib.ABI_VERSION
+    for name in EXPORTS:
+        assert name in _lib.PUBLIC_SYMBOLS and hasattr(L, name)
+
+
+def test_lens_host_statuses():
+    L = _lib.lib()
+    fov = (C.c_double * 2)(1.0, 2.0)
+    out = (C.c_float * 8)()
+    p, o = C.cast(fov, C.c_void_p), C.cast(out, C.c_void_p)
+    assert L.cp360_view_lens_host(None, 2, 9, 16, 0.0, o) == NULL
+    assert L.cp360_view_lens_host(p, 2, 9, 16, 0.0, None) == NULL
+    for N, h, w, border in [(0, 9, 16, 0.0), (2, 0, 16, 0.0), (2, 9, 0, 0.0), (2, 9, 16, -1.0), (2, 9, 16, math.inf),
+                            (2, 9, 16, math.nan)]:
+        assert L.cp360_view_lens_host(p, N, h, w, border, o) == BAD_SHAPE, (N, h, w, border)
+    for bad in (0.0, math.pi, -1.0, 4.0, math.nan, math.inf):
+        fov[1] = bad
+        assert L.cp360_view_lens_host(p, 2, 9, 16, 0.0, o) == BAD_SHAPE, bad
+    fov[1] = 2.0
+    assert L.cp360_view_lens_host(p, 2, 9, 16, 3.0, o) == 0
+
+
+def test_render_zoom_statuses_in_the_documented_order():
+    """cp360_view_render's order - NULL, BAD_SHAPE, BAD_DTYPE, UNSUPPORTED - then ALIGN; every call returns before a launch."""
+    L = _lib.lib()
+    a, b, odd, lens = C.c_void_p(4096), C.c_void_p(8192), C.c_void_p(4098), C.c_void_p(4112)
+    f = L.cp360_view_render_zoom
+    ok = dict(dtype=_lib.F32, frames=a, R=a, lens=lens, ss=None, N=2, H=16, W=32, C=3, out=b, h=9, w=16)
+
+    def call(**kw):
+        v = dict(ok, **kw)
+        return f(v['dtype'], v['frames'], v['R'], v['lens'], v['ss'], v['N'], v['H'], v['W'], v['C'], v['out'], v['h'], v['w'], None)
+
+    for name in ('frames', 'R', 'lens', 'out'):
+        assert call(**{name: None, 'N': 0}) == NULL                    # NULL before BAD_SHAPE
+    for kw in (dict(N=0), dict(H=0), dict(W=-1), dict(h=0), dict(w=0), dict(C=0)):
+        assert call(dtype=7, **kw) == BAD_SHAPE                         # BAD_SHAPE before BAD_DTYPE
+    assert call(dtype=_lib.BF16, C=5) == BAD_DTYPE                      # BAD_DTYPE before UNSUPPORTED
+    assert call(C=5, lens=odd) == UNSUPPORTED                           # UNSUPPORTED before ALIGN
+    assert call(dtype=_lib.U8, C=4) == UNSUPPORTED
+    assert call(N=65536) == UNSUPPORTED and call(H=65536) == UNSUPPORTED and call(h=16384, w=16385) == UNSUPPORTED
+    assert call(h=16384, w=1025, ss=a) == UNSUPPORTED                   # 4 h x 4 w beyond the limits, with ss alone
+    assert call(h=20000, w=1, ss=a) == UNSUPPORTED
+    assert call(out=a, lens=odd) == UNSUPPORTED                         # frames == out: a gather
+    assert call(lens=odd) == ALIGN and call(lens=C.c_void_p(4104)) == ALIGN
+    assert call(ss=odd) == ALIGN
+
+
+def test_outline_spread_and_agreement_statuses():
+    L = _lib.lib()
+    a, b, odd, a8 = C.c_void_p(4096), C.c_void_p(8192), C.c_void_p(4098), C.c_void_p(4104)
+    f = L.cp360_view_outline_zoom
+    for k in range(6):
+        args = [a, a, a, 2, 16, 32, a, b, a, 1 << 20, None]
+        args[[0, 1, 2, 6, 7, 8][k]] = None
+        args[3] = 0
+        assert f(*args) == NULL
+    assert f(a, a, a, 0, 16, 32, a, b, a, 1 << 20, None) == BAD_SHAPE
+    assert f(a, a, a, 2, 0, 32, a, b, a, 1 << 20, None) == BAD_SHAPE
+    assert f(a, a, odd, 65536, 16, 32, a, b, a, 1 << 20, None) == UNSUPPORTED      # before the alignment
+    assert f(a, a, a8, 2, 16, 32, a, b, a, 1 << 20, None) == ALIGN
+    assert f(a, a, a, 2, 16, 32, a, b, odd, 1 << 20, None) == ALIGN
+    assert f(a, a, a, 2, 16, 32, a, b, a, 8, None) == BAD_SHAPE                     # the workspace is too small
+
+    g = L.cp360_view_spread
+    for k in (0, 1, 7, 8):
+        args = [a, a, 0, 14, 28, 0.5, 0.5, b, a, 1 << 20, None]
+        args[k] = None
+        assert g(*args) == NULL
+    for F, hm, wm, win, lev in [(0, 14, 28, 0.5, 0.5), (2, 0, 28, 0.5, 0.5), (2, 14, 0, 0.5, 0.5), (2, 14, 28, 0.0, 0.5),
+                                (2, 14, 28, 3.2, 0.5), (2, 14, 28, math.nan, 0.5), (2, 14, 28, 0.5, 0.0), (2, 14, 28, 0.5, 1.0),
+                                (2, 14, 28, 0.5, math.nan), (2, 129, 128, 0.0, 0.5)]:
+        assert g(a, a, F, hm, wm, win, lev, b, a, 1 << 20, None) == BAD_SHAPE, (F, hm, wm, win, lev)
+    assert g(a, a, 2, 129, 128, 0.5, 0.5, b, odd, 1 << 20, None) == UNSUPPORTED     # hm wm > 16384, before the workspace
+    assert g(a, a, 65536, 14, 28, 0.5, 0.5, b, a, 1 << 20, None) == UNSUPPORTED
+    assert g(a, a, 2, 14, 28, math.pi, 0.5, b, odd, 1 << 20, None) == ALIGN
+    assert g(a, a, 2, 14, 28, 0.5, 0.5, b, a, 8, None) == BAD_SHAPE
+
+    z = L.cp360_head_agreement_zoom
+    ok = [a, a, a, a, 3, 2, 12, 24, 1.5, 0.5, a, a, b, a, 1 << 20, None]
+    for k in (0, 1, 2, 3, 10, 11, 12, 13):
+        args = list(ok)
+        args[k] = None
+        assert z(*args) == NULL, k
+    for k, v in [(5, 0), (6, 0), (7, 0), (4, -1), (8, 0.0), (8, 4.0), (9, 0.0)]:
+        args = list(ok)
+        args[k] = v
+        assert z(*args) == BAD_SHAPE, (k, v)
+    args = list(ok)
+    args[6], args[7], args[1] = 2048, 2048, odd
+    assert z(*args) == UNSUPPORTED                                                  # h w > 2^21, before the alignment
+    for k, v in [(1, a8), (1, odd), (0, odd), (10, odd), (11, C.c_void_p(4100)), (13, a8)]:
+        args = list(ok)
+        args[k] = v
+        assert z(*args) == ALIGN, (k, v)
+    args = list(ok)
+    args[14] = 8
+    assert z(*args) == BAD_SHAPE
+    args = list(ok)
+    args[4], args[2], args[11], args[12] = 0, None, None, None
+    assert z(*args) == 0                                                            # no pairs: valid, nothing launched
+
+
+def test_the_wrappers_refuse_bad_arguments():
+    frames = torch.zeros((2, 16, 32, 3), dtype=torch.uint8)
+    R, lens = torch.zeros((2, 3, 3)), torch.zeros((2, 4))
+    with pytest.raises(RuntimeError):                                   # no CPU fallback
+        ops.viewport_render_zoom(frames, R, (9, 16), lens)
+    with pytest.raises(RuntimeError):
+        ops.viewport_outline_zoom(frames, R, lens)
+    with pytest.raises(RuntimeError):
+        ops.sphere_spread(torch.zeros((2, 14, 28)), torch.zeros((2, 3)))
+    with pytest.raises(RuntimeError):
+        ops.head_agreement_zoom(R, lens, R, torch.zeros(3, dtype=torch.int32), (12, 24), ((9, 16), 100.0),
+                                torch.zeros(12, dtype=torch.int32))
+    for bad in (dict(hfov_deg=0.0), dict(hfov_deg=[60.0, 180.0]), dict(hfov_deg=[[60.0]]), dict(hfov_deg=[]), dict(hw=(0, 16)),
+                dict(border_px=-1.0), dict(border_px=math.nan), dict(hfov_deg=[60.0, 70.0], n=3)):
+        with pytest.raises(ValueError):
+            ops.viewport_lens_host(**dict(dict(hfov_deg=90.0, hw=(9, 16)), **bad))
+    assert ops.viewport_lens_host(90.0, (9, 16), n=5).shape == (5, 4) and ops.viewport_lens_host(90.0, (9, 16)).shape == (1, 4)
+    assert ops.viewport_lens(np.array([50.0, 60.0]), (9, 16), device='cpu').shape == (2, 4)
+    for bad in (dict(zoom_sigmas=0.0), dict(zoom_range_deg=(0.0, 90.0)), dict(zoom_range_deg=(90.0, 60.0)), dict(zoom_window_deg=0.0),
+                dict(zoom_level=1.0), dict(zoom_alpha=1.0)):
+        with pytest.raises(ValueError):
+            vp.ViewportPilot((9, 16), device='cpu', **bad)
+
+
+# ----------------------------------------------------------------------------- the lens
+@pytest.mark.parametrize('hw', [(9, 16), (1, 1), (5, 300)])
+def test_lens_host_is_the_formula_and_k12s_own_floats(hw):
+    h, w = hw
+    fovs = np.array([1.0, 40.0, 60.0, 90.0, 107.3, 120.0, 179.0])
+    for border in (0.0, 1.0, 3.0, 2.5):
+        got = ops.viewport_lens_host(fovs, hw, border)
+        assert got.dtype == np.float32 and got.shape == (len(fovs), 4)
+        for n, v in enumerate(fovs):
+            t = math.tan(0.5 * math.radians(v))
+            want = [np.float32(t), np.float32(t * float(h) / float(w)), np.float32(border * 2.0 * t / float(w)) if border else 0.0, 0.0]
+            assert [float(x) for x in got[n]] == [float(x) for x in want], (v, border)
+            # what the restatement of K12a (view_tangents) and of K12b (outline's thresholds) derives
+            tx, ty = vr.view_tangents(hw, v, np.float32)
+            assert got[n, 0] == tx and got[n, 1] == ty
+            if border:
+                thr = vr.outline(np.eye(3), 4, 8, hw, v, border, np.float32)[4]
+                assert thr[2] == tx - got[n, 2] and thr[3] == ty - got[n, 2]
+        assert np.array_equal(got.view(np.int32), zr.lens(fovs, hw, border).view(np.int32))
+    assert np.array_equal(ops.viewport_lens_host(75.0, hw, 2.0, n=3), np.repeat(ops.viewport_lens_host([75.0], hw, 2.0), 3, 0))
+
+
+# ----------------------------------------------------------------------------- the spread's definition
+def test_spread_constant_agrees_with_numerical_integration():
+    for level in (0.1, 0.3, 0.5, 0.7, 0.9):
+        assert abs(vp.spread_constant(level) - zr.spread_constant_numeric(level)) <= 1e-9, level
+        assert vp.spread_constant(level) == zr.spread_constant(level)
+    assert abs(vp.spread_constant(0.5) - 0.21713) < 5e-6 and abs(math.sqrt(vp.spread_constant(0.5)) - 0.466) < 5e-4
+    for bad in (0.0, 1.0, -0.5, math.nan):
+        with pytest.raises(ValueError):
+            vp.spread_constant(bad)
+
+
+CENTRES = [(20.0, 10.0), (175.0, -30.0), (-100.0, 50.0)]               # generic; next to the seam; at a high latitude
+
+
+@pytest.mark.parametrize('k', range(len(CENTRES)))
+def test_the_restatement_recovers_the_width_of_a_blob(k):
+    """32 x 64, noise of 0.1 of the peak, a second target of the same height 90 degrees away: sqrt(q / c) is the blob's width
+    within 15 % for 10, 15, 20 and 30 degrees, and grows with it."""
+    d = zr.direction(*CENTRES[k])
+    c, widths, got = zr.spread_constant(0.5), (10.0, 15.0, 20.0, 30.0), []
+    for sigma in widths:
+        q = zr.spread(zr.scene(7 + k, 32, 64, d, sigma)[None], d[None])[0]
+        got.append(math.degrees(math.sqrt(q / c)))
+    rel = [g / s - 1.0 for g, s in zip(got, widths)]
+    print('centre %s: recovered %s of %s degrees (%s)' % (CENTRES[k], np.round(got, 2), widths, np.round(rel, 3)))
+    assert all(abs(r) <= 0.15 for r in rel)
+    assert all(a < b for a, b in zip(got[:-1], got[1:]))
+
+
+def test_the_restatement_on_a_constant_map_gives_the_caps_own_value():
+    """Every pixel of the cap counts alike: q = the mean of 1 - cos over the cap = (1 - cos window) / 2.  On 120 x 240 the cap's
+    edge is known to half a pixel's diagonal, delta = sqrt(2) / 2 x 1.5 degrees, and dq / q = delta sin w / (1 - cos w) = delta
+    / tan(w / 2) at the worst: 6.9 % at 30 degrees, 4.5 % at 45.  Measured: 0.43 % and 0.08 %."""
+    delta = math.radians(0.5 * math.sqrt(2.0) * 180.0 / 120.0)
+    for window in (30.0, 45.0):
+        want = 0.5 * (1.0 - math.cos(math.radians(window)))
+        q = zr.spread(np.full((1, 120, 240), 3.0), zr.direction(33.0, 21.0)[None], window)[0]
+        print('constant map, window %g: q = %.6f, the cap %.6f (%+.2e)' % (window, q, want, q / want - 1.0))
+        assert abs(q / want - 1.0) <= delta / math.tan(0.5 * math.radians(window))
+
+
+def test_the_restatements_nan_cases():
+    s = zr.scene(3, 14, 28, zr.direction(10.0, 5.0), 20.0)
+    d = zr.direction(10.0, 5.0)[None]
+    assert np.isfinite(zr.spread(s[None], d))[0]
+    assert np.isnan(zr.spread(np.full((1, 14, 28), np.nan), d))[0]                   # no finite pixel in the cap
+    assert np.isnan(zr.spread(-s[None], d))[0] and np.isnan(zr.spread(np.zeros((1, 14, 28)), d))[0]      # top <= 0
+    assert np.isnan(zr.spread(s[None], np.array([[np.nan, 0.0, 1.0]])))[0] and np.isnan(zr.spread(s[None], np.array([[np.inf, 0, 0]])))[0]
+    holes = s.copy()
+    holes[0, 0], holes[7, 3] = np.nan, np.inf
+    assert np.isfinite(zr.spread(holes[None], d))[0]
+
+
+# ----------------------------------------------------------------------------- the host chain
+def test_zoom_from_spread():
+    c = vp.spread_constant(0.5)
+    q = c * np.deg2rad(np.array([2.0, 8.0, 12.0, 16.0, 25.0, 60.0])) ** 2
+    for hw in [(9, 16), (16, 9), (10, 10), (720, 1280)]:
+        got = vp.zoom_from_spread(q, hw)
+        assert got.dtype == np.float64 and np.allclose(got, zr.zoom_from_spread(q, hw), rtol=0, atol=1e-12)
+        assert got[0] == 40.0 and got[-1] == 110.0                      # the clamps
+        assert np.all(np.diff(got) >= 0.0)
+    # the shorter side spans +- sigmas sigma_b: the vertical half-angle for 16:9, the horizontal one for 9:16
+    half = 2.5 * 12.0
+    wide = vp.zoom_from_spread(q[2:3], (9, 16), range_deg=(1.0, 179.0))[0]
+    tall = vp.zoom_from_spread(q[2:3], (16, 9), range_deg=(1.0, 179.0))[0]
+    assert abs(math.degrees(math.atan(math.tan(math.radians(0.5 * wide)) * 9.0 / 16.0)) - half) <= 1e-9
+    assert abs(0.5 * tall - half) <= 1e-9
+    assert abs(vp.zoom_from_spread([q[2]], (9, 16), sigmas=2.0, range_deg=(1.0, 179.0))[0]
+               - 2.0 * math.degrees(math.atan(math.tan(math.radians(24.0)) * 16.0 / 9.0))) <= 1e-9
+    # sigmas sigma_b is held to 89 degrees; NaN is no target
+    assert vp.zoom_from_spread([50.0], (10, 10), range_deg=(1.0, 179.0))[0] == pytest.approx(178.0, abs=1e-9)
+    got = vp.zoom_from_spread([np.nan, q[1], np.nan], (9, 16), default_deg=77.0)
+    assert got[0] == 77.0 and got[2] == 77.0 and 40.0 < got[1] < 110.0
+    assert vp.zoom_from_spread([0.0], (9, 16))[0] == 40.0
+    for bad in (dict(sigmas=0.0), dict(range_deg=(0.0, 90.0)), dict(range_deg=(100.0, 90.0)), dict(default_deg=180.0), dict(hw=(0, 4))):
+        with pytest.raises(ValueError):
+            vp.zoom_from_spread(**dict(dict(q=q, hw=(9, 16)), **bad))
+
+
+def test_smooth_zoom():
+    rng = np.random.default_rng(22)
+    x = 40.0 + 70.0 * rng.random(17)
+    for alpha in (0.0, 0.5, 0.9):
+        got = vp.smooth_zoom(x, alpha)
+        assert np.allclose(got, zr.smooth_zoom(x, alpha), rtol=0, atol=1e-12)
+        assert np.array_equal(vp.smooth_zoom(x[::-1], alpha), got[::-1])             # symmetric under time reversal: every bit
+        assert np.allclose(vp.smooth_zoom(np.full(9, 63.0), alpha), 63.0, rtol=0, atol=1e-12)      # keeps a constant
+        assert got.min() >= x.min() - 1e-9 and got.max() <= x.max() + 1e-9
+    assert np.allclose(vp.smooth_zoom(x, 0.0), x, rtol=0, atol=1e-12)
+    assert np.ptp(vp.smooth_zoom(x, 0.9)) < 0.5 * np.ptp(x)
+    # zoom multiplies: a geometric ramp of tan(hfov / 2) keeps its midpoint's geometric mean
+    t = np.exp(np.linspace(np.log(0.4), np.log(1.4), 9))
+    mid = vp.smooth_zoom(np.rad2deg(2.0 * np.arctan(t)), 0.8)[4]
+    assert abs(math.tan(math.radians(0.5 * mid)) - t[4]) <= 1e-12
+    # shot by shot
+    cuts = [5, 11]
+    got = vp.smooth_zoom(x, 0.9, cuts)
+    want = np.concatenate([vp.smooth_zoom(x[:5], 0.9), vp.smooth_zoom(x[5:11], 0.9), vp.smooth_zoom(x[11:], 0.9)])
+    assert np.array_equal(got, want) and np.allclose(got, zr.smooth_zoom(x, 0.9, cuts), rtol=0, atol=1e-12)
+    assert not np.allclose(got, vp.smooth_zoom(x, 0.9))
+    for bad in ([0.0, 50.0], [50.0, 180.0], [[50.0]], []):
+        with pytest.raises(ValueError):
+            vp.smooth_zoom(bad)
+    with pytest.raises(ValueError):
+        vp.smooth_zoom(x, 1.0)
+
+
+def _host_pilot(monkeypatch, dirs, q, **kw):
+    """A pilot on the CPU whose two device steps are replaced by given results: what is left of ``track`` is its host chain."""
+    pilot = vp.ViewportPilot((9, 16), 80.0, device='cpu', **kw)
+    monkeypatch.setattr(pilot, 'peaks', lambda maps: torch.from_numpy(dirs.astype(np.float32)))
+    monkeypatch.setattr(ops, 'sphere_spread', lambda maps, d, window_deg, level, work=None: torch.from_numpy(q.astype(np.float32)))
+    monkeypatch.setattr(pilot, '_tab_work', lambda t: None)
+    return pilot
+
+
+def test_track_without_zoom_is_paths_host_chain(monkeypatch):
+    F = 12
+    dirs = np.stack([zr.direction(150.0 + 7.0 * t, 10.0 + 3.0 * t) for t in range(F)])
+    maps = np.zeros((F, 14, 28), np.float32)
+    pilot = _host_pilot(monkeypatch, dirs, np.zeros(F), max_step_deg=6.0)
+    R, hfov = pilot.track(maps)
+    assert R.dtype == torch.float32 and tuple(R.shape) == (F, 3, 3) and hfov.dtype == np.float64
+    assert np.array_equal(hfov, np.full(F, 80.0))
+    assert torch.equal(R, pilot.path(maps))                             # path's cameras, bit for bit
+    want, fov = zr.track(dirs.astype(np.float32), None, (9, 16), 80.0, max_step_deg=6.0, zoom=False)
+    assert np.array_equal(fov, hfov)
+    assert float(np.max(np.abs(R.numpy() - want))) <= 2.0 ** -24 + 1e-12                 # rounded to float32 once
+    host = vp.cameras(vp.smooth_path(dirs.astype(np.float32), 0.85, 6.0))
+    assert float(np.max(np.abs(host - want))) <= 1e-12
+
+
+def test_track_with_zoom_is_the_restated_chain(monkeypatch):
+    F = 12
+    dirs = np.stack([zr.direction(150.0 + 7.0 * t, 10.0) for t in range(F)])
+    q = vp.spread_constant(0.5) * np.deg2rad(np.linspace(8.0, 25.0, F)) ** 2
+    q[4] = np.nan
+    pilot = _host_pilot(monkeypatch, dirs, q, zoom=True)
+    R, hfov = pilot.track(np.zeros((F, 14, 28), np.float32), cuts=[7])
+    assert torch.equal(R, vp.ViewportPilot.path(pilot, np.zeros((F, 14, 28), np.float32), cuts=[7]))
+    q32 = q.astype(np.float32)
+    want = zr.smooth_zoom(zr.zoom_from_spread(q32, (9, 16), default_deg=80.0), 0.9, [7])
+    assert np.allclose(hfov, want, rtol=0, atol=1e-12)
+    assert np.all((hfov >= 40.0) & (hfov <= 110.0)) and hfov[6] > hfov[0]
+    assert hfov[7] > hfov[6] + 10.0                                     # nothing is smoothed across the cut
