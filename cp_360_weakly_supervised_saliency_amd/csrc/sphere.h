@@ -1,5 +1,5 @@
 // The sphere geometry of an equirectangular image, shared by stabilize.hip (K11), viewport.hip (K12), sphere_eval.hip (K14),
-// fixations.hip (K15), headtrack.hip (K17) and, through sphere_eval.hip's resampler, suploss.hip (K18): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
+// fixations.hip (K15), headtrack.hip (K17), egomotion.hip (K23) and, through sphere_eval.hip's resampler, suploss.hip (K18): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
 // of the pixel centres and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry;
 // tests/stabilize_restate.py restates it); and what their kernels and entry points repeat: the von Mises-Fisher term, whether a
 // direction lies in a camera's view, the items of a frame in CSR form, the ordered sum of a 256-thread workgroup, how a caller's

@@ -1489,6 +1489,66 @@ def equirect_rotate(frames, R, out=None, work=None):
     return out
 
 
+# ----------------------------------------------------------------------------- K23: ego-motion from flow (csrc/egomotion.hip)
+def _ego_work(F, H, W, device, work=None):
+    """The workspace of one K23 call: `work` when it is large enough, else a new one (F = 0: the tables alone).  It is never
+    smaller than K11's for the same sizes, so the fit's internal K11 start runs in it first."""
+    return _work(lib().cp360_ego_work_bytes, "ego-motion", F, H, W, device, work)
+
+
+def _ego_flow(flow):
+    if flow.dim() != 4 or flow.shape[3] != 2 or flow.numel() == 0:
+        raise ValueError("flow must be a non-empty [F, H, W, 2], got %s" % (tuple(flow.shape),))
+    _check_buf('flow', flow, torch.float32)
+    return (int(s) for s in flow.shape[:3])
+
+
+def egomotion_fit(flow, R0=None, iters=8, c_min_px=0.25, t_min_px=0.25, min_share=0.25, work=None):
+    """cp360_ego_fit: flow f32 [F, H, W, 2] (K10's convention) -> (R f32 [F, 3, 3], e f32 [F, 3], diag f64 [F, 8]): the camera
+    rotation of every pair (K11's convention) and the unit direction of its translation in frame t's axes, fitted from R0 f32
+    [F, 3, 3] (None: ``rotation_fit`` of the same flow with the same iters and c_min_px).  A pair of which less than min_share of
+    the sphere moves by more than t_min_px at R0 has no translation: e = (0, 0, 0) and R = R0 bit for bit (both thresholds are
+    conventions).  diag = (share, sum of weights, weighted RMS of the epipolar residual in px, lambda_0 / lambda_2 and lambda_1 /
+    lambda_2 of the last scatter matrix, |delta| of the last rotation step, the scale in px, flag: 0 fitted, 1 gated, 2 singular)."""
+    require_gpu(flow, R0, work)
+    F, H, W = _ego_flow(flow)
+    if int(iters) < 1 or not float(c_min_px) > 0.0 or not float(t_min_px) >= 0.0 or not float(min_share) >= 0.0:
+        raise ValueError("iters must be at least 1, c_min_px positive, t_min_px and min_share not negative, got %r, %r, %r, %r"
+                         % (iters, c_min_px, t_min_px, min_share))
+    work = _ego_work(F, H, W, flow.device, work)
+    if R0 is None:
+        R0 = rotation_fit(flow, iters, c_min_px, work=work)[0]
+    _stab_rotations(R0, F)
+    if R0.device != flow.device:
+        raise ValueError("R0 must be on the flow's device")
+    R = torch.empty((F, 3, 3), dtype=torch.float32, device=flow.device)
+    e = torch.empty((F, 3), dtype=torch.float32, device=flow.device)
+    diag = torch.empty((F, 8), dtype=torch.float64, device=flow.device)
+    check(lib().cp360_ego_fit(ptr(flow), ptr(R0), F, H, W, int(iters), float(c_min_px), float(t_min_px), float(min_share), ptr(R),
+                              ptr(e), ptr(diag), ptr(work), work.numel() * 8, stream()))
+    return R, e, diag
+
+
+def egomotion_residual(flow, R, e, out=None, want_mag=False, work=None):
+    """cp360_ego_residual: flow f32 [F, H, W, 2], R f32 [F, 3, 3], e f32 [F, 3] (unit, or exactly 0: ``egomotion_fit``'s) -> res
+    f32 [F, H, W, 2], the part of the flow that the camera motion (R, e) and a static scene cannot explain at any depth, a flow
+    in K10's pixels (e = 0: the de-rotated flow); with want_mag also mag f32 [F, H, W], its size in equator pixels.  A non-finite
+    flow value gives NaN in its pixel."""
+    require_gpu(flow, R, e, out, work)
+    F, H, W = _ego_flow(flow)
+    _stab_rotations(R, F)
+    if e.dim() != 2 or tuple(e.shape) != (F, 3):
+        raise ValueError("e must be [%d, 3], got %s" % (F, tuple(e.shape)))
+    _check_buf('e', e, torch.float32)
+    if R.device != flow.device or e.device != flow.device:
+        raise ValueError("R and e must be on the flow's device")
+    out = _out_for(out, (F, H, W, 2), torch.float32, flow.device, flow)
+    mag = torch.empty((F, H, W), dtype=torch.float32, device=flow.device) if want_mag else None
+    work = _ego_work(0, H, W, flow.device, work)
+    check(lib().cp360_ego_residual(ptr(flow), ptr(R), ptr(e), F, H, W, ptr(out), ptr(mag), ptr(work), work.numel() * 8, stream()))
+    return (out, mag) if want_mag else out
+
+
 # ----------------------------------------------------------------------------- K12: the viewport pilot (csrc/viewport.hip)
 def _view_geometry(hw, hfov_deg):
     h, w = (int(v) for v in hw)

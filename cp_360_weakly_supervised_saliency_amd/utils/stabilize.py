@@ -7,7 +7,9 @@ to the optical flow of every frame pair (K10 + ``ops.rotation_fit``) and removed
 ``Stabilizer`` is the driver: ``rotations`` gives the per-pair and the cumulative camera rotations of F + 1 frames, ``stabilize``
 the frames in the first frame's orientation - the input of ``SaliencyEngine`` and ``FarnebackFlow`` alike - and ``from_frames``
 the flows of the stabilised video, which is what ``utils.npy_io.save_motions`` and ``train_step`` are fed for a moving camera.
-Translation and parallax of the camera stay in the flow.
+Translation and parallax of the camera stay in that flow.  For a camera that travels, ``egomotion`` also fits the direction of
+translation of every pair (K23, csrc/egomotion.hip) and ``independent_flow`` gives the part of the stabilised video's flow that
+no static scene explains under that camera motion: the flow to feed ``save_motions`` / ``train_step`` then (DESIGN.md "K23").
 """
 import numpy as np
 import torch
@@ -57,6 +59,7 @@ class Stabilizer:
         self.iters, self.c_min_px = int(iters), float(c_min_px)
         self.flow = FarnebackFlow(self.hw, device=device)
         self._fit_work = None
+        self._ego_work = None
         self._tab_work = TabWork()
         self.diag = None                         # f64 [F, 4] of the last fit (device)
 
@@ -109,3 +112,40 @@ class Stabilizer:
         from_frames(frames[lo:hi])``."""
         H, W = self.hw
         return self.flow.from_frames(self.stabilize(frames)[0], res=(W, H))
+
+    def _ego(self, flows, cuts, t_min_px, min_share):
+        """K23a on the flows, from K11's fit of them; pairs that straddle a cut get R = I, e = 0 and a diag row of zeros."""
+        F, (H, W) = int(flows.shape[0]), self.hw
+        self._ego_work = ops._ego_work(F, H, W, flows.device, self._ego_work)
+        R, e, diag = ops.egomotion_fit(flows, None, self.iters, self.c_min_px, t_min_px, min_share, work=self._ego_work)
+        if cuts:
+            pairs = torch.tensor([t - 1 for t in cuts], device=R.device)
+            R[pairs] = torch.eye(3, dtype=R.dtype, device=R.device)
+            e[pairs] = 0.0
+            diag[pairs] = 0.0
+        return R, e, diag
+
+    def egomotion(self, frames, cuts=None, t_min_px=0.25, min_share=0.25):
+        """frames u8 [F + 1, h, w, 3] -> (R f32 [F, 3, 3], e f32 [F, 3], diag f64 [F, 8]) on the device: K10 at ``hw``, K11, then
+        K23a (``ops.egomotion_fit``).  e is the unit direction of the camera's translation in the pair's own camera frame (frame
+        t's axes), or 0 where the pair shows no translation; its length is not observable.  A pair that straddles a cut has
+        R = I, e = 0 and a diag row of zeros, as ``rotations`` treats it."""
+        frames = self._frames(frames)
+        cuts = check_cuts(cuts, int(frames.shape[0]))
+        H, W = self.hw
+        flows = self.flow.from_frames(frames, res=(W, H))
+        return self._ego(flows, cuts, t_min_px, min_share)
+
+    def independent_flow(self, frames, cuts=None, t_min_px=0.25, min_share=0.25):
+        """frames u8 [F + 1, h, w, 3] -> (res f32 [F, H, W, 2], e f32 [F, 3], diag f64 [F, 8]) on the device: the frames are
+        stabilised as ``stabilize`` does, K10 runs on the result, K23a fits what rotation is left and the direction of translation
+        to those flows and K23b removes what they explain.  res is what ``npy_io.save_motions`` and ``train_step`` are fed for a
+        travelling camera.  e is in each pair's own stabilised camera frame: the axes of the first frame of its shot.  With
+        ``cuts`` the pair that straddles a cut has e = 0 and its res is the plain flow across the cut, which means nothing: keep
+        it out of training as ``from_frames`` says.  One host synchronisation, that of ``rotations``."""
+        frames = self._frames(frames)
+        cuts = check_cuts(cuts, int(frames.shape[0]))
+        H, W = self.hw
+        flows = self.flow.from_frames(self.stabilize(frames, cuts)[0], res=(W, H))
+        R, e, diag = self._ego(flows, cuts, t_min_px, min_share)
+        return ops.egomotion_residual(flows, R, e, work=self._ego_work), e, diag

@@ -1015,6 +1015,30 @@ int cp360_resnet_forward_multi(cp360_ctx* ctx, const void* const* faces_p3, int 
                                float* const* cam_out, void* workspace, size_t workspace_bytes, void* stream);
 int cp360_resnet_plan_describe_multi(cp360_ctx* ctx, int n_groups, int n_img, int cube_dim, char* buf, size_t cap);
 
+/* ------------------------------------------------------------------ K23: ego-motion from flow, the independent-motion flow
+ * A travelling 360-degree camera: the rotation R and the unit direction of translation e of every frame pair fitted to the flow
+ * K10 computes, and the part of the flow that this camera motion and a static scene cannot explain at any depth.  The
+ * specification is the package's own, DESIGN.md "K23" (7o), restated in float64 in tests/egomotion_restate.py; geometry and
+ * conventions are K11's (R: a scene direction p of frame t's camera is seen at R p in frame t + 1; flow f32 [F, H, W, 2]).
+ * Per pixel p = dir(x, y), g = R^T dir(x + dx, y + dy); a static point at depth d has g = normalize(p - (|T| / d) e).
+ *   fit       R0 f32 [F, 3, 3] (the start, K11's fit) -> R f32 [F, 3, 3], e f32 [F, 3], diag f64 [F, 8] = (share of the sphere
+ *             that moves by more than t_min_px at R0, sum of weights, weighted RMS of the epipolar residual in px, lambda_0 /
+ *             lambda_2 and lambda_1 / lambda_2 of the last scatter matrix, |delta| of the last rotation step, the scale c in
+ *             px, flag: 0 fitted, 1 gated, 2 singular).  share < min_share (no translation), no finite pixel or a scatter
+ *             matrix of rank <= 1: e = (0, 0, 0) and R = R0 bit for bit.  Non-finite flow values weigh 0.  iters >= 1,
+ *             c_min_px > 0, t_min_px >= 0, min_share >= 0 (else CP360_ERR_BAD_SHAPE).
+ *   residual  res f32 [F, H, W, 2] = pix(g) - pix(g*), x wrapped into [-W / 2, W / 2), g* the point of the legal arc from p to -e
+ *             nearest to g (e = 0: g* = p, the de-rotated flow; p an epipole: g* = g); mag f32 [F, H, W] = angle(g, g*) W / 2 pi,
+ *             or NULL when not wanted.  e is a unit vector or exactly 0.  A non-finite flow value: NaN in that pixel.
+ * work: 16-byte aligned device memory of cp360_ego_work_bytes(F, H, W) bytes for fit (never less than cp360_stab_work_bytes(F, H,
+ * W)), of (0, H, W) for residual (K11's tables); 0 = bad or unsupported sizes; too small: CP360_ERR_BAD_SHAPE.  Asynchronous on
+ * the stream, no atomics, bit-reproducible, a pair's result independent of F and of its place in the batch. */
+size_t cp360_ego_work_bytes(int F, int H, int W);
+int cp360_ego_fit(const float* flow, const float* R0, int F, int H, int W, int iters, double c_min_px, double t_min_px,
+                  double min_share, float* R, float* e, double* diag, void* work, size_t work_bytes, void* stream);
+int cp360_ego_residual(const float* flow, const float* R, const float* e, int F, int H, int W, float* res, float* mag, void* work,
+                       size_t work_bytes, void* stream);
+
 /* Diagnostic only (bench.py `held_clock_ghz`): a bare bf16 MFMA loop on pseudo-random operands, n_workgroups x 4 waves, each
  * wave stamped once around `iters` x 16 MFMAs.  stamps: device u64 [n_workgroups * 4][2] = {d s_memtime (shader cycles),
  * d s_memrealtime (100 MHz ticks)} per wave; held clock of a wave = 0.1 GHz * [0] / [1].  A buffer of its own: no output of

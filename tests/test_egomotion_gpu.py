@@ -1,0 +1,289 @@
+"""Ego-motion from flow on the GPU (K23, csrc/egomotion.hip) against the float64 restatement of its specification
+(tests/egomotion_restate.py, whose own claims tests/test_egomotion_cpu.py pins) on the same float32 inputs.
+
+Bounds are K11's rule (tests/test_stabilize_gpu.py): the kernels evaluate every per-pixel term in float32 and every sum in
+float64, the restatement does the same with ``dtype=np.float32``, so d32 = max|restate(f32) - restate(f64)| on an input is the
+size of float32's roundings on it; the device is held to 8 d32, plus 2^-22 of the result's scale where the result is stored as
+float32 or is a sum of float32 terms (R, e and diag: relative to max(1, |value|)).  Horizontal displacements are compared modulo W.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import ops
+from cp_360_weakly_supervised_saliency_amd.utils.stabilize import Stabilizer
+from tests import egomotion_restate as er
+from tests import farneback_restate as fb
+from tests import stabilize_restate as sr
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+FLOOR = 2.0 ** -22
+SIZES = [(16, 32), (33, 66), (120, 240)]
+SMALL = dict(c_min_px=0.05, t_min_px=0.05)          # below 120 x 240 a pixel is many degrees
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def host(*ts):
+    return tuple(t.cpu().numpy().astype(np.float64) for t in ts)
+
+
+def kwargs_for(hw):
+    return SMALL if hw[0] < 100 else {}
+
+
+# ----------------------------------------------------------------------------- fit
+@functools.lru_cache(maxsize=None)
+def fit_case(hw, F=3):
+    """F scene flows (translations of 0.3, 0.5 and 0.4 along three directions, 0.05 px of noise, the first with the mover; one
+    pair: 0.1 with the mover), the float64 fit and d32 of R, e and the diagnostics.  Every pair is well conditioned: lambda_0 /
+    lambda_1 <= 0.05 in the restatement (asserted here, on the CPU)."""
+    H, W = hw
+    dirs = (er.E_TRUE, np.array([-0.5, 0.3, 0.81]) / np.linalg.norm([-0.5, 0.3, 0.81]), np.array([0.1, -0.6, -0.79]) / np.linalg.norm([0.1, -0.6, -0.79]))
+    ts = (0.1,) if F == 1 else (0.3, 0.5, 0.4)[:F]
+    flow = np.stack([er.scene_flow(H, W, t, e_true=dirs[i], noise_px=0.05, seed=300 + i, mover=(2.5, 0.0) if i == 0 else None)[0]
+                     for i, t in enumerate(ts)]).astype(np.float32)
+    want = er.egomotion_fit(flow, **kwargs_for(hw))
+    w32 = er.egomotion_fit(flow, dtype=np.float32, **kwargs_for(hw))
+    assert np.all(want[2][:, 7] == er.OK) and np.all(want[2][:, 3] <= 0.05 * want[2][:, 4])
+    for i in range(len(ts)):
+        assert er.angle_deg(want[1][i], dirs[i]) < (1.0 if hw[0] >= 32 else 3.0)
+    return flow, want, tuple(np.max(np.abs(a - b), 0) for a, b in zip(w32, want))
+
+
+def check_fit(got, want, d32, what):
+    for name, g, w, d in zip(('R', 'e', 'diag'), got, want, d32):
+        err = np.max(np.abs(g - w), 0) if g.ndim == w.ndim else np.abs(g - w)
+        tol = 8 * d + FLOOR * np.maximum(1.0, np.max(np.abs(w), 0))
+        print('%s %s: max err %.2e (d32 %.2e, bound %.2e)' % (what, name, np.max(err), np.max(d), np.max(tol)))
+        assert np.all(err <= tol), (name, err, tol)
+
+
+@pytest.mark.parametrize('hw', SIZES)
+def test_fit_matches_the_restatement(hw):
+    """16 x 32 is one workgroup per pair, 33 x 66 two with a tail and an odd row length, 120 x 240 fifteen partials per pair."""
+    flow, want, d32 = fit_case(hw)
+    R, e, D = ops.egomotion_fit(dev(flow), **kwargs_for(hw))
+    assert R.shape == (3, 3, 3) and R.dtype == torch.float32 and e.shape == (3, 3) and e.dtype == torch.float32
+    assert D.shape == (3, 8) and D.dtype == torch.float64
+    check_fit(host(R, e, D), want, d32, 'fit %s' % (hw,))
+    # other parameters travel: 3 iterations, another floor and gate
+    kw = dict(iters=3, c_min_px=0.1, t_min_px=0.02, min_share=0.1)
+    w64, w32 = er.egomotion_fit(flow, **kw), er.egomotion_fit(flow, dtype=np.float32, **kw)
+    check_fit(host(*ops.egomotion_fit(dev(flow), **kw)), w64, tuple(np.max(np.abs(a - b), 0) for a, b in zip(w32, w64)),
+              'fit %s, 3 iterations' % (hw,))
+
+
+def test_fit_full_size():
+    """One pair at the driver's 480 x 960: 225 partials."""
+    flow, want, d32 = fit_case((480, 960), 1)
+    check_fit(host(*ops.egomotion_fit(dev(flow))), want, d32, 'fit 480 x 960')
+
+
+def same(a, b):
+    return all(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x.view(torch.int64),
+                           y.view(torch.int32) if y.dtype == torch.float32 else y.view(torch.int64)) for x, y in zip(a, b))
+
+
+def test_fit_is_reproducible_and_independent_of_the_batch():
+    hw = (33, 66)
+    kw = kwargs_for(hw)
+    flow = dev(fit_case(hw)[0])
+    full = ops.egomotion_fit(flow, **kw)
+    assert same(full, ops.egomotion_fit(flow, **kw))                                # two runs
+    for p in range(3):                                                              # batched against single pairs
+        assert same(ops.egomotion_fit(flow[p:p + 1], **kw), [t[p:p + 1] for t in full])
+    swapped = ops.egomotion_fit(flow[[2, 1, 0]].contiguous(), **kw)                 # a pair at places 0 and 2
+    assert same([t[2] for t in swapped], [t[0] for t in full]) and same([t[0] for t in swapped], [t[2] for t in full])
+    # a caller's workspace full of NaN
+    n = ops._ego_work(3, hw[0], hw[1], flow.device).numel()
+    work = torch.full((n,), float('nan'), dtype=torch.float64, device=DEV)
+    assert same(full, ops.egomotion_fit(flow, work=work, **kw))
+    # a given R0 against the internal K11 start
+    R0 = ops.rotation_fit(flow, 8, kw['c_min_px'])[0]
+    assert same(full, ops.egomotion_fit(flow, R0=R0, **kw))
+
+
+def test_a_gated_pair_beside_an_ungated_one():
+    hw = (33, 66)
+    kw = kwargs_for(hw)
+    moving = fit_case(hw)[0][1]
+    turning = er.scene_flow(hw[0], hw[1], 0.0, mover=(2.5, 0.0))[0].astype(np.float32)
+    flow = dev(np.stack([turning, moving, turning]))
+    R0 = ops.rotation_fit(flow, 8, kw['c_min_px'])[0]
+    R, e, D = ops.egomotion_fit(flow, **kw)
+    want = er.egomotion_fit(turning, dtype=np.float32, **kw)         # the share is a ratio of sums of the float32 cos phi
+    assert want[2][7] == er.GATED
+    for p in (0, 2):
+        assert float(D[p, 7]) == er.GATED and torch.equal(e[p], torch.zeros(3, device=DEV)) and torch.equal(R[p], R0[p])
+        assert abs(float(D[p, 0]) - want[2][0]) <= 1e-9 and np.array_equal(D[p, 1:6].cpu().numpy(), np.zeros(5))
+    assert same([t[1:2] for t in (R, e, D)], ops.egomotion_fit(flow[1:2], **kw)) and float(D[1, 7]) == er.OK
+    # with the gate open the same pair is fitted
+    assert float(ops.egomotion_fit(flow[:1], min_share=0.0, **kw)[2][0, 7]) == er.OK
+
+
+def test_fit_odd_inputs():
+    hw = (33, 66)
+    kw = kwargs_for(hw)
+    flow = fit_case(hw)[0][:1].copy()
+    bad, bad2 = flow.copy(), flow.copy()
+    for b, v in ((bad, np.nan), (bad2, np.inf)):
+        b[0, 4:11, 7:30] = v
+        b[0, 32, 65], b[0, 5, 40, 0], b[0, 6, 41] = (v, 1.0), -v, (1.0, v)
+    got = ops.egomotion_fit(dev(bad), **kw)
+    assert same(got, ops.egomotion_fit(dev(bad2), **kw))
+    w64, w32 = er.egomotion_fit(bad, **kw), er.egomotion_fit(bad, dtype=np.float32, **kw)
+    check_fit(host(*got), w64, tuple(np.max(np.abs(a - b), 0) for a, b in zip(w32, w64)), 'fit with NaN pixels')
+    # nothing to fit: all NaN, zero flow behind the gate and with the gate open, a single pixel -> e = 0, R = R0 bit for bit
+    turned, eye = dev(sr.rot(sr.AXIS, 0.01).astype(np.float32)[None]), torch.eye(3, device=DEV)[None]
+    for t, R0, kw2, flag in ((torch.full((1, 16, 32, 2), float('nan'), device=DEV), turned, {}, er.SINGULAR),
+                             (torch.zeros(1, 16, 32, 2, device=DEV), turned, {}, er.GATED),
+                             (torch.zeros(1, 16, 32, 2, device=DEV), eye, dict(min_share=0.0), er.SINGULAR),
+                             (torch.ones(1, 1, 1, 2, device=DEV), turned, dict(min_share=0.0), er.SINGULAR)):
+        R, e, D = ops.egomotion_fit(t, R0=R0, **kw2)
+        assert torch.equal(R, R0) and torch.equal(e, torch.zeros(1, 3, device=DEV)) and float(D[0, 1]) == 0.0
+        assert float(D[0, 7]) == flag
+    R, e, D = ops.egomotion_fit(torch.zeros(2, 16, 32, 2, device=DEV))              # the internal start of a zero flow is I exactly
+    assert np.array_equal(R.cpu().numpy(), np.stack([np.eye(3, dtype=np.float32)] * 2)) and not e.any()
+    with pytest.raises(ValueError):
+        ops.egomotion_fit(torch.zeros(1, 16, 32, 2, device=DEV), iters=0)
+    with pytest.raises(ValueError):
+        ops.egomotion_fit(torch.zeros(16, 32, 2, device=DEV))
+    with pytest.raises(ValueError):
+        ops.egomotion_fit(torch.zeros(1, 16, 32, 2, device=DEV), R0=torch.eye(3, device=DEV)[None].repeat(2, 1, 1))
+
+
+# ----------------------------------------------------------------------------- the independent-motion flow
+def circular(d, W):
+    d = d.copy()
+    d[..., 0] = np.mod(d[..., 0] + 0.5 * W, W) - 0.5 * W
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def residual_case(hw):
+    """Seven (flow, R, e): e = 0; an epipole on a pixel centre; an e next to a pole; a 40-degree turn across the seam; every pixel
+    3 degrees toward +e (clamped at 0) and 20 degrees away from it (clamped at alpha_max around -e); NaN and infinite pixels."""
+    H, W = hw
+    f32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+    unit = lambda v: f32(np.asarray(v, np.float64) / np.linalg.norm(v))
+    scene = er.scene_flow(H, W, 0.3, noise_px=0.05, seed=400, mover=(2.5, 0.0))[0]
+    small, seam = sr.rot(sr.AXIS, er.TURN), sr.rot((0, 1, 0), np.deg2rad(40.0))
+    across = er.scene_flow(H, W, 0.3, R_true=seam, noise_px=0.05, seed=401)[0]
+    e_px = f32(sr.dir_(W // 2 + 3, H // 3, H, W))
+    holes = scene.copy()
+    holes[2:5, 3:9] = np.nan
+    holes[H - 1, W - 1, 0], holes[H // 2, 0, 1], holes[0, 7] = np.inf, -np.inf, (np.nan, 1.0)
+    cases = [(scene, small, np.zeros(3)), (np.full((H, W, 2), 0.7), np.eye(3), e_px), (scene, small, unit([0.02, 1.0, 0.01])),
+             (across, seam, unit(er.E_TRUE)), (er.arc_flow(H, W, unit(er.E_TRUE), -3.0)[0], np.eye(3), unit(er.E_TRUE)),
+             (er.arc_flow(H, W, unit(er.E_TRUE), 20.0)[0], np.eye(3), unit(er.E_TRUE)), (holes, small, unit(er.E_TRUE))]
+    flow = np.stack([c[0] for c in cases]).astype(np.float32)
+    R, e = np.stack([c[1] for c in cases]), np.stack([c[2] for c in cases])
+    res64, mag64 = er.egomotion_residual(flow, R, e)
+    res32, mag32 = er.egomotion_residual(flow, R, e, np.float32)
+    with np.errstate(invalid='ignore'):
+        d_res = np.nanmax(np.abs(circular(res32 - res64, W)), axis=(1, 2, 3))
+        d_mag = np.nanmax(np.abs(mag32 - mag64), axis=(1, 2))
+    # the cases do what they are for
+    assert np.array_equal(res64[1, H // 3, W // 2 + 3], [0, 0]) and np.nanmax(mag64[4]) > 2.9 * W / 360 and np.nanmin(mag64[5]) < 1e-6
+    assert 0 < np.nanmax(mag64[5]) < 20.0 * W / 360 and np.isnan(res64[6]).any() and not np.isnan(res64[:6]).any()
+    x_to = np.arange(W)[None, :] + across[..., 0]
+    assert ((x_to < -0.5) | (x_to >= W - 0.5)).any()
+    return flow, R.astype(np.float32), e.astype(np.float32), res64, mag64, d_res, d_mag
+
+
+@pytest.mark.parametrize('hw', SIZES)
+def test_residual_matches_the_restatement(hw):
+    H, W = hw
+    flow, R, e, res64, mag64, d_res, d_mag = residual_case(hw)
+    res, mag = ops.egomotion_residual(dev(flow), dev(R), dev(e), want_mag=True)
+    assert res.shape == flow.shape and res.dtype == torch.float32 and mag.shape == flow.shape[:3] and mag.dtype == torch.float32
+    res, mag = host(res, mag)
+    assert np.array_equal(np.isnan(res), np.isnan(res64)) and np.array_equal(np.isnan(mag), np.isnan(mag64))
+    assert np.all(res[..., 0][~np.isnan(res[..., 0])] >= -W / 2) and np.all(res[..., 0][~np.isnan(res[..., 0])] <= W / 2)
+    with np.errstate(invalid='ignore'):
+        e_res = np.nanmax(np.abs(circular(res - res64, W)), axis=(1, 2, 3))
+        e_mag = np.nanmax(np.abs(mag - mag64), axis=(1, 2))
+    print('residual %s: res err %s (d32 %s); mag err %s (d32 %s)' % (hw, e_res, d_res, e_mag, d_mag))
+    assert np.all(e_res <= 8 * d_res) and np.all(e_mag <= 8 * d_mag)
+    # out= is used, and mag changes no bit of res
+    out = torch.empty(flow.shape, dtype=torch.float32, device=DEV)
+    got = ops.egomotion_residual(dev(flow), dev(R), dev(e), out=out)
+    assert got is out and np.array_equal(out.cpu().numpy().view(np.int32), res.astype(np.float32).view(np.int32))
+    with pytest.raises(ValueError):
+        ops.egomotion_residual(dev(flow), dev(R), dev(e)[:, :2].contiguous())
+    with pytest.raises(ValueError):
+        ops.egomotion_residual(dev(flow), dev(R), dev(e), out=out[:1])
+
+
+# ----------------------------------------------------------------------------- the driver
+E2E_HW = (64, 128)
+E2E_GATE = dict(t_min_px=0.1)
+E2E_T, E2E_FADE = 0.4, 15.0            # the camera's step and the distance at which the ground's texture has faded by half
+
+
+@functools.lru_cache(maxsize=None)
+def travelling_camera():
+    """Three frames of egomotion_restate.render_travelling: (frames u8 [3, 64, 128, 3], R_true [2, 3, 3], e_true [2, 3])."""
+    return er.render_travelling(E2E_HW, 3, E2E_T, E2E_FADE)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_reference():
+    """The float64 chain farneback_restate -> stabilize_restate -> egomotion_restate on the same frames."""
+    flows = fb.farneback(fb.gray_from_rgb(travelling_camera()[0]))
+    return er.egomotion_fit(flows, **E2E_GATE)
+
+
+def test_driver_recovers_the_camera():
+    """Stabilizer.egomotion against the truth: the device's errors of e and R are at most twice those of the float64 chain on the
+    same frames (the margin covers Farneback's float32 noise).  Measured on an MI355X: e within 3.605 / 6.389 degrees, R within
+    0.1763 / 0.1398 px-equivalents, the float64 chain the same to these digits - the error is Farneback's at 64 x 128."""
+    frames, R_true, e_true = travelling_camera()
+    Rc, ec, Dc = chain_reference()
+    st = Stabilizer(E2E_HW)
+    before = st.rotations(frames)
+    R, e, D = st.egomotion(frames, **E2E_GATE)
+    assert R.shape == (2, 3, 3) and e.shape == (2, 3) and D.shape == (2, 8) and R.is_cuda and e.is_cuda and D.is_cuda
+    R, e, D = host(R, e, D)
+    W = E2E_HW[1]
+    for p in range(2):
+        assert D[p, 7] == er.OK and Dc[p, 7] == er.OK
+        ee, ec_err = er.angle_deg(e[p], e_true[p]), er.angle_deg(ec[p], e_true[p])
+        re, rc_err = sr.angle_between(R[p], R_true[p]) * W / (2 * np.pi), sr.angle_between(Rc[p], R_true[p]) * W / (2 * np.pi)
+        print('pair %d: e error %.3f deg (float64 chain %.3f deg); R error %.4f px (float64 chain %.4f px)' % (p, ee, ec_err, re, rc_err))
+        assert ee <= 2 * ec_err and re <= 2 * rc_err
+        assert ec_err < 10.0                                 # the chain itself finds the direction of travel
+    # the earlier methods return the bits they returned before
+    after = st.rotations(frames)
+    assert same(before, after)
+    R11, D11 = ops.rotation_fit(st.flow.from_frames(dev(frames), res=(W, E2E_HW[0])))
+    assert torch.equal(after[0], R11)
+
+
+def test_driver_independent_flow_and_cuts():
+    frames = travelling_camera()[0]
+    st = Stabilizer(E2E_HW)
+    S0, C0 = st.stabilize(frames)
+    res, e, D = st.independent_flow(frames, **E2E_GATE)
+    assert res.shape == (2, 64, 128, 2) and res.dtype == torch.float32 and res.is_cuda and e.shape == (2, 3) and D.shape == (2, 8)
+    flows = st.from_frames(frames)
+    w = torch.from_numpy(sr.tables(64, 128, np.float32)[2]).to(DEV)[None, :, None, None]
+    print('weighted mean |flow|: stabilised %.4f px, independent %.4f px' % (float((w * flows.abs()).mean()), float((w * res.abs()).mean())))
+    assert float((w * res.abs()).mean()) < 0.5 * float((w * flows.abs()).mean())    # the parallax is gone from the flow
+    # it is K23a and K23b on the stabilised video's flows
+    R2, e2, D2 = ops.egomotion_fit(flows, t_min_px=E2E_GATE['t_min_px'])
+    assert torch.equal(e, e2) and torch.equal(D, D2) and torch.equal(res, ops.egomotion_residual(flows, R2, e2))
+    # a cut before frame 1: the pair that straddles it has e = 0, R = I; the other pair is what its own shot gives
+    res_c, e_c, D_c = st.independent_flow(frames, cuts=[1], **E2E_GATE)
+    assert not e_c[0].any() and not D_c[0].any() and float(D_c[1, 7]) == er.OK and float(e_c[1].norm()) > 0.99
+    R_c, e_c2, _ = st.egomotion(frames, cuts=[1], **E2E_GATE)
+    assert torch.equal(R_c[0], torch.eye(3, device=DEV)) and not e_c2[0].any()
+    # stabilize is untouched by all this
+    S1, C1 = st.stabilize(frames)
+    assert torch.equal(S0, S1) and torch.equal(C0, C1)
