@@ -88,6 +88,8 @@ PUBLIC_SYMBOLS = [
     'cp360_view_lens_host', 'cp360_view_render_zoom', 'cp360_view_outline_zoom', 'cp360_view_spread', 'cp360_head_agreement_zoom',
     # K23: ego-motion from flow, the independent-motion flow
     'cp360_ego_work_bytes', 'cp360_ego_fit', 'cp360_ego_residual',
+    # K24: viewport-adaptive streaming
+    'cp360_view_incidence', 'cp360_tile_incidence', 'cp360_view_expect', 'cp360_view_quality_work_bytes', 'cp360_view_quality',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -344,6 +346,12 @@ def lib():
     L.cp360_ego_work_bytes.argtypes = [i, i, i]
     L.cp360_ego_fit.argtypes = [vp, vp, i, i, i, i, dbl, dbl, dbl, vp, vp, vp, vp, sz, vp]
     L.cp360_ego_residual.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.cp360_view_incidence.argtypes = [vp, i, i, i, dbl, dbl, vp, vp, sz, vp]
+    L.cp360_tile_incidence.argtypes = [vp, i, i, i, i, i, vp, vp]
+    L.cp360_view_expect.argtypes = [vp, i, i, i, vp, vp, i, vp, vp, vp]
+    L.cp360_view_quality_work_bytes.restype = sz
+    L.cp360_view_quality_work_bytes.argtypes = [i, i]
+    L.cp360_view_quality.argtypes = [vp, vp, C.c_longlong, i, i, i, dbl, dbl, vp, vp, i, i, i, vp, vp, sz, vp]
     L.cp360_sup_loss_work_bytes.restype = sz
     L.cp360_sup_loss_work_bytes.argtypes = [i, i, i, i, i]
     L.cp360_sup_loss_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, vp, vp, sz, vp]

@@ -31,7 +31,6 @@ constexpr int kHeadChunk = 64;               // K17a: cameras staged at a time, 
 static_assert(kHeadChunk <= 64, "K17a counts the finite cameras in the one wave that stages them");
 constexpr int kHeadPairs = 4;                // K17b: pairs (waves) per workgroup
 constexpr int kMaxWeight = 1024;
-constexpr double kPi = 3.14159265358979323846;
 
 // ------------------------------------------------------------------ K17a: footprints
 // grid (ceil(P / 256), F), 256 threads
@@ -146,15 +145,6 @@ __global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_zoom_kernel(co
 }
 
 // ------------------------------------------------------------------ host side
-// the two tangents of a view, rounded once; false for a view that is refused
-bool head_tangents(double hfov_rad, double aspect, float* tx, float* ty) {
-    if (!(hfov_rad > 0.0) || !(hfov_rad < kPi) || !(aspect > 0.0)) return false;
-    const double t = tan(0.5 * hfov_rad);
-    *tx = (float)t;
-    *ty = (float)(t * aspect);
-    return isfinite(*tx) && isfinite(*ty);
-}
-
 // the viewers: R may be NULL when there are none
 int head_cameras(const float* R, const int32_t* offsets, long long N, int F, int h, int w) {
     if (!offsets || (!R && N > 0)) return CP360_ERR_NULL;

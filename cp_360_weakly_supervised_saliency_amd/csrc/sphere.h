@@ -1,5 +1,5 @@
 // The sphere geometry of an equirectangular image, shared by stabilize.hip (K11), viewport.hip (K12), sphere_eval.hip (K14),
-// fixations.hip (K15), headtrack.hip (K17), egomotion.hip (K23) and, through sphere_eval.hip's resampler, suploss.hip (K18): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
+// fixations.hip (K15), headtrack.hip (K17), egomotion.hip (K23), streaming.hip (K24) and, through sphere_eval.hip's resampler, suploss.hip (K18): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
 // of the pixel centres and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry;
 // tests/stabilize_restate.py restates it); and what their kernels and entry points repeat: the von Mises-Fisher term, whether a
 // direction lies in a camera's view, the items of a frame in CSR form, the ordered sum of a 256-thread workgroup, how a caller's
@@ -207,6 +207,16 @@ int launch_tables(void* work, int H, int W, hipStream_t s, SphereTabs* t) {
 int open_tabs(void* work, size_t work_bytes, size_t need, int H, int W, hipStream_t s, SphereTabs* t) {
     const int st = check_work(work, work_bytes, need);
     return st != CP360_OK ? st : launch_tables(work, H, W, s, t);
+}
+
+// the two tangents of a view (K17, K24), tx = tan(hfov / 2), ty = tx aspect in double, each rounded once; false for a view that
+// is refused
+bool head_tangents(double hfov_rad, double aspect, float* tx, float* ty) {
+    if (!(hfov_rad > 0.0) || !(hfov_rad < 3.14159265358979323846) || !(aspect > 0.0)) return false;
+    const double t = tan(0.5 * hfov_rad);
+    *tx = (float)t;
+    *ty = (float)(t * aspect);
+    return isfinite(*tx) && isfinite(*ty);
 }
 
 // f(T(), integral_constant<int, C>()) for the pixel types of K11c and K12a: u8 x 3 or f32 x 1 .. 4 (the caller has checked)

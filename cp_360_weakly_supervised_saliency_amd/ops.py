@@ -2228,6 +2228,130 @@ def head_agreement_zoom(Rc, cam_lens, R, offsets, hw, view, weights, work=None):
     return inter, uni
 
 
+# ----------------------------------------------------------------------------- K24: viewport-adaptive streaming (csrc/streaming.hip)
+STREAM_MAX_SOURCE = 4096                                               # S = hs ws and T = rows cols
+STREAM_MAX_LEVELS = 8
+
+
+def _stream_grid(hw, tiles=None):
+    """The grid (h, w) and the tiles (rows, cols) on it -> (h, w, rows, cols); without tiles rows = cols = 1."""
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1 or h * w > 1 << 21:
+        raise ValueError("the grid must be between 1 x 1 and 2^21 pixels, got %d x %d" % (h, w))
+    rows, cols = (1, 1) if tiles is None else (int(v) for v in tiles)
+    if not (1 <= rows <= h and 1 <= cols <= w and rows * cols <= STREAM_MAX_SOURCE):
+        raise ValueError("tiles must be 1 .. %d rows and 1 .. %d columns, at most %d in all, got %d x %d"
+                         % (h, w, STREAM_MAX_SOURCE, rows, cols))
+    return h, w, rows, cols
+
+
+def _stream_bits(name, bits, S, P, device):
+    """A bit matrix of S rows over P elements: int32 [S, ceil(P / 32)], the u32 words' bit patterns."""
+    if bits.dim() != 2 or tuple(bits.shape) != (S, (P + 31) // 32) or bits.device != device:
+        raise ValueError("%s must be int32 [%d, %d] on the device of the other operands, got %s"
+                         % (name, S, (P + 31) // 32, tuple(bits.shape)))
+    _check_buf(name, bits, torch.int32)
+
+
+def _stream_out(out, shape, dtype, device, *srcs):
+    """A new destination, or the caller's when it has this shape and dtype on this device and shares no byte with an operand."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise ValueError("out must be %s %s on the operands' device, got %s" % (dtype, tuple(shape), tuple(out.shape)))
+    _check_buf('out', out, dtype)
+    if any(_shares_bytes(out, s) for s in srcs if s.numel() and out.numel()):
+        raise ValueError("out must not share memory with an operand")
+    return out
+
+
+def view_quality_work(h, w, device, work=None):
+    """The workspace of the streaming ops on an h x w grid (the grid's tables and the tile of every column and row; it also
+    serves ``view_incidence``): `work` when it is large enough, else a new one."""
+    return _work(lambda F, hh, ww: lib().cp360_view_quality_work_bytes(hh, ww), "streaming", 0, h, w, device, work, " (h w <= 2^21)")
+
+
+def view_incidence(cams, hw, view_hw, hfov_deg, work=None, out=None):
+    """cp360_view_incidence: cams f32 [S, 3, 3] (camera-to-world, columns forward / up / right; S <= 4096), each with the view
+    (view_hw, hfov_deg) -> int32 [S, ceil(h w / 32)]: bit i % 32 of word i / 32 of row j says whether grid pixel i is in the view
+    of cams[j], ``head_footprints``' decision bit for bit; the bits past h w are 0.  The int32 hold the u32 words' bit patterns."""
+    require_gpu(cams, work, out)
+    if cams.dim() != 3 or tuple(cams.shape[1:]) != (3, 3) or not 1 <= cams.shape[0] <= STREAM_MAX_SOURCE:
+        raise ValueError("cams must be float32 [S, 3, 3] with 1 <= S <= %d, got %s" % (STREAM_MAX_SOURCE, tuple(cams.shape)))
+    _check_buf('cams', cams, torch.float32)
+    h, w, _, _ = _stream_grid(hw)
+    hfov, aspect = _head_view(view_hw, hfov_deg)
+    S = int(cams.shape[0])
+    work = head_work(h, w, cams.device, work)
+    out = _stream_out(out, (S, (h * w + 31) // 32), torch.int32, cams.device, cams)
+    check(lib().cp360_view_incidence(ptr(cams), S, h, w, hfov, aspect, ptr(out), ptr(work), work.numel() * 8, stream()))
+    return out
+
+
+def tile_incidence(inc, hw, tiles, out=None):
+    """cp360_tile_incidence: inc int32 [S, ceil(h w / 32)] (``view_incidence``), tiles = (rows, cols) on the grid (pixel (x, y) in
+    tile ((y rows) / h) cols + (x cols) / w) -> int32 [S, ceil(rows cols / 32)]: bit t of row j is the OR of inc[j, i] over the
+    pixels of tile t."""
+    require_gpu(inc, out)
+    h, w, rows, cols = _stream_grid(hw, tiles)
+    if inc.dim() != 2 or not 1 <= inc.shape[0] <= STREAM_MAX_SOURCE:
+        raise ValueError("inc must be int32 [S, %d] with 1 <= S <= %d, got %s" % ((h * w + 31) // 32, STREAM_MAX_SOURCE, tuple(inc.shape)))
+    S = int(inc.shape[0])
+    _stream_bits('inc', inc, S, h * w, inc.device)
+    out = _stream_out(out, (S, (rows * cols + 31) // 32), torch.int32, inc.device, inc)
+    check(lib().cp360_tile_incidence(ptr(inc), S, h, w, rows, cols, ptr(out), stream()))
+    return out
+
+
+def view_expect(sal, weights, bits, P, out=None):
+    """cp360_view_expect: sal f32 [F, hs, ws] (F = 0 is valid), weights int32 [hs] (``sphere_eval_weights``), bits int32 [hs ws,
+    ceil(P / 32)] (``view_incidence`` with P = h w, or ``tile_incidence`` with P = rows cols) -> (out f32 [F, P], total f32 [F]):
+    with m[f, j] = sal[f, j] (float)a_y where sal[f, j] > 0 and finite, else 0, out[f, i] = (the sum of m[f, j] over the j whose
+    bit i is set) / total[f], total[f] the sum over every j, both summed in float32 for j ascending; 0 where total is 0.  On the
+    device, without a synchronisation; a frame's numbers do not depend on F or on its place in the batch."""
+    require_gpu(sal, weights, bits, out)
+    if sal.dim() != 3 or sal.shape[1] < 1 or sal.shape[2] < 1 or sal.shape[1] * sal.shape[2] > STREAM_MAX_SOURCE or sal.shape[0] > 65535:
+        raise ValueError("sal must be float32 [F, hs, ws] with F <= 65535 and 1 <= hs ws <= %d, got %s" % (STREAM_MAX_SOURCE, tuple(sal.shape)))
+    _check_buf('sal', sal, torch.float32)
+    F, hs, ws = (int(s) for s in sal.shape)
+    P = int(P)
+    if not 1 <= P <= 1 << 21:
+        raise ValueError("P must be 1 .. 2^21, got %d" % P)
+    if tuple(weights.shape) != (hs,) or weights.device != sal.device:
+        raise ValueError("weights must be int32 [%d] on sal's device" % hs)
+    _check_buf('weights', weights, torch.int32)
+    _stream_bits('bits', bits, hs * ws, P, sal.device)
+    out = _stream_out(out, (F, P), torch.float32, sal.device, sal, bits, weights)
+    total = torch.empty((F,), dtype=torch.float32, device=sal.device)
+    check(lib().cp360_view_expect(ptr(sal), F, hs, ws, ptr(weights), ptr(bits), P, ptr(out), ptr(total), stream()))
+    return out, total
+
+
+def view_quality(R, offsets, hw, view, weights, levels, tiles, L, work=None):
+    """cp360_view_quality: the viewers R f32 [N, 3, 3], offsets int32 [F + 1] of ``head_footprints`` with view = ((h_v, w_v),
+    hfov_deg), weights int32 [h], levels uint8 [F, rows cols] (the quality level of every tile in every frame; a value >= L counts
+    as L - 1), tiles = (rows, cols), 1 <= L <= 8 -> qarea int64 [N, L]: the weighted pixels in viewer k's window whose tile has
+    level l in its frame.  Exact integers, on the device, without a synchronisation; a non-finite viewer gets zeros."""
+    require_gpu(R, offsets, weights, levels, work)
+    N, F, _, _ = _head_cameras(R, offsets, hw)
+    h, w, rows, cols = _stream_grid(hw, tiles)
+    L = int(L)
+    if not 1 <= L <= STREAM_MAX_LEVELS:
+        raise ValueError("L must be 1 .. %d, got %d" % (STREAM_MAX_LEVELS, L))
+    if tuple(weights.shape) != (h,) or weights.device != R.device:
+        raise ValueError("weights must be int32 [%d] on R's device" % h)
+    _check_buf('weights', weights, torch.int32)
+    if tuple(levels.shape) != (F, rows * cols) or levels.device != R.device:
+        raise ValueError("levels must be uint8 [%d, %d] on R's device, got %s" % (F, rows * cols, tuple(levels.shape)))
+    _check_buf('levels', levels, torch.uint8)
+    hfov, aspect = _head_view(*view)
+    work = view_quality_work(h, w, R.device, work)
+    qarea = torch.empty((N, L), dtype=torch.int64, device=R.device)
+    check(lib().cp360_view_quality(ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights), ptr(levels), rows, cols, L, ptr(qarea),
+                                   ptr(work), work.numel() * 8, stream()))
+    return qarea
+
+
 # ----------------------------------------------------------------------------- K18: the supervised loss (csrc/suploss.hip)
 SUP_LOSS_STATS = 16                                                    # CP360_SUP_LOSS_STATS
 

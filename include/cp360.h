@@ -1039,6 +1039,44 @@ int cp360_ego_fit(const float* flow, const float* R0, int F, int H, int W, int i
 int cp360_ego_residual(const float* flow, const float* R, const float* e, int F, int H, int W, float* res, float* mag, void* work,
                        size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K24: viewport-adaptive streaming
+ * From a saliency map to "how likely is this pixel, or this tile, to be in somebody's window", and the quality that a tile plan
+ * delivers to the viewers who watched.  The specification is the package's own, DESIGN.md "K24" (7p), restated in
+ * tests/streaming_restate.py.  Source pixel j of an hs x ws map (S = hs ws <= 4096) stands for a viewer whose camera is cams[j]
+ * (f32 [S, 9], K12's convention, built on the host: utils/streaming.py); the window is K17's (hfov_rad, aspect), its tangents
+ * rounded as K17's; the grid has h x w pixels (P = h w <= 2^21) in rows x cols tiles (T = rows cols <= 4096, rows <= h, cols <= w),
+ * pixel (x, y) in tile ((y rows) / h) cols + (x cols) / w.  All DEVICE memory.
+ *
+ *   view_incidence  inc u32 [S, ceil(P / 32)]: bit i % 32 of word i / 32 of row j = whether dir(i) is inside the view of cams[j],
+ *                   cp360_head_footprints' decision bit for bit (a non-finite camera: an empty row); the bits past P are 0.
+ *                   work: cp360_fix_work_bytes(0, h, w) bytes, K11's tables.
+ *   tile_incidence  tinc u32 [S, ceil(T / 32)]: bit t of row j = the OR of inc[j, i] over the pixels of tile t.
+ *   view_expect     sal f32 [F, S], weights int32 [hs] as for cp360_seval_scores (clamped to 0 .. 1024), bits u32 [S, ceil(P / 32)]
+ *                   (inc, or tinc with P = T) -> out f32 [F, P], total f32 [F].  m[f, j] = sal[f, j] (float)a_y(j / ws) where
+ *                   sal[f, j] > 0 and finite, else 0; acc = 0, then for j = 0 .. S - 1 ascending, acc = acc + m[f, j] where bit
+ *                   (j, i) is set, in f32; total[f] the same sum over every j; out[f, i] = total > 0 ? acc / total : 0.  The order
+ *                   is the definition: a frame's numbers are bit-identical between runs, whatever F and its place in the batch.
+ *   view_quality    R, offsets, N: K17's viewers in CSR form; levels u8 [F, T], 1 <= L <= 8 (a value >= L counts as L - 1) ->
+ *                   qarea int64 [N, L]: for viewer k of frame f, qarea[k, l] = the sum of a_y over the pixels inside its view
+ *                   whose tile has level l in frame f.  Exact integers; sum_l qarea[k, l] is cp360_head_agreement's uni of the
+ *                   viewer against itself.  A non-finite viewer: zeros.  work: cp360_view_quality_work_bytes(h, w) bytes (K11's
+ *                   tables and the tile of every column and row; 0 = bad or unsupported sizes).
+ * Status codes, in this order and before any launch: a NULL pointer (sal, out, total when F = 0 and R, levels, qarea when N = 0 may
+ * be NULL): CP360_ERR_NULL; a size < 1 (F = 0 is valid for view_expect, F = 0 with N = 0 for view_quality), N < 0, rows > h,
+ * cols > w, L outside 1 .. 8 or a window that cp360_head_footprints refuses: CP360_ERR_BAD_SHAPE; S > 4096, T > 4096, P > 2^21,
+ * F > 65535 or N >= 2^31: CP360_ERR_UNSUPPORTED; a pointer not 4-byte (qarea 8-byte, work 16-byte) aligned: CP360_ERR_ALIGN; a
+ * workspace that is too small: CP360_ERR_BAD_SHAPE.  N = 0 and F = 0 launch nothing.  Asynchronous on the stream, no atomics, no
+ * host synchronisation. */
+int cp360_view_incidence(const float* cams, int S, int h, int w, double hfov_rad, double aspect, uint32_t* inc, void* work,
+                         size_t work_bytes, void* stream);
+int cp360_tile_incidence(const uint32_t* inc, int S, int h, int w, int rows, int cols, uint32_t* tinc, void* stream);
+int cp360_view_expect(const float* sal, int F, int hs, int ws, const int32_t* weights, const uint32_t* bits, int P, float* out,
+                      float* total, void* stream);
+size_t cp360_view_quality_work_bytes(int h, int w);
+int cp360_view_quality(const float* R, const int32_t* offsets, long long N, int F, int h, int w, double hfov_rad, double aspect,
+                       const int32_t* weights, const uint8_t* levels, int rows, int cols, int L, long long* qarea, void* work,
+                       size_t work_bytes, void* stream);
+
 /* Diagnostic only (bench.py `held_clock_ghz`): a bare bf16 MFMA loop on pseudo-random operands, n_workgroups x 4 waves, each
  * wave stamped once around `iters` x 16 MFMAs.  stamps: device u64 [n_workgroups * 4][2] = {d s_memtime (shader cycles),
  * d s_memrealtime (100 MHz ticks)} per wave; held clock of a wave = 0.1 GHz * [0] / [1].  A buffer of its own: no output of

@@ -1,0 +1,341 @@
+"""GPU tests of viewport-adaptive streaming (K24, csrc/streaming.hip) against tests/streaming_restate.py: the incidence within
+what float64 leaves float32 to decide (the cap on that is asserted for every case, here and in tests/test_streaming_cpu.py) and
+equal to K17a's decision exactly, the expectation bit for bit against the ordered float32 restatement on the kernel's own bits
+and within the derived bound against float64, the delivered quality between its bounds and exactly against K17b, the launch paths,
+and the planner end to end on K17's scene."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import _lib, ops
+from cp_360_weakly_supervised_saliency_amd.utils import eval_sphere, headtrack, streaming
+from tests import headtrack_restate as hr
+from tests import streaming_restate as sr
+from tests import viewport_restate as vr
+
+pytestmark = pytest.mark.gpu
+NAMES = sorted(sr.CASES)
+
+
+def dev(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return t if dtype is None else t.to(dtype)
+
+
+def bits_equal(a, b):
+    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_bits(name):
+    """The kernels' incidence of a case, once: (inc, tinc) int32 tensors on the device and the same as bool [S, P], [S, T]."""
+    c = sr.case(name)
+    inc = ops.view_incidence(dev(c['cams']), c['grid'], c['view'][0], c['view'][1])
+    tinc = ops.tile_incidence(inc, c['grid'], c['tiles'])
+    P, T = c['grid'][0] * c['grid'][1], c['tiles'][0] * c['tiles'][1]
+    return inc, tinc, sr.unpack_bits(inc.cpu().numpy(), P), sr.unpack_bits(tinc.cpu().numpy(), T)
+
+
+def maps_for(c, seed):
+    """float32 [6, hs, ws]: three random positive frames, one with NaN, inf, negative and zero entries, an all-zero frame and a
+    frame whose mass sits in the first and the last source pixel."""
+    sal = np.concatenate([sr.random_maps(seed, 4, c['src']), np.zeros((2,) + c['src'], np.float32)])
+    flat = sal[3].reshape(-1)
+    flat[:4] = [np.nan, np.inf, -2.0, 0.0]
+    flat[-1] = -np.inf
+    sal[5].reshape(-1)[[0, -1]] = [0.25, 3.0]
+    return sal
+
+
+# ----------------------------------------------------------------------------- incidence
+@pytest.mark.parametrize('name', NAMES)
+def test_incidence(name):
+    c = sr.case(name)
+    n_in, n_und = int(c['ins'].sum()), int(c['und'].sum())
+    assert n_und <= 0.001 * n_in                                       # the cap on what float32 cannot decide
+    inc, _, got, _ = gpu_bits(name)
+    (h, w), S = c['grid'], len(c['cams'])
+    P = h * w
+    assert inc.dtype == torch.int32 and tuple(inc.shape) == (S, (P + 31) // 32)
+    print('%s: %d inside pairs, %d undecided; the kernel differs from float64 in %d pairs' % (name, n_in, n_und, int((got != c['ins']).sum())))
+    assert not ((got != c['ins']) & ~c['und']).any()                   # every decided pair
+    every = sr.unpack_bits(inc.cpu().numpy(), 32 * inc.shape[1])
+    assert not every[:, P:].any()                                      # the bits past P
+    # row j is the footprint of camera j alone: K17a's decision, exactly
+    counts, n_views = ops.head_footprints(dev(c['cams']), torch.arange(S + 1, dtype=torch.int32, device='cuda'), c['grid'],
+                                          c['view'][0], c['view'][1])
+    assert n_views.tolist() == [1] * S and np.array_equal(counts.cpu().numpy().reshape(S, P) == 1, got)
+    assert torch.equal(inc, ops.view_incidence(dev(c['cams']), c['grid'], c['view'][0], c['view'][1]))
+
+
+def test_incidence_of_a_camera_that_is_not_finite():
+    c = sr.case('s2x4_g5x9')
+    cams = c['cams'].copy()
+    cams[2, 1, 1] = np.nan
+    cams[5, 0, 2] = np.inf
+    inc = ops.view_incidence(dev(cams), c['grid'], c['view'][0], c['view'][1])
+    got = sr.unpack_bits(inc.cpu().numpy(), 45)
+    want = gpu_bits('s2x4_g5x9')[2].copy()
+    want[[2, 5]] = False
+    assert np.array_equal(got, want)
+    out = torch.full((8, 2), -1, dtype=torch.int32, device='cuda')
+    assert ops.view_incidence(dev(cams), c['grid'], c['view'][0], c['view'][1], out=out) is out and torch.equal(out, inc)
+
+
+# ----------------------------------------------------------------------------- tiles
+@pytest.mark.parametrize('name', NAMES)
+def test_tile_incidence(name):
+    c = sr.case(name)
+    inc, tinc, got, tgot = gpu_bits(name)
+    T = c['tiles'][0] * c['tiles'][1]
+    assert tinc.dtype == torch.int32 and tuple(tinc.shape) == (len(c['cams']), (T + 31) // 32)
+    want = sr.pack_bits(sr.tile_or(got, c['grid'], c['tiles']))        # the OR of the downloaded inc; the bits past T are 0
+    assert np.array_equal(tinc.cpu().numpy().view(np.uint32), want)
+    for tiles in ((1, 1), (2, 3), c['grid'], (c['grid'][0], 1)):       # one tile; an uneven division; a tile per pixel; per row
+        if tiles[0] * tiles[1] > 4096:
+            continue
+        t2 = ops.tile_incidence(inc, c['grid'], tiles)
+        assert np.array_equal(t2.cpu().numpy().view(np.uint32), sr.pack_bits(sr.tile_or(got, c['grid'], tiles))), tiles
+    if c['grid'][0] * c['grid'][1] <= 4096:
+        assert torch.equal(ops.tile_incidence(inc, c['grid'], c['grid']), inc)
+
+
+# ----------------------------------------------------------------------------- expectation
+@pytest.mark.parametrize('name', NAMES)
+def test_expect(name):
+    c = sr.case(name)
+    assert int(c['und'].sum()) <= 0.001 * int(c['ins'].sum())
+    inc, tinc, got, tgot = gpu_bits(name)
+    sal = maps_for(c, 70 + NAMES.index(name))
+    a = ops.sphere_eval_weights(c['src'][0], c['mode'], torch.device('cuda', torch.cuda.current_device()))
+    assert np.array_equal(a.cpu().numpy(), c['a_src'])
+    S = len(c['cams'])
+    e = (S + 2) * 2.0 ** -24                                           # S additions of terms >= 0, one product, one quotient
+    lo_bits, hi_bits = c['ins'] & ~c['und'], c['ins'] | c['und']
+    for what, bits_t, bits_np, lo_b, hi_b in (('pixels', inc, got, lo_bits, hi_bits),
+                                              ('tiles', tinc, tgot, sr.tile_or(lo_bits, c['grid'], c['tiles']),
+                                               sr.tile_or(hi_bits, c['grid'], c['tiles']))):
+        P = bits_np.shape[1]
+        out, total = ops.view_expect(dev(sal), a, bits_t, P)
+        out, total = out.cpu().numpy(), total.cpu().numpy()
+        want, want_total = sr.expect32(sal, c['a_src'], bits_np)      # the kernel's own bits: the same float32 sum, bit for bit
+        assert out.shape == (6, P) and bits_equal(out, want) and bits_equal(total, want_total), what
+        assert not out[4].any() and total[4] == 0.0                    # the all-zero frame
+        assert np.all(np.isfinite(out)) and out.min() >= 0.0 and out.max() <= 1.0
+        lo, hi = sr.expect64(sal, c['a_src'], lo_b)[0], sr.expect64(sal, c['a_src'], hi_b)[0]
+        print('%s %s: max |out - float64| = %.3e, bound e = %.3e' % (name, what, float(np.max(np.abs(out - sr.expect64(sal, c['a_src'], bits_np)[0]))), e))
+        assert np.all(lo * (1 - e) <= out) and np.all(out <= hi * (1 + e)), what
+        t64 = sr.expect64(sal, c['a_src'], bits_np)[1]
+        assert np.all(np.abs(total - t64) <= e * t64)
+
+
+@pytest.mark.parametrize('name', ['s2x4_g5x9', 's7x14_g30x60', 's14x28_g30x60'])
+def test_one_hot_maps_give_the_footprints(name):
+    c = sr.case(name)
+    inc, _, got, _ = gpu_bits(name)
+    S, P = got.shape
+    js = sorted({0, 1, S // 2, S - 2, S - 1, 255 % S, 256 % S})
+    sal = np.zeros((len(js), S), np.float32)
+    sal[np.arange(len(js)), js] = 3.7
+    a = ops.sphere_eval_weights(c['src'][0], c['mode'], inc.device)
+    out, total = ops.view_expect(dev(sal.reshape((len(js),) + c['src'])), a, inc, P)
+    assert np.array_equal(out.cpu().numpy(), got[js].astype(np.float32))          # exactly 0 and 1
+    assert np.array_equal(total.cpu().numpy(), np.float32(3.7) * c['a_src'][np.array(js) // c['src'][1]].astype(np.float32))
+
+
+def test_a_frame_does_not_depend_on_the_batch():
+    c = sr.case('s7x14_g30x60')
+    inc, tinc, _, _ = gpu_bits('s7x14_g30x60')
+    a = ops.sphere_eval_weights(7, 'solid_angle', inc.device)
+    sal = dev(sr.random_maps(90, 7, c['src']))
+    for bits, P in ((inc, 1800), (tinc, 72)):
+        alone = ops.view_expect(sal[3:4].contiguous(), a, bits, P)
+        again = ops.view_expect(sal[3:4].contiguous(), a, bits, P)
+        fifth = ops.view_expect(torch.cat([sal[[0, 1, 2, 4]], sal[3:4]]).contiguous(), a, bits, P)
+        whole = ops.view_expect(sal, a, bits, P)
+        for x, k in ((again, 0), (fifth, 4), (whole, 3)):              # a second run; fifth of five; fourth of seven
+            assert torch.equal(x[0][k], alone[0][0]) and torch.equal(x[1][k], alone[1][0])
+    none = ops.view_expect(sal[:0].contiguous(), a, inc, 1800)         # no frames: nothing is launched
+    assert tuple(none[0].shape) == (0, 1800) and tuple(none[1].shape) == (0,)
+
+
+def test_expect_refusals():
+    inc, tinc, _, _ = gpu_bits('s7x14_g30x60')
+    a = ops.sphere_eval_weights(7, 'solid_angle', inc.device)
+    sal = dev(sr.random_maps(91, 2, (7, 14)))
+    for bad in (lambda: ops.view_expect(sal, a, tinc, 1800), lambda: ops.view_expect(sal, a, inc, 1825),
+                lambda: ops.view_expect(sal.double(), a, inc, 1800), lambda: ops.view_expect(sal, a.long(), inc, 1800),
+                lambda: ops.view_expect(sal, a[:6], inc, 1800), lambda: ops.view_expect(sal.transpose(1, 2), a, inc, 1800),
+                lambda: ops.view_expect(sal, a, inc.float(), 1800), lambda: ops.view_expect(sal[0], a, inc, 1800),
+                lambda: ops.view_expect(sal, a, inc, 1800, out=torch.empty(2, 1799, device='cuda')),
+                lambda: ops.view_expect(sal, a, inc, 1800, out=torch.empty(2, 1800, device='cuda', dtype=torch.float64)),
+                lambda: ops.tile_incidence(inc, (30, 60), (6, 12), out=inc[:, :3]),
+                lambda: ops.tile_incidence(inc, (30, 61), (6, 12)), lambda: ops.tile_incidence(inc, (30, 60), (31, 12)),
+                lambda: ops.view_incidence(torch.zeros(4, 3, 2, device='cuda'), (30, 60), (1, 1), 100.0),
+                lambda: ops.view_incidence(torch.zeros(4097, 3, 3, device='cuda'), (30, 60), (1, 1), 100.0),
+                lambda: ops.view_incidence(torch.zeros(4, 3, 3, device='cuda'), (30, 60), (1, 1), 180.0)):
+        with pytest.raises(ValueError):
+            bad()
+    own = torch.empty(2, 1800, device='cuda')
+    res = ops.view_expect(sal, a, inc, 1800, out=own)
+    assert res[0] is own and torch.equal(own, ops.view_expect(sal, a, inc, 1800)[0])
+    big = torch.empty(4 * 1800 + 98, device='cuda')                    # out inside the buffer of sal: refused
+    big[:196] = sal.reshape(-1)
+    with pytest.raises(ValueError, match='share'):
+        ops.view_expect(big[:196].view(2, 7, 14), a, inc, 1800, out=big[98:98 + 3600].view(2, 1800))
+    with pytest.raises(ValueError, match='share'):                     # ... or inside the bits
+        ops.view_expect(sal, a, inc, 1800, out=inc.view(torch.float32).reshape(-1)[:3600].view(2, 1800))
+
+
+# ----------------------------------------------------------------------------- delivered quality
+def viewers(seed, per_frame):
+    """Random viewers in CSR form, with a NaN and an inf camera among them when there are enough."""
+    off = np.concatenate([[0], np.cumsum(per_frame)]).astype(np.int32)
+    R = hr.random_cameras(seed, int(off[-1]))
+    if len(R) > 6:
+        R[2, 1, 1] = np.nan
+        R[6, 0, 2] = -np.inf
+    return R, off
+
+
+@pytest.mark.parametrize('name,L', [('s2x4_g5x9', 3), ('s4x8_g12x24', 1), ('s4x8_g12x24_wide', 8), ('s7x14_g30x60', 3),
+                                    ('s7x14_g30x60_9x16', 4)])
+def test_quality(name, L):
+    c = sr.case(name)
+    (h, w), tiles, view = c['grid'], c['tiles'], c['view']
+    T = tiles[0] * tiles[1]
+    R, off = viewers(200 + L, [0, 1, 4, 5, 0, 3])                      # 0, 1, 4 and 5 viewers: the four pairs of a workgroup
+    N, F = len(R), len(off) - 1
+    ins, und = hr.classify(R, h, w, view)
+    assert int(und.sum()) <= 0.001 * int(ins.sum())                    # the cap, for the viewers
+    from cp_360_weakly_supervised_saliency_amd.utils import hashrng
+    levels = (np.abs(hashrng.normal(300 + L, (F, T), dtype=np.float64)) * 2.0).astype(np.uint8)       # 0 .. 7 or so
+    levels[3, : T // 2] = 200                                          # a level >= L counts as L - 1
+    a = ops.sphere_eval_weights(h, c['mode'], torch.device('cuda', torch.cuda.current_device()))
+    q = ops.view_quality(dev(R), dev(off), (h, w), view, a, dev(levels), tiles, L)
+    assert q.dtype == torch.int64 and tuple(q.shape) == (N, L)
+    got = q.cpu().numpy()
+    lo = sr.qarea(ins & ~und, off, (h, w), tiles, c['a_grid'], levels, L)
+    hi = sr.qarea(ins | und, off, (h, w), tiles, c['a_grid'], levels, L)
+    print('%s: %d viewers, %d undecided pixels, qarea differs from the decided sums in %d entries' % (name, N, int(und.sum()), int((got != lo).sum())))
+    assert np.all(lo <= got) and np.all(got <= hi)
+    assert not got[2].any() and not got[6].any() and got[0].sum() > 0  # the NaN and the inf viewer
+    # the columns add up to the viewer's own area: K17b's union of the viewer with itself, exactly
+    one = torch.arange(N + 1, dtype=torch.int32, device='cuda')
+    own = ops.head_agreement(dev(R), view, dev(R), one, (h, w), view, a)[1]
+    assert torch.equal(q.sum(dim=1), own)
+    for l in range(L):                                                 # every tile at level l: the whole area in column l
+        flat = ops.view_quality(dev(R), dev(off), (h, w), view, a, torch.full((F, T), l, dtype=torch.uint8, device='cuda'), tiles, L)
+        assert torch.equal(flat[:, l], own) and int(flat.sum()) == int(own.sum())
+    high = ops.view_quality(dev(R), dev(off), (h, w), view, a, torch.full((F, T), 255, dtype=torch.uint8, device='cuda'), tiles, L)
+    assert torch.equal(high[:, L - 1], own) and int(high.sum()) == int(own.sum())
+    assert torch.equal(q, ops.view_quality(dev(R), dev(off), (h, w), view, a, dev(levels), tiles, L))
+    # the fourth frame alone: a pair's sums do not depend on N, F or its place
+    k0, k1 = int(off[3]), int(off[4])
+    alone = ops.view_quality(dev(R[k0:k1]), dev(np.array([0, k1 - k0], np.int32)), (h, w), view, a, dev(levels[3:4]), tiles, L)
+    assert torch.equal(alone, q[k0:k1])
+
+
+def test_quality_without_viewers():
+    a = ops.sphere_eval_weights(5, 'solid_angle', torch.device('cuda', torch.cuda.current_device()))
+    off = torch.zeros(4, dtype=torch.int32, device='cuda')
+    q = ops.view_quality(torch.zeros(0, 3, 3, device='cuda'), off, (5, 9), sr.SQ100, a, torch.zeros(3, 6, dtype=torch.uint8, device='cuda'),
+                         (2, 3), 4)
+    assert tuple(q.shape) == (0, 4) and q.dtype == torch.int64
+    R = dev(hr.random_cameras(5, 2))
+    off2 = dev(np.array([0, 2], np.int32))
+    for bad in (lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a, torch.zeros(1, 6, dtype=torch.uint8, device='cuda'), (2, 3), 9),
+                lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a, torch.zeros(1, 6, dtype=torch.uint8, device='cuda'), (2, 3), 0),
+                lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a, torch.zeros(1, 5, dtype=torch.uint8, device='cuda'), (2, 3), 3),
+                lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a, torch.zeros(1, 6, dtype=torch.int32, device='cuda'), (2, 3), 3),
+                lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a[:4], torch.zeros(1, 6, dtype=torch.uint8, device='cuda'), (2, 3), 3),
+                lambda: ops.view_quality(R, off2, (5, 9), sr.SQ100, a, torch.zeros(1, 6, dtype=torch.uint8, device='cuda'), (6, 3), 3)):
+        with pytest.raises(ValueError):
+            bad()
+
+
+# ----------------------------------------------------------------------------- streams and workspaces
+def test_stream_and_workspace():
+    c = sr.case('s7x14_g30x60')
+    inc, tinc, _, _ = gpu_bits('s7x14_g30x60')
+    device = inc.device
+    a_src, a = ops.sphere_eval_weights(7, 'solid_angle', device), ops.sphere_eval_weights(30, 'solid_angle', device)
+    sal = dev(sr.random_maps(95, 5, (7, 14)))
+    R, off = viewers(96, [3, 0, 5, 1, 2])
+    levels = dev((np.arange(5 * 72).reshape(5, 72) % 3).astype(np.uint8))
+    want = (ops.view_expect(sal, a_src, inc, 1800), ops.view_quality(dev(R), dev(off), (30, 60), c['view'], a, levels, (6, 12), 3))
+    work = ops.view_quality_work(120, 240, device)                     # larger than the case needs, and reused
+    ptr0 = work.data_ptr()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        inc2 = ops.view_incidence(dev(c['cams']), c['grid'], c['view'][0], c['view'][1], work=work)
+        tinc2 = ops.tile_incidence(inc2, c['grid'], c['tiles'])
+        out2 = ops.view_expect(sal, a_src, inc2, 1800)
+        q2 = ops.view_quality(dev(R), dev(off), (30, 60), c['view'], a, levels, (6, 12), 3, work=work)
+        q3 = ops.view_quality(dev(R), dev(off), (30, 60), c['view'], a, levels, (6, 12), 3, work=work)
+    torch.cuda.current_stream().wait_stream(s)
+    assert torch.equal(inc2, inc) and torch.equal(tinc2, tinc) and torch.equal(out2[0], want[0][0]) and torch.equal(out2[1], want[0][1])
+    assert torch.equal(q2, want[1]) and torch.equal(q3, want[1])
+    assert ops.view_quality_work(30, 60, device, work).data_ptr() == ptr0 and ops.view_quality_work(240, 480, device, work).data_ptr() != ptr0
+    # a workspace that is too small is refused before any launch
+    L = _lib.lib()
+    need_i, need_q = L.cp360_fix_work_bytes(0, 30, 60), L.cp360_view_quality_work_bytes(30, 60)
+    assert need_q > need_i
+    words = torch.full((98, 57), -7, dtype=torch.int32, device='cuda')
+    q = torch.full((11, 3), -7, dtype=torch.int64, device='cuda')
+    Rd, offd = dev(R), dev(off)
+    assert L.cp360_view_incidence(_lib.ptr(dev(c['cams'])), 98, 30, 60, 1.7, 1.0, _lib.ptr(words), _lib.ptr(work), need_i - 1, _lib.stream()) == -1
+    assert L.cp360_view_quality(_lib.ptr(Rd), _lib.ptr(offd), 11, 5, 30, 60, 1.7, 1.0, _lib.ptr(a), _lib.ptr(levels), 6, 12, 3, _lib.ptr(q),
+                                _lib.ptr(work), need_q - 1, _lib.stream()) == -1
+    torch.cuda.synchronize()
+    assert int((words != -7).sum()) == 0 and int((q != -7).sum()) == 0
+
+
+# ----------------------------------------------------------------------------- end to end
+def test_planner_end_to_end():
+    """K17's scene: a target that moves 3 degrees a frame, a saliency blob on it, twelve viewers who follow it with offsets of up
+    to 6 degrees.  The plan from the maps stays within the budget of the uniform plan at level 1 and delivers more utility to the
+    viewers; the coverage from the maps correlates with the viewers' coverage better than the raw map does.  Comparisons only."""
+    F, fps = 24, 8.0
+    lon = np.deg2rad(-40.0 + 3.0 * np.arange(F))
+    lat = np.deg2rad(10.0 + 0.5 * np.arange(F))
+    target = np.stack([np.cos(lat) * np.cos(lon), np.sin(lat), np.cos(lat) * np.sin(lon)], -1)
+    maps = np.stack([vr.vmf_blob(t, 7, 14, 10.0) for t in target]).astype(np.float32)
+    tf = (np.arange(F) + 0.5) / fps
+    d = np.deg2rad(np.array([[-6, 2], [5, -3], [0, 4], [3, 3], [-4, -4], [6, 0], [-2, 5], [1, -5], [4, 2], [-5, 1], [2, -2], [0, 0]], float))
+    R, off, _ = headtrack.head_cameras([(tf, lon + dx, lat + dy) for dx, dy in d], fps, F)
+    assert off.tolist() == (12 * np.arange(F + 1)).tolist()
+    sp = streaming.StreamPlanner(grid_hw=(30, 60), src_hw=(7, 14), tiles=(6, 12))
+    rates = [1.0e6, 4.0e6, 1.6e7]
+    budget = rates[1] * 1.0 * (1.0 + 1e-9)                             # the cost of the uniform plan at level 1
+    res = sp.evaluate(maps, R, off, rates, budget, fps)
+    print('plan: utility %.4f, %.0f bits a segment; uniform level %d: utility %.4f, %.0f bits; levels used %s'
+          % (res['plan_utility'], res['plan_bits'], res['uniform_level'], res['uniform_utility'], res['uniform_bits'],
+             np.bincount(res['levels'].reshape(-1), minlength=3).tolist()))
+    assert res['segments'].tolist() == [0, 8, 16, 24] and res['levels'].shape == (3, 72) and res['uniform_level'] == 1
+    assert np.all(streaming.plan_bits(res['levels'], sp.area, rates) <= budget) and res['plan_bits'] <= budget
+    assert abs(res['uniform_utility'] - np.log(rates[1])) <= 1e-12
+    assert res['plan_utility'] > res['uniform_utility']
+    # the pieces that evaluate is made of
+    vis = sp.visibility(maps)
+    cov = sp.coverage(maps)
+    assert tuple(vis.shape) == (F, 72) and tuple(cov.shape) == (F, 30, 60) and cov.dtype == torch.float32
+    assert float(vis.max()) <= 1.0 and float(cov.max()) <= 1.0 and float(cov.min()) >= 0.0
+    assert bool((vis >= cov.reshape(F, 6, 5, 12, 5).amax(dim=(2, 4)).reshape(F, 72)).all())            # a tile against its pixels
+    assert sp.inc is sp.inc and sp.tinc is sp.tinc                     # built once
+    demand = sp.demand(vis, res['segments'])
+    assert torch.equal(demand[1], vis[8:16].max(dim=0).values)
+    qarea, u = sp.delivered(res['levels'], res['segments'], R, off, np.log(rates))
+    assert tuple(qarea.shape) == (12 * F, 3) and u.dtype == torch.float64 and abs(float(u.mean()) - res['plan_utility']) <= 1e-12
+    # maps of another size go through the resampler
+    fine = np.stack([vr.vmf_blob(t, 14, 28, 10.0) for t in target[:2]]).astype(np.float32)
+    assert torch.equal(sp.coverage(fine), sp.coverage(ops.sphere_eval_resample(dev(fine), (7, 14))))
+    # like with like: the expected coverage against the share of the viewers who had the pixel in view
+    gt = headtrack.HeadMaps(grid_hw=(30, 60)).coverage(R, off)
+    ev = eval_sphere.SphereEval(grid_hw=(30, 60))
+    cc_cov, cc_raw = float(ev.evaluate(cov, gt).cc.mean()), float(ev.evaluate(maps, gt).cc.mean())
+    print('CC against the viewers\' coverage: coverage(sal) %.4f, the resampled raw map %.4f' % (cc_cov, cc_raw))
+    assert cc_cov > cc_raw
