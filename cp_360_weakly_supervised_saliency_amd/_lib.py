@@ -90,6 +90,9 @@ PUBLIC_SYMBOLS = [
     'cp360_ego_work_bytes', 'cp360_ego_fit', 'cp360_ego_residual',
     # K24: viewport-adaptive streaming
     'cp360_view_incidence', 'cp360_tile_incidence', 'cp360_view_expect', 'cp360_view_quality_work_bytes', 'cp360_view_quality',
+    # K25: the conservative remap on the sphere, with its adjoint
+    'cp360_sresample_run_cap', 'cp360_sresample_axis_host', 'cp360_sresample_plan_bytes', 'cp360_sresample_plan_host',
+    'cp360_sresample_forward', 'cp360_sresample_adjoint',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -356,8 +359,15 @@ def lib():
     L.cp360_sup_loss_work_bytes.argtypes = [i, i, i, i, i]
     L.cp360_sup_loss_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, vp, vp, sz, vp]
     L.cp360_sup_loss_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, dbl, vp, vp, sz, vp]
+    L.cp360_sresample_run_cap.argtypes = [i, i]
+    L.cp360_sresample_axis_host.argtypes = [i, i, i, vp, vp, vp]
+    L.cp360_sresample_plan_bytes.restype = sz
+    L.cp360_sresample_plan_bytes.argtypes = [i, i, i, i]
+    L.cp360_sresample_plan_host.argtypes = [i, i, i, i, vp, sz]
+    L.cp360_sresample_forward.argtypes = [vp, i, i, i, vp, i, i, vp, sz, vp]
+    L.cp360_sresample_adjoint.argtypes = [vp, i, i, i, vp, i, i, vp, sz, vp]
     for name in SYMBOLS:
-        getattr(L, name)        # AttributeError here = header and library disagree
+        getattr(L, name)       # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):
         raise ImportError("%s is a stale build: version %d / cp360_conv_desc %d bytes, the binding expects %d / %d "
                           "- rebuild it (__graft_entry__.build())"

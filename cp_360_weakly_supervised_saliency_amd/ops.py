@@ -2014,6 +2014,120 @@ def sphere_eval_resample(maps, hw, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- K25: the conservative remap (csrc/sphere_resample.hip)
+RESAMPLERS = ('bilinear', 'conservative')
+_RESAMPLE_PLANS = {}
+
+
+def check_resampler(resample):
+    """The ``resample=`` argument of the consumers: 'bilinear' (``sphere_eval_resample``, the default everywhere) or
+    'conservative' (``sphere_resample``); ValueError otherwise."""
+    if resample not in RESAMPLERS:
+        raise ValueError("resample must be 'bilinear' or 'conservative', got %r" % (resample,))
+    return resample
+
+
+def resample_maps(maps, hw, resample='bilinear'):
+    """maps f32 [F, hs, ws] on the GPU -> f32 [F, h, w] by the named resampler: what the consumers call."""
+    if check_resampler(resample) == 'conservative':
+        return sphere_resample(maps, hw)
+    return sphere_eval_resample(maps, hw)
+
+
+def _resample_shapes(src_hw, hw):
+    hs, ws = (int(v) for v in src_hw)
+    h, w = (int(v) for v in hw)
+    if hs < 1 or ws < 1 or h < 1 or w < 1:
+        raise ValueError("the source and the grid must be at least 1 x 1, got %d x %d and %d x %d" % (hs, ws, h, w))
+    return hs, ws, h, w
+
+
+def sphere_resample_tables_host(n_src, n_dst, axis):
+    """cp360_sresample_axis_host: the runs and weights of one axis (0: rows, 1: columns) of the conservative remap from n_src to
+    n_dst pixels -> (start int32 [n_dst], count int32 [n_dst], weights float32 [n_dst, R]) as numpy arrays, the weights
+    zero-padded to the pair's run cap R.  Where the source is not finer the run is ``sphere_sample``'s two taps: start = i0, the
+    second index start + 1 wrapped (columns) or clamped (rows).  Host only: needs no GPU."""
+    n_src, n_dst, axis = int(n_src), int(n_dst), int(axis)
+    R = lib().cp360_sresample_run_cap(n_src, n_dst)
+    if R < 1 or axis not in (0, 1):
+        raise ValueError("n_src, n_dst must be at least 1 and axis 0 or 1, got %d, %d, %d" % (n_src, n_dst, axis))
+    if R > 256:
+        raise ValueError("a run of up to %d source pixels per grid pixel is not supported (at most 256)" % R)
+    start, count = np.empty(n_dst, np.int32), np.empty(n_dst, np.int32)
+    weights = np.empty((n_dst, R), np.float32)
+    check(lib().cp360_sresample_axis_host(n_src, n_dst, axis, start.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+                                          weights.ctypes.data_as(C.c_void_p)))
+    return start, count, weights
+
+
+def sphere_resample_plan(src_hw, hw, device):
+    """The tables of the conservative remap from src_hw to hw on `device` (a uint8 tensor, cp360_sresample_plan_host's layout):
+    made on the host in float64 and uploaded once per (src_hw, hw, device)."""
+    hs, ws, h, w = _resample_shapes(src_hw, hw)
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError("cp360 ops run on the GPU only (HIP); got the device %s - there is no CPU fallback" % device)
+    key = (hs, ws, h, w, device)
+    if key not in _RESAMPLE_PLANS:
+        n = int(lib().cp360_sresample_plan_bytes(hs, ws, h, w))
+        if n == 0:
+            raise ValueError("a conservative remap from %d x %d to %d x %d is not supported (h w <= 2^21, hs <= 65535, hs ws <= "
+                             "2^28, at most 256 source rows or columns per grid pixel)" % (hs, ws, h, w))
+        host = np.zeros(n // 8 + 2, np.int64)                          # 16-byte aligned: the first or the second word
+        off = (-host.ctypes.data) % 16
+        buf = host.view(np.uint8)[off:off + n]
+        check(lib().cp360_sresample_plan_host(hs, ws, h, w, buf.ctypes.data_as(C.c_void_p), n))
+        _RESAMPLE_PLANS[key] = torch.from_numpy(buf.copy()).to(device)
+    return _RESAMPLE_PLANS[key]
+
+
+def _resample_plan(plan, hs, ws, h, w, device):
+    if plan is None:
+        return sphere_resample_plan((hs, ws), (h, w), device)
+    require_gpu(plan)
+    need = int(lib().cp360_sresample_plan_bytes(hs, ws, h, w))
+    if plan.device != device or plan.dim() != 1 or need == 0 or plan.numel() != need:
+        raise ValueError("plan must be sphere_resample_plan((%d, %d), (%d, %d)) on the maps' device" % (hs, ws, h, w))
+    _check_buf('plan', plan, torch.uint8)
+    return plan
+
+
+def sphere_resample(maps, hw, plan=None, out=None):
+    """cp360_sresample_forward: maps f32 [F, hs, ws] (F = 0 is valid) -> f32 [F, h, w], the conservative remap on the sphere: a
+    grid pixel is the solid-angle-weighted mean of the source pixels it overlaps on every axis on which the source is finer, and
+    ``sphere_eval_resample``'s two taps on the others (neither finer: its bits).  One fixed order: a frame's numbers depend
+    neither on F nor on its place in the batch."""
+    require_gpu(maps, out, plan)
+    if maps.dim() != 3 or maps.shape[1] < 1 or maps.shape[2] < 1:
+        raise ValueError("maps must be float32 [F, hs, ws], got %s" % (tuple(maps.shape),))
+    _check_buf('maps', maps, torch.float32)
+    F = int(maps.shape[0])
+    hs, ws, h, w = _resample_shapes(maps.shape[1:], hw)
+    plan = _resample_plan(plan, hs, ws, h, w, maps.device)
+    if out is None:
+        out = torch.empty((F, h, w), dtype=torch.float32, device=maps.device)
+    elif tuple(out.shape) != (F, h, w) or out.device != maps.device:
+        raise ValueError("out must be float32 [%d, %d, %d] on the maps' device" % (F, h, w))
+    _check_buf('out', out, torch.float32)
+    check(lib().cp360_sresample_forward(ptr(maps), F, hs, ws, ptr(out), h, w, ptr(plan), plan.numel(), stream()))
+    return out
+
+
+def sphere_resample_adjoint(d_out, src_hw, plan=None):
+    """cp360_sresample_adjoint: d_out f32 [F, h, w] -> f32 [F, hs, ws], the transpose of ``sphere_resample`` from src_hw to d_out's
+    grid, gathered per source pixel in float64 and rounded once."""
+    require_gpu(d_out, plan)
+    if d_out.dim() != 3 or d_out.shape[1] < 1 or d_out.shape[2] < 1:
+        raise ValueError("d_out must be float32 [F, h, w], got %s" % (tuple(d_out.shape),))
+    _check_buf('d_out', d_out, torch.float32)
+    F = int(d_out.shape[0])
+    hs, ws, h, w = _resample_shapes(src_hw, d_out.shape[1:])
+    plan = _resample_plan(plan, hs, ws, h, w, d_out.device)
+    d_src = torch.empty((F, hs, ws), dtype=torch.float32, device=d_out.device)
+    check(lib().cp360_sresample_adjoint(ptr(d_out), F, h, w, ptr(d_src), hs, ws, ptr(plan), plan.numel(), stream()))
+    return d_src
+
+
 def sphere_eval(S, G, weights, fixations=None, work=None):
     """cp360_seval_scores: S, G f32 [F, h, w] on the evaluation grid, weights int32 [h] (``sphere_eval_weights``), fixations u8 /
     bool [F, h, w] or None (the rule G > mean + 2 std, weighted) -> (scores f64 [F, 5] = (auc, nss, cc, sim, kl), n_fix int32

@@ -51,6 +51,23 @@ class DeviceSupLoss(torch.autograd.Function):
         return dmaps, None, None, None, None
 
 
+class DeviceSphereResample(torch.autograd.Function):
+    """S = DeviceSphereResample.apply(maps, hw): maps f32 [N, mh, mw] -> f32 [N, h, w], the conservative remap on the sphere (K25,
+    ``ops.sphere_resample``) with its adjoint (``ops.sphere_resample_adjoint``) as the gradient, both in HIP on the launch stream.
+    In front of ``DeviceSupLoss`` it brings maps finer than the loss grid down; the loss then sees grid-sized maps and its own
+    resampler copies."""
+
+    @staticmethod
+    def forward(ctx, maps, hw):
+        maps = maps.detach().float().contiguous()
+        ctx.src_hw = tuple(int(v) for v in maps.shape[1:])
+        return ops.sphere_resample(maps, hw)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.sphere_resample_adjoint(g.float().contiguous(), ctx.src_hw), None
+
+
 def _flatten(maps, gt, fixations):
     if maps.dim() != 4 or gt.dim() != 4 or tuple(gt.shape[:2]) != tuple(maps.shape[:2]):
         raise ValueError("maps must be [B, L, mh, mw] and gt [B, L, h, w], got %s and %s" % (tuple(maps.shape), tuple(gt.shape)))
@@ -72,11 +89,15 @@ def _valid_means(terms, valid):
     return out[0], out[1], out[2], counts
 
 
-def supervised_losses(maps, gt, fixations=None, weights='solid_angle', kl_eps=KL_EPS):
+def supervised_losses(maps, gt, fixations=None, weights='solid_angle', kl_eps=KL_EPS, resample='bilinear'):
     """maps f32 [B, L, mh, mw] (the window's maps, on the GPU), gt f32 [B, L, h, w] on the loss grid, fixations u8 / bool
     [B, L, h, w] or None (K14's derived mask) -> (kl, cc, nss, counts): f64 scalars, differentiable with respect to maps, each
-    the mean over that term's valid maps; counts int64 [3] = how many those are.  No synchronisation."""
+    the mean over that term's valid maps; counts int64 [3] = how many those are.  No synchronisation.  resample='conservative'
+    brings the maps to the loss grid by ``DeviceSphereResample`` first (maps finer than the grid keep their mass)."""
+    ops.check_resampler(resample)
     m, g, fx = _flatten(maps, gt, fixations)
+    if resample == 'conservative':
+        m = DeviceSphereResample.apply(m, tuple(g.shape[1:]))
     a = ops.sphere_eval_weights(g.shape[1], weights, m.device)
     kl, cc, nss, valid = DeviceSupLoss.apply(m, g, fx, a, float(kl_eps))
     return _valid_means((kl, cc, nss), valid != 0)
@@ -117,6 +138,27 @@ def resample_torch(maps, hw):
     return top + ty * (bot - top)
 
 
+def _conservative_matrix(n_src, n_dst, axis):
+    """The dense float32 [n_dst, n_src] matrix of one axis of the conservative remap, from the library's host tables."""
+    start, count, weights = ops.sphere_resample_tables_host(n_src, n_dst, axis)
+    M = np.zeros((n_dst, n_src), np.float32)
+    for d in range(n_dst):
+        for k in range(int(count[d])):
+            i = int(start[d]) + k
+            M[d, i % n_src if axis == 1 else min(i, n_src - 1)] += weights[d, k]
+    return M
+
+
+def resample_conservative_torch(maps, hw):
+    """maps [N, mh, mw] -> [N, h, w] in maps' dtype: ``ops.sphere_resample``'s definition as two dense matrix
+    products, Wy @ maps @ Wx^T with the library's host tables; differentiable.  The order of its sums is the matrix product's, not
+    the kernel's: equal to the kernel within rounding, not bit for bit."""
+    h, w = (int(v) for v in hw)
+    Wy = torch.from_numpy(_conservative_matrix(int(maps.shape[1]), h, 0)).to(maps.device, maps.dtype)
+    Wx = torch.from_numpy(_conservative_matrix(int(maps.shape[2]), w, 1)).to(maps.device, maps.dtype)
+    return torch.matmul(torch.matmul(Wy, maps), Wx.t())
+
+
 def _sum(x):
     return x.sum(dim=(1, 2))
 
@@ -142,15 +184,16 @@ def map_terms_torch(S, G, M, a, kl_eps):
     return kl, cc, nss
 
 
-def supervised_losses_torch(maps, gt, fixations=None, weights='solid_angle', kl_eps=KL_EPS):
+def supervised_losses_torch(maps, gt, fixations=None, weights='solid_angle', kl_eps=KL_EPS, resample='bilinear'):
     """``supervised_losses`` composed from torch operations in maps' dtype, on maps' device: the CPU path and the reference for the
     device path.  A term's valid maps are found first (one synchronisation) and only they enter its mean, so that a NaN never
     enters the graph.  The minimum's gradient is torch's (ties share it), where the kernel gives it to the first occurrence."""
+    ops.check_resampler(resample)
     m, g, fx = _flatten(maps, gt, fixations)
     g = g.to(m.dtype)
     h, w = g.shape[1:]
     a = ops.sphere_eval_weights(h, weights, 'cpu').clamp(0, 1024).to(m.device, m.dtype)[:, None]
-    S = resample_torch(m, (h, w))
+    S = resample_conservative_torch(m, (h, w)) if resample == 'conservative' else resample_torch(m, (h, w))
     with torch.no_grad():
         if fx is None:                                                 # K14's rule, decided in float64 as the kernel decides it
             ad, gd = a.double(), g.double()

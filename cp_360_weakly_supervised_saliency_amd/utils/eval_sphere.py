@@ -7,7 +7,8 @@ row.  ``utils/eval_saliency.py`` (K8) keeps the reference's flat, one-frame func
     r = ev.evaluate(sal, gt)                            # [F, ., .] numpy or device maps of any size -> SphereScores on the device
     ev.means(r)                                         # {'auc_judd': .., 'nss': .., 'cc': .., 'sim': .., 'kl': ..}, one synchronisation
 
-Maps are resampled to the grid bilinearly on the sphere's pixel centres, without anti-aliasing (as the reference's resize);
+Maps are resampled to the grid bilinearly on the sphere's pixel centres, without anti-aliasing (as the reference's resize;
+``resample='conservative'`` selects K25's conservative remap for ground truth finer than the grid);
 fixations are an explicit mask on the grid or the reference's rule ``G > mean + 2 std`` with the same weights.  No jitter, no
 random draw: a frame's numbers are bit-identical between runs, batch sizes and places in the batch.  No CPU fallback.
 """
@@ -39,10 +40,13 @@ class SphereScores:
 
 class SphereEval:
     """``SphereEval(grid_hw=(120, 240), weights='solid_angle')``: holds the weight table of the grid and the workspace, which
-    grows to the longest video seen.  ``weights='uniform'`` scores a flat grid, as the reference does."""
+    grows to the longest video seen.  ``weights='uniform'`` scores a flat grid, as the reference does.  ``resample='conservative'``
+    brings maps finer than the grid down by the conservative remap (K25, ``ops.sphere_resample``: every source pixel is read, the
+    mass on the sphere is kept) instead of the four bilinear taps, which stay the default."""
 
-    def __init__(self, grid_hw=(120, 240), weights='solid_angle', device='cuda'):
+    def __init__(self, grid_hw=(120, 240), weights='solid_angle', device='cuda', resample='bilinear'):
         h, w = (int(v) for v in grid_hw)
+        self.resampler = ops.check_resampler(resample)
         if h < 1 or w < 1 or h * w > 1 << 21:
             raise ValueError("the grid must be between 1 x 1 and 2^21 pixels, got %d x %d" % (h, w))
         if weights not in ('solid_angle', 'uniform'):
@@ -65,7 +69,7 @@ class SphereEval:
 
     def resample(self, maps):
         """maps [F, hs, ws] (numpy or tensor) -> float32 [F, h, w] on the device, on the evaluation grid."""
-        return ops.sphere_eval_resample(self._maps('maps', maps), self.grid_hw)
+        return ops.resample_maps(self._maps('maps', maps), self.grid_hw, self.resampler)
 
     def evaluate(self, sal, gt, fixations=None):
         """sal [F, ., .], gt [F, ., .] (numpy or tensors, any sizes) and, optionally, fixations [F, h, w] on the grid (non-zero =
@@ -102,7 +106,8 @@ def dataset_means(per_video_means, frame_counts):
 def evaluate_video_dir(pred_dir, gt_dir, vid_name, evaluator=None):
     """Scores the saliency maps a run left on disk: every ``<pred_dir>/<vid_name>/{:05}.npy`` (``npy_io.saliency_path``) against
     ``<gt_dir>/<vid_name>.mp4/{:05}.npy`` of the same number, in ascending order, in one call -> ``SphereScores`` with
-    ``frames`` = the numbers.  A prediction without ground truth is an error."""
+    ``frames`` = the numbers.  A prediction without ground truth is an error.  The maps are resampled as the evaluator does:
+    ``evaluator=SphereEval(resample='conservative')`` for ground truth much finer than the grid."""
     ev = evaluator or SphereEval()
     vdir = os.path.join(pred_dir, vid_name)
     numbers = sorted(int(n[:-4]) for n in os.listdir(vdir) if re.fullmatch(r'\d{5}\.npy', n))

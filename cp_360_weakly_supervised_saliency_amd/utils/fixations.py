@@ -100,10 +100,12 @@ def scanpaths_to_points(tracks, fps, n_frames, max_gap=0.5):
 
 class FixationMaps:
     """``FixationMaps(grid_hw=(120, 240), sigma_deg=5.0)``: fixation counts, masks, density maps and shuffled AUC on one grid; holds
-    the workspace, which grows to the longest video seen."""
+    the workspace, which grows to the longest video seen.  ``resample='conservative'`` brings saliency maps finer than the grid down
+    by the conservative remap (K25, ``ops.sphere_resample``) instead of the bilinear taps, as ``SphereEval`` does."""
 
-    def __init__(self, grid_hw=(120, 240), sigma_deg=5.0, device='cuda'):
+    def __init__(self, grid_hw=(120, 240), sigma_deg=5.0, device='cuda', resample='bilinear'):
         h, w = (int(v) for v in grid_hw)
+        self.resampler = ops.check_resampler(resample)
         if h < 1 or w < 1 or h * w > 1 << 21:
             raise ValueError("the grid must be between 1 x 1 and 2^21 pixels, got %d x %d" % (h, w))
         sigma_deg = float(sigma_deg)
@@ -155,7 +157,7 @@ class FixationMaps:
         sal = host_tensor(sal, np.float32)
         if sal.dim() != 3 or sal.shape[0] < 1 or not sal.dtype.is_floating_point:
             raise ValueError("sal must be floating-point [F, h, w] with F >= 1, got %s %s" % (sal.dtype, tuple(sal.shape)))
-        S = ops.sphere_eval_resample(sal.detach().to(self.device, torch.float32).contiguous(), self.grid_hw)
+        S = ops.resample_maps(sal.detach().to(self.device, torch.float32).contiguous(), self.grid_hw, self.resampler)
         counts = host_tensor(counts)
         F, (h, w) = int(S.shape[0]), self.grid_hw
         if tuple(counts.shape) != (F, h, w) or counts.dtype.is_floating_point:
@@ -193,7 +195,7 @@ class FixationMaps:
         a = ops.sphere_eval_weights(h, weights, dev)
         one = None
         if sal is not None and sal.dim() == 2:
-            one = ops.sphere_eval_resample(sal.detach()[None].to(dev, torch.float32).contiguous(), self.grid_hw)
+            one = ops.resample_maps(sal.detach()[None].to(dev, torch.float32).contiguous(), self.grid_hw, self.resampler)
         scores = torch.full((N, 2), float('nan'), dtype=torch.float64, device=dev)
         for c0 in range(0, F, POINT_CHUNK):
             c1 = min(F, c0 + POINT_CHUNK)
@@ -205,8 +207,8 @@ class FixationMaps:
             if sal is None:
                 part = ops.fixation_point_scores(lonlat[k0:k1], offs, self.grid_hw, a, sigma_rad=np.deg2rad(self.sigma_deg), work=self._work)
             else:
-                maps = one if one is not None else ops.sphere_eval_resample(
-                    sal[c0:c1].detach().to(dev, torch.float32).contiguous(), self.grid_hw)
+                maps = one if one is not None else ops.resample_maps(
+                    sal[c0:c1].detach().to(dev, torch.float32).contiguous(), self.grid_hw, self.resampler)
                 part = ops.fixation_point_scores(lonlat[k0:k1], offs, self.grid_hw, a, maps=maps, work=self._work)
             scores[k0:k1] = part
         # the means: a frame's points are consecutive, one segment each, added in their order

@@ -129,10 +129,13 @@ def plan_bits(levels, area, rates, seconds=1.0):
 class StreamPlanner:
     """``StreamPlanner(grid_hw=(120, 240), src_hw=(14, 28), view_hw=(1, 1), hfov_deg=100.0, tiles=(6, 12))``: from saliency maps to
     the expected coverage of the grid's pixels and tiles, and the quality a tile plan delivers to recorded viewers.  The
-    incidence of the gaze cameras' windows on the grid (``inc``, ``tinc``) is built on first use and kept."""
+    incidence of the gaze cameras' windows on the grid (``inc``, ``tinc``) is built on first use and kept.
+    ``resample='conservative'`` brings maps finer than src_hw down by the conservative remap (K25, ``ops.sphere_resample``), which
+    keeps their mass on the sphere; the default is the bilinear resampler."""
 
     def __init__(self, grid_hw=(120, 240), src_hw=(14, 28), view_hw=(1, 1), hfov_deg=100.0, tiles=(6, 12), weights='solid_angle',
-                 device='cuda'):
+                 device='cuda', resample='bilinear'):
+        self.resampler = ops.check_resampler(resample)
         h, w, rows, cols = ops._stream_grid(grid_hw, tiles)
         self.grid_hw, self.tiles = (h, w), (rows, cols)
         hs, ws = (int(v) for v in src_hw)
@@ -183,11 +186,12 @@ class StreamPlanner:
         if sal.dim() != 3:
             raise ValueError("sal must be [F, hs, ws], got %s" % (tuple(sal.shape),))
         if tuple(sal.shape[1:]) != self.src_hw:
-            sal = ops.sphere_eval_resample(sal, self.src_hw)
+            sal = ops.resample_maps(sal, self.src_hw, self.resampler)
         return sal
 
     def coverage(self, sal):
-        """sal [F, hs', ws'] (maps of another size than src_hw are resampled by ``ops.sphere_eval_resample``) -> float32 [F, h, w]:
+        """sal [F, hs', ws'] (maps of another size than src_hw are resampled by ``ops.sphere_eval_resample``, or
+        by ``ops.sphere_resample`` with resample='conservative') -> float32 [F, h, w]:
         the expected share of the viewers who have the pixel in view, a viewer's head drawn from the map."""
         sal = self._maps(sal)
         h, w = self.grid_hw

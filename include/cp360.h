@@ -1077,6 +1077,41 @@ int cp360_view_quality(const float* R, const int32_t* offsets, long long N, int 
                        const int32_t* weights, const uint8_t* levels, int rows, int cols, int L, long long* qarea, void* work,
                        size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K25: the conservative remap on the sphere, with its adjoint
+ * The resampler for maps finer than the grid: a grid pixel is the solid-angle-weighted mean of the source pixels it overlaps, so
+ * a constant stays a constant, the integral over the sphere is kept and every source pixel is read.  cp360_seval_resample (four
+ * bilinear taps, no pre-filter) stays the default of every consumer.  The specification is the package's own, DESIGN.md "K25"
+ * (7q), restated in tests/resample_restate.py.  Source hs x ws, grid h x w, same seam and poles; per axis:
+ *   n_src > n_dst   conservative: the run of grid index d is floor(d n_src / n_dst) .. ceil((d + 1) n_src / n_dst) - 1; column
+ *                   weight (float)((double)ov / ws) with the integer overlap ov, row weight the overlap in z = cos(pi t) over the
+ *                   band's own z range, formed in float64 and rounded once
+ *   otherwise       sphere_sample's two taps: the run (i0, i1) with the weights (1 - t, t), t in f32 as cp360_seval_resample forms
+ *                   it; columns wrap, rows clamp
+ *   forward   dst f32 [F, h, w]: col[j] = sum over the run of y, ascending, of wy src[r, j]; out = sum over the run of x, in run
+ *             order, of wx col[j]; f32, every product and sum rounded on its own, the order fixed by the two shapes alone.  Where
+ *             neither axis is finer the call is cp360_seval_resample's, bit for bit.  Non-finite values are not hidden.
+ *   adjoint   d_src f32 [F, hs, ws] = the transpose applied to d_dst f32 [F, h, w], gathered per source pixel, both sums in f64
+ *             and rounded once.
+ *   run_cap   R of one axis: ceil(n_src / n_dst) + 1 where conservative, else 2; 0 for a size < 1.  R > 256 on either axis:
+ *             CP360_ERR_UNSUPPORTED.
+ *   axis_host HOST only, no GPU: axis 0 = rows, 1 = columns -> start int32 [n_dst], count int32 [n_dst], weights f32 [n_dst, R]
+ *             zero-padded (tapped: start = i0, count = 2, the second index is start + 1, wrapped or clamped).
+ *   plan      plan_host fills plan_bytes bytes of HOST memory (16-byte aligned) with both axes' tables; the caller uploads them
+ *             once per (hs, ws, h, w) and hands the DEVICE copy to forward and adjoint, which clamp whatever they read from it.
+ * Limits are cp360_seval_resample's (F <= 65535, h w <= 2^21, hs <= 65535, hs ws <= 2^28); F = 0 is valid and launches nothing.
+ * Status codes, in this order and before any launch: a NULL pointer (src, dst may be NULL when F = 0): CP360_ERR_NULL; a size < 1 or
+ * F < 0: CP360_ERR_BAD_SHAPE; a limit or the run cap: CP360_ERR_UNSUPPORTED; a pointer not 4-byte (plan 16-byte) aligned:
+ * CP360_ERR_ALIGN; a plan below plan_bytes: CP360_ERR_BAD_SHAPE.  Asynchronous on the stream, no atomics, no host synchronisation;
+ * a frame's numbers depend neither on F nor on its place in the batch. */
+int cp360_sresample_run_cap(int n_src, int n_dst);
+int cp360_sresample_axis_host(int n_src, int n_dst, int axis, int32_t* start, int32_t* count, float* weights);
+size_t cp360_sresample_plan_bytes(int hs, int ws, int h, int w);
+int cp360_sresample_plan_host(int hs, int ws, int h, int w, void* plan, size_t plan_bytes);
+int cp360_sresample_forward(const float* src, int F, int hs, int ws, float* dst, int h, int w, const void* plan, size_t plan_bytes,
+                            void* stream);
+int cp360_sresample_adjoint(const float* d_dst, int F, int h, int w, float* d_src, int hs, int ws, const void* plan,
+                            size_t plan_bytes, void* stream);
+
 /* Diagnostic only (bench.py `held_clock_ghz`): a bare bf16 MFMA loop on pseudo-random operands, n_workgroups x 4 waves, each
  * wave stamped once around `iters` x 16 MFMAs.  stamps: device u64 [n_workgroups * 4][2] = {d s_memtime (shader cycles),
  * d s_memrealtime (100 MHz ticks)} per wave; held clock of a wave = 0.1 GHz * [0] / [1].  A buffer of its own: no output of
