@@ -395,6 +395,7 @@ extern "C" int cp360_ego_fit(const float* flow, const float* R0, int F, int H, i
         !(min_share >= 0.0) || !isfinite(min_share))
         return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)flow & 7) != 0) return CP360_ERR_ALIGN;                // read as float2
     const EgoLayout l = ego_layout(F, H, W);
     hipStream_t s = (hipStream_t)stream;
     SphereTabs t;
@@ -426,6 +427,7 @@ extern "C" int cp360_ego_residual(const float* flow, const float* R, const float
     if (!flow || !R || !e || !res || !work) return CP360_ERR_NULL;         // mag may be null: not wanted
     if (bad_image(F, H, W)) return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
+    if ((((uintptr_t)flow | (uintptr_t)res) & 7) != 0) return CP360_ERR_ALIGN;     // read and written as float2
     hipStream_t s = (hipStream_t)stream;
     SphereTabs t;
     const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &t);

@@ -269,6 +269,7 @@ extern "C" int cp360_stab_fit(const float* flow, int F, int H, int W, int iters,
     if (!flow || !R || !diag || !work) return CP360_ERR_NULL;
     if (bad_image(F, H, W) || iters < 1 || !(c_min_px > 0.0) || !isfinite(c_min_px)) return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)flow & 7) != 0) return CP360_ERR_ALIGN;                // read as float2
     const WorkLayout l = work_layout(F, H, W);
     hipStream_t s = (hipStream_t)stream;
     SphereTabs t;
@@ -296,6 +297,7 @@ extern "C" int cp360_stab_flow(const float* R, int F, int H, int W, float* G, vo
     if (!R || !G || !work) return CP360_ERR_NULL;
     if (bad_image(F, H, W)) return CP360_ERR_BAD_SHAPE;
     if (big_image(F, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (((uintptr_t)G & 7) != 0) return CP360_ERR_ALIGN;                   // written as float2
     hipStream_t s = (hipStream_t)stream;
     SphereTabs t;
     const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &t);

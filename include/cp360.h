@@ -532,7 +532,8 @@ int cp360_optflow_farneback(const float* gray, int F, int H, int W, double pyr_s
  *            frames u8 [N, H, W, 3] (rintf, half to even) or f32 [N, H, W, C], C <= 4 (CP360_ERR_UNSUPPORTED above); not in place
  * work: 16-byte aligned device memory of cp360_stab_work_bytes(F, H, W) bytes for fit, of cp360_stab_work_bytes(0, H, W) bytes
  * for flow and rotate (the per-row and per-column sin / cos tables every call rebuilds); 0 = bad or unsupported sizes.  A
- * workspace that is too small: CP360_ERR_BAD_SHAPE. */
+ * workspace that is too small: CP360_ERR_BAD_SHAPE.  flow and G are read and written as pairs of floats: 8-byte aligned, else
+ * CP360_ERR_ALIGN, before any launch. */
 size_t cp360_stab_work_bytes(int F, int H, int W);
 int cp360_stab_fit(const float* flow, int F, int H, int W, int iters, double c_min_px, float* R, double* diag, void* work,
                    size_t work_bytes, void* stream);
@@ -1031,8 +1032,9 @@ int cp360_resnet_plan_describe_multi(cp360_ctx* ctx, int n_groups, int n_img, in
  *             nearest to g (e = 0: g* = p, the de-rotated flow; p an epipole: g* = g); mag f32 [F, H, W] = angle(g, g*) W / 2 pi,
  *             or NULL when not wanted.  e is a unit vector or exactly 0.  A non-finite flow value: NaN in that pixel.
  * work: 16-byte aligned device memory of cp360_ego_work_bytes(F, H, W) bytes for fit (never less than cp360_stab_work_bytes(F, H,
- * W)), of (0, H, W) for residual (K11's tables); 0 = bad or unsupported sizes; too small: CP360_ERR_BAD_SHAPE.  Asynchronous on
- * the stream, no atomics, bit-reproducible, a pair's result independent of F and of its place in the batch. */
+ * W)), of (0, H, W) for residual (K11's tables); 0 = bad or unsupported sizes; too small: CP360_ERR_BAD_SHAPE.  flow and res are
+ * read and written as pairs of floats: 8-byte aligned, else CP360_ERR_ALIGN, before any launch.  Asynchronous on the stream, no
+ * atomics, bit-reproducible, a pair's result independent of F and of its place in the batch. */
 size_t cp360_ego_work_bytes(int F, int H, int W);
 int cp360_ego_fit(const float* flow, const float* R0, int F, int H, int W, int iters, double c_min_px, double t_min_px,
                   double min_share, float* R, float* e, double* diag, void* work, size_t work_bytes, void* stream);

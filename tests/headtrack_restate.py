@@ -140,7 +140,12 @@ def case(name):
     """-> dict: grid (h, w), R float32 [N, 3, 3], offsets int32 [F + 1], Rc float32 [F, 3, 3], view, cam_view, mode, weights, and
     the float64 classification of the viewers (ins, und) and of the cameras (cins, cund).  'gaps_30x60' holds a NaN camera, an
     inf camera and two rolled pole cameras among its viewers, and an inf camera for its fourth frame."""
-    (h, w), per_frame, view, cam_view, mode, seed = CASES[name]
+    return make_case(name, *CASES[name])
+
+
+def make_case(name, grid, per_frame, view, cam_view, mode, seed):
+    """``case`` for inputs that are not in CASES (tests/test_sphere_paths_gpu.py builds the wide grids with it)."""
+    h, w = grid
     offsets = _offsets(per_frame)
     N, F = int(offsets[-1]), len(per_frame)
     R, Rc = random_cameras(seed, N), random_cameras(seed + 1000, F)

@@ -150,7 +150,11 @@ CASES = {
 def case(name):
     """-> dict: src, grid, view, tiles, mode, cams float32 [S, 3, 3], the float64 classification of the gaze cameras on the grid
     (ins, und bool [S, P]), the row weights of the source map (a_src) and of the grid (a_grid)."""
-    src, grid, view, tiles, mode = CASES[name]
+    return make_case(name, *CASES[name])
+
+
+def make_case(name, src, grid, view, tiles, mode):
+    """``case`` for inputs that are not in CASES (tests/test_sphere_paths_gpu.py builds the large grids and sources with it)."""
     cams = cameras(src)
     ins, und = hr.classify(cams, grid[0], grid[1], view)
     S = src[0] * src[1]

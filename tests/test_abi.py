@@ -149,6 +149,32 @@ def test_round2_entry_points_validate_without_gpu():
     assert L.cp360_set_launch_order(1) == 2 and L.cp360_set_launch_order(7) == 1 and L.cp360_set_launch_order(old) == 0
 
 
+def test_flow_entry_points_refuse_misaligned_float2_buffers_without_gpu():
+    """K11a / K11b / K23a / K23b read flow and write G and res as float2: a pointer that is not a multiple of 8 comes back as
+    CP360_ERR_ALIGN before anything is launched.  The pointers are integers that are never followed."""
+    import ctypes as C
+    L = _lib.lib()
+    one, two, big = C.c_void_p(16), C.c_void_p(32), 1 << 20
+    for off in (4, 1, 2, 12):
+        bad = C.c_void_p(64 + off)
+        assert L.cp360_stab_fit(bad, 1, 16, 32, 8, 0.25, one, one, one, big, None) == -6, off
+        assert L.cp360_stab_flow(one, 1, 16, 32, bad, one, big, None) == -6, off
+        assert L.cp360_ego_fit(bad, one, 1, 16, 32, 8, 0.25, 0.25, 0.25, one, one, one, one, big, None) == -6, off
+        assert L.cp360_ego_residual(bad, one, one, 1, 16, 32, two, two, one, big, None) == -6, off         # flow
+        assert L.cp360_ego_residual(one, one, one, 1, 16, 32, bad, two, one, big, None) == -6, off         # res
+    # the earlier checks keep their order: NULL, shape and size come first
+    bad = C.c_void_p(68)
+    assert L.cp360_stab_fit(bad, 1, 16, 32, 8, 0.25, None, one, one, big, None) == -5
+    assert L.cp360_stab_fit(bad, 0, 16, 32, 8, 0.25, one, one, one, big, None) == -1
+    assert L.cp360_stab_flow(one, 70000, 16, 32, bad, one, big, None) == -8
+    assert L.cp360_ego_fit(bad, one, 1, 16, 32, 0, 0.25, 0.25, 0.25, one, one, one, one, big, None) == -1
+    assert L.cp360_ego_residual(bad, one, None, 1, 16, 32, two, two, one, big, None) == -5
+    # 8 bytes are enough: no 16-byte demand on a float2 buffer (the workspace that is too small is the next check)
+    ok = C.c_void_p(72)
+    assert L.cp360_stab_flow(one, 1, 16, 32, ok, one, 8 * 48 - 1, None) == -1
+    assert L.cp360_ego_residual(ok, one, one, 1, 16, 32, ok, two, one, 8 * 48 - 1, None) == -1
+
+
 def _desc(dtype, n_img, face, c_in, c_out, k, stride=1, clip_resident=0):
     d = _lib.ConvDesc()
     pad = 1 if k == 3 else 0

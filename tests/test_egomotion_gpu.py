@@ -199,6 +199,10 @@ def residual_case(hw):
 
 @pytest.mark.parametrize('hw', SIZES)
 def test_residual_matches_the_restatement(hw):
+    check_residual(hw)
+
+
+def check_residual(hw):
     H, W = hw
     flow, R, e, res64, mag64, d_res, d_mag = residual_case(hw)
     res, mag = ops.egomotion_residual(dev(flow), dev(R), dev(e), want_mag=True)

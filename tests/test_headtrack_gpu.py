@@ -31,7 +31,11 @@ def run_case(c, work=None):
 # ----------------------------------------------------------------------------- against float64
 @pytest.mark.parametrize('name', sorted(hr.CASES))
 def test_against_float64(name):
-    c = hr.case(name)
+    check_against_float64(hr.case(name))
+
+
+def check_against_float64(c):
+    name = c['name']
     n_in, n_und = int(c['ins'].sum()), int(c['und'].sum())
     assert n_und <= 0.001 * n_in and int(c['cund'].sum()) <= 0.001 * int(c['cins'].sum())
     counts, n_views, inter, uni = run_case(c)
@@ -60,7 +64,10 @@ def self_agreement(R, view, grid, a, work=None):
 
 @pytest.mark.parametrize('name', ['chunks_12x24', 'gaps_30x60', 'uniform_12x24', 'one_frame_5x9'])
 def test_identities(name):
-    c = hr.case(name)
+    check_identities(hr.case(name))
+
+
+def check_identities(c):
     grid, view = c['grid'], c['view']
     R, off = dev(c['R']), dev(c['offsets'])
     a = ops.sphere_eval_weights(grid[0], c['mode'], R.device)

@@ -1,0 +1,392 @@
+"""Launch paths of the sphere kernels of K16 to K24 (csrc/headtrack.hip "K17", "K22c", csrc/streaming.hip "K24", csrc/egomotion.hip
+"K23", csrc/viewport.hip "K16b", "K22b") that the shapes of their own tests never reach: the wave-per-pair pixel walk on a grid wider
+than the wave, the second block of the incidence and tile-incidence kernels, the source limit of the expectation, rows of the
+independent-motion flow and of the zoom outline that are wider than one block, and the second block of the two kernels that give a
+thread to every pair or sequence.  Every test's docstring names the kernel, the path and why the shape reaches it; where a later
+change could un-reach the path, an assertion on the host says so.
+
+Bounds: no new numbers.  Every comparison is the one the kernel's own test file makes, through the ``check_*`` functions those files
+share: integer bounds from the float64 classification and exact identities (tests/test_headtrack_gpu.py, test_streaming_gpu.py),
+bit equality with ``expect32``, 8 d32 + 2^-22 for ego-motion (tests/test_egomotion_gpu.py), equality with the one-frame calls for
+the zoom outline and with the scalar calls for the zoom agreement (tests/test_zoom_gpu.py), equality with the restated path
+(tests/test_campath_gpu.py).
+
+Conditions on the inputs (the share of the pairs float32 cannot decide, the conditioning of the 65 fits, the blocks the outlines'
+borders lie in, the launch geometry) are functions without a GPU call, asserted here before the device runs and again by
+tests/test_sphere_paths_cpu.py where no GPU is present."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cp_360_weakly_supervised_saliency_amd import ops
+from cp_360_weakly_supervised_saliency_amd.utils import hashrng
+from tests import campath_restate as cr
+from tests import egomotion_restate as er
+from tests import headtrack_restate as hr
+from tests import streaming_restate as sr
+from tests import test_campath_gpu as k16
+from tests import test_egomotion_gpu as k23
+from tests import test_headtrack_gpu as k17
+from tests import test_streaming_gpu as k24
+from tests import test_zoom_gpu as k22
+from tests import viewport_aa_restate as ar
+from tests import viewport_restate as vr
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+FLOOR = 2.0 ** -22
+dev = k24.dev
+
+
+# ============================================================================= K17b, K22c, K24d: the walk of a wave over a wide grid
+# name -> headtrack_restate.make_case's arguments and the float64 classification's (undecided, inside) of the viewers and of the
+# cameras, as this restatement gives them
+WIDE_HEAD = {
+    'wide_120x240': (((120, 240), [3, 0, 5, hr.CHUNK + 1], hr.VIEW_A, hr.VIEW_B, 'solid_angle', 178), (102, 289804, 4, 30685)),
+    'wide_33x130': (((33, 130), [4, 1, 0, 2], hr.VIEW_B, hr.VIEW_A, 'uniform', 179), (0, 8217, 0, 1744)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def head_case(name):
+    """The case, once.  Asserts the walk's geometry - every lane of the wave starts in row 0 and a step of 64 wraps once or not at
+    all (w > 64); 130 columns are no multiple of the step and 33 x 130 pixels leave a partial last stride - and the cap on what
+    float32 cannot decide."""
+    args, counts = WIDE_HEAD[name]
+    c = hr.make_case(name, *args)
+    h, w = c['grid']
+    assert w > 64
+    if name == 'wide_33x130':
+        assert w % 64 != 0 and (h * w) % 64 != 0
+    assert (int(c['und'].sum()), int(c['ins'].sum()), int(c['cund'].sum()), int(c['cins'].sum())) == counts
+    assert counts[0] <= 0.001 * counts[1] and counts[2] <= 0.001 * counts[3]
+    return c
+
+
+@pytest.mark.parametrize('name', sorted(WIDE_HEAD))
+def test_agreement_and_footprints_on_wide_grids(name):
+    """head_agreement_kernel, grid ceil(N / 4): with w > 64 lane / w is 0 for the whole wave and the while loop of a step runs
+    once or not at all - at 240 columns three steps in four do not wrap, at 130 columns every second one - where on the grids of
+    at most 60 columns of test_headtrack_gpu it always runs.  Frame 3 of the 120 x 240 case has
+    kHeadChunk + 1 viewers, so head_footprints_kernel (grid (113, 4)) stages a second chunk there.  test_against_float64's checks:
+    the counts and both sums between the bounds the float64 classification leaves."""
+    k17.check_against_float64(head_case(name))
+
+
+@pytest.mark.parametrize('name', sorted(WIDE_HEAD))
+def test_identities_on_wide_grids(name):
+    """test_identities' exact checks on the same walk: a viewer against itself has inter == uni, sum a_y counts == the sum of the
+    viewers' own areas (a pixel per thread in K17a against a wave per viewer in K17b), opposite views share nothing, and with
+    uniform weights uni == 1024 times the pixels of the footprints' union.  A walk that skipped or repeated a row breaks them."""
+    k17.check_identities(head_case(name))
+
+
+def zoom_case(name):
+    """(offsets, R, Rc) of the wide case: four frames, one for each field of view of test_zoom_gpu.AGREE_FOVS."""
+    c = head_case(name)
+    assert len(c['Rc']) == len(k22.AGREE_FOVS)
+    return c['offsets'], c['R'], c['Rc']
+
+
+@functools.lru_cache(maxsize=None)
+def zoom_bounds_case(name):
+    """The classification under a 9 x 16 camera with a field of view per frame; asserts test_agreement_against_the_restatement's cap
+    and that some windows overlap (so that inter is not 0 throughout)."""
+    c = head_case(name)
+    b = k22.agreement_bounds_case(zoom_case(name), c['grid'], c['view'], (9, 16))
+    assert int(b['und'].sum() + b['cund'].sum()) <= 0.02 * int(b['ins'].sum())
+    lo = hr.agreement_bounds(b)
+    assert (lo[0] > 0).any() and (lo[1] < lo[2]).any()
+    return b
+
+
+@pytest.mark.parametrize('name', sorted(WIDE_HEAD))
+def test_zoom_agreement_on_wide_grids(name):
+    """head_agreement_zoom_kernel (K22c), the same walk with the camera's tangents per frame: equal to the scalar head_agreement
+    call of every frame's field of view (an 8 x 16 camera view: the two tangents are the same floats), and within the float64
+    bounds under a 9 x 16 camera view."""
+    c = head_case(name)
+    k22.check_agreement_equals_the_scalar_calls(zoom_case(name), c['grid'], c['view'], (8, 16), c['mode'])
+    k22.check_agreement_against_the_restatement(zoom_bounds_case(name))
+
+
+# name -> (grid, tiles, weights, L) and the (undecided, inside) pixels of test_quality's 13 viewers, viewers(200 + L, ...), eleven
+# of them finite, under the 100-degree square window
+WIDE_QUALITY = {
+    'q_120x240': (((120, 240), (6, 12), 'solid_angle', 3), (18, 54905)),
+    'q_33x130': (((33, 130), (3, 5), 'uniform', 8), (0, 9494)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def quality_case(name):
+    """A streaming case whose source map plays no part (2 x 4), with the viewers' cap asserted."""
+    (grid, tiles, mode, L), counts = WIDE_QUALITY[name]
+    assert grid[1] > 64
+    c = sr.make_case(name, (2, 4), grid, sr.SQ100, tiles, mode)
+    R, _ = k24.viewers(200 + L, [0, 1, 4, 5, 0, 3])
+    ins, und = hr.classify(R, grid[0], grid[1], c['view'])
+    assert (int(und.sum()), int(ins.sum())) == counts and counts[0] <= 0.001 * counts[1]
+    return c, L
+
+
+@pytest.mark.parametrize('name', sorted(WIDE_QUALITY))
+def test_quality_on_wide_grids(name):
+    """view_quality_kernel (K24d), grid ceil(13 / 4): K17b's walk with the tile tables read at (x, y).  At 240 columns 20 pixels a
+    tile column, at 130 columns 26: the walk's x and y pick the tile.  test_quality's checks: between the float64 bounds; the row
+    sums equal the viewer's own area from head_agreement; every tile at level l puts the whole area in column l; 255 lands in
+    column L - 1; the fourth frame alone."""
+    c, L = quality_case(name)
+    k24.check_quality(c, L)
+
+
+# ============================================================================= K24a, K24c: the default grid
+DEFAULT_GRID = (120, 240)
+# source -> (undecided, inside) pairs of the gaze cameras on the default grid with the 100-degree square window
+DEFAULT_SOURCES = {(4, 8): (64, 203424), (14, 28): (272, 2529984)}
+
+
+@functools.lru_cache(maxsize=None)
+def default_grid_case(src):
+    """view_incidence_kernel's grid is (ceil(W32 / 256), S): 900 words a camera, four blocks, the last one partial."""
+    h, w = DEFAULT_GRID
+    W32 = (h * w + 31) // 32
+    assert W32 > 256 and W32 % 256 != 0
+    c = sr.make_case('s%dx%d_g120x240' % src, src, DEFAULT_GRID, sr.SQ100, (6, 12), 'solid_angle')
+    assert (int(c['und'].sum()), int(c['ins'].sum())) == DEFAULT_SOURCES[src]
+    assert DEFAULT_SOURCES[src][0] <= 0.001 * DEFAULT_SOURCES[src][1]
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def default_grid_bits(src):
+    return k24.bits_of(default_grid_case(src))
+
+
+@pytest.mark.parametrize('src', sorted(DEFAULT_SOURCES))
+def test_incidence_at_the_default_grid(src):
+    """view_incidence_kernel with blockIdx.x = 0 .. 3: 28 800 pixels are 900 words, words 256 and up are the later blocks'.
+    test_incidence's checks: every decided pair as float64 has it, no bit past P, row j equal to head_footprints of camera j
+    alone (a pixel per thread there, 32 pixels per thread here), a second run equal to the first."""
+    k24.check_incidence(default_grid_case(src), default_grid_bits(src))
+
+
+@pytest.mark.parametrize('src', sorted(DEFAULT_SOURCES))
+def test_expect_at_the_default_grid(src):
+    """view_expect_kernel, grid (113, 2): blocks 1 .. 112 read the words that K24a's blocks 0 .. 3 wrote.  test_expect's checks
+    over the pixels: bit for bit expect32 on the kernel's own bits, and within the float64 bracket."""
+    k24.check_expect(default_grid_case(src), default_grid_bits(src), 80 + src[0], tiles=False)
+
+
+# ============================================================================= K24b: more than 2048 tiles
+TILE_GRID = (48, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_case():
+    """4 x 8 source on a 48 x 64 grid with a tile per pixel: T = 3072, T32 = 96, so tile_incidence_kernel (64 threads, a word of
+    32 tiles each) runs a second block, and view_expect_kernel over the tiles has P = 3072: twelve blocks."""
+    T = TILE_GRID[0] * TILE_GRID[1]
+    assert T > 2048 and (T + 31) // 32 > 64 and T <= 4096
+    c = sr.make_case('s4x8_g48x64', (4, 8), TILE_GRID, sr.SQ100, TILE_GRID, 'solid_angle')
+    assert (int(c['und'].sum()), int(c['ins'].sum())) == (0, 21632)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def tile_bits():
+    return k24.bits_of(tile_case())
+
+
+def test_more_than_2048_tiles():
+    """tile_incidence_kernel with blockIdx.x = 1 (tiles 2048 .. 3071).  A tile per pixel: tinc is inc itself, and the packed OR of
+    the downloaded bits.  48 x 1 tiles are whole rows of 64 pixels (any_bit over two full words: both end masks at once leave
+    every bit), 2 x 64 tiles are columns of 24 rows; the three-word span with a middle word is test_tile_incidence's own, a row
+    of 60 pixels on the 30 x 60 grid."""
+    c = tile_case()
+    inc, tinc, got, tgot = tile_bits()
+    assert tuple(tinc.shape) == (32, 96) and torch.equal(tinc, inc)
+    assert np.array_equal(tinc.cpu().numpy().view(np.uint32), sr.pack_bits(sr.tile_or(got, TILE_GRID, TILE_GRID)))
+    assert np.array_equal(tgot, got) and got.any() and not got.all()
+    for tiles in ((48, 1), (2, 64)):
+        t2 = ops.tile_incidence(inc, TILE_GRID, tiles)
+        assert np.array_equal(t2.cpu().numpy().view(np.uint32), sr.pack_bits(sr.tile_or(got, TILE_GRID, tiles))), tiles
+
+
+def test_expect_over_more_than_2048_tiles():
+    """view_expect_kernel with P = T = 3072 on the tile bits (and on the pixels' bits, the same words): test_expect's checks, bit
+    for bit expect32 and the float64 bracket."""
+    k24.check_expect(tile_case(), tile_bits(), 85)
+
+
+# ============================================================================= K24c: the source limit
+@functools.lru_cache(maxsize=None)
+def limit_case():
+    """A 64 x 64 source: S = 4096 = kMaxSource, sixteen staging chunks of 256 in view_expect_kernel, the last one full."""
+    c = sr.make_case('s64x64_g12x24', (64, 64), (12, 24), sr.SQ100, (3, 4), 'solid_angle')
+    assert len(c['cams']) == 4096 == 16 * 256 == ops.STREAM_MAX_SOURCE
+    assert (int(c['und'].sum()), int(c['ins'].sum())) == (0, 263168)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def limit_bits():
+    return k24.bits_of(limit_case())
+
+
+def test_expect_at_the_source_limit():
+    """view_expect_kernel, grid (2, 2), with j0 = 0, 256 .. 3840: test_expect's checks over the pixels - 4096 float32 additions in
+    the definition's order, bit for bit - and the incidence of the 4096 cameras (view_incidence_kernel with blockIdx.y up to
+    4095) against float64."""
+    c, bits = limit_case(), limit_bits()
+    k24.check_incidence(c, bits)
+    k24.check_expect(c, bits, 86, tiles=False)
+
+
+def test_one_hot_maps_at_the_source_limit():
+    """A map with one source pixel lit gives that camera's footprint exactly: the last pixel of the first chunk and the first of
+    the second (255, 256), of the last but one and the last chunk (3839, 3840), and the last source pixel of all."""
+    k24.check_one_hot_maps(limit_case(), limit_bits(), [0, 1, 255, 256, 2048, 3839, 3840, 4094, 4095])
+
+
+def test_a_source_past_the_limit_is_refused():
+    """64 x 65 = 4160 source pixels: ValueError from every op that takes the source, before anything is launched."""
+    a = ops.sphere_eval_weights(64, 'solid_angle', torch.device('cuda', torch.cuda.current_device()))
+    inc = torch.zeros(64 * 65, 9, dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError):
+        ops.view_incidence(torch.zeros(64 * 65, 3, 3, device=DEV), (12, 24), (1, 1), 100.0)
+    with pytest.raises(ValueError):
+        ops.view_expect(torch.ones(1, 64, 65, device=DEV), a, inc, 288)
+    with pytest.raises(ValueError):
+        ops.tile_incidence(inc, (12, 24), (3, 4))
+
+
+# ============================================================================= K23: ego-motion
+WIDE_FLOWS = [(9, 300), (12, 520)]
+
+
+def residual_blocks(hw):
+    """ego_residual_kernel's grid is (ceil(W / 256), H, F).  residual_case asserts what its seven pairs are for at this size, the
+    flow that leaves through the seam among them."""
+    k23.residual_case(hw)
+    return (hw[1] + 255) // 256
+
+
+@pytest.mark.parametrize('hw', WIDE_FLOWS)
+def test_residual_on_wide_rows(hw):
+    """ego_residual_kernel with blockIdx.x = 1 (and 2 at 520 columns, a block of 8 live threads): the table lookups, the pixel
+    index and the wrap of rx into [-W / 2, W / 2] beyond x = 255.  test_residual_matches_the_restatement's checks: 8 d32 for res
+    (modulo W) and mag, the NaN pixels where float64 has them, out= bit-equal."""
+    assert residual_blocks(hw) == (2 if hw[1] == 300 else 3)
+    k23.check_residual(hw)
+
+
+FIT65_HW = (16, 32)
+
+
+@functools.lru_cache(maxsize=None)
+def fit65_case():
+    """65 scene flows of 16 x 32 along test_egomotion_gpu.fit_case's three directions, with translations of 0.3 to 0.63 and 0.05
+    px of noise from 65 seeds: (flow, the float64 fit, d32 of R, e and diag).  Asserts fit_case's condition on every pair: fitted,
+    and lambda_0 <= 0.05 lambda_1 in the restatement."""
+    H, W = FIT65_HW
+    dirs = (er.E_TRUE, np.array([-0.5, 0.3, 0.81]) / np.linalg.norm([-0.5, 0.3, 0.81]), np.array([0.1, -0.6, -0.79]) / np.linalg.norm([0.1, -0.6, -0.79]))
+    flow = np.stack([er.scene_flow(H, W, (0.3, 0.5, 0.4)[i % 3] + 0.002 * i, e_true=dirs[i % 3], noise_px=0.05, seed=500 + i)[0]
+                     for i in range(65)]).astype(np.float32)
+    want = er.egomotion_fit(flow, **k23.SMALL)
+    w32 = er.egomotion_fit(flow, dtype=np.float32, **k23.SMALL)
+    assert flow.shape[0] > 64
+    assert np.all(want[2][:, 7] == er.OK) and np.all(want[2][:, 3] <= 0.05 * want[2][:, 4])
+    for i in range(65):
+        assert er.angle_deg(want[1][i], dirs[i % 3]) < 3.0
+    return flow, want, tuple(np.max(np.abs(a - b), 0) for a, b in zip(w32, want))
+
+
+def test_egomotion_fit_of_65_pairs():
+    """ego_fit_init_kernel, grid ceil(F / 64) of 64 threads: pair 64 is the first thread of the second block, its state R0 and
+    c_min like every other's.  check_fit's rule against the float64 fit, and pairs 0, 63 and 64 alone bit-equal to their place in
+    the batch."""
+    flow, want, d32 = fit65_case()
+    fl = dev(flow)
+    full = ops.egomotion_fit(fl, **k23.SMALL)
+    assert full[0].shape == (65, 3, 3) and full[1].shape == (65, 3) and full[2].shape == (65, 8)
+    k23.check_fit(k23.host(*full), want, d32, 'fit of 65 pairs of 16 x 32')
+    for p in (0, 63, 64):
+        assert k23.same(ops.egomotion_fit(fl[p:p + 1], **k23.SMALL), [t[p:p + 1] for t in full]), p
+
+
+# ============================================================================= K16b: 65 sequences
+PATH_HW, PATH_F, PATH_STEP = (5, 9), 70, 45.0
+
+
+@functools.lru_cache(maxsize=None)
+def path65_case():
+    """70 frames of 5 x 9 cut into 65 sequences: 61 of one frame, sequences 0, 30 and 63 of two, sequence 64 of three.  Returns
+    (s, g, starts, the restated idx, the restated scores).  Asserts that the sequences of more than one frame do not follow their
+    frames' own maxima: there the trace, not the argmax, decides."""
+    hm, wm = PATH_HW
+    lengths = np.ones(65, np.int64)
+    lengths[[0, 30, 63]] = 2
+    lengths[64] = 3
+    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    assert len(starts) - 1 > 64 and int(starts[-1]) == PATH_F
+    s, g, _, _ = k16.random_case(PATH_HW, PATH_F, 1650, 16.0, PATH_STEP)
+    idx, score = cr.path(s, g, 16.0, PATH_STEP, starts.tolist())
+    own = cr.votes(s, g).reshape(PATH_F, -1).argmax(1)
+    for k in (0, 30, 63, 64):
+        assert not np.array_equal(idx[starts[k]:starts[k + 1]], own[starts[k]:starts[k + 1]]), k
+    return s, g, starts, idx, score
+
+
+def test_path_of_65_sequences():
+    """path_trace_kernel, grid ceil(S / 64) of 64 threads, a thread per sequence: sequence 64 is the first thread of the second
+    block and walks three frames back.  test_path_equals_the_restatement's checks - idx and score equal, dirs the pixel centres -
+    and sequences 63 and 64 alone give their idx, dirs and score."""
+    s, g, starts, want_idx, want_score = path65_case()
+    hm, wm = PATH_HW
+    got = k16.run_path(s, g, 16.0, PATH_STEP, starts=starts)
+    assert got[2].shape == (65,)
+    k16.check_equal(got, want_idx, want_score)
+    assert np.max(np.abs(got[1].astype(np.float64) - cr.centres(want_idx, hm, wm))) <= FLOOR
+    for k in (63, 64):
+        lo, hi = int(starts[k]), int(starts[k + 1])
+        alone = k16.run_path(s[lo:hi], g[lo:hi], 16.0, PATH_STEP)
+        assert np.array_equal(alone[0], got[0][lo:hi]) and np.array_equal(alone[1], got[1][lo:hi]) and alone[2][0] == got[2][k], k
+
+
+# ============================================================================= K22b: the zoom outline on wide panoramas
+WIDE_PANORAMAS = [(9, 300), (12, 520)]
+
+
+def zoom_outline_blocks(HW, border_px):
+    """The 256-column blocks of view_outline_zoom_kernel (grid (ceil(W / 256), H, N)) that hold border pixels of each of
+    test_zoom_gpu's four frames, every camera with its own field of view, in float64.  Asserts that every frame draws, that some
+    border lies beyond x = 255, that the 180-degree yaw's border sits astride the seam where the rows are dense enough to catch it
+    (in the first block and a later one), and on 520 columns that the identity camera's border falls in blocks 0 and 1 - on 300
+    columns its 60-degree window spans x = 125 .. 175, block 0 alone."""
+    H, W = HW
+    assert W > 256
+    R = ar.cameras4().astype(np.float32).astype(np.float64)
+    masks = [vr.outline(R[n], H, W, k22.OUTLINE_HW, k22.OUTLINE_FOVS[n], border_px)[0] for n in range(4)]
+    assert all(m.any() for m in masks)
+    blocks = [sorted(set((np.nonzero(m.any(0))[0] // 256).tolist())) for m in masks]
+    assert any(b[-1] >= 1 for b in blocks)
+    if W == 520 or border_px == 3:
+        assert blocks[1][0] == 0 and blocks[1][-1] >= 1
+    if W == 520:
+        assert blocks[0] == [0, 1]
+    return blocks
+
+
+@pytest.mark.parametrize('alias', [False, True])
+@pytest.mark.parametrize('border_px', [1, 3])
+@pytest.mark.parametrize('HW', WIDE_PANORAMAS)
+def test_zoom_outline_on_wide_panoramas(HW, border_px, alias):
+    """view_outline_zoom_kernel with blockIdx.x = 1 (and 2 at 520 columns): the pixel index, the table lookup and the copy of the
+    pixels that are not drawn beyond x = 255.  test_outline_equals_the_one_frame_calls' check: every byte equal to
+    viewport_outline with that frame's field of view, which test_outline_on_wide_panoramas holds to float64 at rows of three
+    blocks."""
+    zoom_outline_blocks(HW, border_px)
+    k22.check_outline_equals_the_one_frame_calls(HW, border_px, alias)

@@ -31,7 +31,11 @@ def bits_equal(a, b):
 @functools.lru_cache(maxsize=None)
 def gpu_bits(name):
     """The kernels' incidence of a case, once: (inc, tinc) int32 tensors on the device and the same as bool [S, P], [S, T]."""
-    c = sr.case(name)
+    return bits_of(sr.case(name))
+
+
+def bits_of(c):
+    """``gpu_bits`` of a case that is not in streaming_restate.CASES; the caller keeps the result."""
     inc = ops.view_incidence(dev(c['cams']), c['grid'], c['view'][0], c['view'][1])
     tinc = ops.tile_incidence(inc, c['grid'], c['tiles'])
     P, T = c['grid'][0] * c['grid'][1], c['tiles'][0] * c['tiles'][1]
@@ -52,10 +56,14 @@ def maps_for(c, seed):
 # ----------------------------------------------------------------------------- incidence
 @pytest.mark.parametrize('name', NAMES)
 def test_incidence(name):
-    c = sr.case(name)
+    check_incidence(sr.case(name), gpu_bits(name))
+
+
+def check_incidence(c, bits):
+    name = c['name']
     n_in, n_und = int(c['ins'].sum()), int(c['und'].sum())
     assert n_und <= 0.001 * n_in                                       # the cap on what float32 cannot decide
-    inc, _, got, _ = gpu_bits(name)
+    inc, _, got, _ = bits
     (h, w), S = c['grid'], len(c['cams'])
     P = h * w
     assert inc.dtype == torch.int32 and tuple(inc.shape) == (S, (P + 31) // 32)
@@ -105,18 +113,24 @@ def test_tile_incidence(name):
 # ----------------------------------------------------------------------------- expectation
 @pytest.mark.parametrize('name', NAMES)
 def test_expect(name):
-    c = sr.case(name)
+    check_expect(sr.case(name), gpu_bits(name), 70 + NAMES.index(name))
+
+
+def check_expect(c, bits, seed, tiles=True):
+    """tiles=False: the pixels' bits alone."""
+    name = c['name']
     assert int(c['und'].sum()) <= 0.001 * int(c['ins'].sum())
-    inc, tinc, got, tgot = gpu_bits(name)
-    sal = maps_for(c, 70 + NAMES.index(name))
+    inc, tinc, got, tgot = bits
+    sal = maps_for(c, seed)
     a = ops.sphere_eval_weights(c['src'][0], c['mode'], torch.device('cuda', torch.cuda.current_device()))
     assert np.array_equal(a.cpu().numpy(), c['a_src'])
     S = len(c['cams'])
     e = (S + 2) * 2.0 ** -24                                           # S additions of terms >= 0, one product, one quotient
     lo_bits, hi_bits = c['ins'] & ~c['und'], c['ins'] | c['und']
-    for what, bits_t, bits_np, lo_b, hi_b in (('pixels', inc, got, lo_bits, hi_bits),
-                                              ('tiles', tinc, tgot, sr.tile_or(lo_bits, c['grid'], c['tiles']),
-                                               sr.tile_or(hi_bits, c['grid'], c['tiles']))):
+    todo = [('pixels', inc, got, lo_bits, hi_bits)]
+    if tiles:
+        todo.append(('tiles', tinc, tgot, sr.tile_or(lo_bits, c['grid'], c['tiles']), sr.tile_or(hi_bits, c['grid'], c['tiles'])))
+    for what, bits_t, bits_np, lo_b, hi_b in todo:
         P = bits_np.shape[1]
         out, total = ops.view_expect(dev(sal), a, bits_t, P)
         out, total = out.cpu().numpy(), total.cpu().numpy()
@@ -133,10 +147,13 @@ def test_expect(name):
 
 @pytest.mark.parametrize('name', ['s2x4_g5x9', 's7x14_g30x60', 's14x28_g30x60'])
 def test_one_hot_maps_give_the_footprints(name):
-    c = sr.case(name)
-    inc, _, got, _ = gpu_bits(name)
+    S = len(sr.case(name)['cams'])
+    check_one_hot_maps(sr.case(name), gpu_bits(name), sorted({0, 1, S // 2, S - 2, S - 1, 255 % S, 256 % S}))
+
+
+def check_one_hot_maps(c, bits, js):
+    inc, _, got, _ = bits
     S, P = got.shape
-    js = sorted({0, 1, S // 2, S - 2, S - 1, 255 % S, 256 % S})
     sal = np.zeros((len(js), S), np.float32)
     sal[np.arange(len(js)), js] = 3.7
     a = ops.sphere_eval_weights(c['src'][0], c['mode'], inc.device)
@@ -203,7 +220,11 @@ def viewers(seed, per_frame):
 @pytest.mark.parametrize('name,L', [('s2x4_g5x9', 3), ('s4x8_g12x24', 1), ('s4x8_g12x24_wide', 8), ('s7x14_g30x60', 3),
                                     ('s7x14_g30x60_9x16', 4)])
 def test_quality(name, L):
-    c = sr.case(name)
+    check_quality(sr.case(name), L)
+
+
+def check_quality(c, L):
+    name = c['name']
     (h, w), tiles, view = c['grid'], c['tiles'], c['view']
     T = tiles[0] * tiles[1]
     R, off = viewers(200 + L, [0, 1, 4, 5, 0, 3])                      # 0, 1, 4 and 5 viewers: the four pairs of a workgroup

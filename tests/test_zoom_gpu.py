@@ -138,6 +138,10 @@ OUTLINE_FOVS = (60.0, 90.0, 120.0, 60.0)                               # three f
 @pytest.mark.parametrize('border_px', [1, 3])
 @pytest.mark.parametrize('HW', [(33, 66), (64, 128)])
 def test_outline_equals_the_one_frame_calls(HW, border_px, alias):
+    check_outline_equals_the_one_frame_calls(HW, border_px, alias)
+
+
+def check_outline_equals_the_one_frame_calls(HW, border_px, alias):
     H, W = HW
     frames = np.stack([np.rint(255.0 * vr.texture(2250 + n, H, W, 3)).astype(np.uint8) for n in range(4)])
     R = dev(ar.cameras4().astype(np.float32))
@@ -204,8 +208,12 @@ def agreement_case():
 def test_agreement_equals_the_scalar_calls(cam_hw, mode):
     """h / w is a power of two: the lens's (float)(t h / w) and the scalar entry's (float)(t aspect) are the same float, so the
     integers must be equal."""
-    offsets, R, Rc = agreement_case()
-    view = hr.VIEW_A
+    check_agreement_equals_the_scalar_calls(agreement_case(), AGREE_GRID, hr.VIEW_A, cam_hw, mode)
+
+
+def check_agreement_equals_the_scalar_calls(case, AGREE_GRID, view, cam_hw, mode):
+    """case = (offsets, R, Rc) with four frames, one per field of view of AGREE_FOVS."""
+    offsets, R, Rc = case
     a = ops.sphere_eval_weights(AGREE_GRID[0], mode, DEV)
     lens = ops.viewport_lens(AGREE_FOVS, cam_hw, device=DEV)
     inter, uni = ops.head_agreement_zoom(dev(Rc), lens, dev(R), dev(offsets), AGREE_GRID, view, a)
@@ -225,13 +233,24 @@ def test_agreement_equals_the_scalar_calls(cam_hw, mode):
 def test_agreement_against_the_restatement():
     """A 9 x 16 camera view: the sums lie between the restatement's with every pixel float32 cannot decide (tests/
     headtrack_restate.py: within 8 d32 of a threshold) counted outside and inside."""
-    offsets, R, Rc = agreement_case()
-    h, w = AGREE_GRID
-    view, cam_hw = hr.VIEW_A, (9, 16)
+    check_agreement_against_the_restatement(agreement_bounds_case(agreement_case(), AGREE_GRID, hr.VIEW_A, (9, 16)))
+
+
+def agreement_bounds_case(case, grid, view, cam_hw):
+    """The float64 classification of the viewers and of every frame's camera under its own field of view, as a case of
+    ``headtrack_restate.agreement_bounds``; no GPU call."""
+    offsets, R, Rc = case
+    h, w = grid
     ins, und = hr.classify(R, h, w, view)
     cams = [hr.classify(Rc[f:f + 1], h, w, (cam_hw, AGREE_FOVS[f])) for f in range(len(AGREE_FOVS))]
-    c = dict(R=R, offsets=offsets, weights=hr.row_weights(h, 'solid_angle'), ins=ins, und=und,
-             cins=np.concatenate([x[0] for x in cams]), cund=np.concatenate([x[1] for x in cams]))
+    return dict(R=R, Rc=Rc, offsets=offsets, grid=grid, view=view, cam_hw=cam_hw, weights=hr.row_weights(h, 'solid_angle'), ins=ins,
+                und=und, cins=np.concatenate([x[0] for x in cams]), cund=np.concatenate([x[1] for x in cams]))
+
+
+def check_agreement_against_the_restatement(c):
+    offsets, R, Rc, AGREE_GRID, view, cam_hw = c['offsets'], c['R'], c['Rc'], c['grid'], c['view'], c['cam_hw']
+    h, w = AGREE_GRID
+    assert int(c['und'].sum() + c['cund'].sum()) <= 0.02 * int(c['ins'].sum())     # float32 has (almost) nothing to decide
     b = hr.agreement_bounds(c)
     a = ops.sphere_eval_weights(h, 'solid_angle', DEV)
     inter, uni = ops.head_agreement_zoom(dev(Rc), ops.viewport_lens(AGREE_FOVS, cam_hw, device=DEV), dev(R), dev(offsets),
@@ -239,7 +258,6 @@ def test_agreement_against_the_restatement():
     inter, uni = inter.cpu().numpy(), uni.cpu().numpy()
     print('agreement zoom: inter %s in [%s, %s]' % (inter.tolist(), b[0].tolist(), b[1].tolist()))
     assert np.all(b[0] <= inter) and np.all(inter <= b[1]) and np.all(b[2] <= uni) and np.all(uni <= b[3])
-    assert int(c['und'].sum() + c['cund'].sum()) <= 0.02 * int(c['ins'].sum())     # float32 has (almost) nothing to decide
     # a NaN tangent is an empty view: inter 0, uni the viewer's own area
     lens = ops.viewport_lens_host(AGREE_FOVS, cam_hw)
     lens[2, 0] = np.nan
