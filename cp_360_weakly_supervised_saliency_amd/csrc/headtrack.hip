@@ -19,7 +19,8 @@
 //   K17b  agreement: a wave per pair, four pairs per workgroup; the wave finds its frame by a search in offsets, strides over the
 //         pixels with int32 partial sums (at most 2^15 pixels of weight 1024 a lane) and adds them up in 64 bits by
 //         wave_sum_down; no LDS, no barrier
-//   K22c  K17b with the camera's tangents per frame, from K22's lens table (DESIGN.md "K22")
+//   K22c  K17b's kernel with the camera's tangents per frame, from K22's lens table (DESIGN.md "K22"): one kernel template over
+//         sphere.h's lens sources serves both
 #pragma clang fp contract(off)
 #include "roc.h"
 
@@ -68,56 +69,23 @@ __global__ __launch_bounds__(256) void head_footprints_kernel(const float* __res
     }
 }
 
-// ------------------------------------------------------------------ K17b: agreement
-// grid ceil(N / 4), 256 threads; the frame of pair k is sphere.h's fix_frame
-__global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_kernel(const float* __restrict__ Rc, const float* __restrict__ R,
-                                                                         const int* __restrict__ offsets, int N, int F,
-                                                                         const float2* __restrict__ tabx, const float2* __restrict__ taby,
-                                                                         const int* __restrict__ weights, long long* __restrict__ inter,
-                                                                         long long* __restrict__ uni, int h, int w, float ctx, float cty,
-                                                                         float tx, float ty) {
-    const int lane = threadIdx.x & 63;
-    const long long k = (long long)blockIdx.x * kHeadPairs + (threadIdx.x >> 6);
-    if (k >= N) return;                                                // the whole wave; the kernel has no barrier
-    const Rot cam = view_rot(Rc + (size_t)fix_frame(offsets, F, (int)k) * 9);
-    const Rot view = view_rot(R + k * 9);
-    const int P = h * w;
-    int x = lane % w, y = lane / w;
-    int si = 0, su = 0;
-    for (int i = lane; i < P; i += 64) {
-        float px, py, pz;
-        stab_dir(tabx[x], taby[y], px, py, pz);
-        const bool c = view_inside(cam, ctx, cty, px, py, pz), v = view_inside(view, tx, ty, px, py, pz);
-        const int a = fix_clamp(weights[y], 0, kMaxWeight);
-        si += c && v ? a : 0;
-        su += c || v ? a : 0;
-        x += 64;
-        while (x >= w) {
-            x -= w;
-            ++y;
-        }
-    }
-    const long long ti = wave_sum_down((long long)si), tu = wave_sum_down((long long)su);
-    if (lane == 0) {
-        inter[k] = ti;
-        uni[k] = tu;
-    }
-}
-
-// K22c: K17b with a lens per frame for the camera: head_agreement_kernel with (ctx, cty) = the first two values of
-// cam_lens[frame of pair k] (K22's lens (tx, ty, b, 0), one 16-byte load, uniform over the wave); the viewers' window stays the
-// call's.  A tangent that is not finite fails every comparison of view_inside: that camera's view is empty.
-__global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_zoom_kernel(const float* __restrict__ Rc, const float4* __restrict__ cam_lens,
-                                                                              const float* __restrict__ R, const int* __restrict__ offsets,
-                                                                              int N, int F, const float2* __restrict__ tabx,
-                                                                              const float2* __restrict__ taby, const int* __restrict__ weights,
-                                                                              long long* __restrict__ inter, long long* __restrict__ uni, int h,
-                                                                              int w, float tx, float ty) {
+// ------------------------------------------------------------------ K17b, K22c: agreement
+// grid ceil(N / 4), 256 threads; the frame of pair k is sphere.h's fix_frame.  The camera's tangents (ctx, cty) are the first two
+// values of its lens at that frame - sphere.h's LensFixed for the one view of K17b, LensTable for K22's table (one 16-byte load,
+// uniform over the wave); the viewers' window (tx, ty) is the call's.  A tangent that is not finite fails every comparison of
+// view_inside: that camera's view is empty.
+template <typename Lens>
+__global__ __launch_bounds__(64 * kHeadPairs) void head_agreement_kernel(const float* __restrict__ Rc, const Lens cam_lens,
+                                                                         const float* __restrict__ R, const int* __restrict__ offsets,
+                                                                         int N, int F, const float2* __restrict__ tabx,
+                                                                         const float2* __restrict__ taby, const int* __restrict__ weights,
+                                                                         long long* __restrict__ inter, long long* __restrict__ uni, int h,
+                                                                         int w, float tx, float ty) {
     const int lane = threadIdx.x & 63;
     const long long k = (long long)blockIdx.x * kHeadPairs + (threadIdx.x >> 6);
     if (k >= N) return;                                                // the whole wave; the kernel has no barrier
     const int f = fix_frame(offsets, F, (int)k);
-    const float4 L = cam_lens[f];
+    const float4 L = cam_lens.at(f);
     const float ctx = L.x, cty = L.y;
     const Rot cam = view_rot(Rc + (size_t)f * 9);
     const Rot view = view_rot(R + k * 9);
@@ -156,6 +124,31 @@ int head_cameras(const float* R, const int32_t* offsets, long long N, int F, int
     return CP360_OK;
 }
 
+// K17b and K22c: the checks of both entry points in the order of their statuses, the tables and the launch.  cam_st is what the
+// entry point found about the camera's lens: CP360_OK, or the status to return where these checks reach it.
+template <typename Lens>
+int head_agreement(const float* Rc, Lens cam_lens, int cam_st, const float* R, const int32_t* offsets, long long N, int F, int h, int w,
+                   double hfov_rad, double aspect, const int32_t* weights, long long* inter, long long* uni, void* work,
+                   size_t work_bytes, void* stream) {
+    if (!Rc || !weights || !work || ((!inter || !uni) && N > 0) || cam_st == CP360_ERR_NULL) return CP360_ERR_NULL;
+    int st = head_cameras(R, offsets, N, F, h, w);
+    if (st != CP360_OK) return st;
+    float tx, ty;
+    if (cam_st == CP360_ERR_BAD_SHAPE || !head_tangents(hfov_rad, aspect, &tx, &ty)) return CP360_ERR_BAD_SHAPE;
+    if ((((uintptr_t)Rc | (uintptr_t)weights) & 3) != 0 || cam_st == CP360_ERR_ALIGN || (((uintptr_t)inter | (uintptr_t)uni) & 7) != 0)
+        return CP360_ERR_ALIGN;
+    st = check_work(work, work_bytes, tab_bytes(h, w));
+    if (st != CP360_OK || N == 0) return st;                           // no pairs: nothing to launch
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs t;
+    st = launch_tables(work, h, w, s, &t);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(head_agreement_kernel<Lens>, dim3((unsigned)((N + kHeadPairs - 1) / kHeadPairs)), dim3(64 * kHeadPairs), 0, s, Rc,
+                       cam_lens, R, (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, inter, uni, h, w, tx, ty);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
@@ -180,44 +173,16 @@ extern "C" int cp360_head_footprints(const float* R, const int32_t* offsets, lon
 extern "C" int cp360_head_agreement(const float* Rc, double cam_hfov_rad, double cam_aspect, const float* R, const int32_t* offsets,
                                     long long N, int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights,
                                     long long* inter, long long* uni, void* work, size_t work_bytes, void* stream) {
-    if (!Rc || !weights || !work || ((!inter || !uni) && N > 0)) return CP360_ERR_NULL;
-    int st = head_cameras(R, offsets, N, F, h, w);
-    if (st != CP360_OK) return st;
-    float ctx, cty, tx, ty;
-    if (!head_tangents(cam_hfov_rad, cam_aspect, &ctx, &cty) || !head_tangents(hfov_rad, aspect, &tx, &ty)) return CP360_ERR_BAD_SHAPE;
-    if ((((uintptr_t)Rc | (uintptr_t)weights) & 3) != 0 || (((uintptr_t)inter | (uintptr_t)uni) & 7) != 0) return CP360_ERR_ALIGN;
-    st = check_work(work, work_bytes, tab_bytes(h, w));
-    if (st != CP360_OK || N == 0) return st;                           // no pairs: nothing to launch
-    hipStream_t s = (hipStream_t)stream;
-    SphereTabs t;
-    st = launch_tables(work, h, w, s, &t);
-    if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(head_agreement_kernel, dim3((unsigned)((N + kHeadPairs - 1) / kHeadPairs)), dim3(64 * kHeadPairs), 0, s, Rc, R,
-                       (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, inter, uni, h, w, ctx, cty, tx, ty);
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    LensFixed cam = {};
+    const int cam_st = head_tangents(cam_hfov_rad, cam_aspect, &cam.tx, &cam.ty) ? CP360_OK : CP360_ERR_BAD_SHAPE;
+    return head_agreement(Rc, cam, cam_st, R, offsets, N, F, h, w, hfov_rad, aspect, weights, inter, uni, work, work_bytes, stream);
 }
 
-// K22c: cp360_head_agreement's checks in its order, the cameras' lenses in place of their view
+// K22c: the cameras' lenses in place of their view
 extern "C" int cp360_head_agreement_zoom(const float* Rc, const float* cam_lens, const float* R, const int32_t* offsets, long long N,
                                          int F, int h, int w, double hfov_rad, double aspect, const int32_t* weights, long long* inter,
                                          long long* uni, void* work, size_t work_bytes, void* stream) {
-    if (!Rc || !cam_lens || !weights || !work || ((!inter || !uni) && N > 0)) return CP360_ERR_NULL;
-    int st = head_cameras(R, offsets, N, F, h, w);
-    if (st != CP360_OK) return st;
-    float tx, ty;
-    if (!head_tangents(hfov_rad, aspect, &tx, &ty)) return CP360_ERR_BAD_SHAPE;
-    if ((((uintptr_t)Rc | (uintptr_t)weights) & 3) != 0 || !aligned16(cam_lens) || (((uintptr_t)inter | (uintptr_t)uni) & 7) != 0)
-        return CP360_ERR_ALIGN;
-    st = check_work(work, work_bytes, tab_bytes(h, w));
-    if (st != CP360_OK || N == 0) return st;                           // no pairs: nothing to launch
-    hipStream_t s = (hipStream_t)stream;
-    SphereTabs t;
-    st = launch_tables(work, h, w, s, &t);
-    if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(head_agreement_zoom_kernel, dim3((unsigned)((N + kHeadPairs - 1) / kHeadPairs)), dim3(64 * kHeadPairs), 0, s, Rc,
-                       (const float4*)cam_lens, R, (const int*)offsets, (int)N, F, t.x, t.y, (const int*)weights, inter, uni, h, w, tx,
-                       ty);
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    const int cam_st = !cam_lens ? CP360_ERR_NULL : (!aligned16(cam_lens) ? CP360_ERR_ALIGN : CP360_OK);
+    return head_agreement(Rc, LensTable{(const float4*)cam_lens}, cam_st, R, offsets, N, F, h, w, hfov_rad, aspect, weights, inter, uni,
+                          work, work_bytes, stream);
 }

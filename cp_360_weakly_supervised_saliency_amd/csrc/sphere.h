@@ -2,7 +2,7 @@
 // fixations.hip (K15), headtrack.hip (K17), egomotion.hip (K23), streaming.hip (K24) and, through sphere_eval.hip's resampler, suploss.hip (K18): the one definition of dir, pix, the rotation of a direction, the (cos, sin) tables
 // of the pixel centres and the bilinear sample that wraps in x and clamps in y (DESIGN.md "K11" geometry;
 // tests/stabilize_restate.py restates it); and what their kernels and entry points repeat: the von Mises-Fisher term, whether a
-// direction lies in a camera's view, the items of a frame in CSR form, the ordered sum of a 256-thread workgroup, how a caller's
+// direction lies in a camera's view, the lens of a view as a value or a table, the items of a frame in CSR form, the ordered sum of a 256-thread workgroup, how a caller's
 // workspace is opened and the dispatch on the pixel type (DESIGN.md "What the sphere kernels share").
 //
 //     theta = (2 (x + 1/2) / W - 1) pi        phi = (1 - 2 (y + 1/2) / H) pi / 2        dir = (cos phi cos theta, sin phi, cos phi sin theta)
@@ -119,28 +119,54 @@ __device__ __forceinline__ float vmf(float kappa, float px, float py, float pz, 
 }
 
 // ------------------------------------------------------------------ the view of a camera on the panorama (K17; K12b's decision)
+// whether every entry of R is finite: one sum, which a single non-finite entry leaves non-finite
+__device__ __forceinline__ bool rot_finite(const Rot& R) {
+    const float s = fabsf(R.r00) + fabsf(R.r01) + fabsf(R.r02) + fabsf(R.r10) + fabsf(R.r11) + fabsf(R.r12) + fabsf(R.r20) +
+                    fabsf(R.r21) + fabsf(R.r22);
+    return isfinite(s);
+}
+
 // A camera is K12's: camera-to-world, columns (forward, up, right).  view_rot loads one for view_inside: a camera with a
 // non-finite entry comes back all NaN, so that every comparison below fails - its view is empty.
 __device__ __forceinline__ Rot view_rot(const float* R) {
     Rot r = load_rot(R);
-    const float s = fabsf(r.r00) + fabsf(r.r01) + fabsf(r.r02) + fabsf(r.r10) + fabsf(r.r11) + fabsf(r.r12) + fabsf(r.r20) +
-                    fabsf(r.r21) + fabsf(r.r22);
-    if (!isfinite(s)) r.r00 = r.r01 = r.r02 = r.r10 = r.r11 = r.r12 = r.r20 = r.r21 = r.r22 = NAN;
+    if (!rot_finite(r)) r.r00 = r.r01 = r.r02 = r.r10 = r.r11 = r.r12 = r.r20 = r.r21 = r.r22 = NAN;
     return r;
 }
 
 __device__ __forceinline__ bool view_rot_finite(const Rot& r) { return r.r00 == r.r00; }   // of view_rot's result
 
-// whether the direction p lies in the view of the camera R (from view_rot) with the tangents tx = tan(hfov / 2), ty = tx h / w:
-// d = R^T p = (d_f, d_u, d_r), u = d_r / d_f, v = d_u / d_f, inside <=> d_f > 0, |u| <= tx, |v| <= ty - view_outline_kernel's
-// terms in its order
-__device__ __forceinline__ bool view_inside(const Rot& R, float tx, float ty, float px, float py, float pz) {
-    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
+// the view-frame terms of the direction p under the camera R: d = R^T p = (d_f, d_u, d_r) -> d_f, au = |d_r / d_f|, av =
+// |d_u / d_f|.  K12b's decision and K17's are comparisons of these three, so both see the same bits.
+__device__ __forceinline__ void view_terms(const Rot& R, float px, float py, float pz, float& df, float& au, float& av) {
+    df = R.r00 * px + R.r10 * py + R.r20 * pz;
     const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
     const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
-    const float au = fabsf(dr / df), av = fabsf(du / df);
+    au = fabsf(dr / df);
+    av = fabsf(du / df);
+}
+
+// whether the direction p lies in the view of the camera R (from view_rot) with the tangents tx = tan(hfov / 2), ty = tx h / w:
+// inside <=> d_f > 0, |u| <= tx, |v| <= ty
+__device__ __forceinline__ bool view_inside(const Rot& R, float tx, float ty, float px, float py, float pz) {
+    float df, au, av;
+    view_terms(R, px, py, pz, df, au, av);
     return df > 0.f && au <= tx && av <= ty;
 }
+
+// ------------------------------------------------------------------ the lens of a view, as a value a kernel asks for (K22)
+// A lens is (tx, ty, b, 0): the two tangents and K12b's border in tangent units.  A kernel template takes either source and
+// calls at(frame).  LensFixed is one lens for every frame, by value in the kernel's arguments; LensTable is a lens per frame,
+// f32 [N][4] on the device, 16-byte aligned: one 16-byte load at an address that a workgroup (a wave) shares.
+struct LensFixed {
+    float tx, ty, b;
+    __device__ __forceinline__ float4 at(int) const { return make_float4(tx, ty, b, 0.f); }
+};
+
+struct LensTable {
+    const float4* lens;
+    __device__ __forceinline__ float4 at(int frame) const { return lens[frame]; }
+};
 
 // ------------------------------------------------------------------ items in CSR form (K15's points, K17's cameras)
 __device__ __forceinline__ int fix_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

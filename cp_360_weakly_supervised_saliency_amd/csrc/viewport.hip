@@ -7,7 +7,9 @@
 // reference's utils/fov_visual.py (box_proh, fov_module, draw_cube_fov_box) has this purpose and does not compile; the
 // specification is the package's own, DESIGN.md "K12", "K16", "K20", "K21" and "K22"; tests/viewport_restate.py restates K12 in
 // float64, tests/campath_restate.py K16 in integers, tests/director_restate.py K20, tests/viewport_aa_restate.py K21,
-// tests/zoom_restate.py K22.  Geometry, tables and the bilinear sample are sphere.h's.
+// tests/zoom_restate.py K22.  Geometry, tables and the bilinear sample are sphere.h's, and so are the view-frame terms of K12b
+// and the two sources of a lens: the view (K12a, K21, K22a) and its frame (K12b, K22b) are one kernel template each, which asks
+// its source for the lens of a frame - one lens by value for the scalar entry points, K22's table for the _zoom ones.
 //
 // Camera: R f32 [N, 3, 3] row-major, camera-to-world, columns (forward, up, right).  R = I looks along dir of the panorama's
 // centre (1, 0, 0) with up +y and right +z.  tx = tan(hfov / 2), ty = tx h / w (double on the host, rounded to f32 once).
@@ -43,12 +45,6 @@
 namespace {
 
 constexpr int kMaxMapPx = 16384;             // K12c is all pairs: P^2 terms per frame
-
-__device__ __forceinline__ bool rot_finite(const Rot& R) {
-    const float s = fabsf(R.r00) + fabsf(R.r01) + fabsf(R.r02) + fabsf(R.r10) + fabsf(R.r11) + fabsf(R.r12) + fabsf(R.r20) +
-                    fabsf(R.r21) + fabsf(R.r22);
-    return isfinite(s);
-}
 
 // K12d's argmax, one step of its tree (the tree of sphere.h's ordered sum): the candidate (ov, oi) replaces (best, bi) when it
 // has the larger value, or the same value at a lower index; an index below 0 is no candidate
@@ -116,44 +112,39 @@ __device__ __forceinline__ void view_pixel_ss(const T* __restrict__ img, const R
     }
 }
 
-// grid (ceil(w / 256), h, N): one thread per view pixel, all C channels
-template <typename T, int C>
-__global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ src, const float* __restrict__ Rs, T* __restrict__ dst,
-                                                          int H, int W, int h, int w, float tx, float ty) {
-    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
-    if (i >= w) return;
-    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    view_pixel<T, C>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j, dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
-}
+// The factor of a frame, as sphere.h's lens a value the kernel asks for.  FactorFixed<NS> is one factor for every frame, known
+// when the kernel is compiled: 1 is K12a's pixel, 2 .. 4 K21's.  FactorTable is K22a's factor per frame, int32 [N] on the device:
+// uniform over the workgroup, so view_pixel_ss's switch does not diverge; a factor outside 2 .. 4 is 1 there.
+template <int NS>
+struct FactorFixed {
+    template <typename T, int C>
+    __device__ __forceinline__ void pixel(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty, int i,
+                                          int j, int, T* __restrict__ o) const {
+        if constexpr (NS == 1) view_pixel<T, C>(img, R, H, W, h, w, tx, ty, i, j, o);
+        else view_pixel_aa<T, C, NS>(img, R, H, W, h, w, tx, ty, i, j, o);
+    }
+};
 
-// K21: the anti-aliased view, NS = 2, 3, 4.  K12a's grid and thread mapping: one thread per view pixel, its NS NS samples one after
-// the other in registers
-template <typename T, int C, int NS>
-__global__ __launch_bounds__(256) void view_render_aa_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
-                                                             T* __restrict__ dst, int H, int W, int h, int w, float tx, float ty) {
-    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
-    if (i >= w) return;
-    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    view_pixel_aa<T, C, NS>(src + (size_t)blockIdx.z * H * W * C, R, H, W, h, w, tx, ty, i, j,
-                            dst + (((size_t)blockIdx.z * h + j) * w + i) * C);
-}
+struct FactorTable {
+    const int* ss;
+    template <typename T, int C>
+    __device__ __forceinline__ void pixel(const T* __restrict__ img, const Rot& R, int H, int W, int h, int w, float tx, float ty, int i,
+                                          int j, int frame, T* __restrict__ o) const {
+        view_pixel_ss<T, C>(img, R, H, W, h, w, tx, ty, i, j, ss[frame], o);
+    }
+};
 
-// K22a: K12a / K21 with a lens per frame.  K12a's grid and thread mapping; frame blockIdx.z takes (tx, ty) from its lens (tx, ty, b,
-// 0) in one 16-byte load, the same address for the whole workgroup, and with AA its factor from ss[blockIdx.z]: uniform over the
-// workgroup, so view_pixel_ss's switch does not diverge; a factor outside 2 .. 4 is 1 there.  AA = false never reads ss and calls
-// view_pixel.  A tangent that is not finite or not positive decides no address: it ends in the sampler's guard, as a non-finite R.
-template <typename T, int C, bool AA>
-__global__ __launch_bounds__(256) void view_render_zoom_kernel(const T* __restrict__ src, const float* __restrict__ Rs,
-                                                               const float4* __restrict__ lens, const int* __restrict__ ss,
-                                                               T* __restrict__ dst, int H, int W, int h, int w) {
-    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+// K12a, K21 and K22a: the view of frame blockIdx.z under its camera, with the (tx, ty) of its lens and its factor.  grid
+// (ceil(w / 256), h, N): one thread per view pixel, all C channels, the samples of a factor above 1 one after the other in
+// registers.  A tangent that is not finite or not positive decides no address: it ends in the sampler's guard, as a non-finite R.
+template <typename T, int C, typename Lens, typename Factor>
+__global__ __launch_bounds__(256) void view_render_kernel(const T* __restrict__ src, const float* __restrict__ Rs, const Lens lens,
+                                                          const Factor factor, T* __restrict__ dst, int H, int W, int h, int w) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, n = blockIdx.z;
     if (i >= w) return;
-    const float4 L = lens[blockIdx.z];
-    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    const T* img = src + (size_t)blockIdx.z * H * W * C;
-    T* o = dst + (((size_t)blockIdx.z * h + j) * w + i) * C;
-    if (AA) view_pixel_ss<T, C>(img, R, H, W, h, w, L.x, L.y, i, j, ss[blockIdx.z], o);
-    else view_pixel<T, C>(img, R, H, W, h, w, L.x, L.y, i, j, o);
+    const float4 L = lens.at(n);
+    const Rot R = load_rot(Rs + (size_t)n * 9);
+    factor.template pixel<T, C>(src + (size_t)n * H * W * C, R, H, W, h, w, L.x, L.y, i, j, n, dst + (((size_t)n * h + j) * w + i) * C);
 }
 
 // ------------------------------------------------------------------ K20b: several views on one canvas
@@ -243,53 +234,23 @@ __global__ __launch_bounds__(256) void view_exclude_kernel(const float* maps, co
     else if (out != maps) out[o] = maps[o];
 }
 
-// ------------------------------------------------------------------ K12b: the view's frame on the panorama
-// grid (ceil(W / 256), H, N); element-wise, so dst may be src
-__global__ __launch_bounds__(256) void view_outline_kernel(const uint8_t* src, const float* __restrict__ Rs,
+// ------------------------------------------------------------------ K12b, K22b: the view's frame on the panorama
+// grid (ceil(W / 256), H, N); element-wise, so dst may be src.  Frame blockIdx.z takes (tx, ty, b) from its lens and compares
+// sphere.h's view-frame terms with them.  A frame whose b is not greater than 0 (a NaN too) draws nothing: a table may hold
+// one; for the one lens of cp360_view_outline, finite and not below 0, the term changes nothing, since with b = 0 inner is the
+// au / av half of inside.
+template <typename Lens>
+__global__ __launch_bounds__(256) void view_outline_kernel(const uint8_t* src, const float* __restrict__ Rs, const Lens lens,
                                                            const float2* __restrict__ tabx, const float2* __restrict__ taby,
-                                                           uint8_t* dst, int H, int W, float tx, float ty, float b, int cr, int cg,
-                                                           int cb) {
+                                                           uint8_t* dst, int H, int W, int cr, int cg, int cb) {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
-    const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    float px, py, pz;
-    stab_dir(tabx[x], taby[y], px, py, pz);
-    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
-    const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
-    const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
-    const float au = fabsf(dr / df), av = fabsf(du / df);
-    const bool inside = df > 0.f && au <= tx && av <= ty;
-    const bool inner = au <= tx - b && av <= ty - b;
-    const size_t o = (((size_t)blockIdx.z * H + y) * W + x) * 3;
-    if (inside && !inner && rot_finite(R)) {
-        dst[o] = (uint8_t)cr;
-        dst[o + 1] = (uint8_t)cg;
-        dst[o + 2] = (uint8_t)cb;
-    } else if (dst != src) {
-        const uint8_t v0 = src[o], v1 = src[o + 1], v2 = src[o + 2];
-        dst[o] = v0;
-        dst[o + 1] = v1;
-        dst[o + 2] = v2;
-    }
-}
-
-// K22b: K12b with a lens per frame: view_outline_kernel's decision with (tx, ty, b) of frame blockIdx.z, its terms in its order.
-// A frame whose b is not greater than 0 (a NaN too) draws nothing.  Element-wise, so dst may be src.
-__global__ __launch_bounds__(256) void view_outline_zoom_kernel(const uint8_t* src, const float* __restrict__ Rs,
-                                                                const float4* __restrict__ lens, const float2* __restrict__ tabx,
-                                                                const float2* __restrict__ taby, uint8_t* dst, int H, int W, int cr,
-                                                                int cg, int cb) {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= W) return;
-    const float4 L = lens[blockIdx.z];
+    const float4 L = lens.at(blockIdx.z);
     const float tx = L.x, ty = L.y, b = L.z;
     const Rot R = load_rot(Rs + (size_t)blockIdx.z * 9);
-    float px, py, pz;
+    float px, py, pz, df, au, av;
     stab_dir(tabx[x], taby[y], px, py, pz);
-    const float df = R.r00 * px + R.r10 * py + R.r20 * pz;
-    const float du = R.r01 * px + R.r11 * py + R.r21 * pz;
-    const float dr = R.r02 * px + R.r12 * py + R.r22 * pz;
-    const float au = fabsf(dr / df), av = fabsf(du / df);
+    view_terms(R, px, py, pz, df, au, av);
     const bool inside = df > 0.f && au <= tx && av <= ty;
     const bool inner = au <= tx - b && av <= ty - b;
     const size_t o = (((size_t)blockIdx.z * H + y) * W + x) * 3;
@@ -391,6 +352,13 @@ __device__ __forceinline__ void mean_shift_step(const float* __restrict__ s, con
     dir[2] = oz;
 }
 
+// "look ahead": the direction of a frame without a target, the panorama's centre
+__device__ __forceinline__ void look_ahead(float* __restrict__ dir) {
+    dir[0] = 1.f;
+    dir[1] = 0.f;
+    dir[2] = 0.f;
+}
+
 // ------------------------------------------------------------------ K12d: the peak and one mean-shift step
 // grid F, 256 threads: thread t takes pixels t, t + 256, .. in order, then the shuffle tree, then the 4 waves in order
 __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict__ smooth, const float* __restrict__ maps,
@@ -431,9 +399,7 @@ __global__ __launch_bounds__(256) void view_peak_kernel(const float* __restrict_
     nfin = waves4_sum(red_n, 1);
     if (bi < 0 || nfin == 0) {                                          // nothing finite: look ahead
         if (tid == 0) {
-            dir_out[(size_t)f * 3] = 1.f;
-            dir_out[(size_t)f * 3 + 1] = 0.f;
-            dir_out[(size_t)f * 3 + 2] = 0.f;
+            look_ahead(dir_out + (size_t)f * 3);
             idx_out[f] = -1;
             val_out[f] = nanf("");
         }
@@ -662,11 +628,7 @@ __global__ __launch_bounds__(256) void view_refine_kernel(const float* __restric
     __shared__ double red_c[4][3];
     const int P = hm * wm, f = blockIdx.x, bi = idx[f];
     if (bi < 0 || bi >= P) {
-        if (threadIdx.x == 0) {
-            dir_out[(size_t)f * 3] = 1.f;
-            dir_out[(size_t)f * 3 + 1] = 0.f;
-            dir_out[(size_t)f * 3 + 2] = 0.f;
-        }
+        if (threadIdx.x == 0) look_ahead(dir_out + (size_t)f * 3);
         return;
     }
     mean_shift_step(maps + (size_t)f * P, tabx, taby, hm, wm, kappa, bi, red_c, dir_out + (size_t)f * 3);
@@ -679,43 +641,17 @@ bool bad_hfov(double hfov) { return !(hfov > 0.0 && hfov < kPi); }
 
 // The lens of a view (h, w) of hfov radians with a border of border_px view pixels, each value rounded to f32 once: what every
 // entry point hands its kernel, and a row of cp360_view_lens_host's table (K22)
-struct ViewLens {
-    float tx, ty, b;
-};
-
-ViewLens view_lens(double hfov_rad, int h, int w, double border_px) {
+LensFixed view_lens(double hfov_rad, int h, int w, double border_px) {
     const double t = tan(0.5 * hfov_rad);
     return {(float)t, (float)(t * (double)h / (double)w), border_px == 0.0 ? 0.f : (float)(border_px * 2.0 * t / (double)w)};
 }
 bool bad_sigma(double sigma) { return !(sigma > 0.0) || !isfinite(sigma); }
 
-template <typename T, int C>
-int launch_render(const void* frames, const float* R, void* out, int N, int H, int W, int h, int w, float tx, float ty,
+template <typename T, int C, typename Lens, typename Factor>
+int launch_render(const void* frames, const float* R, Lens lens, Factor factor, void* out, int N, int H, int W, int h, int w,
                   hipStream_t s) {
-    hipLaunchKernelGGL((view_render_kernel<T, C>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R, (T*)out, H, W,
-                       h, w, tx, ty);
-    CP360_CHECK_HIP();
-    return CP360_OK;
-}
-
-template <typename T, int C, int NS>
-int launch_render_aa(const void* frames, const float* R, void* out, int N, int H, int W, int h, int w, float tx, float ty,
-                     hipStream_t s) {
-    hipLaunchKernelGGL((view_render_aa_kernel<T, C, NS>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R, (T*)out,
-                       H, W, h, w, tx, ty);
-    CP360_CHECK_HIP();
-    return CP360_OK;
-}
-
-// K22a: ss = the N factors on the device, or nullptr for one sample per pixel in every frame
-template <typename T, int C>
-int launch_render_zoom(const void* frames, const float* R, const float* lens, const int32_t* ss, void* out, int N, int H, int W,
-                       int h, int w, hipStream_t s) {
-    const dim3 grid((w + 255) / 256, h, N);
-    if (ss) hipLaunchKernelGGL((view_render_zoom_kernel<T, C, true>), grid, dim3(256), 0, s, (const T*)frames, R, (const float4*)lens,
-                               (const int*)ss, (T*)out, H, W, h, w);
-    else hipLaunchKernelGGL((view_render_zoom_kernel<T, C, false>), grid, dim3(256), 0, s, (const T*)frames, R, (const float4*)lens,
-                            (const int*)nullptr, (T*)out, H, W, h, w);
+    hipLaunchKernelGGL((view_render_kernel<T, C, Lens, Factor>), dim3((w + 255) / 256, h, N), dim3(256), 0, s, (const T*)frames, R,
+                       lens, factor, (T*)out, H, W, h, w);
     CP360_CHECK_HIP();
     return CP360_OK;
 }
@@ -802,34 +738,62 @@ int path_big_lds() {
     return CP360_OK;
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------ C ABI
-// K12a and K21 behind one list of checks: ss = 1 is K12a's kernel.  The fine view (ss h, ss w) must be a view K12a would take, so
-// that the identity with it holds wherever the call is accepted (h, w are within big_image's range before they are multiplied)
-static int view_render_ss(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad, int ss,
-                          void* out, int h, int w, void* stream) {
-    if (!frames || !R || !out) return CP360_ERR_NULL;
-    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1 || bad_hfov(hfov_rad) || ss < 1 || ss > 4) return CP360_ERR_BAD_SHAPE;
+// The checks of every view render, in the order of their statuses.  ss_max is the largest factor a frame may take: the fine view
+// (ss h, ss w) must be a view K12a would take, so that the identity with it holds wherever the call is accepted (h, w are
+// within big_image's range before they are multiplied).  lens_st is what the entry point found about its own lens and factors:
+// CP360_OK, or the status to return where the shared checks reach it.
+int render_args(int dtype, const void* frames, const float* R, const void* out, int N, int H, int W, int C, int h, int w, int ss_max,
+                int lens_st) {
+    if (!frames || !R || !out || lens_st == CP360_ERR_NULL) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1 || lens_st == CP360_ERR_BAD_SHAPE) return CP360_ERR_BAD_SHAPE;
     if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
-    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || big_image(N, ss * h, ss * w))
+    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || big_image(N, ss_max * h, ss_max * w))
         return CP360_ERR_UNSUPPORTED;
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
-    const ViewLens lens = view_lens(hfov_rad, h, w, 0.0);
-    const float tx = lens.tx, ty = lens.ty;
+    return lens_st;
+}
+
+// K12a and K21: ss = 1 is K12a's pixel
+int view_render_ss(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad, int ss, void* out,
+                   int h, int w, void* stream) {
+    const bool bad = bad_hfov(hfov_rad) || ss < 1 || ss > 4;
+    const int st = render_args(dtype, frames, R, out, N, H, W, C, h, w, bad ? 1 : ss, bad ? CP360_ERR_BAD_SHAPE : CP360_OK);
+    if (st != CP360_OK) return st;
+    const LensFixed lens = view_lens(hfov_rad, h, w, 0.0);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
         using T = decltype(px);
         constexpr int Cn = decltype(c)::value;
         switch (ss) {
-            case 2: return launch_render_aa<T, Cn, 2>(frames, R, out, N, H, W, h, w, tx, ty, s);
-            case 3: return launch_render_aa<T, Cn, 3>(frames, R, out, N, H, W, h, w, tx, ty, s);
-            case 4: return launch_render_aa<T, Cn, 4>(frames, R, out, N, H, W, h, w, tx, ty, s);
-            default: return launch_render<T, Cn>(frames, R, out, N, H, W, h, w, tx, ty, s);
+            case 2: return launch_render<T, Cn>(frames, R, lens, FactorFixed<2>(), out, N, H, W, h, w, s);
+            case 3: return launch_render<T, Cn>(frames, R, lens, FactorFixed<3>(), out, N, H, W, h, w, s);
+            case 4: return launch_render<T, Cn>(frames, R, lens, FactorFixed<4>(), out, N, H, W, h, w, s);
+            default: return launch_render<T, Cn>(frames, R, lens, FactorFixed<1>(), out, N, H, W, h, w, s);
         }
     });
 }
 
+// K12b and K22b: the checks of both entry points, the tables and the launch; lens_st as render_args's
+template <typename Lens>
+int view_outline(const uint8_t* frames, const float* R, Lens lens, int lens_st, int N, int H, int W, const uint8_t* rgb, uint8_t* out,
+                 void* work, size_t work_bytes, void* stream) {
+    if (!frames || !R || !rgb || !out || !work || lens_st == CP360_ERR_NULL) return CP360_ERR_NULL;
+    if (bad_image(N, H, W) || lens_st == CP360_ERR_BAD_SHAPE) return CP360_ERR_BAD_SHAPE;
+    if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
+    if (lens_st != CP360_OK) return lens_st;
+    hipStream_t s = (hipStream_t)stream;
+    SphereTabs tabs;
+    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
+    if (st != CP360_OK) return st;
+    hipLaunchKernelGGL(view_outline_kernel<Lens>, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, lens, tabs.x, tabs.y, out, H,
+                       W, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
+    CP360_CHECK_HIP();
+    return CP360_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI
 extern "C" int cp360_view_render(int dtype, const void* frames, const float* R, int N, int H, int W, int C, double hfov_rad,
                                  void* out, int h, int w, void* stream) {
     return view_render_ss(dtype, frames, R, N, H, W, C, hfov_rad, 1, out, h, w, stream);
@@ -842,19 +806,9 @@ extern "C" int cp360_view_render_aa(int dtype, const void* frames, const float* 
 
 extern "C" int cp360_view_outline(const uint8_t* frames, const float* R, int N, int H, int W, double hfov_rad, int h, int w,
                                   double border_px, const uint8_t* rgb, uint8_t* out, void* work, size_t work_bytes, void* stream) {
-    if (!frames || !R || !rgb || !out || !work) return CP360_ERR_NULL;
-    if (bad_image(N, H, W) || bad_image(N, h, w) || bad_hfov(hfov_rad) || !(border_px > 0.0) || !isfinite(border_px))
-        return CP360_ERR_BAD_SHAPE;
-    if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    SphereTabs tabs;
-    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
-    if (st != CP360_OK) return st;
-    const ViewLens lens = view_lens(hfov_rad, h, w, border_px);
-    hipLaunchKernelGGL(view_outline_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, tabs.x, tabs.y, out, H, W,
-                       lens.tx, lens.ty, lens.b, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    const bool bad = bad_image(N, h, w) || bad_hfov(hfov_rad) || !(border_px > 0.0) || !isfinite(border_px);
+    const LensFixed lens = bad ? LensFixed{} : view_lens(hfov_rad, h, w, border_px);
+    return view_outline(frames, R, lens, bad ? CP360_ERR_BAD_SHAPE : CP360_OK, N, H, W, rgb, out, work, work_bytes, stream);
 }
 
 extern "C" int cp360_view_smooth(const float* maps, int F, int hm, int wm, double sigma_rad, float* out, void* work,
@@ -1003,7 +957,7 @@ static int view_render_multi_ss(int dtype, const void* frames, const float* R, i
     if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
     float tx[kMaxTiles], ty[kMaxTiles];
     for (int k = 0; k < K; ++k) {                                       // cp360_view_render's, per tile
-        const ViewLens lens = view_lens(hfov_rad[k], tiles[4 * k + 3], tiles[4 * k + 2], 0.0);
+        const LensFixed lens = view_lens(hfov_rad[k], tiles[4 * k + 3], tiles[4 * k + 2], 0.0);
         tx[k] = lens.tx;
         ty[k] = lens.ty;
     }
@@ -1035,7 +989,7 @@ extern "C" int cp360_view_lens_host(const double* hfov_rad, int N, int h, int w,
     for (int n = 0; n < N; ++n)
         if (bad_hfov(hfov_rad[n])) return CP360_ERR_BAD_SHAPE;
     for (int n = 0; n < N; ++n) {
-        const ViewLens l = view_lens(hfov_rad[n], h, w, border_px);
+        const LensFixed l = view_lens(hfov_rad[n], h, w, border_px);
         lens[4 * n] = l.tx;
         lens[4 * n + 1] = l.ty;
         lens[4 * n + 2] = l.b;
@@ -1044,36 +998,26 @@ extern "C" int cp360_view_lens_host(const double* hfov_rad, int N, int h, int w,
     return CP360_OK;
 }
 
-// view_render_ss's checks in its order, the lens in place of the field of view; then the alignment
+// view_render_ss with the lens in place of the field of view; the alignment is its last check
 extern "C" int cp360_view_render_zoom(int dtype, const void* frames, const float* R, const float* lens, const int32_t* ss, int N,
                                       int H, int W, int C, void* out, int h, int w, void* stream) {
-    if (!frames || !R || !lens || !out) return CP360_ERR_NULL;
-    if (bad_image(N, H, W) || bad_image(N, h, w) || C < 1) return CP360_ERR_BAD_SHAPE;
-    if (dtype != CP360_F32 && dtype != CP360_U8) return CP360_ERR_BAD_DTYPE;
-    if (C > 4 || (dtype == CP360_U8 && C != 3) || big_image(N, H, W) || big_image(N, h, w) || (ss && big_image(N, 4 * h, 4 * w)))
-        return CP360_ERR_UNSUPPORTED;
-    if (frames == out) return CP360_ERR_UNSUPPORTED;                   // a gather: not in place
-    if (!aligned16(lens) || ((uintptr_t)ss & 3) != 0) return CP360_ERR_ALIGN;
+    const int lens_st = !lens ? CP360_ERR_NULL : (!aligned16(lens) || ((uintptr_t)ss & 3) != 0 ? CP360_ERR_ALIGN : CP360_OK);
+    const int st = render_args(dtype, frames, R, out, N, H, W, C, h, w, ss ? 4 : 1, lens_st);
+    if (st != CP360_OK) return st;
+    const LensTable table = {(const float4*)lens};
     hipStream_t s = (hipStream_t)stream;
     return dispatch_pixels(dtype, C, [&](auto px, auto c) {
-        return launch_render_zoom<decltype(px), decltype(c)::value>(frames, R, lens, ss, out, N, H, W, h, w, s);
+        using T = decltype(px);
+        constexpr int Cn = decltype(c)::value;
+        if (ss) return launch_render<T, Cn>(frames, R, table, FactorTable{(const int*)ss}, out, N, H, W, h, w, s);
+        return launch_render<T, Cn>(frames, R, table, FactorFixed<1>(), out, N, H, W, h, w, s);
     });
 }
 
 extern "C" int cp360_view_outline_zoom(const uint8_t* frames, const float* R, const float* lens, int N, int H, int W,
                                        const uint8_t* rgb, uint8_t* out, void* work, size_t work_bytes, void* stream) {
-    if (!frames || !R || !lens || !rgb || !out || !work) return CP360_ERR_NULL;
-    if (bad_image(N, H, W)) return CP360_ERR_BAD_SHAPE;
-    if (big_image(N, H, W)) return CP360_ERR_UNSUPPORTED;
-    if (!aligned16(lens)) return CP360_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    SphereTabs tabs;
-    const int st = open_tabs(work, work_bytes, tab_bytes(H, W), H, W, s, &tabs);
-    if (st != CP360_OK) return st;
-    hipLaunchKernelGGL(view_outline_zoom_kernel, dim3((W + 255) / 256, H, N), dim3(256), 0, s, frames, R, (const float4*)lens, tabs.x,
-                       tabs.y, out, H, W, (int)rgb[0], (int)rgb[1], (int)rgb[2]);
-    CP360_CHECK_HIP();
-    return CP360_OK;
+    const int lens_st = !lens ? CP360_ERR_NULL : (!aligned16(lens) ? CP360_ERR_ALIGN : CP360_OK);
+    return view_outline(frames, R, LensTable{(const float4*)lens}, lens_st, N, H, W, rgb, out, work, work_bytes, stream);
 }
 
 extern "C" int cp360_view_spread(const float* maps, const float* dirs, int F, int hm, int wm, double window_rad, double level,

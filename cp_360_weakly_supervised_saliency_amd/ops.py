@@ -209,6 +209,40 @@ def _frames_nhwc(frames, u8_only, n='N'):
     return tuple(int(s) for s in frames.shape)
 
 
+def _map_shape(maps, why=''):
+    """The map checks of K12c, K12d, K16c, K20a and K22d -> (F, hm, wm): a non-empty contiguous float32 [F, hm, wm] of at most
+    16384 pixels."""
+    if maps.dim() != 3 or maps.numel() == 0:
+        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+    _check_buf('maps', maps, torch.float32)
+    F, hm, wm = (int(s) for s in maps.shape)
+    if hm * wm > 16384:
+        raise ValueError("maps of more than 16384 pixels are not supported%s, got %d x %d" % (why, hm, wm))
+    return F, hm, wm
+
+
+def _render_args(frames, R, h, w, out, *more):
+    """What K12a / K21 and K22a check alike (``viewport_render``, ``viewport_render_zoom``): the frames, a camera each and the
+    destination of h x w views -> (N, H, W, C, out).  `more`: the call's other tensors, which must be on the GPU too."""
+    require_gpu(frames, R, out, *more)
+    N, H, W, C_ = _frames_nhwc(frames, u8_only=False)
+    _stab_rotations(R, N)
+    return N, H, W, C_, _out_for(out, (N, h, w, C_), frames.dtype, frames.device, frames)
+
+
+def _outline_args(frames, R, rgb, out, work, *more):
+    """What K12b and K22b check alike (``viewport_outline``, ``viewport_outline_zoom``): the frames, a camera each, the colour,
+    the destination, which may be the frames, and the workspace -> (N, H, W, out, work, the colour as the library takes it)."""
+    require_gpu(frames, R, out, *more)
+    N, H, W, _ = _frames_nhwc(frames, u8_only=True)
+    _stab_rotations(R, N)
+    rgb = tuple(int(v) for v in rgb)
+    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise ValueError("rgb must be three values of 0 .. 255, got %r" % (rgb,))
+    out = _out_for(out, (N, H, W, 3), torch.uint8, frames.device, frames, same_ok=True)
+    return N, H, W, out, _stab_work(0, H, W, frames.device, work), C.cast((C.c_ubyte * 3)(*rgb), C.c_void_p)
+
+
 def _work(bytes_fn, what, F, h, w, device, work, limits=''):
     """The workspace of one call of the library, bytes_fn(F, h, w) bytes: `work` when it is a contiguous float64 tensor on
     `device` that holds as many, else a new one.  The callers hand the library work.numel() * 8 as the byte count, so a tensor
@@ -1574,15 +1608,12 @@ def viewport_render(frames, R, hw, hfov_deg, out=None, supersample=1):
     f32 row by row - anti-aliased for up to n source pixels per view pixel (``utils.viewport.supersample_for``); 1: no
     anti-aliasing, today's call."""
     ss = _supersample(supersample)[0]
-    require_gpu(frames, R, out)
-    N, H, W, C = _frames_nhwc(frames, u8_only=False)
-    _stab_rotations(R, N)
     h, w, hfov = _view_geometry(hw, hfov_deg)
-    out = _out_for(out, (N, h, w, C), frames.dtype, frames.device, frames)
+    N, H, W, C_, out = _render_args(frames, R, h, w, out)
     if ss == 1:
-        check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ptr(out), h, w, stream()))
+        check(lib().cp360_view_render(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, hfov, ptr(out), h, w, stream()))
     else:
-        check(lib().cp360_view_render_aa(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C, hfov, ss, ptr(out), h, w,
+        check(lib().cp360_view_render_aa(dtype_code(frames.dtype), ptr(frames), ptr(R), N, H, W, C_, hfov, ss, ptr(out), h, w,
                                          stream()))
     return out
 
@@ -1590,30 +1621,20 @@ def viewport_render(frames, R, hw, hfov_deg, out=None, supersample=1):
 def viewport_outline(frames, R, hw, hfov_deg, border_px=3, rgb=(0, 255, 0), out=None, work=None):
     """cp360_view_outline: the frame of the view (hw, hfov_deg) of camera R[n], border_px view pixels wide, drawn in rgb on the
     panorama: frames u8 [N, H, W, 3] -> u8 [N, H, W, 3]; out may be frames (every other pixel is copied)."""
-    require_gpu(frames, R, out)
-    N, H, W, _ = _frames_nhwc(frames, u8_only=True)
-    _stab_rotations(R, N)
     h, w, hfov = _view_geometry(hw, hfov_deg)
     rgb = tuple(int(v) for v in rgb)
     if not float(border_px) > 0.0 or len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
         raise ValueError("border_px must be positive and rgb three values of 0 .. 255, got %r, %r" % (border_px, rgb))
-    out = _out_for(out, (N, H, W, 3), torch.uint8, frames.device, frames, same_ok=True)
-    work = _stab_work(0, H, W, frames.device, work)
-    colour = (C.c_ubyte * 3)(*rgb)
-    check(lib().cp360_view_outline(ptr(frames), ptr(R), N, H, W, hfov, h, w, float(border_px), C.cast(colour, C.c_void_p),
-                                   ptr(out), ptr(work), work.numel() * 8, stream()))
+    N, H, W, out, work, colour = _outline_args(frames, R, rgb, out, work)
+    check(lib().cp360_view_outline(ptr(frames), ptr(R), N, H, W, hfov, h, w, float(border_px), colour, ptr(out), ptr(work),
+                                   work.numel() * 8, stream()))
     return out
 
 
 def _view_maps(maps, sigma_deg):
-    if maps.dim() != 3 or maps.numel() == 0:
-        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
-    _check_buf('maps', maps, torch.float32)
+    F, hm, wm = _map_shape(maps, ' (all pairs)')
     if not float(sigma_deg) > 0.0 or not math.isfinite(float(sigma_deg)):
         raise ValueError("sigma_deg must be positive, got %r" % (sigma_deg,))
-    F, hm, wm = (int(s) for s in maps.shape)
-    if hm * wm > 16384:
-        raise ValueError("maps of more than 16384 pixels are not supported (all pairs), got %d x %d" % (hm, wm))
     return F, hm, wm, math.radians(float(sigma_deg))
 
 
@@ -1737,17 +1758,12 @@ def sphere_exclude(maps, dirs, radius_deg, out=None, work=None):
     (1 <= Kx <= 7) set to +0: a pixel goes where the f32 dot of its centre with any direction of its frame is at least
     cos(radius_deg); every other pixel keeps its bits.  A direction with a non-finite component excludes nothing.  out may be
     maps."""
-    if maps.dim() != 3 or maps.numel() == 0:
-        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
+    F, hm, wm = _map_shape(maps)
     if dirs.dim() != 3 or dirs.shape[0] != maps.shape[0] or not 1 <= dirs.shape[1] <= 7 or dirs.shape[2] != 3:
         raise ValueError("dirs must be float32 [%d, Kx, 3] with 1 <= Kx <= 7, got %s" % (maps.shape[0], tuple(dirs.shape)))
     if not 0.0 < float(radius_deg) <= 180.0:
         raise ValueError("radius_deg must be in (0, 180], got %r" % (radius_deg,))
     require_gpu(maps, dirs, out, work)
-    _check_buf('maps', maps, torch.float32)
-    F, hm, wm = (int(s) for s in maps.shape)
-    if hm * wm > 16384:
-        raise ValueError("maps of more than 16384 pixels are not supported, got %d x %d" % (hm, wm))
     if dirs.device != maps.device:
         raise ValueError("dirs must be on the maps' device")
     _check_buf('dirs', dirs, torch.float32)
@@ -1853,18 +1869,15 @@ def viewport_render_zoom(frames, R, hw, lens, out=None, supersample=None):
     sample per pixel), or int32 [N] on the device, a factor per frame; a value outside 2 .. 4 renders as 1."""
     if supersample is not None and not torch.is_tensor(supersample):
         raise ValueError("supersample must be None or an int32 tensor [N] on the frames' device, got %r" % (supersample,))
-    require_gpu(frames, R, lens, out, supersample)
-    N, H, W, C_ = _frames_nhwc(frames, u8_only=False)
-    _stab_rotations(R, N)
     h, w = (int(v) for v in hw)
     if h < 1 or w < 1:
         raise ValueError("a view needs h, w >= 1, got %r" % (hw,))
+    N, H, W, C_, out = _render_args(frames, R, h, w, out, lens, supersample)
     _lens(lens, N, frames.device)
     if supersample is not None:
         if tuple(supersample.shape) != (N,) or supersample.device != frames.device:
             raise ValueError("supersample must be None or int32 [%d] on the frames' device" % N)
         _check_buf('supersample', supersample, torch.int32)
-    out = _out_for(out, (N, h, w, C_), frames.dtype, frames.device, frames)
     check(lib().cp360_view_render_zoom(dtype_code(frames.dtype), ptr(frames), ptr(R), ptr(lens), ptr(supersample), N, H, W, C_,
                                        ptr(out), h, w, stream()))
     return out
@@ -1874,18 +1887,10 @@ def viewport_outline_zoom(frames, R, lens, rgb=(0, 255, 0), out=None, work=None)
     """cp360_view_outline_zoom: ``viewport_outline`` with a lens per frame (``viewport_lens(hfov_deg, hw, border_px)``): frame n is
     ``viewport_outline`` with that frame's field of view and border, bit for bit; a frame whose b is not above 0 draws nothing.
     out may be frames."""
-    require_gpu(frames, R, lens, out)
-    N, H, W, _ = _frames_nhwc(frames, u8_only=True)
-    _stab_rotations(R, N)
+    N, H, W, out, work, colour = _outline_args(frames, R, rgb, out, work, lens)
     _lens(lens, N, frames.device)
-    rgb = tuple(int(v) for v in rgb)
-    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
-        raise ValueError("rgb must be three values of 0 .. 255, got %r" % (rgb,))
-    out = _out_for(out, (N, H, W, 3), torch.uint8, frames.device, frames, same_ok=True)
-    work = _stab_work(0, H, W, frames.device, work)
-    colour = (C.c_ubyte * 3)(*rgb)
-    check(lib().cp360_view_outline_zoom(ptr(frames), ptr(R), ptr(lens), N, H, W, C.cast(colour, C.c_void_p), ptr(out), ptr(work),
-                                        work.numel() * 8, stream()))
+    check(lib().cp360_view_outline_zoom(ptr(frames), ptr(R), ptr(lens), N, H, W, colour, ptr(out), ptr(work), work.numel() * 8,
+                                        stream()))
     return out
 
 
@@ -1896,12 +1901,7 @@ def sphere_spread(maps, dirs, window_deg=45.0, level=0.5, work=None):
     against the cap q = ``utils.viewport.spread_constant(level)`` sigma_b^2.  NaN for a non-finite direction, a cap without a
     finite pixel or a peak that is not positive."""
     require_gpu(maps, dirs, work)
-    if maps.dim() != 3 or maps.numel() == 0:
-        raise ValueError("maps must be a non-empty float32 [F, hm, wm], got %s" % (tuple(maps.shape),))
-    _check_buf('maps', maps, torch.float32)
-    F, hm, wm = (int(s) for s in maps.shape)
-    if hm * wm > 16384:
-        raise ValueError("maps of more than 16384 pixels are not supported, got %d x %d" % (hm, wm))
+    F, hm, wm = _map_shape(maps)
     if tuple(dirs.shape) != (F, 3) or dirs.device != maps.device:
         raise ValueError("dirs must be float32 [%d, 3] on the maps' device, got %s" % (F, tuple(dirs.shape)))
     _check_buf('dirs', dirs, torch.float32)
@@ -2303,21 +2303,27 @@ def head_footprints(R, offsets, hw, view_hw, hfov_deg, work=None):
     return counts, n_views
 
 
-def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
-    """cp360_head_agreement: the camera Rc f32 [F, 3, 3] with cam_view = ((h_c, w_c), hfov_deg) against every viewer of its frame
-    (R, offsets as in ``head_footprints``, view = ((h_v, w_v), hfov_deg)); weights int32 [h] (``sphere_eval_weights``) -> (inter
-    int64 [N], uni int64 [N]): the weighted pixels inside both windows and inside either, on the device, without a
-    synchronisation."""
-    require_gpu(Rc, R, offsets, weights, work)
+def _agreement_args(Rc, R, offsets, hw, weights, work, *more):
+    """What the two agreement ops check alike; the workspace and the two results -> (N, F, h, w, work, inter, uni)."""
+    require_gpu(Rc, R, offsets, weights, work, *more)
     N, F, h, w = _head_cameras(R, offsets, hw)
     _stab_rotations(Rc, F)
     if Rc.device != R.device or tuple(weights.shape) != (h,) or weights.device != R.device:
         raise ValueError("Rc [%d, 3, 3] and weights int32 [%d] must be on R's device" % (F, h))
     _check_buf('weights', weights, torch.int32)
-    (cam_hfov, cam_aspect), (hfov, aspect) = _head_view(*cam_view), _head_view(*view)
     work = head_work(h, w, R.device, work)
     inter = torch.empty((N,), dtype=torch.int64, device=R.device)
     uni = torch.empty((N,), dtype=torch.int64, device=R.device)
+    return N, F, h, w, work, inter, uni
+
+
+def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
+    """cp360_head_agreement: the camera Rc f32 [F, 3, 3] with cam_view = ((h_c, w_c), hfov_deg) against every viewer of its frame
+    (R, offsets as in ``head_footprints``, view = ((h_v, w_v), hfov_deg)); weights int32 [h] (``sphere_eval_weights``) -> (inter
+    int64 [N], uni int64 [N]): the weighted pixels inside both windows and inside either, on the device, without a
+    synchronisation."""
+    N, F, h, w, work, inter, uni = _agreement_args(Rc, R, offsets, hw, weights, work)
+    (cam_hfov, cam_aspect), (hfov, aspect) = _head_view(*cam_view), _head_view(*view)
     check(lib().cp360_head_agreement(ptr(Rc), cam_hfov, cam_aspect, ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
                                      ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
     return inter, uni
@@ -2326,17 +2332,9 @@ def head_agreement(Rc, cam_view, R, offsets, hw, view, weights, work=None):
 def head_agreement_zoom(Rc, cam_lens, R, offsets, hw, view, weights, work=None):
     """cp360_head_agreement_zoom (K22c): ``head_agreement`` with a lens per frame for the camera, cam_lens f32 [F, 4]
     (``viewport_lens`` of the camera's view and its field of view per frame); the viewers' window stays ``view``."""
-    require_gpu(Rc, cam_lens, R, offsets, weights, work)
-    N, F, h, w = _head_cameras(R, offsets, hw)
-    _stab_rotations(Rc, F)
-    if Rc.device != R.device or tuple(weights.shape) != (h,) or weights.device != R.device:
-        raise ValueError("Rc [%d, 3, 3] and weights int32 [%d] must be on R's device" % (F, h))
-    _check_buf('weights', weights, torch.int32)
+    N, F, h, w, work, inter, uni = _agreement_args(Rc, R, offsets, hw, weights, work, cam_lens)
     _lens(cam_lens, F, R.device, 'cam_lens')
     hfov, aspect = _head_view(*view)
-    work = head_work(h, w, R.device, work)
-    inter = torch.empty((N,), dtype=torch.int64, device=R.device)
-    uni = torch.empty((N,), dtype=torch.int64, device=R.device)
     check(lib().cp360_head_agreement_zoom(ptr(Rc), ptr(cam_lens), ptr(R), ptr(offsets), N, F, h, w, hfov, aspect, ptr(weights),
                                           ptr(inter), ptr(uni), ptr(work), work.numel() * 8, stream()))
     return inter, uni

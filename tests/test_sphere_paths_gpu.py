@@ -104,7 +104,7 @@ def zoom_bounds_case(name):
 
 @pytest.mark.parametrize('name', sorted(WIDE_HEAD))
 def test_zoom_agreement_on_wide_grids(name):
-    """head_agreement_zoom_kernel (K22c), the same walk with the camera's tangents per frame: equal to the scalar head_agreement
+    """head_agreement_kernel with a lens table (K22c), the same walk with the camera's tangents per frame: equal to the scalar head_agreement
     call of every frame's field of view (an 8 x 16 camera view: the two tangents are the same floats), and within the float64
     bounds under a 9 x 16 camera view."""
     c = head_case(name)
@@ -361,8 +361,8 @@ WIDE_PANORAMAS = [(9, 300), (12, 520)]
 
 
 def zoom_outline_blocks(HW, border_px):
-    """The 256-column blocks of view_outline_zoom_kernel (grid (ceil(W / 256), H, N)) that hold border pixels of each of
-    test_zoom_gpu's four frames, every camera with its own field of view, in float64.  Asserts that every frame draws, that some
+    """The 256-column blocks of view_outline_kernel with a lens table (grid (ceil(W / 256), H, N)) that hold border pixels of
+    each of test_zoom_gpu's four frames, every camera with its own field of view, in float64.  Asserts that every frame draws, that some
     border lies beyond x = 255, that the 180-degree yaw's border sits astride the seam where the rows are dense enough to catch it
     (in the first block and a later one), and on 520 columns that the identity camera's border falls in blocks 0 and 1 - on 300
     columns its 60-degree window spans x = 125 .. 175, block 0 alone."""
@@ -384,8 +384,8 @@ def zoom_outline_blocks(HW, border_px):
 @pytest.mark.parametrize('border_px', [1, 3])
 @pytest.mark.parametrize('HW', WIDE_PANORAMAS)
 def test_zoom_outline_on_wide_panoramas(HW, border_px, alias):
-    """view_outline_zoom_kernel with blockIdx.x = 1 (and 2 at 520 columns): the pixel index, the table lookup and the copy of the
-    pixels that are not drawn beyond x = 255.  test_outline_equals_the_one_frame_calls' check: every byte equal to
+    """view_outline_kernel with a lens table and blockIdx.x = 1 (and 2 at 520 columns): the pixel index, the table lookup and the
+    copy of the pixels that are not drawn beyond x = 255.  test_outline_equals_the_one_frame_calls' check: every byte equal to
     viewport_outline with that frame's field of view, which test_outline_on_wide_panoramas holds to float64 at rows of three
     blocks."""
     zoom_outline_blocks(HW, border_px)

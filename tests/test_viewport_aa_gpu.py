@@ -1,4 +1,4 @@
-"""K21 on the GPU (csrc/viewport.hip: view_pixel_aa, view_render_aa_kernel, view_render_multi_kernel with a factor per tile).
+"""K21 on the GPU (csrc/viewport.hip: view_pixel_aa, view_render_kernel with a factor, view_render_multi_kernel with a factor per tile).
 
 Exact: the sub-samples of the view (h, w) with the factor n are the pixels of ops.viewport_render's view (n h, n w) of the float
 frames, so the result must EQUAL their ordered float32 sum and quotient, formed here on the CPU in numpy float32 in the

@@ -210,6 +210,19 @@ def test_outline_edge_cases():
         ops.viewport_outline(dev(frames.astype(np.float32)), dev(R), (36, 64), 90.0)
 
 
+@pytest.mark.parametrize('alias', [False, True])
+def test_outline_with_a_border_that_rounds_to_nothing_draws_nothing(alias):
+    """border_px = 1e-60 is positive, so the call is accepted, and b = border_px 2 tx / w rounds to +0 in float32: inner is then
+    the |u|, |v| half of inside, no pixel is on the border, and the frame comes back as it was - copied, or left alone."""
+    frames = np.rint(255.0 * vr.texture(741, 33, 66, 3)).astype(np.uint8)[None]
+    assert ops.viewport_lens_host(90.0, (36, 64), 1e-60)[0, 2] == 0.0
+    src = dev(frames)
+    got = ops.viewport_outline(src, dev(np.eye(3, dtype=np.float32)[None]), (36, 64), 90.0, border_px=1e-60,
+                               out=src if alias else None)
+    assert (got is src) == alias
+    assert np.array_equal(got.cpu().numpy(), frames) and np.array_equal(src.cpu().numpy(), frames)
+
+
 # ----------------------------------------------------------------------------- smooth and peak
 MAP_SIZES = [(5, 9), (14, 28), (32, 64)]       # less than one tile of 256; one tile and a tail of 136; eight tiles
 

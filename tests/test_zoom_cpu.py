@@ -124,6 +124,59 @@ def test_outline_spread_and_agreement_statuses():
     assert z(*args) == 0                                                            # no pairs: valid, nothing launched
 
 
+def _twins():
+    """The scalar entry points and their zoom twins, each as (the arguments both take, the scalar call, the zoom call); every
+    pointer is a made-up address, so a call must return before it launches."""
+    L = _lib.lib()
+    a, b, lens = C.c_void_p(4096), C.c_void_p(8192), C.c_void_p(4112)
+    return {
+        'render': (dict(dtype=_lib.F32, frames=a, R=a, N=2, H=16, W=32, C=3, out=b, h=9, w=16),
+                   lambda v: L.cp360_view_render(v['dtype'], v['frames'], v['R'], v['N'], v['H'], v['W'], v['C'], 1.5, v['out'], v['h'],
+                                                 v['w'], None),
+                   lambda v: L.cp360_view_render_zoom(v['dtype'], v['frames'], v['R'], lens, None, v['N'], v['H'], v['W'], v['C'],
+                                                      v['out'], v['h'], v['w'], None)),
+        'outline': (dict(frames=a, R=a, N=2, H=16, W=32, rgb=a, out=b, work=a, work_bytes=1 << 20),
+                    lambda v: L.cp360_view_outline(v['frames'], v['R'], v['N'], v['H'], v['W'], 1.5, 9, 16, 3.0, v['rgb'], v['out'],
+                                                   v['work'], v['work_bytes'], None),
+                    lambda v: L.cp360_view_outline_zoom(v['frames'], v['R'], lens, v['N'], v['H'], v['W'], v['rgb'], v['out'], v['work'],
+                                                        v['work_bytes'], None)),
+        'agreement': (dict(Rc=a, R=a, offsets=a, N=3, F=2, H=12, W=24, weights=a, inter=a, uni=b, work=a, work_bytes=1 << 20),
+                      lambda v: L.cp360_head_agreement(v['Rc'], 1.5, 0.5, v['R'], v['offsets'], v['N'], v['F'], v['H'], v['W'], 1.5, 0.5,
+                                                       v['weights'], v['inter'], v['uni'], v['work'], v['work_bytes'], None),
+                      lambda v: L.cp360_head_agreement_zoom(v['Rc'], lens, v['R'], v['offsets'], v['N'], v['F'], v['H'], v['W'], 1.5, 0.5,
+                                                            v['weights'], v['inter'], v['uni'], v['work'], v['work_bytes'], None)),
+    }
+
+
+@pytest.mark.parametrize('pair', ['render', 'outline', 'agreement'])
+def test_a_scalar_entry_point_and_its_zoom_twin_refuse_alike(pair):
+    """The argument faults that both members of a pair can be handed - a null pointer, a size of 0, a bad dtype, C = 5, u8 with
+    C != 3, frames == out, a misaligned workspace, a workspace one byte short - get the same status from both, the documented
+    one.  (H, W) is the panorama, or the grid of the agreement; the tables at the head of a workspace are its 16-aligned
+    columns' and rows' (cos, sin)."""
+    ok, scalar, zoom = _twins()[pair]
+    odd = C.c_void_p(4098)
+    need = (8 * ok['W'] + 15) // 16 * 16 + (8 * ok['H'] + 15) // 16 * 16
+    assert need == _lib.lib().cp360_stab_work_bytes(0, ok['H'], ok['W'])
+    faults = [({k: None}, NULL) for k, v in ok.items() if isinstance(v, C.c_void_p)]
+    faults += [({k: 0}, BAD_SHAPE) for k in ('N', 'F', 'H', 'W', 'h', 'w')]
+    faults += [(dict(dtype=7), BAD_DTYPE), (dict(dtype=_lib.BF16), BAD_DTYPE), (dict(C=5), UNSUPPORTED),
+               (dict(dtype=_lib.U8, C=4), UNSUPPORTED), (dict(dtype=_lib.U8, C=1), UNSUPPORTED)]
+    if pair == 'render':                                                # a gather; the outline is element-wise and takes it
+        faults += [(dict(out=ok['frames']), UNSUPPORTED)]
+    faults += [(dict(work=odd), ALIGN), (dict(work_bytes=need - 1), BAD_SHAPE), (dict(work_bytes=0), BAD_SHAPE)]
+    if pair == 'agreement':                                             # no pairs: valid, and nothing is launched
+        faults = [(kw, 0 if kw == dict(N=0) else want) for kw, want in faults]
+    seen = 0
+    for kw, want in faults:
+        if not set(kw) <= set(ok):                                      # not an argument of this pair
+            continue
+        got = scalar(dict(ok, **kw)), zoom(dict(ok, **kw))
+        assert got == (want, want), (pair, kw, got)
+        seen += 1
+    assert seen == {'render': 14, 'outline': 11, 'agreement': 14}[pair]
+
+
 def test_the_wrappers_refuse_bad_arguments():
     frames = torch.zeros((2, 16, 32, 3), dtype=torch.uint8)
     R, lens = torch.zeros((2, 3, 3)), torch.zeros((2, 4))

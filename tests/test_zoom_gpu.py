@@ -1,5 +1,5 @@
-"""K22 on the GPU (csrc/viewport.hip: view_render_zoom_kernel, view_outline_zoom_kernel, view_spread_kernel; csrc/headtrack.hip:
-head_agreement_zoom_kernel).
+"""K22 on the GPU (csrc/viewport.hip: view_render_kernel and view_outline_kernel with a lens table, view_spread_kernel;
+csrc/headtrack.hip: head_agreement_kernel with a lens table).
 
 Exact: every launch with a lens per frame has an earlier call as its oracle - frame n of the result must EQUAL the one-frame call
 with that frame's field of view (and factor, and border), every bit, every byte.  Independent: against the float64 restatements

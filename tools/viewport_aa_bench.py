@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Times the anti-aliased view (K21, csrc/viewport.hip: view_render_aa_kernel and the canvas kernel with a factor per tile) at the
-sizes a video is run at: HIP events around each call on the current stream, the median after warm-up, as tools/viewport_bench.py
+"""Times the anti-aliased view (K21, csrc/viewport.hip: view_render_kernel with a factor and the canvas kernel with a factor per
+tile) at the sizes a video is run at: HIP events around each call on the current stream, the median after warm-up, as tools/viewport_bench.py
 does.  64 u8 frames of 2048 x 4096, cameras along a pan.
 
   cases      720 x 1280 at 90 degrees (supersample_for: 2) and at 120 degrees (2); a canvas of two 360 x 640 tiles and a gutter of 8

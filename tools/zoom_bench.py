@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times zoom (K22, csrc/viewport.hip: view_render_zoom_kernel, view_spread_kernel) at the sizes a video is run at: HIP events
+"""Times zoom (K22, csrc/viewport.hip: view_render_kernel with a lens table, view_spread_kernel) at the sizes a video is run at: HIP events
 around each call on the current stream, the median after warm-up, as tools/viewport_bench.py does.  64 u8 frames of 1024 x 2048
 into views of 720 x 1280, cameras along a pan.  In one run:
 
