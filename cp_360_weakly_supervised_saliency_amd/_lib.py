@@ -93,6 +93,8 @@ PUBLIC_SYMBOLS = [
     # K25: the conservative remap on the sphere, with its adjoint
     'cp360_sresample_run_cap', 'cp360_sresample_axis_host', 'cp360_sresample_plan_bytes', 'cp360_sresample_plan_host',
     'cp360_sresample_forward', 'cp360_sresample_adjoint',
+    # K26: video quality on the sphere, per cell
+    'cp360_sphere_quality_work_bytes', 'cp360_sphere_quality',
 ]
 # ... and of include/cp360_internal.h: the shape-specific fused kernels the stage contexts are built from (exported for
 # tests and the CP360_CTX=0 planner; not part of the boundary)
@@ -366,6 +368,9 @@ def lib():
     L.cp360_sresample_plan_host.argtypes = [i, i, i, i, vp, sz]
     L.cp360_sresample_forward.argtypes = [vp, i, i, i, vp, i, i, vp, sz, vp]
     L.cp360_sresample_adjoint.argtypes = [vp, i, i, i, vp, i, i, vp, sz, vp]
+    L.cp360_sphere_quality_work_bytes.restype = sz
+    L.cp360_sphere_quality_work_bytes.argtypes = [i, i, i, i, i]
+    L.cp360_sphere_quality.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, sz, vp]
     for name in SYMBOLS:
         getattr(L, name)       # AttributeError here = header and library disagree
     if L.cp360_version() != ABI_VERSION or L.cp360_conv_desc_bytes() != C.sizeof(ConvDesc):

@@ -2464,6 +2464,86 @@ def view_quality(R, offsets, hw, view, weights, levels, tiles, L, work=None):
     return qarea
 
 
+# ----------------------------------------------------------------------------- K26: video quality on the sphere (csrc/sphere_quality.hip)
+def _quality_cells(H, W, cells):
+    rows, cols = (int(v) for v in cells)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or not 1 <= rows <= H or not 1 <= cols <= W:
+        raise ValueError("cells must be (rows, cols) with 1 <= rows <= %d and 1 <= cols <= %d, got %r" % (H, W, tuple(cells)))
+    return H, W, rows, cols
+
+
+def _quality_ssim_ok(H, W):
+    return H % 4 == 0 and W % 4 == 0 and H >= 8 and W >= 8
+
+
+def quality_cell_weights(H, W, cells):
+    """int64 numpy [rows cols]: the sum of the row weights a_y (``shot_weights_host``) over the cell's pixels, pixel (y, x) in cell
+    ((y rows) // H, (x cols) // W).  Exact; host only: needs no GPU."""
+    H, W, rows, cols = _quality_cells(H, W, cells)
+    per_row = np.zeros(rows, np.int64)
+    np.add.at(per_row, (np.arange(H, dtype=np.int64) * rows) // H, shot_weights_host(H)[0].astype(np.int64))
+    per_col = np.bincount((np.arange(W, dtype=np.int64) * cols) // W, minlength=cols).astype(np.int64)
+    return (per_row[:, None] * per_col[None, :]).reshape(-1)
+
+
+def quality_window_weights(H, W, cells):
+    """int64 numpy [rows cols]: the sum of ww_i = a_4i + .. + a_4i+7 over the windows (i, j), i = 0 .. H / 4 - 2, j = 0 .. W / 4 - 1,
+    whose pixel (4 i + 4, (4 j + 4) % W) lies in the cell; 0 for a cell without a window, and everywhere where the frame has no
+    windows (H, W not multiples of 4 or below 8).  Exact; host only."""
+    H, W, rows, cols = _quality_cells(H, W, cells)
+    out = np.zeros((rows, cols), np.int64)
+    if not _quality_ssim_ok(H, W):
+        return out.reshape(-1)
+    a = shot_weights_host(H)[0].astype(np.int64)
+    i = np.arange(H // 4 - 1, dtype=np.int64)
+    ww = np.array([a[4 * k:4 * k + 8].sum() for k in i], np.int64)
+    per_row = np.zeros(rows, np.int64)
+    np.add.at(per_row, ((4 * i + 4) * rows) // H, ww)
+    per_col = np.bincount((((4 * np.arange(W // 4, dtype=np.int64) + 4) % W) * cols) // W, minlength=cols).astype(np.int64)
+    return (per_row[:, None] * per_col[None, :]).reshape(-1)
+
+
+def sphere_quality_work(F, H, W, cells, device, work=None):
+    """The workspace of one cp360_sphere_quality call: `work` when it is large enough, else a new one."""
+    H, W, rows, cols = _quality_cells(H, W, cells)
+    return _work(lambda f, h, w: lib().cp360_sphere_quality_work_bytes(f, h, w, rows, cols), "sphere quality", F, H, W, device, work,
+                 " (F, H <= 65535, H W <= 2^28, W <= 2^21)")
+
+
+def sphere_quality(ref, dist, cells, ssim=True, work=None, weights=None):
+    """cp360_sphere_quality: ref, dist u8 [F, H, W, 3] (contiguous; either may start at any byte), cells = (rows, cols) ->
+    (sse int64 [F, rows cols, 3], ssim_q int64 [F, rows cols] or None with ssim=False), on the device, without a synchronisation.
+    sse[f, t, c] = the sum over the pixels of cell t of a_y (ref - dist)^2; ssim_q[f, t] = the sum over the cell's windows of
+    ww q, q = the window's structural similarity on integer luma times 2^24 (needs H, W multiples of 4, at least 8).
+    Exact integers: the same bits whatever F, the frames' addresses and the launch."""
+    require_gpu(ref, dist, work, weights)
+    F, H, W, _ = _frames_nhwc(ref, u8_only=True, n='F')
+    if _frames_nhwc(dist, u8_only=True, n='F') != (F, H, W, 3) or dist.device != ref.device:
+        raise ValueError("dist must be uint8 %s on ref's device, got %s" % ((F, H, W, 3), tuple(dist.shape)))
+    H, W, rows, cols = _quality_cells(H, W, cells)
+    if ssim and not _quality_ssim_ok(H, W):
+        raise ValueError("the structural similarity needs H and W multiples of 4 and at least 8, got %d x %d (ssim=False measures "
+                         "the squared error alone)" % (H, W))
+    if weights is None:
+        weights = shot_weights(H, ref.device)
+    elif tuple(weights.shape) != (H,) or weights.device != ref.device:
+        raise ValueError("weights must be int32 [%d] on the frames' device" % H)
+    _check_buf('weights', weights, torch.int32)
+    if work is None:
+        work = sphere_quality_work(F, H, W, (rows, cols), ref.device)
+    else:
+        need = int(lib().cp360_sphere_quality_work_bytes(F, H, W, rows, cols))
+        _check_buf('work', work, torch.float64)
+        if need == 0 or work.device != ref.device or work.numel() * 8 < need:
+            raise ValueError("work must be float64 of at least %d bytes on the frames' device (sphere_quality_work)" % need)
+    sse = torch.empty((F, rows * cols, 3), dtype=torch.int64, device=ref.device)
+    ssim_q = torch.empty((F, rows * cols), dtype=torch.int64, device=ref.device) if ssim else None
+    check(lib().cp360_sphere_quality(ptr(ref), ptr(dist), F, H, W, rows, cols, ptr(weights), ptr(sse), ptr(ssim_q), ptr(work),
+                                     work.numel() * 8, stream()))
+    return sse, ssim_q
+
+
 # ----------------------------------------------------------------------------- K18: the supervised loss (csrc/suploss.hip)
 SUP_LOSS_STATS = 16                                                    # CP360_SUP_LOSS_STATS
 

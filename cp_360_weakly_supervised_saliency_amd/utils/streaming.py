@@ -10,6 +10,7 @@ points at its centre (a level camera, ``gaze_cameras``); the window is K17's.  T
     seg = segment_offsets(F, fps, seconds=1.0, cuts=cuts)
     levels = allocate(sp.demand(vis, seg), sp.area, rates, budget)
     qarea, u = sp.delivered(levels, seg, R, offsets, np.log(rates))          # against the people who watched (head_cameras)
+    levels = allocate_measured(demand, bits, dist, budget)     # on a measured rate-distortion table (utils.quality, K26)
 
 The incidence of the windows on the grid depends on the two grids and the window only: a planner computes it once, on first use.
 No CPU fallback for the maps and the score; the allocation is host numpy in float64.
@@ -103,6 +104,70 @@ def allocate(demand, area, rates, budget, utility=None, seconds=1.0):
                 left -= step
                 levels[g, t] += 1
                 open_[t] = levels[g, t] < L - 1
+            else:
+                open_[t] = False
+    return levels
+
+
+def _hull_next(bits, dist):
+    """bits, dist float64 [L] -> int64 [L]: from level l the next level along the lower convex hull of the points (bits, dist)
+    that starts at level 0 - the higher level with the steepest fall of dist per bit, the lowest on a tie; -1 where every
+    higher level has a larger dist (and from the top).  A level of equal dist is a step of gain 0, which ``allocate`` takes too."""
+    L = bits.size
+    nxt = np.full(L, -1, np.int64)
+    for l in range(L - 1):
+        slope = (dist[l] - dist[l + 1:]) / (bits[l + 1:] - bits[l])
+        k = int(np.argmax(slope))                                      # the first of the largest
+        if slope[k] >= 0.0:
+            nxt[l] = l + 1 + k
+    return nxt
+
+
+def allocate_measured(demand, bits, dist, budget):
+    """``allocate`` on measured tables: demand [G, T], bits float64 [G, T, L] or [T, L] (the bits of the tile at the level,
+    ascending in l), dist float64 [G, T, L] (``SphereQuality.rd_table``: the distortion of the tile at the level), budget the
+    bits of one segment -> levels int64 [G, T].  The same loop, tie rule and closing rule as ``allocate``; the gain of an upgrade
+    is demand[g, t] (dist[from] - dist[to]) / (bits[to] - bits[from]).  Upgrades run along each tile's lower convex hull of
+    (bits, dist) from level 0: a level above the hull is skipped, the upgrade goes to the next hull level and costs the sum, so a
+    level above the hull is never where a tile ends; a tile whose every higher level is worse is closed (a level that is no
+    worse is an upgrade of gain 0, taken while the budget lasts, as ``allocate`` takes an upgrade of slope 0).  Tiles with demand 0 stay
+    at 0."""
+    d = np.asarray(demand.detach().cpu() if torch.is_tensor(demand) else demand, np.float64)
+    dist = np.asarray(dist.detach().cpu() if torch.is_tensor(dist) else dist, np.float64)
+    bits = np.asarray(bits.detach().cpu() if torch.is_tensor(bits) else bits, np.float64)
+    if dist.ndim != 3 or dist.shape[2] < 1 or not np.all(np.isfinite(dist)):
+        raise ValueError("dist must be finite [G, T, L], got %s" % (dist.shape,))
+    G, T, L = dist.shape
+    if bits.ndim == 2:
+        bits = np.broadcast_to(bits[None], (G,) + bits.shape)
+    if bits.shape != dist.shape or not np.all(np.isfinite(bits)) or np.any(bits[..., 0] < 0.0) or np.any(np.diff(bits, axis=2) <= 0.0):
+        raise ValueError("bits must be finite, not negative and ascending in l, [%d, %d, %d] or [%d, %d], got %s" % (G, T, L, T, L, bits.shape))
+    if d.shape != (G, T) or not np.all(np.isfinite(d)) or np.any(d < 0.0):
+        raise ValueError("demand must be finite, not negative, [%d, %d], got %s" % (G, T, d.shape))
+    budget = float(budget)
+    levels = np.zeros((G, T), np.int64)
+    for g in range(G):
+        base = bits[g, :, 0].sum()
+        if not base <= budget:
+            raise ValueError("every tile at level 0 costs %g, above the budget %g" % (base, budget))
+        nxt = np.stack([_hull_next(bits[g, t], dist[g, t]) for t in range(T)])          # [T, L]
+        tiles = np.arange(T)
+        to = nxt[tiles, 0]
+        left = budget - base
+        open_ = (d[g] > 0.0) & (to >= 0)
+        while open_.any():
+            lv = levels[g]
+            safe = np.where(to >= 0, to, lv)
+            step = bits[g, tiles, safe] - bits[g, tiles, lv]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                slope = (dist[g, tiles, lv] - dist[g, tiles, safe]) / step
+            gain = np.where(open_, d[g] * slope, -np.inf)
+            t = int(np.argmax(gain))                                   # the first of the largest: the lowest t on a tie
+            if step[t] <= left:
+                left -= step[t]
+                levels[g, t] = to[t]
+                to[t] = nxt[t, to[t]]
+                open_[t] = to[t] >= 0
             else:
                 open_[t] = False
     return levels

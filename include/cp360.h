@@ -1114,6 +1114,32 @@ int cp360_sresample_forward(const float* src, int F, int hs, int ws, float* dst,
 int cp360_sresample_adjoint(const float* d_dst, int F, int h, int w, float* d_src, int hs, int ws, const void* plan,
                             size_t plan_bytes, void* stream);
 
+/* ------------------------------------------------------------------ K26: video quality on the sphere, per cell
+ * The weighted squared error behind WS-PSNR and a windowed structural similarity on integer luma behind WS-SSIM, of a decoded
+ * video against its source.  The specification is the package's own, DESIGN.md "K26" (7r), restated in tests/quality_restate.py.
+ * ref, dist u8 [F, H, W, 3], contiguous, each from any byte address; rows x cols cells (1 <= rows <= H, 1 <= cols <= W), pixel
+ * (y, x) in cell ((y rows) / H) cols + (x cols) / W (K24's tile rule), T = rows cols; weights int32 [H] as for
+ * cp360_shot_signatures (clamped to 0 .. 1024).  All DEVICE memory.
+ *   sse     int64 [F, T, 3]: sse[f, t, c] = the sum over the pixels of cell t of a_y (ref - dist)^2.  Exact.
+ *   ssim_q  int64 [F, T] or NULL (not computed; needs H % 4 == 0, W % 4 == 0, H >= 8, W >= 8).  Y = (4899 R + 9617 G + 1868 B +
+ *           8192) >> 14; a 4 x 4 block has s1 = sum Yr, s2 = sum Yd, ss = sum (Yr^2 + Yd^2), s12 = sum Yr Yd; window (i, j), i = 0
+ *           .. H / 4 - 2, j = 0 .. W / 4 - 1, is the blocks (i, j), (i, j + 1), (i + 1, j), (i + 1, j + 1), column j + 1 modulo
+ *           W / 4.  With the window's sums in int64: vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2, A = (2 s1 s2 + 416)
+ *           (2 covar + 235963), B = (s1^2 + s2^2 + 416)(vars + 235963), q = (int64)rint((double)A / (double)B 2^24).
+ *           ssim_q[f, t] = the sum over the windows whose pixel (4 i + 4, (4 j + 4) % W) lies in cell t of ww_i q, ww_i = a_4i + ..
+ *           + a_4i+7.  Exact up to the one correctly rounded f64 quotient per window.
+ *   work    cp360_sphere_quality_work_bytes(F, H, W, rows, cols) bytes (the cell of every column and row, the weights; 0 = bad
+ *           or unsupported sizes).
+ * No result depends on the order of accumulation, the launch geometry, F or the frames' addresses.
+ * Status codes, in this order and before any launch: a NULL pointer (ssim_q may be NULL): CP360_ERR_NULL; a size < 1, rows > H,
+ * cols > W, or ssim_q with H % 4, W % 4 != 0 or H, W < 8: CP360_ERR_BAD_SHAPE; H W 65025 1024 >= 2^62, F or H > 65535, H W > 2^28,
+ * W > 2^21, or ssim_q with H W >= 2^29: CP360_ERR_UNSUPPORTED; sse, ssim_q not 8-byte, weights not 4-byte, work not 16-byte
+ * aligned: CP360_ERR_ALIGN; a workspace that is too small: CP360_ERR_BAD_SHAPE.  Asynchronous on the stream, no host
+ * synchronisation; the results are zeroed on the stream and added to with 64-bit integer atomics. */
+size_t cp360_sphere_quality_work_bytes(int F, int H, int W, int rows, int cols);
+int cp360_sphere_quality(const uint8_t* ref, const uint8_t* dist, int F, int H, int W, int rows, int cols, const int32_t* weights,
+                         long long* sse, long long* ssim_q, void* work, size_t work_bytes, void* stream);
+
 /* Diagnostic only (bench.py `held_clock_ghz`): a bare bf16 MFMA loop on pseudo-random operands, n_workgroups x 4 waves, each
  * wave stamped once around `iters` x 16 MFMAs.  stamps: device u64 [n_workgroups * 4][2] = {d s_memtime (shader cycles),
  * d s_memrealtime (100 MHz ticks)} per wave; held clock of a wave = 0.1 GHz * [0] / [1].  A buffer of its own: no output of
